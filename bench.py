@@ -5,13 +5,17 @@ Metric (BASELINE.json): SAI-megapixels/s of the full HT + Wiener denoise, sigma 
 17x17x512x512 synthetic light field with the README "Stanford" parameters.
 One "step" = run_bm5d_1st_step + run_bm5d_2nd_step over the whole light field, inputs already
 resident in HBM, noise from the reference's MT19937 stream (seed 1).  The PSNR of the run is part of
-the JSON line.
+the --full JSON line.
 
-    python bench.py --gpus 1 --steps 2 --warmup 1
+    python bench.py --gpus 1 --steps 2 --warmup 1 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the headline; `--full` adds
+the measurements and checks below the first entry (roofline, kernel_ms_per_step, psnr, seam, cpu_baseline), each of
+which takes work of its own outside the timed region (the one-lane measurement step, the host-seam runs, the CPU oracle).
+`--dump-outputs DIR` writes what the last timed step handed its caller (denoised, basic, noisy) as DIR/<name>.npy, float32;
+the inputs are the same from run to run, so two builds can be compared output for output (see dump_outputs).
   value      whole-job throughput of the timed region (default execution: the step's windows as a dependency
              graph on LFBM5D_LANES = 2 streams, bit-identical to the window-after-window order)
   roofline   the transform + aggregate kernel pair (k_group* + k_aggregate; the SURVEY 8d algorithmic bytes
@@ -28,6 +32,7 @@ Prints ONE JSON line on rank 0.
              run_bm5d_1st_step + run_bm5d_2nd_step of liblfbm5d_dropin.so on vector<vector<float>> light fields, i.e. the
              interval the reference times (main.cpp:189-201, :241-247), and run_bm5d (one job).  Since round 5 the SAIs are
              streamed through the window graph.
+  psnr       quality of this run: mean PSNR of the noisy input, the basic and the denoised estimate against the clean light field.
   cpu_baseline  the CPU oracle (oracle/, a restatement of the reference: kind "port") on the GPU box's host
              cores: the first windows of each step of the SAME noisy light field (up to 3, bounded by a
              time limit), extrapolated by the window count; untiled parity mode.
@@ -213,16 +218,40 @@ def parity_vs_gpu(wl, noisy_rgb_9, basic_rgb_9, ctx):
     return out
 
 
+DUMP_SAMPLE = 4 << 20      # elements per dumped array: 3 arrays x 16 MiB stay within 64 MB
+DUMP_SEED = 20240601
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: each [asize][C*H*W] output of the timed path as DIR/<name>.npy, float32.  An array of more than
+    DUMP_SAMPLE elements is written as the sample at the flat indices np.unique(default_rng(DUMP_SEED).integers(0, size,
+    DUMP_SAMPLE)) (sorted, the same for every run of a workload), the whole array otherwise."""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        flat = t.reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), DUMP_SAMPLE))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(d, name + ".npy"), flat.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="lf17x17x512x512_sigma25", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-seam", action="store_true", help="skip the host-seam measurements (`seam` in the line; +3 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements and checks outside the headline: roofline (one extra one-lane step), kernel_ms_per_step, "
+                         "psnr, the host-seam runs (unless --no-seam) and the CPU baseline (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (denoised, basic, noisy) as DIR/<name>.npy, float32; arrays above "
+                         f"{DUMP_SAMPLE} elements as a fixed, seeded sample of them")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-seam", action="store_true", help="--full: skip the host-seam measurements (`seam` in the line; +3 s)")
     ap.add_argument("--parity-check", action="store_true",
-                    help="also run the centre window of each step through the oracle and the C-ABI and report the differences (+20 s)")
+                    help="--full: also run the centre window of each step through the oracle and the C-ABI and report the differences (+20 s)")
     ap.add_argument("--lanes", type=int, default=0, help="window lanes of the timed region (0: the library's default, 2)")
     ap.add_argument("--noise", default="mt19937", choices=["mt19937", "torch"],
                     help="mt19937: the reference's noise stream, seed 1 (default); torch: quick GPU noise for kernel iteration")
@@ -395,9 +424,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # roofline measurement: the kernel pair alone on the GPU (one lane).  Outside the timed region.
+    if args.dump_outputs and rank == 0:
+        # what the timed path handed its caller in the last timed step (noisy is in / out, like the reference's LF_noisy)
+        dump_outputs(args.dump_outputs, {"denoised": den, "basic": basic, "noisy": noisy})
+
+    # roofline measurement (--full): the kernel pair alone on the GPU (one lane).  Outside the timed region.
     roof, roof_steps = timed, args.steps
-    if (lanes_timed != 1 or fused) and world == 1:
+    if args.full and (lanes_timed != 1 or fused) and world == 1:
         os.environ["LFBM5D_LANES"] = "1"
         roof, roof_steps = {"ht": {}, "wiener": {}}, 1
         one_step(roof, two_calls=True)
@@ -408,120 +441,6 @@ def main():
         total_mp = asize * H * W / 1e6
         ms_per_step = 1e3 * elapsed / max(1, args.steps)
         value = total_mp * args.steps / elapsed
-
-        def psnr_lf(x):   # quality: PSNR against the clean light field (mean over SAIs), this run
-            mse = ((x - clean) ** 2).mean(dim=1)
-            return float((20 * torch.log10(255.0 / torch.sqrt(mse))).mean().item())
-
-        traffic = None
-        tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
-        if os.path.exists(tpath):
-            try:
-                tj = json.load(open(tpath))
-                if args.workload == tj.get("workload"):
-                    traffic = tj
-            except Exception:
-                traffic = None
-
-        valu = None
-        vpath = os.path.join(ROOT, "profiles", "valu_latest.json")
-        if os.path.exists(vpath):
-            try:
-                vj = json.load(open(vpath))
-                if args.workload == vj.get("workload"):
-                    valu = vj
-            except Exception:
-                valu = None
-        # SURVEY 8d's compulsory floor of a window pass: every window image read once, num / den read and written once
-        comp = {}
-        for kind, pk, S in (("ht", wl["p1"], 1), ("wiener", wl["p2"], 2)):
-            nHW = pk[1] + pk[2]
-            comp[kind] = (S + 4) * 4.0 * 9 * 3 * (W + 2 * nHW) * (H + 2 * nHW)
-        SIMDS, CLK = 1024, 2.4e9      # 256 CUs x 4 SIMD-32; a wave64 VALU instruction occupies its SIMD for 2 cycles (MI355X_MICROARCH.md)
-        HBM_ACHIEVABLE_GBS = 6300.0   # what a streaming kernel reaches on MI355X (MI355X_MICROARCH.md, HBM section): the floors' rate
-
-        def valu_frac(classes, ms):
-            """share of the chip's VALU issue slots the kernels of `classes` use during `ms` (their time alone on the GPU)"""
-            if not valu or ms <= 0:
-                return None
-            k = valu.get("kernels", {})
-            if any(c not in k for c in classes):
-                return None
-            insts = sum(k[c]["valu_insts_per_launch"] for c in classes)
-            # valu_frac prices every instruction at 2 cycles; the packed-fp32 instructions these kernels are largely made of take 4
-            # (measured, profiles/r06_a_valu_rate.txt: v_pk_fma / mul / add_f32 2.0-2.2 ns per wave-instruction and SIMD against 1.0-1.2
-            # for the plain forms), as do DPP moves and v_mad_u32_u24: valu_frac_all_packed is the same count at 4 cycles -- the truth lies between
-            return {"valu_insts": insts, "valu_frac": insts * 2.0 / (SIMDS * CLK * ms * 1e-3),
-                    "valu_frac_all_packed": insts * 4.0 / (SIMDS * CLK * ms * 1e-3)}
-
-        def pair(kind):
-            a = roof[kind]
-            n = max(1, int(a.get("launches_group", 0)))
-            ms = (a.get("ms_group", 0.0) + a.get("ms_aggregate", 0.0)) / n
-            by = a.get("algorithmic_bytes", 0.0) / n
-            ach = by / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
-            d = {"algorithmic_bytes_per_launch": by, "avg_launch_ms": ms, "ms_group": a.get("ms_group", 0.0) / n,
-                 "ms_aggregate": a.get("ms_aggregate", 0.0) / n, "launches": n, "achieved": ach, "frac": ach / HBM_PEAK_GBS}
-            if d["frac"] > 1.0:
-                d["flag"] = ("above 1: the SURVEY 8d byte model charges 16 B of num/den read-modify-write per stacked pixel, "
-                             "the gather-form aggregation moves 8 B (filt written once, read once) and the stack gathers hit L2")
-            if traffic and kind in traffic.get("per_step", {}):
-                tb = traffic["per_step"][kind]["hbm_bytes_per_launch"]
-                d["traffic"] = tb
-                d["frac_physical"] = tb / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS if ms > 0 else None
-                d["traffic_over_compulsory"] = tb / comp[kind]
-            d["compulsory_bytes"] = comp[kind]
-            # distance to the floor of THIS design (round 6; `frac` is saturated by the byte model): what each kernel class must move
-            # through HBM once -- group: the window images in (the stack gathers re-read them from L2) + `filt` out; aggregation: `filt`
-            # in + num / den in and out -- at the rate a streaming kernel reaches, next to the class's time alone on the GPU
-            pk_, S_ = (wl["p1"], 1) if kind == "ht" else (wl["p2"], 2)
-            nHW_, k_ = pk_[1] + pk_[2], pk_[3]
-            plane_b = 4.0 * 9 * 3 * (W + 2 * nHW_) * (H + 2 * nHW_)
-            n_pass = max(1, int(a.get("passes", 0)))
-            filt_b = a.get("stack_patches", 0.0) / n_pass * 9 * 3 * k_ * k_ * 4.0
-            design = {"group": S_ * plane_b + filt_b, "aggregate": filt_b + 4 * plane_b}
-            d["filt_bytes"] = filt_b
-            d["gather_bytes_from_l2"] = S_ * filt_b
-            d["design_bytes"] = design["group"] + design["aggregate"]
-            d["floor_ms"] = d["design_bytes"] / HBM_ACHIEVABLE_GBS / 1e6
-            d["x_over_floor"] = ms / d["floor_ms"] if d["floor_ms"] > 0 else None
-            d["floor_by_class"] = {cn: {"design_bytes": design[cn], "floor_ms": design[cn] / HBM_ACHIEVABLE_GBS / 1e6,
-                                        "ms": d["ms_" + cn], "x_over_floor": (d["ms_" + cn] / (design[cn] / HBM_ACHIEVABLE_GBS / 1e6)) if design[cn] > 0 else None}
-                                   for cn in ("group", "aggregate")}
-            # what binds: per kernel class of this pass, the share of VALU issue slots it uses next to the share of the HBM peak it
-            # moves (PMC bytes of the class / its time); neither near 1 = latency- / occupancy-bound
-            n_p = max(1, int(a.get("passes", 0)))
-            cls = {"block_matching": ((f"scan/{kind}", "select", "argmin"), a.get("ms_bm", 0.0) / n_p),
-                   "group": ((f"group/{kind}",), d["ms_group"]), "aggregate": ((f"aggregate/{kind}",), d["ms_aggregate"])}
-            bound = {}
-            for cname, (classes, cms) in cls.items():
-                e = {"ms": cms}
-                v = valu_frac(classes, cms)
-                if v:
-                    e.update(v)
-                if traffic and cms > 0:
-                    tk = traffic.get("kernels", {})
-                    by_c = 0.0
-                    for c in classes:
-                        kk = tk.get(c) or tk.get(c.split("/")[0] + "/both")
-                        if kk:
-                            by_c += kk["fetch_bytes_per_launch_x2"] + kk["write_bytes_per_launch"]   # FETCH_SIZE halves every shape (profiles/r06_b_fetch_calib.txt)
-                    if by_c:
-                        e["hbm_bytes"] = by_c
-                        e["hbm_frac"] = by_c / (cms * 1e-3) / 1e9 / HBM_PEAK_GBS
-                if "valu_frac" in e or "hbm_frac" in e:
-                    vf, hf = e.get("valu_frac", 0.0), e.get("hbm_frac", 0.0)
-                    e["closest_bound"] = ("valu issue" if vf >= hf else "hbm") + f" at {max(vf, hf):.2f} -- " + (
-                        "bound by it" if max(vf, hf) > 0.7 else "latency / occupancy: neither the VALUs nor HBM are saturated")
-                bound[cname] = e
-            d["bound_by_class"] = bound
-            return d
-        ph, pw = pair("ht"), pair("wiener")
-        n_all = ph["launches"] + pw["launches"]
-        alg_bytes = (ph["algorithmic_bytes_per_launch"] * ph["launches"] + pw["algorithmic_bytes_per_launch"] * pw["launches"]) / n_all
-        pair_ms = (ph["avg_launch_ms"] * ph["launches"] + pw["avg_launch_ms"] * pw["launches"]) / n_all
-        achieved = alg_bytes / (pair_ms * 1e-3) / 1e9 if pair_ms > 0 else 0.0
-        t_bytes = traffic.get("hbm_bytes_per_launch") if traffic else None
         tot = {f: timed["ht"].get(f, 0) + timed["wiener"].get(f, 0) for f in FIELDS}
         out = {
             "metric": "SAI-megapixels/sec (HT+Wiener, sigma=25)",
@@ -545,41 +464,6 @@ def main():
                                        f"{world} x blocks of angular windows + 1 RCCL all-reduce of num/den per step (NOT the reference's result)"
                                        if args.sharding == "blocks" else
                                        f"{world} x reference-patch rows of every pass + RCCL all-reduce per pass")},
-            "roofline": {"bound": "hbm", "kernel": "k_group* + k_aggregate (5-D transform + shrinkage + aggregation)",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": t_bytes,
-                         "frac_physical": (t_bytes / (pair_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if (t_bytes and pair_ms > 0) else None,
-                         "traffic_source": (traffic or {}).get("source"),
-                         "compulsory_bytes": (comp["ht"] * ph["launches"] + comp["wiener"] * pw["launches"]) / n_all,
-                         "valu_source": (valu or {}).get("source"),
-                         "valu_frac": (lambda v: v["valu_frac"] if v else None)(valu_frac(("group/ht", "aggregate/ht", "group/wiener", "aggregate/wiener"), 2 * pair_ms)),
-                         "valu_note": "VALU wave-instructions (rocprofv3 --pmc SQ_INSTS_VALU of this command, profiles/valu_latest.json) x 2 cycles / "
-                                      "(1024 SIMDs x 2.4 GHz x live kernel time); per kernel class under per_step.*.bound_by_class",
-                         "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": pair_ms, "launches": n_all,
-                         # the contract's `frac` per step, and the distance to this design's own floor (what to read instead of a saturated frac)
-                         "frac_ht": ph["frac"], "frac_wiener": pw["frac"],
-                         "design_bytes": (ph["design_bytes"] * ph["launches"] + pw["design_bytes"] * pw["launches"]) / n_all,
-                         "floor_ms": (ph["floor_ms"] * ph["launches"] + pw["floor_ms"] * pw["launches"]) / n_all,
-                         "x_over_floor": pair_ms / ((ph["floor_ms"] * ph["launches"] + pw["floor_ms"] * pw["launches"]) / n_all) if (ph["floor_ms"] + pw["floor_ms"]) > 0 else None,
-                         "x_over_floor_by_class": {"ht": {cn: v["x_over_floor"] for cn, v in ph["floor_by_class"].items()},
-                                                   "wiener": {cn: v["x_over_floor"] for cn, v in pw["floor_by_class"].items()}},
-                         "floor_note": "design_bytes = window images read once + filt written once (group), filt read once + num/den read and written "
-                                       "once (aggregation); floor_ms = design_bytes / 6.3 TB/s (the rate MI355X_MICROARCH.md calls achievable); the stack "
-                                       "gathers (gather_bytes_from_l2 under per_step) are served by L2 and are not in the floor",
-                         "measured_with": ((f"the timed region ({lanes_timed} lane{'s' if lanes_timed != 1 else ''}"
-                                            + ("; kernels of different windows overlap, the intervals are not kernel-alone times)" if lanes_timed != 1 else ")"))
-                                           if roof is timed else
-                                           f"{roof_steps} extra untimed step with LFBM5D_LANES=1, the two calls one after the other (kernels alone on the GPU); the timed region ran {lanes_timed} lanes" + (", fused job" if fused else "")),
-                         "per_step": {"ht": ph, "wiener": pw}},
-            # kernel classes alone on the GPU (the one-lane measurement step); with several lanes the HIP-event intervals of
-            # different windows overlap and add up to more than the step, so those are reported under their own key
-            "kernel_ms_per_step": {"block_matching": (roof["ht"].get("ms_bm", 0.0) + roof["wiener"].get("ms_bm", 0.0)) / roof_steps,
-                                   "group": (roof["ht"].get("ms_group", 0.0) + roof["wiener"].get("ms_group", 0.0)) / roof_steps,
-                                   "aggregate": (roof["ht"].get("ms_aggregate", 0.0) + roof["wiener"].get("ms_aggregate", 0.0)) / roof_steps,
-                                   "comm": (roof["ht"].get("ms_comm", 0.0) + roof["wiener"].get("ms_comm", 0.0)) / roof_steps,
-                                   "measured_with": (f"the timed region ({lanes_timed} lanes: overlapped intervals)" if (roof is timed and lanes_timed != 1)
-                                                     else "the timed region (one lane)" if roof is timed else "the one-lane measurement step (kernels alone on the GPU)")},
             "kernel_ms_per_step_overlapped": {"block_matching": tot["ms_bm"] / args.steps, "group": tot["ms_group"] / args.steps,
                                               "aggregate": tot["ms_aggregate"] / args.steps, "comm": tot["ms_comm"] / args.steps,
                                               "note": "HIP-event intervals on each lane's stream during the timed region; intervals of "
@@ -587,65 +471,216 @@ def main():
             "rccl_ranks_seen": ctx.comm_ranks() if world > 1 else 1,
             "passes_per_step": tot["passes"] / args.steps, "windows_per_step": tot["windows"] / args.steps,
             "lane_windows_per_step": tot["lane_windows"] / args.steps, "messages_per_step": tot["messages"] / args.steps,
-            "psnr": {"noisy": psnr_lf(noisy0), "basic": psnr_lf(basic), "denoised": psnr_lf(den)},
         }
-        if not args.no_seam and world == 1:
-            # the job through the reference's own seam (host memory in and out), outside the timed region
-            try:
-                seam = {"note": "pageable host memory, SAIs streamed through the window graph (upload at first use, outputs behind the last "
-                                "window on a SAI); value above = device-resident buffers; outputs compared with the timed region's"}
-                n_src = noisy_h if noisy_h is not None else noisy0.cpu().numpy()
-                den_ref = den.cpu().numpy()
-                hb, hd = np.zeros_like(n_src), np.zeros_like(n_src)
-                best = None
-                for _ in range(2):
-                    hn = n_src.copy()
-                    t1 = time.perf_counter()
-                    ctx.denoise(P1, P2, hn, mask, hb, hd, L.ROWMAJOR, aw, ah, 1, 1, W, H, 3)
-                    dt = time.perf_counter() - t1
-                    best = dt if best is None else min(best, dt)
-                seam["host_flat"] = {"entry": "lfbm5d_denoise_host", "ms_per_step": best * 1e3, "value": total_mp / best,
-                                     "vs_device": best * 1e3 / ms_per_step, "identical_to_device": bool(np.array_equal(hd, den_ref))}
-                del hb, hd, hn
-                for key, one_job in (("dropin_vectors", False), ("dropin_vectors_one_job", True)):
-                    msv, _, _, dd = core.dropin_probe(n_src, mask, aw, ah, W, H, 3, sigma, 2.7, wl["p1"], wl["p2"], one_job=one_job, reps=2)
-                    tt = float(msv[1].sum()) * 1e-3
-                    seam[key] = {"entry": ("run_bm5d (both steps as one job)" if one_job else
-                                           "run_bm5d_1st_step + run_bm5d_2nd_step (src/bm5d.h:11-62; the interval of main.cpp:189-201 + :241-247)"),
-                                 "ms_per_step": tt * 1e3, "ms_calls": [float(msv[1, 0]), float(msv[1, 1])], "value": total_mp / tt,
-                                 "vs_device": tt * 1e3 / ms_per_step, "identical_to_device": bool(np.array_equal(dd, den_ref))}
-                    del dd
-                out["seam"] = seam
-            except Exception as e:  # noqa: BLE001
-                out["seam"] = {"error": str(e)}
-        if not args.no_cpu_baseline and world == 1:   # the CPU baseline is timed on rank 0 of the 1-GPU run only
-            try:
-                n_h = noisy_h if noisy_h is not None else noisy0.cpu().numpy()
-                basic_full = basic.clone()
-                out["cpu_baseline"] = cpu_baseline(wl, n_h, basic_full.cpu().numpy(), int(round(tot["windows"] / args.steps / 2)), total_mp)
+        if args.full:
+            def psnr_lf(x):   # quality: PSNR against the clean light field (mean over SAIs), this run
+                mse = ((x - clean) ** 2).mean(dim=1)
+                return float((20 * torch.log10(255.0 / torch.sqrt(mse))).mean().item())
 
-                def run_gpu(key, n0, b_full):
-                    n_in = n0.clone()
-                    if key == "basic":
-                        est = torch.zeros_like(n0)
-                        ctx.step1(P1, n_in, mask, est, L.ROWMAJOR, aw, ah, 1, W, H, 3)
-                    else:
-                        b_in, est = b_full.clone(), torch.zeros_like(n0)
-                        ctx.step2(P2, n_in, mask, b_in, est, L.ROWMAJOR, aw, ah, 1, W, H, 3)
-                    torch.cuda.synchronize()
-                    return (n_in if key == "basic" else b_in), est
+            traffic = None
+            tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
+            if os.path.exists(tpath):
                 try:
-                    out["cpu_baseline"]["psnr_delta_db"] = psnr_delta_vs_cpu(out["cpu_baseline"], clean, noisy0, basic_full, run_gpu)
+                    tj = json.load(open(tpath))
+                    if args.workload == tj.get("workload"):
+                        traffic = tj
+                except Exception:
+                    traffic = None
+
+            valu = None
+            vpath = os.path.join(ROOT, "profiles", "valu_latest.json")
+            if os.path.exists(vpath):
+                try:
+                    vj = json.load(open(vpath))
+                    if args.workload == vj.get("workload"):
+                        valu = vj
+                except Exception:
+                    valu = None
+            # SURVEY 8d's compulsory floor of a window pass: every window image read once, num / den read and written once
+            comp = {}
+            for kind, pk, S in (("ht", wl["p1"], 1), ("wiener", wl["p2"], 2)):
+                nHW = pk[1] + pk[2]
+                comp[kind] = (S + 4) * 4.0 * 9 * 3 * (W + 2 * nHW) * (H + 2 * nHW)
+            SIMDS, CLK = 1024, 2.4e9      # 256 CUs x 4 SIMD-32; a wave64 VALU instruction occupies its SIMD for 2 cycles
+            HBM_ACHIEVABLE_GBS = 6300.0   # what a streaming kernel reaches on MI355X's HBM: the floors' rate
+
+            def valu_frac(classes, ms):
+                """share of the chip's VALU issue slots the kernels of `classes` use during `ms` (their time alone on the GPU)"""
+                if not valu or ms <= 0:
+                    return None
+                k = valu.get("kernels", {})
+                if any(c not in k for c in classes):
+                    return None
+                insts = sum(k[c]["valu_insts_per_launch"] for c in classes)
+                # valu_frac prices every instruction at 2 cycles; the packed-fp32 instructions these kernels are largely made of take 4
+                # (measured, profiles/r06_a_valu_rate.txt: v_pk_fma / mul / add_f32 2.0-2.2 ns per wave-instruction and SIMD against 1.0-1.2
+                # for the plain forms), as do DPP moves and v_mad_u32_u24: valu_frac_all_packed is the same count at 4 cycles -- the truth lies between
+                return {"valu_insts": insts, "valu_frac": insts * 2.0 / (SIMDS * CLK * ms * 1e-3),
+                        "valu_frac_all_packed": insts * 4.0 / (SIMDS * CLK * ms * 1e-3)}
+
+            def pair(kind):
+                a = roof[kind]
+                n = max(1, int(a.get("launches_group", 0)))
+                ms = (a.get("ms_group", 0.0) + a.get("ms_aggregate", 0.0)) / n
+                by = a.get("algorithmic_bytes", 0.0) / n
+                ach = by / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
+                d = {"algorithmic_bytes_per_launch": by, "avg_launch_ms": ms, "ms_group": a.get("ms_group", 0.0) / n,
+                     "ms_aggregate": a.get("ms_aggregate", 0.0) / n, "launches": n, "achieved": ach, "frac": ach / HBM_PEAK_GBS}
+                if d["frac"] > 1.0:
+                    d["flag"] = ("above 1: the SURVEY 8d byte model charges 16 B of num/den read-modify-write per stacked pixel, "
+                                 "the gather-form aggregation moves 8 B (filt written once, read once) and the stack gathers hit L2")
+                if traffic and kind in traffic.get("per_step", {}):
+                    tb = traffic["per_step"][kind]["hbm_bytes_per_launch"]
+                    d["traffic"] = tb
+                    d["frac_physical"] = tb / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS if ms > 0 else None
+                    d["traffic_over_compulsory"] = tb / comp[kind]
+                d["compulsory_bytes"] = comp[kind]
+                # distance to the floor of THIS design (round 6; `frac` is saturated by the byte model): what each kernel class must move
+                # through HBM once -- group: the window images in (the stack gathers re-read them from L2) + `filt` out; aggregation: `filt`
+                # in + num / den in and out -- at the rate a streaming kernel reaches, next to the class's time alone on the GPU
+                pk_, S_ = (wl["p1"], 1) if kind == "ht" else (wl["p2"], 2)
+                nHW_, k_ = pk_[1] + pk_[2], pk_[3]
+                plane_b = 4.0 * 9 * 3 * (W + 2 * nHW_) * (H + 2 * nHW_)
+                n_pass = max(1, int(a.get("passes", 0)))
+                filt_b = a.get("stack_patches", 0.0) / n_pass * 9 * 3 * k_ * k_ * 4.0
+                design = {"group": S_ * plane_b + filt_b, "aggregate": filt_b + 4 * plane_b}
+                d["filt_bytes"] = filt_b
+                d["gather_bytes_from_l2"] = S_ * filt_b
+                d["design_bytes"] = design["group"] + design["aggregate"]
+                d["floor_ms"] = d["design_bytes"] / HBM_ACHIEVABLE_GBS / 1e6
+                d["x_over_floor"] = ms / d["floor_ms"] if d["floor_ms"] > 0 else None
+                d["floor_by_class"] = {cn: {"design_bytes": design[cn], "floor_ms": design[cn] / HBM_ACHIEVABLE_GBS / 1e6,
+                                            "ms": d["ms_" + cn], "x_over_floor": (d["ms_" + cn] / (design[cn] / HBM_ACHIEVABLE_GBS / 1e6)) if design[cn] > 0 else None}
+                                       for cn in ("group", "aggregate")}
+                # what binds: per kernel class of this pass, the share of VALU issue slots it uses next to the share of the HBM peak it
+                # moves (PMC bytes of the class / its time); neither near 1 = latency- / occupancy-bound
+                n_p = max(1, int(a.get("passes", 0)))
+                cls = {"block_matching": ((f"scan/{kind}", "select", "argmin"), a.get("ms_bm", 0.0) / n_p),
+                       "group": ((f"group/{kind}",), d["ms_group"]), "aggregate": ((f"aggregate/{kind}",), d["ms_aggregate"])}
+                bound = {}
+                for cname, (classes, cms) in cls.items():
+                    e = {"ms": cms}
+                    v = valu_frac(classes, cms)
+                    if v:
+                        e.update(v)
+                    if traffic and cms > 0:
+                        tk = traffic.get("kernels", {})
+                        by_c = 0.0
+                        for c in classes:
+                            kk = tk.get(c) or tk.get(c.split("/")[0] + "/both")
+                            if kk:
+                                by_c += kk["fetch_bytes_per_launch_x2"] + kk["write_bytes_per_launch"]   # FETCH_SIZE halves every shape (profiles/r06_b_fetch_calib.txt)
+                        if by_c:
+                            e["hbm_bytes"] = by_c
+                            e["hbm_frac"] = by_c / (cms * 1e-3) / 1e9 / HBM_PEAK_GBS
+                    if "valu_frac" in e or "hbm_frac" in e:
+                        vf, hf = e.get("valu_frac", 0.0), e.get("hbm_frac", 0.0)
+                        e["closest_bound"] = ("valu issue" if vf >= hf else "hbm") + f" at {max(vf, hf):.2f} -- " + (
+                            "bound by it" if max(vf, hf) > 0.7 else "latency / occupancy: neither the VALUs nor HBM are saturated")
+                    bound[cname] = e
+                d["bound_by_class"] = bound
+                return d
+            ph, pw = pair("ht"), pair("wiener")
+            n_all = ph["launches"] + pw["launches"]
+            alg_bytes = (ph["algorithmic_bytes_per_launch"] * ph["launches"] + pw["algorithmic_bytes_per_launch"] * pw["launches"]) / n_all
+            pair_ms = (ph["avg_launch_ms"] * ph["launches"] + pw["avg_launch_ms"] * pw["launches"]) / n_all
+            achieved = alg_bytes / (pair_ms * 1e-3) / 1e9 if pair_ms > 0 else 0.0
+            t_bytes = traffic.get("hbm_bytes_per_launch") if traffic else None
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": "k_group* + k_aggregate (5-D transform + shrinkage + aggregation)",
+                             "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS,
+                             "traffic": t_bytes,
+                             "frac_physical": (t_bytes / (pair_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if (t_bytes and pair_ms > 0) else None,
+                             "traffic_source": (traffic or {}).get("source"),
+                             "compulsory_bytes": (comp["ht"] * ph["launches"] + comp["wiener"] * pw["launches"]) / n_all,
+                             "valu_source": (valu or {}).get("source"),
+                             "valu_frac": (lambda v: v["valu_frac"] if v else None)(valu_frac(("group/ht", "aggregate/ht", "group/wiener", "aggregate/wiener"), 2 * pair_ms)),
+                             "valu_note": "VALU wave-instructions (rocprofv3 --pmc SQ_INSTS_VALU of this command, profiles/valu_latest.json) x 2 cycles / "
+                                          "(1024 SIMDs x 2.4 GHz x live kernel time); per kernel class under per_step.*.bound_by_class",
+                             "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": pair_ms, "launches": n_all,
+                             # the contract's `frac` per step, and the distance to this design's own floor (what to read instead of a saturated frac)
+                             "frac_ht": ph["frac"], "frac_wiener": pw["frac"],
+                             "design_bytes": (ph["design_bytes"] * ph["launches"] + pw["design_bytes"] * pw["launches"]) / n_all,
+                             "floor_ms": (ph["floor_ms"] * ph["launches"] + pw["floor_ms"] * pw["launches"]) / n_all,
+                             "x_over_floor": pair_ms / ((ph["floor_ms"] * ph["launches"] + pw["floor_ms"] * pw["launches"]) / n_all) if (ph["floor_ms"] + pw["floor_ms"]) > 0 else None,
+                             "x_over_floor_by_class": {"ht": {cn: v["x_over_floor"] for cn, v in ph["floor_by_class"].items()},
+                                                       "wiener": {cn: v["x_over_floor"] for cn, v in pw["floor_by_class"].items()}},
+                             "floor_note": "design_bytes = window images read once + filt written once (group), filt read once + num/den read and written "
+                                           "once (aggregation); floor_ms = design_bytes / 6.3 TB/s (the rate a streaming kernel reaches on MI355X); the stack "
+                                           "gathers (gather_bytes_from_l2 under per_step) are served by L2 and are not in the floor",
+                             "measured_with": ((f"the timed region ({lanes_timed} lane{'s' if lanes_timed != 1 else ''}"
+                                                + ("; kernels of different windows overlap, the intervals are not kernel-alone times)" if lanes_timed != 1 else ")"))
+                                               if roof is timed else
+                                               f"{roof_steps} extra untimed step with LFBM5D_LANES=1, the two calls one after the other (kernels alone on the GPU); the timed region ran {lanes_timed} lanes" + (", fused job" if fused else "")),
+                             "per_step": {"ht": ph, "wiener": pw}},
+                # kernel classes alone on the GPU (the one-lane measurement step); with several lanes the HIP-event intervals of
+                # different windows overlap and add up to more than the step, so those are reported under their own key
+                "kernel_ms_per_step": {"block_matching": (roof["ht"].get("ms_bm", 0.0) + roof["wiener"].get("ms_bm", 0.0)) / roof_steps,
+                                       "group": (roof["ht"].get("ms_group", 0.0) + roof["wiener"].get("ms_group", 0.0)) / roof_steps,
+                                       "aggregate": (roof["ht"].get("ms_aggregate", 0.0) + roof["wiener"].get("ms_aggregate", 0.0)) / roof_steps,
+                                       "comm": (roof["ht"].get("ms_comm", 0.0) + roof["wiener"].get("ms_comm", 0.0)) / roof_steps,
+                                       "measured_with": (f"the timed region ({lanes_timed} lanes: overlapped intervals)" if (roof is timed and lanes_timed != 1)
+                                                         else "the timed region (one lane)" if roof is timed else "the one-lane measurement step (kernels alone on the GPU)")},
+                "psnr": {"noisy": psnr_lf(noisy0), "basic": psnr_lf(basic), "denoised": psnr_lf(den)},
+            })
+            if not args.no_seam and world == 1:
+                # the job through the reference's own seam (host memory in and out), outside the timed region
+                try:
+                    seam = {"note": "pageable host memory, SAIs streamed through the window graph (upload at first use, outputs behind the last "
+                                    "window on a SAI); value above = device-resident buffers; outputs compared with the timed region's"}
+                    n_src = noisy_h if noisy_h is not None else noisy0.cpu().numpy()
+                    den_ref = den.cpu().numpy()
+                    hb, hd = np.zeros_like(n_src), np.zeros_like(n_src)
+                    best = None
+                    for _ in range(2):
+                        hn = n_src.copy()
+                        t1 = time.perf_counter()
+                        ctx.denoise(P1, P2, hn, mask, hb, hd, L.ROWMAJOR, aw, ah, 1, 1, W, H, 3)
+                        dt = time.perf_counter() - t1
+                        best = dt if best is None else min(best, dt)
+                    seam["host_flat"] = {"entry": "lfbm5d_denoise_host", "ms_per_step": best * 1e3, "value": total_mp / best,
+                                         "vs_device": best * 1e3 / ms_per_step, "identical_to_device": bool(np.array_equal(hd, den_ref))}
+                    del hb, hd, hn
+                    for key, one_job in (("dropin_vectors", False), ("dropin_vectors_one_job", True)):
+                        msv, _, _, dd = core.dropin_probe(n_src, mask, aw, ah, W, H, 3, sigma, 2.7, wl["p1"], wl["p2"], one_job=one_job, reps=2)
+                        tt = float(msv[1].sum()) * 1e-3
+                        seam[key] = {"entry": ("run_bm5d (both steps as one job)" if one_job else
+                                               "run_bm5d_1st_step + run_bm5d_2nd_step (src/bm5d.h:11-62; the interval of main.cpp:189-201 + :241-247)"),
+                                     "ms_per_step": tt * 1e3, "ms_calls": [float(msv[1, 0]), float(msv[1, 1])], "value": total_mp / tt,
+                                     "vs_device": tt * 1e3 / ms_per_step, "identical_to_device": bool(np.array_equal(dd, den_ref))}
+                        del dd
+                    out["seam"] = seam
                 except Exception as e:  # noqa: BLE001
-                    out["cpu_baseline"].pop("_results", None); out["cpu_baseline"].pop("_sampled", None)
-                    out["cpu_baseline"]["psnr_delta_db"] = {"basic": None, "denoised": None, "note": f"failed: {e}"}
-                if args.parity_check:
-                    cc = (ah // 2) * aw + aw // 2
-                    idx = [cc + ds * aw + dt for ds in (-1, 0, 1) for dt in (-1, 0, 1)]
-                    out["cpu_baseline"]["parity_vs_gpu"] = parity_vs_gpu(wl, n_h[idx], basic[idx].cpu().numpy(), ctx)
-            except Exception as e:  # the baseline is a reported aside, never a reason to lose the bench line
-                out["cpu_baseline"] = {"value": None, "unit": "SAI-megapixels/s", "cores": 0, "kind": "port",
-                                       "sample": f"failed: {e}"}
+                    out["seam"] = {"error": str(e)}
+            if not args.no_cpu_baseline and world == 1:   # the CPU baseline is timed on rank 0 of the 1-GPU run only
+                try:
+                    n_h = noisy_h if noisy_h is not None else noisy0.cpu().numpy()
+                    basic_full = basic.clone()
+                    out["cpu_baseline"] = cpu_baseline(wl, n_h, basic_full.cpu().numpy(), int(round(tot["windows"] / args.steps / 2)), total_mp)
+
+                    def run_gpu(key, n0, b_full):
+                        n_in = n0.clone()
+                        if key == "basic":
+                            est = torch.zeros_like(n0)
+                            ctx.step1(P1, n_in, mask, est, L.ROWMAJOR, aw, ah, 1, W, H, 3)
+                        else:
+                            b_in, est = b_full.clone(), torch.zeros_like(n0)
+                            ctx.step2(P2, n_in, mask, b_in, est, L.ROWMAJOR, aw, ah, 1, W, H, 3)
+                        torch.cuda.synchronize()
+                        return (n_in if key == "basic" else b_in), est
+                    try:
+                        out["cpu_baseline"]["psnr_delta_db"] = psnr_delta_vs_cpu(out["cpu_baseline"], clean, noisy0, basic_full, run_gpu)
+                    except Exception as e:  # noqa: BLE001
+                        out["cpu_baseline"].pop("_results", None); out["cpu_baseline"].pop("_sampled", None)
+                        out["cpu_baseline"]["psnr_delta_db"] = {"basic": None, "denoised": None, "note": f"failed: {e}"}
+                    if args.parity_check:
+                        cc = (ah // 2) * aw + aw // 2
+                        idx = [cc + ds * aw + dt for ds in (-1, 0, 1) for dt in (-1, 0, 1)]
+                        out["cpu_baseline"]["parity_vs_gpu"] = parity_vs_gpu(wl, n_h[idx], basic[idx].cpu().numpy(), ctx)
+                except Exception as e:  # the baseline is a reported aside, never a reason to lose the bench line
+                    out["cpu_baseline"] = {"value": None, "unit": "SAI-megapixels/s", "cores": 0, "kind": "port",
+                                           "sample": f"failed: {e}"}
         print(json.dumps(out))
     if dist:
         dist.barrier()

@@ -1,6 +1,9 @@
-"""CPU tests of the oracle's leaf routines: against the compiled reference (oracle/_ref, built from
-lib_transforms.cpp and mt19937ar.c), against scipy's DCT (the published REDFT10/REDFT01
-definitions) and against structural properties the reference relies on."""
+"""CPU tests of the oracle's leaf routines: against the compiled reference (outputs of lib_transforms.cpp and
+mt19937ar.c, compiled unmodified, on fixed inputs: tests/golden/ref_leaf_vectors.npz, written by
+tools/make_golden_leaf.py), against scipy's DCT (the published REDFT10/REDFT01 definitions) and against
+structural properties the reference relies on."""
+import os
+
 import numpy as np
 import pytest
 import scipy.fft
@@ -9,54 +12,48 @@ from oracle import oracle as O
 
 L = O.lib()
 rng = np.random.default_rng(7)
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 @pytest.fixture(scope="module")
 def R():
-    """The compiled reference leaf routines (oracle/_ref), loaded only when one of the tests that pin against it runs:
-    a `-m gpu` run deselects them and never maps compiled reference code."""
-    r = O.ref_lib()
-    if r is None:
-        pytest.skip("compiled reference leaf library not available")
-    return r
+    """The compiled reference leaf routines' outputs on fixed inputs (tests/golden/ref_leaf_vectors.npz)."""
+    with np.load(os.path.join(GOLDEN, "ref_leaf_vectors.npz")) as z:
+        return dict(z)
 
 
 @pytest.mark.parametrize("n", [1, 2, 4, 8, 16, 32])
 def test_haar_hadamard_bit_exact_vs_reference(R, n):
-    for _ in range(20):
-        v = (rng.normal(size=n) * 100).astype(np.float32)
-        for mine, ref in ((L.orc_haar_forward, R.ref_haar_forward), (L.orc_haar_inverse, R.ref_haar_inverse),
-                          (L.orc_hadamard, R.ref_hadamard)):
-            a, b = v.copy(), v.copy()
+    vs = R[f"haar_in_{n}"]
+    assert vs.shape == (20, n)
+    for i, v in enumerate(vs):
+        for mine, key in ((L.orc_haar_forward, "haar_fwd"), (L.orc_haar_inverse, "haar_inv"), (L.orc_hadamard, "hadamard")):
+            a = v.copy()
             mine(a, n)
-            ref(b, n)
-            assert np.array_equal(a, b)
+            assert np.array_equal(a, R[f"{key}_{n}"][i])
 
 
 @pytest.mark.parametrize("n", [2, 4, 8, 16])
 def test_bior_bit_exact_vs_reference(R, n):
-    for _ in range(5):
-        img = (rng.normal(size=(n + 3, n + 5)) * 60 + 128).astype(np.float32)
+    imgs = R[f"bior_in_{n}"]
+    assert imgs.shape == (5, n + 3, n + 5)
+    for i, img in enumerate(imgs):
         stride = img.shape[1]
         a = np.zeros(n * n, np.float32)
-        b = np.zeros(n * n, np.float32)
-        L.orc_bior_forward(img.reshape(-1), stride, a, n)
-        R.ref_bior_forward(img.reshape(-1), stride, img.size, b, n)
-        assert np.array_equal(a, b)
+        L.orc_bior_forward(np.ascontiguousarray(img).reshape(-1), stride, a, n)
+        assert np.array_equal(a, R[f"bior_fwd_{n}"][i])
         L.orc_bior_inverse(a, n)
-        R.ref_bior_inverse(b, n)
-        assert np.array_equal(a, b)
+        assert np.array_equal(a, R[f"bior_inv_{n}"][i])
         if n <= 4:   # the reference's pair reconstructs exactly only up to 4x4 (measured: not for 8/16)
             np.testing.assert_allclose(a.reshape(n, n), img[:n, :n], atol=2e-3)
 
 
 def test_mt19937_res53_bit_exact_vs_reference(R):
-    for seed in (1, 5489, 123456789):
-        L.orc_mt_seed(seed)
-        R.ref_mt_seed(seed)
-        a = [L.orc_mt_res53() for _ in range(2000)]
-        b = [R.ref_mt_res53() for _ in range(2000)]
-        assert a == b
+    assert list(R["mt_seeds"]) == [1, 5489, 123456789] and R["mt_res53"].shape == (3, 2000)
+    for seed, b in zip(R["mt_seeds"], R["mt_res53"]):
+        L.orc_mt_seed(int(seed))
+        a = [L.orc_mt_res53() for _ in range(len(b))]
+        assert a == list(b)
 
 
 def test_mt19937_known_answer():

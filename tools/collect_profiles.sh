@@ -9,7 +9,7 @@
 tag=${1:-r04_x}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=gpurun_out/$tag; rm -rf $out; mkdir -p $out
-python3 bench.py --gpus 1 --steps 2 --warmup 1 > $out/bench.log 2>&1; tail -1 $out/bench.log > $out/bench.json
+python3 bench.py --gpus 1 --steps 2 --warmup 1 --full > $out/bench.log 2>&1; tail -1 $out/bench.log > $out/bench.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats1 -o s -- python3 bench.py --gpus 1 --steps 2 --warmup 1 --lanes 1 --no-cpu-baseline --no-seam > $out/bench_prof_lanes1.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats3 -o s -- python3 bench.py --gpus 1 --steps 2 --warmup 1 --no-cpu-baseline --no-seam > $out/bench_prof_default.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch -- python3 bench.py --steps 1 --warmup 0 --lanes 1 --no-cpu-baseline --no-seam > /dev/null 2>&1

@@ -4,7 +4,7 @@ tag=${1:-r04_x}
 cd $GRAFT_REPO_ROOT; out=gpurun_out/$tag; mkdir -p $out
 for wl in lf3x3x256x256_sigma25 lf3x3x256x256_sigma25_dct lf9x9x512x512_sigma25 lf17x17x512x512_sigma25 lf17x17x512x512_sigma10_bior lf15x15x625x434_sigma50_n1; do
   steps=3; case $wl in lf3x3*) steps=50;; lf9x9*) steps=8;; esac
-  python3 bench.py --workload $wl --steps $steps --warmup 2 --no-cpu-baseline > $out/$wl.log 2>&1
+  python3 bench.py --workload $wl --steps $steps --warmup 2 --full --no-cpu-baseline > $out/$wl.log 2>&1
   tail -1 $out/$wl.log > $out/$wl.json
   python3 - $out/$wl.json <<'PY'
 import json, sys
