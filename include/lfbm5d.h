@@ -319,6 +319,39 @@ int lfbm5d_bm3d_lf_host(lfbm5d_ctx* ctx, const lfbm5d_bm3d_params* hard, const l
                         float* h_noisy, const unsigned* h_mask, float* h_basic, float* h_denoised,
                         unsigned asize, unsigned W, unsigned H, unsigned C);
 
+/* ---- blind noise level: the `sigma` every entry point above needs, estimated from the noisy light field itself ----
+ * Not in the reference, whose README asks the caller of `LFSourceDir = none` for "an estimated value of the noise level" without
+ * providing one (its estimate_sigma, utilities.cpp:633, only scales a given sigma per channel of the colour space).  The PCA statistic
+ * of Chen, Zhu & Heng (ICCV 2015) pooled over the SAIs: for every non-empty SAI a and channel c (as stored: no colour transform) the
+ * n_ac = (H-r+1)(W-r+1) overlapping r x r patches at stride 1, as vectors x of d = r*r values in row-major order, give s_ac = sum x,
+ * S_ac = sum x x^T and M_ac = S_ac - s_ac s_ac^T / n_ac; Cov = sum M_ac / sum n_ac over (a, c) for the light field, over a for a
+ * channel, over c for a SAI.  With the eigenvalues of Cov ascending, lambda_1 <= ... <= lambda_d, the statistic takes the first
+ * m = d, d-1, ..., 1 at which as many of lambda_1..m lie above their mean mu_m as below it, and returns sqrt(max(mu_m, 0)) and m
+ * (the size of the noise subspace found).  Units: grey levels of the channels as stored, i.e. lfbm5d_params.sigma.
+ * The statistic assumes additive white Gaussian noise: signal-dependent (Poisson-Gaussian) or spatially correlated noise (e.g.
+ * demosaicked raw data) is outside it, and values clipped to 0..255 (8-bit files) bias it low at large sigma.
+ * The patch sums run on the GPU in double, every sum in a fixed order: repeated calls, and the device and host forms, return the
+ * same bits; only the pooled d x d matrices leave the device; the eigenvalues are found on the host (double).  One GPU. */
+typedef struct {
+    double   sigma;             /* all non-empty SAIs and channels pooled: the value to pass as lfbm5d_params.sigma */
+    double   sigma_channel[3];  /* per stored channel, all SAIs pooled (grey: [0] only, rest 0)                      */
+    unsigned components;        /* m of the light-field estimate                                                    */
+    unsigned patch;             /* r used                                                                           */
+    unsigned long long patches; /* sum of n_ac                                                                      */
+} lfbm5d_noise_level;
+/* d_lf [asize][C*H*W] in HBM, read only; h_mask [asize] (0 = empty SAI); C = 1 or 3; patch r = 4..8 (0 = 8); W, H >= 2 r.
+ * h_sigma_sai [asize] or NULL: the estimate of every SAI on its own (0 for empty SAIs); h_eigen [r*r] or NULL: the eigenvalues of the
+ * light field's covariance, ascending.  Returns 1 with a message on a rejected input (C, patch, W / H, a mask without a non-empty
+ * SAI, a NULL buffer that is required). */
+int lfbm5d_noise_level_device(lfbm5d_ctx* ctx, const float* d_lf, const unsigned* h_mask, unsigned asize, unsigned W, unsigned H,
+                              unsigned C, unsigned patch, lfbm5d_noise_level* out, double* h_sigma_sai, double* h_eigen);
+/* The same on host light fields, one pointer per SAI (NULL allowed for empty SAIs), staged through HBM: bit-identical results. */
+int lfbm5d_noise_level_host_sai(lfbm5d_ctx* ctx, const float* const* h_lf, const unsigned* h_mask, unsigned asize, unsigned W,
+                                unsigned H, unsigned C, unsigned patch, lfbm5d_noise_level* out, double* h_sigma_sai, double* h_eigen);
+/* Host only, needs no GPU: the statistic above on one covariance, cov row-major d x d symmetric, 1 <= d <= 64; h_eigen [d] or NULL
+ * receives the eigenvalues ascending.  Returns 1 on bad arguments (no message: there is no context). */
+int lfbm5d_noise_level_statistic(unsigned d, const double* cov, double* sigma, unsigned* components, double* h_eigen);
+
 /* ---- inspection of the last pass's block matching (parity tests) ----
  * n_refs reference patches in raster order; h_refs[n_refs] flat index i*Wb+j;
  * h_self_idx[n_refs*N], h_self_cnt[n_refs] (precompute_BM, core:3301);

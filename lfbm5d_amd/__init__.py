@@ -8,9 +8,10 @@ anywhere, creating a context without a GPU raises.
 """
 from .core import (Context, Params, Bm3dParams, Stats, run_bm5d_1st_step, run_bm5d_2nd_step, run_bm3d_LF, shard_rows,
                    YUV, YCBCR, OPP, RGB, ID, DCT, SADCT, BIOR, HADAMARD, HAAR, ROWMAJOR, COLMAJOR,
-                   TAU, COLOR_SPACE, LfBm5dError, library_path, build_library)
+                   TAU, COLOR_SPACE, LfBm5dError, library_path, build_library, NoiseLevel, noise_level,
+                   noise_level_statistic)
 
 __all__ = ["Context", "Params", "Bm3dParams", "Stats", "run_bm5d_1st_step", "run_bm5d_2nd_step", "run_bm3d_LF", "shard_rows",
            "YUV", "YCBCR", "OPP", "RGB", "ID", "DCT", "SADCT", "BIOR", "HADAMARD", "HAAR",
            "ROWMAJOR", "COLMAJOR", "TAU", "COLOR_SPACE", "LfBm5dError", "library_path",
-           "build_library"]
+           "build_library", "NoiseLevel", "noise_level", "noise_level_statistic"]

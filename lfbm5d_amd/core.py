@@ -7,6 +7,8 @@ import ctypes as C
 import os
 import subprocess
 
+from typing import NamedTuple, Optional
+
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -47,6 +49,24 @@ class Stats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class NoiseLevelStruct(C.Structure):
+    """lfbm5d_noise_level: the blind noise-level estimate (include/lfbm5d.h)."""
+    _fields_ = [("sigma", C.c_double), ("sigma_channel", C.c_double * 3), ("components", C.c_uint), ("patch", C.c_uint),
+                ("patches", C.c_ulonglong)]
+
+
+class NoiseLevel(NamedTuple):
+    """Result of Context.noise_level / noise_level: sigma of the whole light field (what to pass as `sigma`), per stored channel
+    (grey: [0] only), the size m of the noise subspace, the patches pooled, the eigenvalues of the pooled covariance (ascending)
+    and, when asked for, every SAI's own estimate (0 for empty SAIs)."""
+    sigma: float
+    sigma_channel: tuple
+    components: int
+    patches: int
+    eigen: np.ndarray
+    sigma_sai: Optional[np.ndarray]
 
 
 def library_path():
@@ -134,6 +154,11 @@ def lib():
     L.lfbm5d_last_scores.restype = C.c_size_t
     L.lfbm5d_last_scan_version.argtypes = [vp]
     L.lfbm5d_last_scan_version.restype = C.c_int
+    if hasattr(L, "lfbm5d_noise_level_device"):   # (absent from older builds loaded through LFBM5D_HIP_LIB for A/B runs)
+        dp, np_ = C.POINTER(C.c_double), C.POINTER(NoiseLevelStruct)
+        L.lfbm5d_noise_level_device.argtypes = [vp, fp, up] + [C.c_uint] * 5 + [np_, dp, dp]
+        L.lfbm5d_noise_level_host_sai.argtypes = [vp, fp, up] + [C.c_uint] * 5 + [np_, dp, dp]
+        L.lfbm5d_noise_level_statistic.argtypes = [C.c_uint, dp, dp, up, dp]
     L.lfbm5d_malloc.argtypes = [C.POINTER(vp), C.c_size_t]
     L.lfbm5d_free.argtypes = [vp]
     L.lfbm5d_memcpy_h2d.argtypes = [vp, vp, C.c_size_t]
@@ -210,6 +235,18 @@ def auto_bands(awidth, aheight, height, halo, world):
     ranks it can keep busy (a power of two within 0.8 ceil(a / 3)), bands take the rest, as long as a band stays twice as tall as its
     halo.  1 = the graph alone (bit-identical to one GPU)."""
     return int(lib().lfbm5d_auto_bands(int(awidth), int(aheight), int(height), int(halo), int(world)))
+
+
+def noise_level_statistic(cov):
+    """lfbm5d_noise_level_statistic (host only, no GPU): (sigma, components, eigenvalues ascending) of one symmetric d x d
+    covariance, d <= 64."""
+    cov = np.ascontiguousarray(cov, np.float64)
+    d = cov.shape[0]
+    sig, m, lam = C.c_double(), C.c_uint(), np.zeros(d, np.float64)
+    dp = C.POINTER(C.c_double)
+    if lib().lfbm5d_noise_level_statistic(d, cov.ctypes.data_as(dp), C.byref(sig), C.byref(m), lam.ctypes.data_as(dp)) != 0:
+        raise LfBm5dError("lfbm5d_noise_level_statistic: bad arguments (d must be 1..64)")
+    return sig.value, m.value, lam
 
 
 def shard_rows(n_rows, rank, world):
@@ -436,6 +473,30 @@ class Context:
             self._ck(self._L.lfbm5d_bm3d_lf_device(self._h, C.byref(hard), C.byref(wien), _dev_ptr(noisy), mp, _dev_ptr(basic),
                                                    _dev_ptr(denoised), m.size, W, H, Cc))
 
+    # ---- blind noise level ----
+    def noise_level(self, LF, LF_SAI_mask, width, height, chnls, patch=8, per_sai=False):
+        """Estimate the standard deviation of additive white Gaussian noise (lfbm5d_noise_level_*, include/lfbm5d.h) in the units
+        of `sigma`.  LF: a CUDA float32 tensor [asize][C*H*W] (device form, read only), a float32 numpy array of that shape or a
+        list of per-SAI float32 arrays (host form, staged through HBM; bit-identical).  Returns a NoiseLevel."""
+        m = _u32(LF_SAI_mask)
+        asize, C_ = m.size, int(chnls)
+        res = NoiseLevelStruct()
+        d = int(patch) * int(patch) if 4 <= int(patch) <= 8 else 64
+        eig = np.zeros(d, np.float64)
+        sai = np.zeros(max(asize, 1), np.float64) if per_sai else None
+        dp = C.POINTER(C.c_double)
+        tail = (m.ctypes.data_as(C.POINTER(C.c_uint)), asize, int(width), int(height), C_, int(patch), C.byref(res),
+                sai.ctypes.data_as(dp) if per_sai else None, eig.ctypes.data_as(dp))
+        if isinstance(LF, (list, tuple)) or isinstance(LF, np.ndarray):
+            arrays = list(LF) if isinstance(LF, (list, tuple)) else [np.ascontiguousarray(a) for a in LF]
+            if isinstance(LF, np.ndarray) and LF.dtype != np.float32:
+                raise LfBm5dError("host light fields must be float32")
+            self._ck(self._L.lfbm5d_noise_level_host_sai(self._h, _sai_ptrs(arrays, m), *tail))
+        else:
+            self._ck(self._L.lfbm5d_noise_level_device(self._h, _dev_ptr(LF), *tail))
+        return NoiseLevel(res.sigma, tuple(res.sigma_channel[:C_]), int(res.components), int(res.patches), eig[:int(res.patch) ** 2],
+                          sai[:asize] if per_sai else None)
+
     def last_windows(self):
         """Processed SAI of every window the last step call ran, in order."""
         n = self._L.lfbm5d_last_windows(self._h, None, 0)
@@ -526,6 +587,11 @@ def run_bm3d_LF(sigma, LF_noisy, LF_SAI_mask, LF_basic, LF_denoised, width, heig
     wien = make_bm3d_params(sigma, lambdaHard3D, NWien, nWien, kWien, pWien, tau_2D_wien, useSD_w, color_space)
     (ctx or _ctx()).bm3d_lf(hard, wien, LF_noisy, LF_SAI_mask, LF_basic, LF_denoised, width, height, chnls)
     return 0
+
+
+def noise_level(LF, LF_SAI_mask, width, height, chnls, patch=8, per_sai=False, ctx=None):
+    """Context.noise_level on the default context (device 0): the blind estimate of the light field's noise sigma."""
+    return (ctx or _ctx()).noise_level(LF, LF_SAI_mask, width, height, chnls, patch, per_sai)
 
 
 _TAU = {"id": 4, "dct": 5, "sadct": 6, "bior": 7, "hw": 8, "hadamard": 8, "haar": 9}

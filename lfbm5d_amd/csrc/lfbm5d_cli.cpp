@@ -13,7 +13,10 @@
  *   LFBM5D_SEED=<n>   seed MT19937 once with n and draw the noise SAI by SAI in st order
  *                     (reproducible); unset = time + pid seeding like the reference;
  *   LFBM5D_DEVICE=<i> HIP device index;
- *   LFBM5D_TILED=1    honour nbThreads > 1 the reference's way (tiles with a discarded halo, bm5d.cpp:411-708).
+ *   LFBM5D_TILED=1    honour nbThreads > 1 the reference's way (tiles with a discarded halo, bm5d.cpp:411-708);
+ *   LFBM5D_SIGMA=auto estimate sigma from the noisy light field (noise_level_LF, run_bm5d.h) once it exists -- loaded with
+ *                     LFSourceDir = none, or made with the argument's sigma from a ground truth -- and use the estimate for both
+ *                     steps and the diff images; any other value is an error.
  * Without LFBM5D_TILED nbThreads is parsed and ignored: the GPU path has the reference's untiled
  * (nb_threads == 1) semantics, half a dB better than its tiled mode.
  *
@@ -226,6 +229,24 @@ void add_noise_LF(const vector<vector<float> >& LF, const vector<unsigned>& mask
     }
 }
 
+/* LFBM5D_SIGMA: unset -> 0 (the argument's sigma), "auto" -> 1 (estimate it), anything else -> -1 (error, message printed) */
+int sigma_mode() {
+    const char* e = getenv("LFBM5D_SIGMA");
+    if (!e) return 0;
+    if (!strcmp(e, "auto")) return 1;
+    cout << "LFBM5D_SIGMA must be \"auto\" (estimate sigma from the noisy light field) or unset; got \"" << e << "\"" << endl;
+    return -1;
+}
+
+/* LFBM5D_SIGMA=auto: replace `sigma` with the estimate on the noisy light field */
+bool estimate_sigma_LF(const vector<vector<float> >& LF_noisy, const vector<unsigned>& mask, unsigned W, unsigned H, unsigned C, float& sigma) {
+    float est = 0.0f;
+    if (noise_level_LF(LF_noisy, mask, W, H, C, est) != EXIT_SUCCESS) return false;
+    cout << endl << "Estimated noise level: sigma = " << setprecision(8) << est << setprecision(6) << " (argument: " << sigma << ")" << endl;
+    sigma = est;
+    return true;
+}
+
 [[maybe_unused]] int tau(const char* s, int which) {
     if (!strcmp(s, "id")) return LFBM5D_ID;
     if (!strcmp(s, "dct")) return LFBM5D_DCT;
@@ -266,7 +287,8 @@ int main(int argc, char** argv) {
     a += 2;   /* aswSizeHard, aswSizeWien: parsed by the reference, unused by BM3D */
     const char* maj = argv[a++];
     const unsigned ang_major = !strcmp(maj, "row") ? LFBM5D_ROWMAJOR : !strcmp(maj, "col") ? LFBM5D_COLMAJOR : 0;
-    const float sigma = (float)atof(argv[a++]), lambda = (float)atof(argv[a++]);
+    float sigma = (float)atof(argv[a++]);
+    const float lambda = (float)atof(argv[a++]);
     const char* d_noisy = argv[a++]; const char* d_basic = argv[a++]; const char* d_den = argv[a++]; const char* d_diff = argv[a++];
     unsigned N[2], n[2], k[2], p[2], sd[2]; int t2[2];
     for (int i = 0; i < 2; i++) {
@@ -281,6 +303,8 @@ int main(int argc, char** argv) {
     const unsigned nb_threads = atoi(argv[a++]);
     const char* results = argv[a++];
     if (!ang_major || cs < 0) { cout << "Problem while reading parameters from command line !" << endl; return EXIT_FAILURE; }
+    const int smode = sigma_mode();
+    if (smode < 0) return EXIT_FAILURE;
 
     vector<vector<float> > LF, LF_noisy, LF_basic, LF_den, LF_diff;
     vector<unsigned> mask;
@@ -299,6 +323,7 @@ int main(int argc, char** argv) {
     } else {
         if (load_LF(d_noisy, name, sep, LF_noisy, mask, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
     }
+    if (smode == 1 && !estimate_sigma_LF(LF_noisy, mask, W, H, C, sigma)) return EXIT_FAILURE;
     LF_basic.assign(awh, vector<float>((size_t)W * H * C, 0.0f));
     LF_den = LF_basic; LF_diff = LF_basic;
     vector<float> ps, rm; float ap_n = 0, sp = 0, ar = 0, sr = 0, ap_b = 0;
@@ -361,7 +386,8 @@ int main(int argc, char** argv) {
     const unsigned anH = atoi(argv[a++]), anW = atoi(argv[a++]);
     const char* maj = argv[a++];
     const unsigned ang_major = !strcmp(maj, "row") ? LFBM5D_ROWMAJOR : !strcmp(maj, "col") ? LFBM5D_COLMAJOR : 0;
-    const float sigma = (float)atof(argv[a++]), lambda = (float)atof(argv[a++]);
+    float sigma = (float)atof(argv[a++]);
+    const float lambda = (float)atof(argv[a++]);
     const char* d_noisy = argv[a++]; const char* d_basic = argv[a++]; const char* d_den = argv[a++]; const char* d_diff = argv[a++];
     unsigned N[2], nSim[2], nDisp[2], k[2], p[2], sd[2]; int t2[2], t4[2], t5[2];
     for (int i = 0; i < 2; i++) {
@@ -374,6 +400,8 @@ int main(int argc, char** argv) {
     const unsigned nb_threads = atoi(argv[a++]);
     const char* results = argv[a++];
     if (!ang_major || cs < 0) { cout << "Problem while reading parameters from command line !" << endl; usage(argv[0]); return EXIT_FAILURE; }
+    const int smode = sigma_mode();
+    if (smode < 0) return EXIT_FAILURE;
 
     vector<vector<float> > LF, LF_noisy, LF_basic, LF_den, LF_diff;
     vector<unsigned> mask;
@@ -392,6 +420,7 @@ int main(int argc, char** argv) {
     } else {
         if (load_LF(d_noisy, name, sep, LF_noisy, mask, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
     }
+    if (smode == 1 && !estimate_sigma_LF(LF_noisy, mask, W, H, C, sigma)) return EXIT_FAILURE;
     LF_basic.assign(awh, vector<float>((size_t)W * H * C, 0.0f));
     LF_den = LF_basic; LF_diff = LF_basic;
     vector<float> ps, rm; float ap_n = 0, sp = 0, ar = 0, sr = 0, ap_b = 0;

@@ -138,6 +138,8 @@ struct lfbm5d_ctx {
     Options opt_store; Options* opt = &opt_store;
     hipStream_t io_in = nullptr, io_out = nullptr;
     unsigned* h_small = nullptr; /* pinned, 64 uints */
+    /* noise-level estimate (lfbm5d_noise.hip): non-empty SAI list, bulk partial sums, lag cells, centred scatters, pooled covariances */
+    struct NoiseBufs { DevBuf sai, part, cells, m, pool; } noise;
     /* window lanes (run_step, pipelined form): extra contexts on the same device, each with its own stream, window
      * buffers and per-pass work buffers; owned by this context */
     std::vector<lfbm5d_ctx*> lanes;

@@ -183,6 +183,29 @@ int run_bm5d(const float sigma, const float lambdaHard5D, std::vector<std::vecto
     return EXIT_SUCCESS;
 }
 
+/* blind noise level on the caller's vectors (one pointer per SAI, no flat copy) */
+int noise_level_LF(const std::vector<std::vector<float> >& LF, const std::vector<unsigned>& LF_SAI_mask, unsigned width, unsigned height,
+                   unsigned chnls, float& sigma) {
+    if (LF.size() != LF_SAI_mask.size()) {
+        std::cout << "noise_level_LF: light field and mask must hold the same number of SAIs" << std::endl;
+        return EXIT_FAILURE;
+    }
+    lfbm5d_ctx* ctx = context();
+    if (!ctx) return EXIT_FAILURE;
+    const size_t img = (size_t)width * height * chnls;
+    std::vector<const float*> p(LF.size(), nullptr);
+    for (size_t st = 0; st < LF.size(); st++) if (LF_SAI_mask[st] && LF[st].size() == img) p[st] = LF[st].data();
+    for (size_t st = 0; st < LF.size(); st++)
+        if (LF_SAI_mask[st] && !p[st]) { std::cout << "noise_level_LF: a non-empty SAI does not hold width*height*chnls values" << std::endl; return EXIT_FAILURE; }
+    lfbm5d_noise_level r;
+    if (lfbm5d_noise_level_host_sai(ctx, p.data(), LF_SAI_mask.data(), (unsigned)LF.size(), width, height, chnls, 0, &r, nullptr, nullptr) != 0) {
+        std::cout << "LFBM5D GPU backend: " << lfbm5d_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+    }
+    sigma = (float)r.sigma;
+    return EXIT_SUCCESS;
+}
+
 /* run_bm3d_LF (src/bm3d_LF.h:10-35, bm3d_LF.cpp:75-125): BM3D on every SAI of the mask */
 #include "run_bm3d_lf.h"
 int run_bm3d_LF(const float sigma, std::vector<std::vector<float> >& LF_noisy, std::vector<unsigned>& LF_SAI_mask,

@@ -93,4 +93,18 @@ int run_bm5d(
 ,   const unsigned nb_threads
 );
 
+//! Blind noise level -- not in the reference: the standard deviation of additive white Gaussian noise in LF (the units of `sigma`:
+//! grey levels of the channels as stored), estimated on the GPU from the light field itself (lfbm5d_noise_level_host_sai,
+//! include/lfbm5d.h; 8 x 8 patches pooled over every non-empty SAI and channel).  What to pass as `sigma` to the functions above
+//! when nobody knows it (the reference's LFSourceDir = none).  LF is only read.  Returns EXIT_SUCCESS, or EXIT_FAILURE with the
+//! message on stdout.
+int noise_level_LF(
+    const std::vector<std::vector<float> > &LF
+,   const std::vector<unsigned> &LF_SAI_mask
+,   unsigned width
+,   unsigned height
+,   unsigned chnls
+,   float &sigma
+);
+
 #endif
