@@ -370,6 +370,12 @@ size_t lfbm5d_last_scores(lfbm5d_ctx* ctx, float* h_scores, size_t n_floats);
 /* Aggregation weights of the groups of the last pass, [reference patch][channel] (core:413-421: 1 / (sigma_c^2 * retained
  * coefficients) in the hard-threshold step): same calling convention.  Lets a test compare survivor counts group by group. */
 size_t lfbm5d_last_weights(lfbm5d_ctx* ctx, float* h_w, size_t n_floats);
+/* The group list of the last group launch: the (group, channel) pairs the ordinary kernels of a 3x3 window left to the list
+ * launch behind them.  Each entry is group | channel mask << 29: mask 7 for a group whose angular shape is not the whole window
+ * (every channel; listed by the shape pre-pass), a single channel bit for a (group, channel) in which a wave of the fast
+ * hard-thresholding chain came within the guard band of a threshold.  *n = number of entries (any order); copies min(*n, cap)
+ * of them to out (may be NULL).  Returns 0, or -1 on a bad context or a failed copy.  For the tests of the guard band. */
+int lfbm5d_last_group_list(lfbm5d_ctx* ctx, unsigned* n, unsigned* out, unsigned cap);
 /* Which generation of the table kernel the last pass used, i.e. what lfbm5d_last_tables returns:
  *   3 = ring-sharing workgroups, combined form (the default): the disparity tables never reach memory; the buffer holds
  *       [slot][workgroup of the slot][strip][chunk of 8 steps][lane * 8 + step] pairs of (smallest value of the workgroup's tables,

@@ -150,6 +150,8 @@ def lib():
     L.lfbm5d_last_tables.restype = C.c_size_t
     L.lfbm5d_last_weights.argtypes = [vp, vp, C.c_size_t]
     L.lfbm5d_last_weights.restype = C.c_size_t
+    if hasattr(L, "lfbm5d_last_group_list"):   # (absent from older builds loaded through LFBM5D_HIP_LIB for A/B runs)
+        L.lfbm5d_last_group_list.argtypes = [vp, up, vp, C.c_uint]
     L.lfbm5d_last_scores.argtypes = [vp, vp, C.c_size_t]
     L.lfbm5d_last_scores.restype = C.c_size_t
     L.lfbm5d_last_scan_version.argtypes = [vp]
@@ -304,7 +306,8 @@ OPTION_ENV = ("LFBM5D_LANES", "LFBM5D_EMULATE_WORLD", "LFBM5D_MAX_WINDOWS", "LFB
               "LFBM5D_DATA_DRIVEN_SCHEDULE", "LFBM5D_HOST_BLOCKING", "LFBM5D_BAND_MB", "LFBM5D_BM3D_LANES", "LFBM5D_SCAN_LDS_CAP",
               "LFBM5D_FORCE_REDO", "LFBM5D_SPATIAL_BANDS", "LFBM5D_BAND_HALO", "LFBM5D_SCAN_V1", "LFBM5D_SCAN_ANY", "LFBM5D_SCAN_FULL_TABLES", "LFBM5D_DCT8W_V2",
               "LFBM5D_GROUP_GENERIC", "LFBM5D_NO_SA_KERNELS", "LFBM5D_NO_SLAB_KERNEL", "LFBM5D_WIDE_NOSPLIT", "LFBM5D_AGG_64BIT",
-              "LFBM5D_AGG_SCALAR_SCAN", "LFBM5D_SUBSET_LIST_HOST", "LFBM5D_SUBSET_SCAN_V1", "LFBM5D_FILT_GROUP_MAJOR")
+              "LFBM5D_AGG_SCALAR_SCAN", "LFBM5D_SUBSET_LIST_HOST", "LFBM5D_SUBSET_SCAN_V1", "LFBM5D_FILT_GROUP_MAJOR",
+              "LFBM5D_HT_REF_ORDER")
 
 
 class Context:
@@ -541,6 +544,17 @@ class Context:
         got = self._L.lfbm5d_last_weights(self._h, out.ctypes.data, out.size)
         assert got == out.size
         return out.reshape(n_groups, C_)
+
+    def last_group_list(self):
+        """The list of the last group launch (lfbm5d_last_group_list): uint32 entries group | channel mask << 29, mask 7 for a
+        group of a shape that is not the whole window, one channel bit for a guard-band (group, channel) of the fast chain."""
+        n = C.c_uint(0)
+        if self._L.lfbm5d_last_group_list(self._h, C.byref(n), None, 0) != 0:
+            raise LfBm5dError("lfbm5d_last_group_list failed")
+        out = np.zeros(max(1, n.value), np.uint32)
+        if self._L.lfbm5d_last_group_list(self._h, C.byref(n), out.ctypes.data, out.size) != 0:
+            raise LfBm5dError("lfbm5d_last_group_list failed")
+        return out[:min(n.value, out.size)]
 
     def last_scan_version(self):
         return int(self._L.lfbm5d_last_scan_version(self._h))

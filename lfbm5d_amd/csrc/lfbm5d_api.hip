@@ -621,6 +621,22 @@ size_t lfbm5d_last_weights(lfbm5d_ctx* c, float* h_w, size_t n_floats) {
     return n;
 }
 
+int lfbm5d_last_group_list(lfbm5d_ctx* c, unsigned* n, unsigned* out, unsigned cap) {
+    if (!c || !n) return -1;
+    (void)hipSetDevice(c->device);
+    *n = 0;
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return -1;
+    if (!c->sa_list.p) return 0;
+    const size_t slots = c->sa_list.cap / sizeof(unsigned);
+    unsigned cnt = 0;
+    if (hipMemcpy(&cnt, c->sa_list.p, sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    cnt = (unsigned)std::min((size_t)cnt, slots - 1);
+    *n = cnt;
+    const unsigned m = std::min(cnt, cap);
+    if (out && m && hipMemcpy(out, c->sa_list.as<unsigned>() + 1, m * sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return 0;
+}
+
 size_t lfbm5d_last_scores(lfbm5d_ctx* c, float* h_scores, size_t n_floats) {
     if (!c) return 0;
     (void)hipSetDevice(c->device);

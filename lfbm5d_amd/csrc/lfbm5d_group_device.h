@@ -114,6 +114,7 @@ struct __attribute__((packed, aligned(4))) f4u { float v[4]; };   /* 16-byte loa
  * constant factors into the stage matrices saves a third of the multiplies but moves results by an ulp, enough
  * to flip the odd hard-threshold decision against the reference) */
 __device__ __forceinline__ void dct9_fwd2(v2f* x, TbPtr tb) {
+#pragma clang fp contract(on)   /* multiply-adds fused within an expression only: the same arithmetic in every kernel that inlines it */
     v2f t[9];
 #pragma unroll
     for (int s = 0; s < 3; s++)
@@ -183,6 +184,7 @@ __device__ __forceinline__ void dct9_inv2_fast(v2f* x, TbPtr tb) {
  * C[0..NS/2) (a permutation of the reference order -- the shrinkage treats all coefficients alike); the inverse
  * takes that layout back to P. */
 template <int NS> __device__ __forceinline__ void haar_fwd_pairs(v2f* P) {
+#pragma clang fp contract(on)   /* (S01 + S23) * s is not fused with the products behind S01: the list kernel decides like k_group_id_haar */
     const float s = 0.70710678118654752f;
     if (NS == 8) {
         const v2f S01 = (P[0] + P[1]) * s, D01 = (P[0] - P[1]) * s, S23 = (P[2] + P[3]) * s, D23 = (P[2] - P[3]) * s;

@@ -44,15 +44,23 @@ namespace {
  * -- about 0.4 of the VALU cycles.  Mathematically the same numbers; in floating point a coefficient within round-off of
  * the threshold could decide differently than the reference-order form (tools/flip_count.py, profiles/r06_c_ht_fast_flips.txt:
  * 1, 1, 1 decisions of 864 M per 560 x 560 pass against the CPU oracle, where the reference-order form has 0, 0, 1).  So the
- * chain also watches its distance to the threshold: a wave in which ANY coefficient comes within a guard band of its threshold
- * (2^-16 ... 2^-18 of it, ht_guard) reports it, and its (group, channel) is redone in the reference-order form by the list launch behind the kernel
- * (one to two in a hundred on natural data, whose coefficients are far denser around the threshold than noise alone).  The two forms differ by float round-off of sums of at most 72 pixel values -- below 1e-5 of
- * a threshold for 8-bit-range data, a tenth of the guard band -- so every decision is the reference-order form's decision:
- * the survivor counts, hence the weights and `den`, are bit-identical to rounds 1-5; the filtered values agree to an ulp or two.
- * Returns true when the caller has to fall back.  LFBM5D_HT_REFERENCE_ORDER (build flag): no fast chain at all. */
-/* guard band, relative to the threshold, by angular frequency: emulated over 3 M near-threshold coefficients of 8-bit-range data
+ * chain also watches its distance to the threshold: a wave in which ANY coefficient comes within a guard band Gq of its
+ * threshold reports it, and its (group, channel) is redone in the reference-order form by the list launch behind the kernel.
+ * The two forms differ by float round-off of sums of at most 72 pixel values: an error that scales with the values, not with
+ * the threshold.  So the band has two parts,
+ *   Gq = max(Tq ht_guard(st), kHtGuardAbs[st][l] M)   (as Tq max(ht_guard(st), K[c][st] M), K = GroupArgs::ht3_K from the host)
+ * a relative one (2^-16 ... 2^-18 of the threshold: the rounding of the constants and of Tq) and an absolute floor, M = the
+ * largest |input| of the lane.  A band relative to the threshold alone let decisions escape at small sigma and on data of a
+ * wider range (sigma 0.5 and 16 x 8-bit data: tests/test_gpu_ht_decisions.py).  The floor is 2.3 x the largest form difference
+ * tests/test_ht_guard_model.py measures (sigma 0.5 ... 50, 8-bit data, 16 x and 256 x that range, signed opponent channels,
+ * N = 1 ... 8, thresholds placed on coefficients); the GPU tests hold the two forms to identical decisions over the same range,
+ * tools/flip_count.py --referee on 560 x 560 windows.  So every decision is the reference-order form's decision: the survivor
+ * counts, hence the weights and `den`, are bit-identical to rounds 1-5; the filtered values agree to an ulp or two.
+ * Returns true when the caller has to fall back.  LFBM5D_HT_REFERENCE_ORDER (build flag) or the option ht_reference_order: no
+ * fast chain at all. */
+/* relative part of the guard band, by angular frequency: emulated over 3 M near-threshold coefficients of 8-bit-range data
  * (brightness 0..255, contrast up to +-100, sigma 25) the two forms differ by at most 7.9e-6 of a threshold at st = 0 (sums of
- * 72 bright pixels), 2.3e-6 at st = 3, 6 and 1.2e-6 elsewhere */
+ * 72 bright pixels), 2.3e-6 at st = 3, 6 and 1.2e-6 elsewhere.  tests/test_ht_guard_model.py reads this definition. */
 __device__ __forceinline__ constexpr float ht_guard(int st) { return st == 0 ? 1.0f / 65536.0f : (st == 3 || st == 6) ? 1.0f / 131072.0f : 1.0f / 262144.0f; }
 template <int NS> __device__ __forceinline__ void haar_fwd_pairs_u(v2f* P) {
     if (NS == 8) {
@@ -83,6 +91,11 @@ __device__ __forceinline__ bool group_id_compute_fast(const GroupArgs& a, int c,
     constexpr int NH = NS > 1 ? NS / 2 : 1;
     constexpr int LV = NS == 8 ? 3 : NS == 4 ? 2 : NS == 2 ? 1 : 0;       /* Haar levels; the pair P[h] holds coefficients of level lvl(h) */
     const TbPtr tb = (TbPtr)a.tb;
+    float M = 0.0f;                    /* largest |input| of this lane: the scale of the round-off the guard band's floor covers */
+#pragma unroll
+    for (int h = 0; h < NH; h++)
+#pragma unroll
+        for (int st = 0; st < 9; st++) M = fmaxf(M, fmaxf(fabsf(V[h][st].x), fabsf(V[h][st].y)));
     /* forward 3x3, unnormalised: along u (x[s*3 + u]), then along s */
 #pragma unroll
     for (int h = 0; h < NH; h++) {
@@ -107,10 +120,11 @@ __device__ __forceinline__ bool group_id_compute_fast(const GroupArgs& a, int c,
 #pragma unroll
         for (int h = 0; h < NH; h++) P[h] = V[h][st];
         haar_fwd_pairs_u<NS>(P);
+        const float gs = fmaxf(ht_guard(st), a.ht3_K[c][st] * M);   /* Gq = max(Tq ht_guard, Tq K M), Tq K M >= kHtGuardAbs[st][lvl] M */
 #pragma unroll
         for (int h = 0; h < NH; h++) {
             const int lvl = h == 0 ? LV : (NS == 8 && h == 1) ? 2 : 1;
-            const float Tq = a.ht3_T[c][st][lvl], Gq = Tq * ht_guard(st);
+            const float Tq = a.ht3_T[c][st][lvl], Gq = Tq * gs;
             const float ax = fabsf(P[h].x), ay = fabsf(P[h].y);
             const bool kx = ax > Tq, ky = (NS > 1) && ay > Tq;
             near |= __ballot(fabsf(ax - Tq) < Gq);
@@ -731,8 +745,8 @@ hipError_t launch_group_ht(hipStream_t s, const GroupArgs& a, bool all_sa, bool*
         }
         else {
             if (!a.sa_list) return hipErrorInvalidValue;
-#ifndef LFBM5D_HT_REFERENCE_ORDER
-            const bool fast = a.tau5 == 9 && (a.tau4 == 5 || a.tau4 == 6) && a.C <= 3;
+#ifndef LFBM5D_HT_REFERENCE_ORDER   /* kOptHtReferenceOrder (test hook): the reference-order kernel, as in such a build */
+            const bool fast = a.tau5 == 9 && (a.tau4 == 5 || a.tau4 == 6) && a.C <= 3 && !(a.opt & kOptHtReferenceOrder);
 #else
             const bool fast = false;
 #endif

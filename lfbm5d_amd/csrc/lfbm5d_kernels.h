@@ -97,6 +97,16 @@ struct GroupTables {
     float ht3_gf[9];            /* F[st] cni4[st] coef4inv gamma_v gamma_u: times 1 / nSx, the inverse's input scale */
 };
 
+/* Absolute floor of the fast hard-thresholding chain's guard band (lfbm5d_group_ht.hip, group_id_compute_fast), by angular frequency
+ * st and Haar level l: the two forms of the chain differ by float round-off of sums of up to 72 pixel values, which grows with the
+ * values, not with the threshold.  2.3 x the largest (form difference - half the relative band) / M that tests/test_ht_guard_model.py
+ * measures (M = largest |input| of the lane; golden light field at sigma 0.5 ... 50, 16 x and 256 x its range, signed opponent
+ * channels, thresholds placed on coefficients, with and without multiply-add contraction).  That test reads this table. */
+constexpr float kHtGuardAbs[9][4] = {
+    {1.5e-7f, 8.1e-6f, 1.7e-5f, 3.5e-5f}, {5.6e-7f, 1.4e-6f, 1.9e-6f, 3.5e-6f}, {7.8e-7f, 2.3e-6f, 2.8e-6f, 3.7e-6f},
+    {2.1e-6f, 3.6e-6f, 5.4e-6f, 6.4e-6f}, {4.1e-7f, 1.1e-6f, 1.6e-6f, 2.4e-6f}, {5.3e-7f, 1.8e-6f, 2.3e-6f, 4.0e-6f},
+    {3.8e-6f, 6.6e-6f, 9.4e-6f, 1.4e-5f}, {7.6e-7f, 1.7e-6f, 2.5e-6f, 4.2e-6f}, {1.0e-6f, 3.0e-6f, 3.9e-6f, 6.5e-6f}};
+
 constexpr unsigned kShapeInfoBytes = (5 * kMaxA + 2 * kMaxAw + 1) * 4;          /* per-group SADCT record, windows of up to 7x7 SAIs */
 constexpr unsigned kShapeInfoBigBytes = (5 * kBigA + 2 * kBigAw + 1) * 4;      /* ... larger windows */
 
@@ -134,6 +144,7 @@ struct GroupArgs {
     float sigma[3];
     float ht3_T[3][9][4];       /* group_id_compute_fast: the hard threshold of channel c for the UNNORMALISED Haar coefficients of level l at
                                  * angular frequency st: T_c / (ht3_f[st] 2^(-l/2)), evaluated in double on the host (run_pass) */
+    float ht3_K[3][9];          /* ... and the absolute floor of its guard band: max over l of kHtGuardAbs[st][l] / ht3_T[c][st][l], rounded up */
     float* scratch;             /* generic path, stacks beyond the LDS: HBM slices for k_group_big (or NULL) */
     unsigned long long scratch_floats;   /* size of scratch */
     unsigned opt;               /* kOpt* bits (lfbm5d_options.h): kernel-generation selectors of the context */

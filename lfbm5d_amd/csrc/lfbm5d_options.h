@@ -35,6 +35,7 @@ enum : unsigned {
     kOptSubsetListHost = 1u << 10,  /* subset passes: reference list built on the host */
     kOptSubsetScanV1 = 1u << 11,    /* subset passes: round 2's table kernel through the position map */
     kOptFiltGroupMajor = 1u << 12,  /* wide windows (11 x 11 SAIs and more): filtered patches group-major like the 3 x 3 windows' (rounds 1-5) instead of SAI-major */
+    kOptHtReferenceOrder = 1u << 13,   /* 3x3 hard-thresholding windows: k_group_id_haar (reference-order arithmetic) instead of k_group_id_haar_fast */
 };
 
 struct Options {
@@ -75,6 +76,7 @@ inline const OptionKey* option_keys(size_t* n) {
         {"agg_64bit", "LFBM5D_AGG_64BIT", nullptr, kOptAgg64Bit}, {"agg_scalar_scan", "LFBM5D_AGG_SCALAR_SCAN", nullptr, kOptAggScalarScan},
         {"subset_list_host", "LFBM5D_SUBSET_LIST_HOST", nullptr, kOptSubsetListHost}, {"subset_scan_v1", "LFBM5D_SUBSET_SCAN_V1", nullptr, kOptSubsetScanV1},
         {"filt_group_major", "LFBM5D_FILT_GROUP_MAJOR", nullptr, kOptFiltGroupMajor},
+        {"ht_reference_order", "LFBM5D_HT_REF_ORDER", nullptr, kOptHtReferenceOrder},
     };
     *n = sizeof(keys) / sizeof(keys[0]);
     return keys;

@@ -462,6 +462,11 @@ int pass_impl(lfbm5d_ctx* c, int step, const lfbm5d_params* P, unsigned aw, unsi
             const float T = lambda * sig[ch] * 1.41421356237309505f;   /* the kernels' own float expression (core:2431) */
             for (int st = 0; st < 9; st++)
                 for (int l = 0; l < 4; l++) ga.ht3_T[ch][st][l] = (float)((double)T / ((double)ht.ht3_f[st] * std::pow(2.0, -0.5 * l)));
+            for (int st = 0; st < 9; st++) {   /* floor of the guard band: Tq K M >= kHtGuardAbs[st][l] M at every level l */
+                double K = 0.0;
+                for (int l = 0; l < 4; l++) K = std::max(K, (double)kHtGuardAbs[st][l] / (double)ga.ht3_T[ch][st][l]);
+                ga.ht3_K[ch][st] = std::nextafter((float)std::min(K, 1e30), INFINITY);
+            }
         }
     }
     ga.bm3d = bm3d ? 1u : 0u;
