@@ -133,19 +133,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((VEC4 && TW 
                     val[u][2] = *reinterpret_cast<const float*>(fp + 2 * cstride);
                 } else {
                     const int vo = (int)((ha.y + o) * 4u);
-#if defined(LFBM5D_AGG_EXP) && LFBM5D_AGG_EXP == 1     /* timing experiment (results garbage): one gather per hit instead of three */
-                    val[u][0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_filt, vo, 0, 0));
-                    val[u][1] = val[u][0]; val[u][2] = val[u][0];
-#elif defined(LFBM5D_AGG_EXP) && LFBM5D_AGG_EXP == 2   /* timing experiment: one 12-byte gather per hit (as if the channels were interleaved) */
-                    { typedef float v3f __attribute__((ext_vector_type(3)));
-                      const v3f t3 = __builtin_bit_cast(v3f, __builtin_amdgcn_raw_buffer_load_b96(rs_filt, (int)(ha.y * 4u + o * 12u), 0, 0));
-                      val[u][0] = t3[0]; val[u][1] = t3[1]; val[u][2] = t3[2]; }
-#else
-                    /* (LFBM5D_FILT_LOAD_AUX = 2, non-temporal: 0.97 -> 1.5 ms per HT pass -- the neighbouring tiles' second reads of a row must find it in L2 / the Infinity Cache) */
-                    val[u][0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_filt, vo, 0, LFBM5D_FILT_LOAD_AUX));
-                    val[u][1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_filt, vo, (int)cstride, LFBM5D_FILT_LOAD_AUX));
-                    val[u][2] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_filt, vo, (int)(2 * cstride), LFBM5D_FILT_LOAD_AUX));
-#endif
+                    /* (kFiltLoadAux = 2, non-temporal: 0.97 -> 1.5 ms per HT pass -- the neighbouring tiles' second reads of a row must find it in L2 / the Infinity Cache) */
+                    val[u][0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_filt, vo, 0, kFiltLoadAux));
+                    val[u][1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_filt, vo, (int)cstride, kFiltLoadAux));
+                    val[u][2] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_filt, vo, (int)(2 * cstride), kFiltLoadAux));
                 }
                 kw[u][0] = on ? kz * __uint_as_float(ha.z) : 0.0f;   /* ... and add it with weight zero */
                 kw[u][1] = on ? kz * __uint_as_float(ha.w) : 0.0f;
@@ -298,15 +289,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((VEC4 && TW 
 
 hipError_t launch_aggregate(hipStream_t s, const AggArgs& a) {
     const bool wide = a.k >= 12;
-#ifndef LFBM5D_AGG16_TW
-#define LFBM5D_AGG16_TW 16
-#define LFBM5D_AGG16_TH 4
-#endif
-#ifndef LFBM5D_AGG8_TW
-#define LFBM5D_AGG8_TW 8
-#define LFBM5D_AGG8_TH 8
-#endif
-    const unsigned tw = wide ? (a.k == 12 ? 16 : LFBM5D_AGG16_TW) : (a.k == 8 ? LFBM5D_AGG8_TW : 8), th = wide ? (a.k == 12 ? 4 : LFBM5D_AGG16_TH) : (a.k == 8 ? LFBM5D_AGG8_TH : 8);
+    constexpr int kAgg16TW = 16, kAgg16TH = 4, kAgg8TW = 8, kAgg8TH = 8;   /* tile of the 16 x 16 / 8 x 8 patches */
+    const unsigned tw = wide ? (a.k == 12 ? 16 : kAgg16TW) : (a.k == 8 ? kAgg8TW : 8), th = wide ? (a.k == 12 ? 4 : kAgg16TH) : (a.k == 8 ? kAgg8TH : 8);
     const unsigned tiles = ((a.Wb + tw - 1) / tw) * ((a.Hb + th - 1) / th) * a.A;
     const dim3 grid(((tiles + 7) / 8) * 8), block(64);
     const bool big = (a.filt_sai_stride ? a.filt_sai_stride * sizeof(float) : a.filt_bytes) > 0xfffff000ull || (a.opt & kOptAgg64Bit);   /* option agg_64bit: exercise the 64-bit path in tests */
@@ -322,21 +306,10 @@ hipError_t launch_aggregate(hipStream_t s, const AggArgs& a) {
          else if (vec4)   hipLaunchKernelGGL((k_aggregate<W_, TW_, TH_, PF_, U_, false, true>), grid, block, 0, s, a); \
          else             hipLaunchKernelGGL((k_aggregate<W_, TW_, TH_, PF_, U_, false, false>), grid, block, 0, s, a); } while (0)
     /* scan / consume depths (candidate chunks per scan round, hits per load round): re-swept in round 6, profiles/r06_n_agg_depths.txt */
-#ifndef LFBM5D_AGG16_PF
-#define LFBM5D_AGG16_PF 3
-#endif
-#ifndef LFBM5D_AGG16_U
-#define LFBM5D_AGG16_U 12
-#endif
-#ifndef LFBM5D_AGG8_PF
-#define LFBM5D_AGG8_PF 3
-#endif
-#ifndef LFBM5D_AGG8_U
-#define LFBM5D_AGG8_U 6
-#endif
+    constexpr int kAgg16PF = 3, kAgg16U = 12, kAgg8PF = 3, kAgg8U = 6;
     if (a.k == 12)      LFBM5D_AGG(true, 16, 4, 3, 12);
-    else if (a.k == 8)  LFBM5D_AGG(true, LFBM5D_AGG8_TW, LFBM5D_AGG8_TH, LFBM5D_AGG8_PF, LFBM5D_AGG8_U);
-    else if (wide)      LFBM5D_AGG(false, LFBM5D_AGG16_TW, LFBM5D_AGG16_TH, LFBM5D_AGG16_PF, LFBM5D_AGG16_U);
+    else if (a.k == 8)  LFBM5D_AGG(true, kAgg8TW, kAgg8TH, kAgg8PF, kAgg8U);
+    else if (wide)      LFBM5D_AGG(false, kAgg16TW, kAgg16TH, kAgg16PF, kAgg16U);
     else                LFBM5D_AGG(false, 8, 8, 2, 6);
 #undef LFBM5D_AGG
     return hipGetLastError();

@@ -64,9 +64,6 @@ __device__ __forceinline__ int grid_index(int v, int n, int last, int nHW, int p
  * column of the table (a K-term chain per row) is computed up front; strips hand their last
  * column to the next strip through `lcol`.
  */
-#ifndef LFBM5D_SCAN_DEPTH
-#define LFBM5D_SCAN_DEPTH(T) 4   /* with two waves per SIMD a shallower pipeline suffices, and it keeps the kernel under 256 VGPRs */
-#endif
 typedef float v4f __attribute__((ext_vector_type(4)));
 template <int K, int MODE, bool WIDE>   /* MODE 0: self search on the regular grid, 1: self search on an irregular list, 2: disparity */
 __device__ __forceinline__ void scan_body(const ScanArgs& a, const int bid, float* lds) {
@@ -77,7 +74,7 @@ __device__ __forceinline__ void scan_body(const ScanArgs& a, const int bid, floa
      * instead of K more ring rows -- half the ring reads and a ring of 64 + 2T rows (the pipeline depth must be a multiple of K) */
     constexpr bool FIFO = K == 8 || K == 16;
     constexpr int T = 4, RR = FIFO ? 64 + 2 * T : 64 + K + 2 * T, CW = 64 + K;
-    constexpr int DEP = LFBM5D_SCAN_DEPTH(T);   /* row-load pipeline depth in chunks */
+    constexpr int DEP = 4;   /* row-load pipeline depth in chunks: with two waves per SIMD a shallower pipeline suffices, and it keeps the kernel under 256 VGPRs */
     constexpr bool stereo = MODE == 2;
     constexpr bool irregular = MODE == 1;
     float* ring = lds;              /* [RR][CW] D rows of the current strip; ring col 0 <-> x = cb-1 */
@@ -547,11 +544,8 @@ __device__ __forceinline__ void scan_body(const ScanArgs& a, const int bid, floa
 /* Two waves per SIMD: the scan is issue-bound with long dependent chains (0.61 of a lone wave's cycles issue), so a
  * second wave on the SIMD is worth a quarter of the kernel's time -- if it fits: 256 VGPRs (round 1 used 298) and an
  * LDS footprint of at most a sixth of the CU's 160 KiB (round 1: 40 KiB, a quarter). */
-#ifndef LFBM5D_SCAN_WAVES_ATTR
-#define LFBM5D_SCAN_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(2, 2)))
-#endif
 template <int K, bool WIDE>
-__global__ __launch_bounds__(64) LFBM5D_SCAN_WAVES_ATTR void k_bm_scan(ScanArgs a) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_bm_scan(ScanArgs a) {
     extern __shared__ float lds[];
     /* one launch covers both searches: blocks [0, n_self) are self-similarity tables, the rest
      * disparity tables (fewer, fuller rounds of resident waves than two launches; dispatching the disparity tables first,
@@ -1004,13 +998,10 @@ hipError_t launch_bm_scan(hipStream_t s, const ScanArgs& a) {
     const unsigned T = 4;
     const bool wide = a.n_ref_rows > 127;   /* row-slot table entries: bytes unless the grid has more than 127 rows */
     const unsigned ring_rows = (a.k == 8 || a.k == 16) ? 64 + 2 * T : 64 + a.k + 2 * T;   /* scan_body: FIFO */
-    size_t lds = (size_t)((ring_rows + T - 1) * (64 + a.k) + nrows + T + 1) * sizeof(float)
+    const size_t lds = (size_t)((ring_rows + T - 1) * (64 + a.k) + nrows + T + 1) * sizeof(float)
                + (a.n_self && !a.refmap ? (size_t)(a.H + 64 + 8) * (wide ? 2 : 1) : 0);     /* row-slot table of the regular grid (+ alignment) */
     const unsigned n = a.n_self + a.n_stereo;
     if (!n) return hipSuccess;
-#ifdef LFBM5D_SCAN_LDS_EXPERIMENT   /* development builds: timing at a smaller LDS footprint (results are garbage) */
-    if (a.lds_cap) lds = std::min<size_t>(lds, (size_t)a.lds_cap);   /* option scan_lds_cap */
-#endif
 #define LFBM5D_SCAN(K_) do { if (wide) hipLaunchKernelGGL((k_bm_scan<K_, true>), dim3(n), dim3(64), lds, s, a); \
                              else      hipLaunchKernelGGL((k_bm_scan<K_, false>), dim3(n), dim3(64), lds, s, a); } while (0)
     /* option scan_any: test hook, the plain any-patch-size kernel for 8 / 12 / 16 too (compared bit for bit with the dedicated ones) */

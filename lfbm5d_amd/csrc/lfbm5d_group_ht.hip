@@ -56,8 +56,7 @@ namespace {
  * N = 1 ... 8, thresholds placed on coefficients); the GPU tests hold the two forms to identical decisions over the same range,
  * tools/flip_count.py --referee on 560 x 560 windows.  So every decision is the reference-order form's decision: the survivor
  * counts, hence the weights and `den`, are bit-identical to rounds 1-5; the filtered values agree to an ulp or two.
- * Returns true when the caller has to fall back.  LFBM5D_HT_REFERENCE_ORDER (build flag) or the option ht_reference_order: no
- * fast chain at all. */
+ * Returns true when the caller has to fall back.  The option ht_reference_order: no fast chain at all. */
 /* relative part of the guard band, by angular frequency: emulated over 3 M near-threshold coefficients of 8-bit-range data
  * (brightness 0..255, contrast up to +-100, sigma 25) the two forms differ by at most 7.9e-6 of a threshold at st = 0 (sums of
  * 72 bright pixels), 2.3e-6 at st = 3, 6 and 1.2e-6 elsewhere.  tests/test_ht_guard_model.py reads this definition. */
@@ -284,11 +283,7 @@ __device__ __forceinline__ bool group_id_body(const GroupArgs& a, unsigned g, in
 #pragma unroll
             for (int st = 0; st < 9; st++) {
                 const unsigned so = ofs[n * A + st] + cbase;   /* absent patches read offset 0 and are zeroed below */
-#if defined(LFBM5D_HT_EXP) && (LFBM5D_HT_EXP & 1)   /* timing experiment: one gather per thread instead of NS * 9 */
-                const float x = (n | st) ? V[0][0].x * 1.0001f + (float)(n + st) : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_in, voff, (int)so, 0));
-#else
                 const float x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_in, voff, (int)so, 0));
-#endif
                 if (n < NH) V[n][st].x = x; else V[n - NH][st].y = x;
             }
         }
@@ -318,11 +313,7 @@ __device__ __forceinline__ bool group_id_body(const GroupArgs& a, unsigned g, in
         for (int st = 0; st < 9; st++) {
             const float r = n < NH ? V[n][st].x : V[n - NH][st].y;
             if (LDSW) work[(n * A + st) * kT16Patch + woff] = r;
-#if defined(LFBM5D_HT_EXP) && (LFBM5D_HT_EXP & 2)   /* timing experiment: the stores are issued at an out-of-range offset (dropped by the buffer's bounds check) */
-            else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, r), rs_out, (n | st) ? 0x7ffffff0 : vout, (int)((((unsigned)(n * A + st) * a.C + c) * k2) * 4u), LFBM5D_FILT_STORE_AUX);
-#else
-            else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, r), rs_out, vout, (int)((((unsigned)(n * A + st) * a.C + c) * k2) * 4u), LFBM5D_FILT_STORE_AUX);
-#endif
+            else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, r), rs_out, vout, (int)((((unsigned)(n * A + st) * a.C + c) * k2) * 4u), kFiltStoreAux);
         }
     return near;
 }
@@ -358,9 +349,6 @@ __device__ __forceinline__ void group_id_one(const GroupArgs& a, const unsigned 
             float nr = 0.0f;
             for (unsigned i = 0; i < (blockDim.x + 63) / 64; i++) nr += red[3][i];
             if (nr != 0.0f) {
-#ifdef LFBM5D_HT_COUNT_NEAR   /* development: the guard-band cases show up as "shape-adaptive groups" in the pass statistics */
-                atomicAdd(&a.counters[1], 1ull);
-#endif
                 a.sa_list[1u + atomicAdd(&a.sa_list[0], 1u)] = g | (1u << (29 + c)); return;
             }
         }
@@ -390,9 +378,6 @@ __device__ __forceinline__ void group_id_one(const GroupArgs& a, const unsigned 
  * (reference-order arithmetic, inline shape-adaptive form; a workgroup per entry) works off behind them -- the one group in a
  * thousand whose angular shape is not the whole window (all channels; listed by k_group_shape), and the (group, channel) pairs
  * in which a wave of the fast chain came within the guard band of a threshold (one to two in a hundred). */
-#ifndef LFBM5D_HT_WAVES
-#define LFBM5D_HT_WAVES 0
-#endif
 template <bool HAAR, int SA_MODE, bool FAST>
 __device__ __forceinline__ void group_id_kernel(const GroupArgs& a) {
     __shared__ float red[4][4];
@@ -413,12 +398,8 @@ __device__ __forceinline__ void group_id_list_kernel(const GroupArgs& a) {
             }
     }
 }
-#if LFBM5D_HT_WAVES > 0
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LFBM5D_HT_WAVES, LFBM5D_HT_WAVES))) void k_group_id_haar_fast(GroupArgs a) { group_id_kernel<true, 3, true>(a); }
-#else
 __global__ __launch_bounds__(256) void k_group_id_haar_fast(GroupArgs a) { group_id_kernel<true, 3, true>(a); }
-#endif
-__global__ __launch_bounds__(256) void k_group_id_haar(GroupArgs a) { group_id_kernel<true, 3, false>(a); }   /* tau_4D = id (no angular DCT to speed up) and -DLFBM5D_HT_REFERENCE_ORDER builds */
+__global__ __launch_bounds__(256) void k_group_id_haar(GroupArgs a) { group_id_kernel<true, 3, false>(a); }   /* tau_4D = id (no angular DCT to speed up) and option ht_reference_order */
 __global__ __launch_bounds__(256) void k_group_id_any(GroupArgs a) { group_id_kernel<false, 3, false>(a); }
 /* windows with an empty SAI (every group shape-adaptive): the transform inline, in registers; 168 VGPRs: three waves per SIMD */
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_group_id_haar_sa(GroupArgs a) { group_id_kernel<true, 2, false>(a); }
@@ -442,17 +423,9 @@ __global__ __launch_bounds__(256) void k_group_id_any_list(GroupArgs a) { group_
  * per group.  Measured at 560^2: 0.90 ms with one group per workgroup, 0.34 / 0.33 / 0.36 / 0.38 / 0.46 / 0.47 / 0.71 ms
  * with 2 / 3 / 4 / 5 / 7 / 8 / 14 -- three groups fill one round of the 16x16 level (216 of 256 threads) and leave
  * room for five workgroups per CU. */
-#ifndef LFBM5D_T16_GROUPS
-#define LFBM5D_T16_GROUPS 3
-#endif
-constexpr int kT16Groups = LFBM5D_T16_GROUPS;
-#ifndef LFBM5D_T16_ROUND
-#define LFBM5D_T16_ROUND 40
-#endif
-#ifndef LFBM5D_T16_WAVES
-#define LFBM5D_T16_WAVES 3
-#endif
-constexpr int kT16Half = LFBM5D_T16_ROUND;   /* patches per round of 2-D transforms: the work area of the Haar kernels (40: two rounds for a full group of 72, three workgroups per CU) */
+constexpr int kT16Groups = 3;
+constexpr int kT16Half = 40;   /* patches per round of 2-D transforms: the work area of the Haar kernels (40: two rounds for a full group of 72, three workgroups per CU) */
+constexpr int kT16Waves = 3;   /* amdgpu_waves_per_eu of the Haar kernels: those three workgroups of four waves */
 template <bool HAAR, bool BIOR, bool MULTI, bool SPLIT = false, bool SA = false>   /* SA: windows with an empty SAI -- the shape-adaptive transform inline, in registers (N = 1 form) */
 __device__ __forceinline__ void group_t16_kernel(const GroupArgs& a) {
     extern __shared__ float lds[];
@@ -485,9 +458,6 @@ __device__ __forceinline__ void group_t16_kernel(const GroupArgs& a) {
     auto patch_src = [&](int patch, bool& ok) -> const float* {
         const unsigned p = a.gpos[(size_t)g * N * A + patch];
         ok = p != 0xffffffffu;            /* empty SAI / never-filled table column: zeros */
-#if defined(LFBM5D_T16_EXP) && LFBM5D_T16_EXP == 1   /* timing experiment (results garbage): every patch row from one cached place */
-        return a.noisy + (size_t)c * plane + (patch & 7) * 16;
-#endif
         return a.noisy + ((size_t)(patch % A) * a.C + c) * plane + (ok ? p : 0u);
     };
     /* patches base .. base + np - 1 of the group -> work area slots 0 .. np - 1 */
@@ -700,17 +670,9 @@ __device__ __forceinline__ void group_t16_kernel(const GroupArgs& a) {
         }
     }
 }
-#ifndef LFBM5D_T16_NOSPLIT
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LFBM5D_T16_WAVES, LFBM5D_T16_WAVES))) void k_group_bior16_haar(GroupArgs a) { group_t16_kernel<true, true, false, true>(a); }
-#else
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_group_bior16_haar(GroupArgs a) { group_t16_kernel<true, true, false>(a); }
-#endif
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kT16Waves, kT16Waves))) void k_group_bior16_haar(GroupArgs a) { group_t16_kernel<true, true, false, true>(a); }
 __global__ __launch_bounds__(256) void k_group_bior16_any(GroupArgs a) { group_t16_kernel<false, true, false>(a); }
-#ifndef LFBM5D_T16_NOSPLIT
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LFBM5D_T16_WAVES, LFBM5D_T16_WAVES))) void k_group_dct16_haar(GroupArgs a) { group_t16_kernel<true, false, false, true>(a); }
-#else
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_group_dct16_haar(GroupArgs a) { group_t16_kernel<true, false, false>(a); }
-#endif
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kT16Waves, kT16Waves))) void k_group_dct16_haar(GroupArgs a) { group_t16_kernel<true, false, false, true>(a); }
 __global__ __launch_bounds__(256) void k_group_dct16_any(GroupArgs a) { group_t16_kernel<false, false, false>(a); }
 /* N = 1: kT16Groups groups per workgroup (the 5th-dimension transform is the identity, HAAR or not) */
 __global__ __launch_bounds__(256) void k_group_bior16_n1(GroupArgs a) { group_t16_kernel<true, true, true>(a); }
@@ -745,11 +707,8 @@ hipError_t launch_group_ht(hipStream_t s, const GroupArgs& a, bool all_sa, bool*
         }
         else {
             if (!a.sa_list) return hipErrorInvalidValue;
-#ifndef LFBM5D_HT_REFERENCE_ORDER   /* kOptHtReferenceOrder (test hook): the reference-order kernel, as in such a build */
+            /* kOptHtReferenceOrder (test hook): the reference-order kernel */
             const bool fast = a.tau5 == 9 && (a.tau4 == 5 || a.tau4 == 6) && a.C <= 3 && !(a.opt & kOptHtReferenceOrder);
-#else
-            const bool fast = false;
-#endif
             if (fast)             hipLaunchKernelGGL(k_group_id_haar_fast, dim3(gx, a.C), dim3(threads), 0, s, a);
             else if (a.tau5 == 9) hipLaunchKernelGGL(k_group_id_haar, dim3(gx, a.C), dim3(threads), 0, s, a);
             else                  hipLaunchKernelGGL(k_group_id_any, dim3(gx, a.C), dim3(threads), 0, s, a);
@@ -775,18 +734,11 @@ hipError_t launch_group_ht(hipStream_t s, const GroupArgs& a, bool all_sa, bool*
             return hipGetLastError();
         }
         if (a.tau2 == 7) {
-#ifndef LFBM5D_T16_NOSPLIT   /* two rounds through a work area of 40 patches: groups of fewer than eight matches fit it whole (N <= 4: 36 patches) */
+            /* two rounds through a work area of 40 patches: groups of fewer than eight matches fit it whole (N <= 4: 36 patches) */
             if (a.tau5 == 9) hipLaunchKernelGGL(k_group_bior16_haar, grid, block, std::min(lb, (size_t)kT16Half * kT16Patch * sizeof(float)), s, a);
-#else
-            if (a.tau5 == 9) hipLaunchKernelGGL(k_group_bior16_haar, grid, block, lb, s, a);
-#endif
             else             hipLaunchKernelGGL(k_group_bior16_any, grid, block, lb, s, a);
         } else {
-#ifndef LFBM5D_T16_NOSPLIT
             if (a.tau5 == 9) hipLaunchKernelGGL(k_group_dct16_haar, grid, block, std::min(lb, (size_t)kT16Half * kT16Patch * sizeof(float)), s, a);
-#else
-            if (a.tau5 == 9) hipLaunchKernelGGL(k_group_dct16_haar, grid, block, lb, s, a);
-#endif
             else             hipLaunchKernelGGL(k_group_dct16_any, grid, block, lb, s, a);
         }
         return hipGetLastError();

@@ -104,7 +104,7 @@ __device__ __forceinline__ void bior_tp(float* Tp, int r, bool fwd, TbPtr tb) { 
 /* One 2-D stage over `np` patches: `src(p, r, x)` delivers row r of patch p (K floats), `dst(p, r, x)` takes it. */
 template <int K, class SRC, class DST>
 __device__ __forceinline__ void patches_2d(float* tmp, int np, unsigned tau2, bool fwd, TbPtr tb, SRC src, DST dst, long long* sub = nullptr) {
-#ifdef LFBM5D_SLAB_PHASES
+#ifdef LFBM5D_PHASE_TIMING
     long long tl = (long long)__builtin_readcyclecounter();
 #define SUB_MARK(i) do { asm volatile("" ::: "memory"); const long long tn = (long long)__builtin_readcyclecounter(); if (sub) sub[i] += tn - tl; tl = tn; } while (0)
 #else
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 8))
         const float sig2 = sig * sig;
         float* const out = a.filt;   /* + filt_patch(a, g, n, st, k2) */
         __syncthreads();
-#ifdef LFBM5D_SLAB_PHASES   /* development builds: cycles per stage, thread 0 of every 64th workgroup (lfbm5d_api.hip prints counters 4..15) */
+#ifdef LFBM5D_PHASE_TIMING   /* development builds: cycles per stage, thread 0 of every 64th workgroup (fold_counters in lfbm5d_pass.hip prints counters 4..15) */
         long long tq[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast = (long long)__builtin_readcyclecounter();
 #define SLAB_MARK(i) do { asm volatile("" ::: "memory"); const long long tn = (long long)__builtin_readcyclecounter(); tq[i] += tn - tlast; tlast = tn; } while (0)
 #else
@@ -252,7 +252,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 8))
 #pragma unroll
                 for (int t = 0; t < K; t += 4) filt_put4(reinterpret_cast<v4f*>(o + t), v4f{x[t], x[t + 1], x[t + 2], x[t + 3]});
             };
-#ifdef LFBM5D_SLAB_PHASES
+#ifdef LFBM5D_PHASE_TIMING
             long long* const subp = tq + 8;
 #else
             long long* const subp = nullptr;
@@ -551,7 +551,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 8))
         }
         __syncthreads();   /* pos / red / the LDS are reused by the next item */
         SLAB_MARK(6);
-#ifdef LFBM5D_SLAB_PHASES
+#ifdef LFBM5D_PHASE_TIMING
         if (tid == 0 && blockIdx.x % 64 == 5) { for (int i = 0; i < 7; i++) atomicAdd(&a.counters[4 + i], (unsigned long long)tq[i]); atomicAdd(&a.counters[11], 1ull); for (int i = 0; i < 4; i++) atomicAdd(&a.counters[12 + i], (unsigned long long)tq[8 + i]); }
 #endif
     }

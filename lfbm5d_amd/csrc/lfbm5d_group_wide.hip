@@ -110,7 +110,7 @@ __global__ __launch_bounds__(256) void k_group_idw(GroupArgs a) {   /* (512 thre
     float wacc = 0.0f, s1 = 0.0f, s2 = 0.0f;
     float* const out = a.filt;   /* + filt_patch(a, g, n, st, k2): group-major, or SAI-major on windows of 11 x 11 SAIs and more */
     const float* const img = a.noisy + (size_t)c * plane;
-#ifdef LFBM5D_WIDE_PHASES   /* development builds (with -DLFBM5D_WIDE_PHASES, which makes lfbm5d_api.hip print them): cycles per phase of the slab loop, summed over the workgroups */
+#ifdef LFBM5D_PHASE_TIMING   /* development builds (-DLFBM5D_PHASE_TIMING, which makes fold_counters in lfbm5d_pass.hip print them): cycles per phase of the slab loop, summed over the workgroups */
     long long tq[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast = (long long)__builtin_readcyclecounter();
     const long long treal0 = (long long)__builtin_amdgcn_s_memrealtime();
 #define WIDE_MARK(i) do { asm volatile("" ::: "memory"); const long long tn = (long long)__builtin_readcyclecounter(); tq[i] += tn - tlast; tlast = tn; } while (0)
@@ -133,7 +133,7 @@ __global__ __launch_bounds__(256) void k_group_idw(GroupArgs a) {   /* (512 thre
                 v[u] = f4u{{0.0f, 0.0f, 0.0f, 0.0f}};
                 if (e < total && pv[u] != 0xffffffffu && px < npx) v[u] = *reinterpret_cast<const f4u*>(img + ((unsigned)(ns % A) * cplane + pv[u] + poff));
             }
-#ifdef LFBM5D_WIDE_PHASES
+#ifdef LFBM5D_PHASE_TIMING
             WIDE_MARK(9);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             WIDE_MARK(6);
@@ -331,7 +331,7 @@ __global__ __launch_bounds__(256) void k_group_idw(GroupArgs a) {   /* (512 thre
         __syncthreads();
         WIDE_MARK(5);
     }
-#ifdef LFBM5D_WIDE_PHASES
+#ifdef LFBM5D_PHASE_TIMING
     if (tid == 0 && blockIdx.x % 64 == 5) {   /* a sample: same-address atomics of every workgroup would queue in L2 and slow every load */
         for (int i = 0; i < 6; i++) atomicAdd(&a.counters[4 + i], (unsigned long long)tq[i]); atomicAdd(&a.counters[12], (unsigned long long)tq[6]); atomicAdd(&a.counters[13], (unsigned long long)tq[7]); atomicAdd(&a.counters[14], (unsigned long long)tq[8]); atomicAdd(&a.counters[15], (unsigned long long)tq[9]); atomicAdd(&a.counters[10], 1ull); atomicAdd(&a.counters[11], (unsigned long long)((long long)__builtin_amdgcn_s_memrealtime() - treal0)); }
 #endif

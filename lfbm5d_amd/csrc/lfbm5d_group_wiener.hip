@@ -24,7 +24,6 @@ namespace {
  * ------------------------------------------------------------------------------------------ */
 constexpr int kDct8Threads = 320;
 
-template <int STEP>
 __global__ __launch_bounds__(kDct8Threads) void k_group_dct8(GroupArgs a) {
     extern __shared__ float lds[];
     __shared__ unsigned pos[kMaxN * kA3];
@@ -39,9 +38,8 @@ __global__ __launch_bounds__(kDct8Threads) void k_group_dct8(GroupArgs a) {
     const int NP = nSx * A;               /* patches per stack */
     const int NPp = (N * A) | 1;          /* row stride of the [pq][patch] stack, odd */
     float* S0 = lds;
-    float* S1 = lds + K2 * NPp;
+    float* S1 = lds + K2 * NPp;           /* the pilot's stack of the retired Wiener form: see `s` below */
     const TbPtr tb = (TbPtr)a.tb;
-    constexpr int S = STEP == 2 ? 2 : 1;
 
     for (int i = tid; i < NP; i += kDct8Threads) pos[i] = a.gpos[(size_t)g * N * A + i];
     ShRef sh = group_shape(a, g);
@@ -49,7 +47,10 @@ __global__ __launch_bounds__(kDct8Threads) void k_group_dct8(GroupArgs a) {
     const bool use_sadct = a.tau4 == 6 && sh.use_sadct;
 
     /* gather + forward 2-D DCT, one thread per patch */
-    for (int task = tid; task < S * NP; task += kDct8Threads) {
+    /* s (here and in the 4-D forward stage) was the stack index of the Wiener form, which also ran the pilot image; with the one
+     * stack that is left it is always 0.  The compiler does not see that, so writing it out of these two loops changes the kernel's
+     * instructions (it saves a division and three selects): a change of its own, to be measured, not part of a cleanup. */
+    for (int task = tid; task < NP; task += kDct8Threads) {
         const int s = task / NP, patch = task % NP, st = patch % A;
         const unsigned p = pos[patch];
         const bool ok = p != 0xffffffffu;
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(kDct8Threads) void k_group_dct8(GroupArgs a) {
     const bool do_dct4 = a.tau4 == 5 || (a.tau4 == 6 && !use_sadct);
     const bool do_sa4 = !do_dct4 && a.tau4 == 6;
     if (do_dct4 || do_sa4) {
-        for (int f = tid; f < S * nSx * K2; f += kDct8Threads) {
+        for (int f = tid; f < nSx * K2; f += kDct8Threads) {
             const int s = f / (nSx * K2), r = f % (nSx * K2), n = r / K2, pq = r % K2;
             float* base = (s ? S1 : S0) + pq * NPp + n * A;
             float x[9];
@@ -106,11 +107,11 @@ __global__ __launch_bounds__(kDct8Threads) void k_group_dct8(GroupArgs a) {
             const bool in_shape = !use_sadct || sh.mask_dct[st];
             const int base = pq * NPp + st;
             switch (nSx) {
-                case 1:  filter5<1, STEP>(S0, S1, base, A, a.tau5, T, sig2, in_shape, wacc, s1, s2, tb); break;
-                case 2:  filter5<2, STEP>(S0, S1, base, A, a.tau5, T, sig2, in_shape, wacc, s1, s2, tb); break;
-                case 4:  filter5<4, STEP>(S0, S1, base, A, a.tau5, T, sig2, in_shape, wacc, s1, s2, tb); break;
-                case 8:  filter5<8, STEP>(S0, S1, base, A, a.tau5, T, sig2, in_shape, wacc, s1, s2, tb); break;
-                default: filter5<16, STEP>(S0, S1, base, A, a.tau5, T, sig2, in_shape, wacc, s1, s2, tb); break;
+                case 1:  filter5<1, 1>(S0, nullptr, base, A, a.tau5, T, sig2, in_shape, wacc, s1, s2, tb); break;
+                case 2:  filter5<2, 1>(S0, nullptr, base, A, a.tau5, T, sig2, in_shape, wacc, s1, s2, tb); break;
+                case 4:  filter5<4, 1>(S0, nullptr, base, A, a.tau5, T, sig2, in_shape, wacc, s1, s2, tb); break;
+                case 8:  filter5<8, 1>(S0, nullptr, base, A, a.tau5, T, sig2, in_shape, wacc, s1, s2, tb); break;
+                default: filter5<16, 1>(S0, nullptr, base, A, a.tau5, T, sig2, in_shape, wacc, s1, s2, tb); break;
             }
         }
     }
@@ -135,13 +136,12 @@ __global__ __launch_bounds__(kDct8Threads) void k_group_dct8(GroupArgs a) {
             if (use_sadct) atomicAdd(&a.counters[1], 1ull);
         }
     }
-    float* F = STEP == 2 ? S1 : S0;
 
     /* 4-D inverse */
     if (do_dct4 || do_sa4) {
         for (int f = tid; f < nSx * K2; f += kDct8Threads) {
             const int n = f / K2, pq = f % K2;
-            float* base = F + pq * NPp + n * A;
+            float* base = S0 + pq * NPp + n * A;
             float x[9];
 #pragma unroll
             for (int st = 0; st < 9; st++) x[st] = base[st];
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(kDct8Threads) void k_group_dct8(GroupArgs a) {
     /* inverse 2-D DCT + store, one thread per patch: filt[g][n][st][c][64] */
     for (int patch = tid; patch < NP; patch += kDct8Threads) {
         float x[8][8];
-        const float* src = F + patch;
+        const float* src = S0 + patch;
 #pragma unroll
         for (int i = 0; i < 8; i++)
 #pragma unroll
@@ -181,18 +181,18 @@ __global__ __launch_bounds__(kDct8Threads) void k_group_dct8(GroupArgs a) {
 }
 
 /* ------------------------------------------------------------------------------------------
- * Wiener step of the 8x8 DCT configuration (step 2, k = 8, tau_2D = dct): packed-fp32 variant.
+ * Wiener step of the 8x8 bior1.5 configuration (step 2, k = 8, tau_2D = bior1.5), k_group_dct8w: packed-fp32 kernel (written in
+ * round 1 for the 8x8 DCT -- hence its name --, which k_group_dct8w2 / k_group_dct8w3 took over; the wavelet is the form that ships).
  * The noisy and the pilot (basic) stacks go through identical forward transforms, so they are kept
  * as the two halves of a float2 everywhere: one LDS stack of float2 laid out [coefficient pq][patch],
  * 64-bit LDS accesses, and v_pk_{add,mul,fma}_f32 arithmetic that transforms both stacks at once.
- * Where only the filtered stack remains (inverse transforms) two fibres / two patches are paired
- * instead.  The arithmetic per element is the same sequence as in k_group_dct8<2>.
+ * Where only the filtered stack remains (inverse transforms) two fibres / two patches are paired instead.
  * Phases (256 threads, barriers between them):
- *   1  cooperative 16-byte gather of both images through LDS, then thread = patch: 16 packed 8-point DCTs, 64 LDS writes
+ *   1  cooperative 16-byte gather of both images through LDS, then thread = patch: packed 2-D bior1.5, 64 LDS writes
  *   2  thread = (n, pq) fibre over the 9 SAIs: packed 3x3 DCT (shape-adaptive variant on the scalar path)
  *   3  thread = (st, pq) fibre over the nSx patches: packed Haar, Wiener shrinkage, inverse Haar
  *   4  thread = two (n, pq) fibres of the filtered stack: packed inverse 3x3 DCT
- *   5  thread = two patches: packed inverse 8x8 DCT, 16-byte stores of the filtered patches
+ *   5  thread = two patches: packed inverse 2-D bior1.5, 16-byte stores of the filtered patches
  * ------------------------------------------------------------------------------------------ */
 
 /* 8-point orthonormal DCT-II / DCT-III of the Wiener kernels (T = float or a packed pair).  The 1/2 of the orthonormal
@@ -327,13 +327,7 @@ __device__ __forceinline__ void dct9_inv2_u(v2f* x, TbPtr tb, const float scale)
  * one correction step instead of the IEEE division sequence -- within one ulp of the quotient, which is well inside
  * the float tolerance of this stage (the division was a tenth of the kernel's instructions) */
 __device__ __forceinline__ float wiener_div(float a, float b) {
-#ifdef LFBM5D_WIENER_DIV_REFINED
-    const float r = __builtin_amdgcn_rcpf(b);
-    const float q = a * r;
-    return __builtin_fmaf(__builtin_fmaf(-b, q, a), r, q);
-#else
     return a * __builtin_amdgcn_rcpf(b);   /* v_rcp_f32 is good to 1 ulp: the quotient to 2 ulp, a Wiener coefficient needs no more */
-#endif
 }
 
 /* phase 3 of k_group_dct8w on one (st, pq) fibre of nSx = NS float2 entries (x: noisy, y: pilot) */
@@ -372,10 +366,7 @@ __device__ __forceinline__ void wiener_fibre2(v2f* stack, int base, int stride, 
     }
 }
 
-#ifndef LFBM5D_DCT8W_THREADS
-#define LFBM5D_DCT8W_THREADS 256
-#endif
-constexpr int kDct8wThreads = LFBM5D_DCT8W_THREADS;
+constexpr int kDct8wThreads = 256;
 
 /* bior1.5 on an 8x8 patch held by ONE thread (rows x[i][0..8)), all three levels in registers; T = float or a packed pair.
  * Same taps, order and unfused arithmetic as bior_fwd_level / bior_inv_level (lib_transforms.cpp:46-204). */
@@ -435,7 +426,7 @@ template <class T> __device__ __forceinline__ void bior8_inv_2d(T (*x)[8], TbPtr
     bior8_pass<8, false, false>(x, tb); bior8_pass<8, false, true>(x, tb);
 }
 
-template <bool HAAR, bool BIOR = false>   /* BIOR: tau_2D = bior1.5 instead of the DCT */
+template <bool HAAR>
 __global__ __launch_bounds__(kDct8wThreads) void k_group_dct8w(GroupArgs a) {
     extern __shared__ float lds[];
     __shared__ float red[3][kDct8wThreads / 64];
@@ -510,20 +501,7 @@ __global__ __launch_bounds__(kDct8wThreads) void k_group_dct8w(GroupArgs a) {
         }
         __syncthreads();             /* every patch is in registers: the area becomes the stack */
         if (patch < NP) {
-            if (BIOR) bior8_fwd_2d(x, tb);
-            else {
-#pragma unroll
-                for (int i = 0; i < 8; i++) dct8_fwd_t(x[i]);
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    v2f col[8];
-#pragma unroll
-                    for (int i = 0; i < 8; i++) col[i] = x[i][j];
-                    dct8_fwd_t(col);
-#pragma unroll
-                    for (int i = 0; i < 8; i++) x[i][j] = col[i];
-                }
-            }
+            bior8_fwd_2d(x, tb);
             v2f* dst = stack + patch;
 #pragma unroll
             for (int i = 0; i < 8; i++)
@@ -646,20 +624,7 @@ __global__ __launch_bounds__(kDct8wThreads) void k_group_dct8w(GroupArgs a) {
         for (int i = 0; i < 8; i++)
 #pragma unroll
             for (int j = 0; j < 8; j++) x[i][j] = v2f{sa[2 * (i * 8 + j) * NPp], sb[2 * (i * 8 + j) * NPp]};
-        if (BIOR) bior8_inv_2d(x, tb);
-        else {
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                v2f col[8];
-#pragma unroll
-                for (int i = 0; i < 8; i++) col[i] = x[i][j];
-                dct8_inv_t(col);
-#pragma unroll
-                for (int i = 0; i < 8; i++) x[i][j] = col[i];
-            }
-#pragma unroll
-            for (int i = 0; i < 8; i++) dct8_inv_t(x[i]);
-        }
+        bior8_inv_2d(x, tb);
         float4* oa = reinterpret_cast<float4*>(a.filt + ((size_t)g * N * A + pa) * a.C * K2 + (size_t)c * K2);
 #pragma unroll
         for (int i = 0; i < 8; i++) {
@@ -685,9 +650,9 @@ __global__ __launch_bounds__(kDct8wThreads) void k_group_dct8w(GroupArgs a) {
 }
 
 /* ------------------------------------------------------------------------------------------
- * Wiener step, 8x8 DCT, second generation: the same arithmetic as k_group_dct8w with the 2-D stages dealt to ALL
- * threads.  k_group_dct8w runs the forward 2-D DCT with one thread per patch (144 of 256 threads busy, fed through an
- * LDS staging area) and the inverse with one thread per patch PAIR (72 of 256): those two phases were 63 % of its time
+ * Wiener step, 8x8 DCT, second generation: the phases of k_group_dct8w with the 2-D stages dealt to ALL
+ * threads.  Round 1's DCT form of k_group_dct8w ran the forward 2-D DCT with one thread per patch (144 of 256 threads busy, fed
+ * through an LDS staging area) and the inverse with one thread per patch PAIR (72 of 256): those two phases were 63 % of its time
  * at a quarter to a half of the lanes.  Here a 2-D DCT is two passes over the LDS stack with an item = one 8-point
  * packed transform:
  *   1a  item = (row i, patch): the thread loads its 32-byte row of both images straight from the window (no staging),
@@ -701,10 +666,7 @@ __global__ __launch_bounds__(kDct8wThreads) void k_group_dct8w(GroupArgs a) {
  * Items are numbered patch-fastest so that the stack accesses of a wavefront are consecutive float2 (no bank conflicts);
  * the global accesses are 32-byte row segments either way.
  * ------------------------------------------------------------------------------------------ */
-#ifndef LFBM5D_DCT8W2_THREADS
-#define LFBM5D_DCT8W2_THREADS 512
-#endif
-constexpr int kDct8w2Threads = LFBM5D_DCT8W2_THREADS;
+constexpr int kDct8w2Threads = 512;
 
 template <bool HAAR>
 __global__ __launch_bounds__(kDct8w2Threads) void k_group_dct8w2(GroupArgs a) {
@@ -744,11 +706,7 @@ __global__ __launch_bounds__(kDct8w2Threads) void k_group_dct8w2(GroupArgs a) {
 #pragma unroll
         for (int q = 0; q < kIt; q++) {
             const int it = tid + q * TH;
-#ifndef LFBM5D_W2_LOAD_ROWFAST
             const int i = (int)__umulhi((unsigned)it, rcpNP), patch = it - i * NP;
-#else
-            const int patch = it >> 3, i = it & 7;     /* row-fastest (measured: the stack writes then conflict, 1.46 vs 1.44 ms) */
-#endif
             if (it < NP * 8) {
                 const unsigned p = pos[patch];
                 const size_t off = ((size_t)(patch % A) * a.C + c) * plane + (p != 0xffffffffu ? p : 0u) + (size_t)i * a.Wb;
@@ -759,11 +717,7 @@ __global__ __launch_bounds__(kDct8w2Threads) void k_group_dct8w2(GroupArgs a) {
 #pragma unroll
         for (int q = 0; q < kIt; q++) {
             const int it = tid + q * TH;
-#ifndef LFBM5D_W2_LOAD_ROWFAST
             const int i = (int)__umulhi((unsigned)it, rcpNP), patch = it - i * NP;
-#else
-            const int patch = it >> 3, i = it & 7;
-#endif
             if (it < NP * 8) {
                 const bool ok = pos[patch] != 0xffffffffu;     /* empty SAI / never-filled table column: zeros */
                 v2f x[8];
@@ -911,27 +865,6 @@ __global__ __launch_bounds__(kDct8w2Threads) void k_group_dct8w2(GroupArgs a) {
     PHASE_MARK();
     /* 5b: inverse transform along the rows + store: filt[g][n][st][c][64].  Items are numbered row-fastest: the eight
      * lanes that hold the rows of one patch write its 256 contiguous bytes */
-#ifdef LFBM5D_W2_ROWS_PAIRED
-    for (int it = tid; it < NPh * 8; it += TH) {
-        const int i = it / NPh, pa = it - i * NPh;
-        const int pb = pa + NPh;
-        const bool has_b = pb < NP;
-        const float* ra = stackf + 2 * ((i * 8) * NPp + pa) + 1;
-        const float* rb = stackf + 2 * ((i * 8) * NPp + (has_b ? pb : pa)) + 1;
-        v2f x[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) x[j] = v2f{ra[2 * j * NPp], rb[2 * j * NPp]};
-        dct8_inv_t(x);
-        float4* oa = reinterpret_cast<float4*>(a.filt + ((size_t)g * N * A + pa) * a.C * K2 + (size_t)c * K2 + i * 8);
-        filt_put4(&oa[0], make_float4(x[0].x, x[1].x, x[2].x, x[3].x));
-        filt_put4(&oa[1], make_float4(x[4].x, x[5].x, x[6].x, x[7].x));
-        if (has_b) {
-            float4* ob = reinterpret_cast<float4*>(a.filt + ((size_t)g * N * A + pb) * a.C * K2 + (size_t)c * K2 + i * 8);
-            filt_put4(&ob[0], make_float4(x[0].y, x[1].y, x[2].y, x[3].y));
-            filt_put4(&ob[1], make_float4(x[4].y, x[5].y, x[6].y, x[7].y));
-        }
-    }
-#else
     for (int it = tid; it < NP * 8; it += TH) {
         const int patch = it >> 3, i = it & 7;
         const float* ra = stackf + 2 * ((i * 8) * NPp + patch) + 1;
@@ -943,7 +876,6 @@ __global__ __launch_bounds__(kDct8w2Threads) void k_group_dct8w2(GroupArgs a) {
         filt_put4(&oa[0], make_float4(x[0], x[1], x[2], x[3]));
         filt_put4(&oa[1], make_float4(x[4], x[5], x[6], x[7]));
     }
-#endif
 #ifdef LFBM5D_PHASE_TIMING
     PHASE_MARK();
     if (tid == 0) {
@@ -970,10 +902,7 @@ __global__ __launch_bounds__(kDct8w2Threads) void k_group_dct8w2(GroupArgs a) {
  * Stack [pq][patch] floats, row stride 146: pairs of patches are 8-byte aligned, and 146 = 18 mod 32 with the lane
  * numbering of the fibre phases (16 values of pq x 2 neighbours in n or st) touches 32 distinct banks.
  * ------------------------------------------------------------------------------------------ */
-#ifndef LFBM5D_DCT8W3_THREADS
-#define LFBM5D_DCT8W3_THREADS 256
-#endif
-constexpr int kDct8w3Threads = LFBM5D_DCT8W3_THREADS;
+constexpr int kDct8w3Threads = 256;
 constexpr int kW3Stride = 146;
 constexpr unsigned kW3Lds = 64 * kW3Stride * sizeof(float);
 constexpr unsigned kW3Empty = 0xf0000000u;   /* byte offset of an absent patch: beyond any window this kernel is launched on */
@@ -993,12 +922,7 @@ __device__ __forceinline__ void w3_load_rows(__amdgpu_buffer_rsrc_t img, unsigne
         if (it < NPh * 8) {
             const int i = it / NPh, pp = it - i * NPh;
             const int pA = 2 * pp, pB = pA + 1 < NP ? pA + 1 : pA;
-#if defined(LFBM5D_W3_EXP) && (LFBM5D_W3_EXP & 4)   /* timing experiment: the same loads at consecutive addresses (eight lines per instruction instead of 64) */
-            const int oa = (int)((pos[0] & ~15u) + (unsigned)((tid & 63) * 64 + q * 4096)), ob = oa + 32;
-            (void)pA; (void)pB; (void)i;
-#else
             const int oa = (int)(pos[pA] + (unsigned)i * row_bytes), ob = (int)(pos[pB] + (unsigned)i * row_bytes);
-#endif
             r.ra0[q] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(img, oa, 0, 0));
             r.ra1[q] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(img, oa + 16, 0, 0));
             r.rb0[q] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(img, ob, 0, 0));
@@ -1409,30 +1333,20 @@ __device__ __forceinline__ void w3_body_u(const GroupArgs& a, float* S, const un
 #pragma unroll
         for (int j = 0; j < 8; j++) x[j] = v2f{ra[j * NPf], ra[j * NPf + (NP > NPh ? NPh : 0)]};
         dct8_inv_t(x);
-#if defined(LFBM5D_W3_EXP) && (LFBM5D_W3_EXP & 2)   /* timing experiment: the whole workgroup stores into one patch's 256 bytes (no HBM write stream) */
-        v4f* oa = reinterpret_cast<v4f*>(a.filt + (size_t)g * N * A * a.C * K2 + i * 8);
-#else
         v4f* oa = reinterpret_cast<v4f*>(a.filt + ((size_t)g * N * A + pa) * a.C * K2 + (size_t)c * K2 + i * 8);
-#endif
         filt_put4_nt(oa, v4f{x[0].x, x[1].x, x[2].x, x[3].x});
         filt_put4_nt(oa + 1, v4f{x[4].x, x[5].x, x[6].x, x[7].x});
         if (has_b) {
-#if defined(LFBM5D_W3_EXP) && (LFBM5D_W3_EXP & 2)
-            v4f* ob = oa;
-#else
             v4f* ob = oa + (size_t)NPh * a.C * (K2 / 4);
-#endif
             filt_put4_nt(ob, v4f{x[0].y, x[1].y, x[2].y, x[3].y});
             filt_put4_nt(ob + 1, v4f{x[4].y, x[5].y, x[6].y, x[7].y});
         }
     }
 }
 
-#ifndef LFBM5D_W3SA_WAVES
-#define LFBM5D_W3SA_WAVES 4   /* 128 VGPRs (a few spills): four workgroups per CU beat 129 without */
-#endif
+constexpr int kW3SaWaves = 4;   /* 128 VGPRs (a few spills): four workgroups per CU beat 129 without */
 template <bool SA>   /* SA: for windows with an empty SAI (every group shape-adaptive): the transform inline, in registers */
-__global__ __launch_bounds__(kDct8w3Threads) __attribute__((amdgpu_waves_per_eu(SA ? LFBM5D_W3SA_WAVES : 1))) void k_group_dct8w3(GroupArgs a) {
+__global__ __launch_bounds__(kDct8w3Threads) __attribute__((amdgpu_waves_per_eu(SA ? kW3SaWaves : 1))) void k_group_dct8w3(GroupArgs a) {
     extern __shared__ float lds[];
     __shared__ float red[3][kDct8w3Threads / 64];
     __shared__ unsigned pos[kMaxN * kA3];
@@ -1449,9 +1363,6 @@ __global__ __launch_bounds__(kDct8w3Threads) __attribute__((amdgpu_waves_per_eu(
         pos[i] = p != 0xffffffffu ? (((unsigned)(i % 9) * a.C + c) * plane + p) * 4u : kW3Empty;
     }
     __syncthreads();
-#ifdef LFBM5D_W3_ONLY16
-    w3_body<16, TH, SA>(a, lds, pos, red, tid, g, c); return;
-#endif
     switch (nSx) {
         case 1:  w3_body<1, TH, SA>(a, lds, pos, red, tid, g, c); break;
         case 2:  w3_body<2, TH, SA>(a, lds, pos, red, tid, g, c); break;
@@ -1462,14 +1373,7 @@ __global__ __launch_bounds__(kDct8w3Threads) __attribute__((amdgpu_waves_per_eu(
 }
 
 /* ordinary windows (round 6): full-shape groups on the unnormalised chain, the listed shape-adaptive ones left to k_group_dct8w3_list */
-#ifndef LFBM5D_W3U_WAVES
-#define LFBM5D_W3U_WAVES 0
-#endif
-#if LFBM5D_W3U_WAVES > 0
-__global__ __launch_bounds__(kDct8w3Threads) __attribute__((amdgpu_waves_per_eu(LFBM5D_W3U_WAVES, LFBM5D_W3U_WAVES))) void k_group_dct8w3_u(GroupArgs a) {
-#else
 __global__ __launch_bounds__(kDct8w3Threads) void k_group_dct8w3_u(GroupArgs a) {
-#endif
     extern __shared__ float lds[];
     __shared__ float red[3][kDct8w3Threads / 64];
     __shared__ unsigned pos[kMaxN * kA3];
@@ -1485,9 +1389,6 @@ __global__ __launch_bounds__(kDct8w3Threads) void k_group_dct8w3_u(GroupArgs a) 
     for (int i = tid; i < nSx * 9; i += TH) {
         const unsigned p = a.gpos[(size_t)g * a.N * 9 + i];
         pos[i] = p != 0xffffffffu ? (((unsigned)(i % 9) * a.C + c) * plane + p) * 4u : kW3Empty;
-#if defined(LFBM5D_W3_EXP) && (LFBM5D_W3_EXP & 1)   /* timing experiment: every patch absent -- the gathers go out of range and move nothing */
-        pos[i] = kW3Empty;
-#endif
     }
     __syncthreads();
     switch (nSx) {
@@ -1680,9 +1581,9 @@ __global__ __launch_bounds__(64 * kBm3dWaves) void k_group_bm3d8(GroupArgs a) {
 
 hipError_t prepare_group_wiener() {
     const void* fns[] = {
-        reinterpret_cast<const void*>(&k_group_dct8<1>),
+        reinterpret_cast<const void*>(&k_group_dct8),
         reinterpret_cast<const void*>(&k_group_dct8w2<true>), reinterpret_cast<const void*>(&k_group_dct8w2<false>),
-        reinterpret_cast<const void*>(&k_group_dct8w<true, true>), reinterpret_cast<const void*>(&k_group_dct8w<false, true>),
+        reinterpret_cast<const void*>(&k_group_dct8w<true>), reinterpret_cast<const void*>(&k_group_dct8w<false>),
         reinterpret_cast<const void*>(&k_group_bm3d8<2, true>), reinterpret_cast<const void*>(&k_group_bm3d8<2, false>)};
     for (const void* f : fns) {
         const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kDedicatedLdsLimit);
@@ -1695,8 +1596,8 @@ hipError_t launch_group_wiener(hipStream_t s, const GroupArgs& a, bool all_sa, b
     *launched = true;
     if (a.tau2 == 7 && a.k == 8 && a.A == 9 && a.step == 2 && a.N <= (unsigned)kMaxN) {   /* 8x8 bior1.5, Wiener step: round 1's kernel with the wavelet in its 2-D stage */
         const size_t l8 = (size_t)2 * 64 * ((a.N * 9) | 1) * sizeof(float);
-        if (a.tau5 == 9) hipLaunchKernelGGL((k_group_dct8w<true, true>), dim3(a.n_groups, a.C), dim3(kDct8wThreads), l8, s, a);
-        else             hipLaunchKernelGGL((k_group_dct8w<false, true>), dim3(a.n_groups, a.C), dim3(kDct8wThreads), l8, s, a);
+        if (a.tau5 == 9) hipLaunchKernelGGL((k_group_dct8w<true>), dim3(a.n_groups, a.C), dim3(kDct8wThreads), l8, s, a);
+        else             hipLaunchKernelGGL((k_group_dct8w<false>), dim3(a.n_groups, a.C), dim3(kDct8wThreads), l8, s, a);
         return hipGetLastError();
     }
     if (a.tau2 == 5 && a.k == 8 && a.A == 9 && a.N <= (unsigned)kMaxN) {   /* 8x8 DCT */
@@ -1704,26 +1605,21 @@ hipError_t launch_group_wiener(hipStream_t s, const GroupArgs& a, bool all_sa, b
         if (a.step == 2) {
             const unsigned gx = ((a.n_groups + 7) / 8) * 8;   /* xcd_group_index */
             /* the README's Wiener step: k_group_dct8w3.  Its two-image predecessor k_group_dct8w2 stays for Hadamard / DCT fibres and for
-             * windows of 1.9 GB and more (32-bit offsets); option dct8w_v2: test hook, that kernel for every configuration.  (Round 1's
-             * k_group_dct8w and the unpacked k_group_dct8<2> were retired as Wiener DCT kernels in round 5: nothing selected them.) */
+             * windows of 1.9 GB and more (32-bit offsets); option dct8w_v2: test hook, that kernel for every configuration.  */
             if (a.tau5 == 9 && (size_t)9 * a.C * a.Wb * a.Hb * 4 < 0x70000000ull && !(a.opt & kOptDct8wV2)) {
                 if (all_sa) hipLaunchKernelGGL(k_group_dct8w3<true>, dim3(gx, a.C), dim3(kDct8w3Threads), kW3Lds, s, a);
-#ifdef LFBM5D_W3_NORMALISED   /* build flag: round 3-5's normalised body for every group (A/B runs) */
-                else        hipLaunchKernelGGL(k_group_dct8w3<false>, dim3(gx, a.C), dim3(kDct8w3Threads), kW3Lds, s, a);
-#else
                 else if (a.tau4 == 5 || a.tau4 == 6) {
                     if (!a.sa_list) return hipErrorInvalidValue;
                     hipLaunchKernelGGL(k_group_dct8w3_u, dim3(gx, a.C), dim3(kDct8w3Threads), kW3Lds, s, a);
                     if (a.tau4 == 6) hipLaunchKernelGGL(k_group_dct8w3_list, dim3(kW3ListBlocks, a.C), dim3(kDct8w3Threads), kW3Lds, s, a);   /* the groups skipped above (usually none) */
                 }
                 else        hipLaunchKernelGGL(k_group_dct8w3<false>, dim3(gx, a.C), dim3(kDct8w3Threads), kW3Lds, s, a);   /* tau_4D = id */
-#endif
             }
             else if (a.tau5 == 9) hipLaunchKernelGGL((k_group_dct8w2<true>), dim3(gx, a.C), dim3(kDct8w2Threads), l8, s, a);
             else                  hipLaunchKernelGGL((k_group_dct8w2<false>), dim3(gx, a.C), dim3(kDct8w2Threads), l8, s, a);
             return hipGetLastError();
         }
-        hipLaunchKernelGGL(k_group_dct8<1>, dim3(a.n_groups, a.C), dim3(kDct8Threads), l8, s, a);   /* hard-thresholding step: one thread per patch for the 2-D stage */
+        hipLaunchKernelGGL(k_group_dct8, dim3(a.n_groups, a.C), dim3(kDct8Threads), l8, s, a);   /* hard-thresholding step: one thread per patch for the 2-D stage */
         return hipGetLastError();
     }
     if (a.bm3d && a.A == 1 && a.k == 8 && a.tau5 == 8 && (a.tau2 == 5 || a.tau2 == 7)) {   /* per-SAI BM3D, 8x8 patches: a group per wavefront */

@@ -16,13 +16,9 @@
  * (profiles/r06_a_nt_filt_ab.txt): non-temporal STORES take k_group_id_haar from 0.93-1.06 to 0.81-0.85 ms per pass and k_group_dct8w3
  * and both aggregation kernels 3 % down (the write stream no longer evicts the window rows the gathers of the same XCD re-read from
  * its L2); non-temporal LOADS in the aggregation cost it half its speed (a filtered row is read by two neighbouring tiles).
- * Build-time knobs for A/B runs (tools/build_variant_files.sh). */
-#ifndef LFBM5D_FILT_STORE_AUX
-#define LFBM5D_FILT_STORE_AUX 2
-#endif
-#ifndef LFBM5D_FILT_LOAD_AUX
-#define LFBM5D_FILT_LOAD_AUX 0
-#endif
+ */
+constexpr int kFiltStoreAux = 2;
+constexpr int kFiltLoadAux = 0;
 
 #if defined(__HIPCC__)
 /* Stores of filtered patches through global pointers.  The non-temporal form ONLY where a wave-instruction (or two back to back)
@@ -36,13 +32,7 @@ __device__ __forceinline__ void filt_put(float* p, const float v) { *p = v; }
 __device__ __forceinline__ void filt_put2(filt_v2f* p, const filt_v2f v) { *p = v; }
 __device__ __forceinline__ void filt_put4(filt_v4f* p, const filt_v4f v) { *p = v; }
 __device__ __forceinline__ void filt_put4(float4* p, const float4 v) { *p = v; }
-__device__ __forceinline__ void filt_put4_nt(filt_v4f* p, const filt_v4f v) {
-#if LFBM5D_FILT_STORE_AUX == 2
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
+__device__ __forceinline__ void filt_put4_nt(filt_v4f* p, const filt_v4f v) { __builtin_nontemporal_store(v, p); }
 #endif
 
 namespace lfbm5d {
@@ -258,7 +248,7 @@ struct ScanArgs {
     /* stereo */
     unsigned long long* dbg;    /* development builds (LFBM5D_PHASE_TIMING): phase clocks; else unused */
     unsigned opt;               /* kOpt* bits (lfbm5d_options.h): which table-kernel generation */
-    unsigned lds_cap;           /* > 0: LDS bytes the first-generation kernel may use (option scan_lds_cap) */
+    unsigned lds_cap;           /* option scan_lds_cap: no kernel reads it (it served a timing experiment; removing it changes every scan kernel's argument block) */
     float* tables;              /* [n_slots][Ns*Ns][stereo_table_stride]: strip-major [strip][row][64 columns] */
     unsigned st_of_slot[kBigA];
     /* second-generation kernel */

@@ -49,7 +49,7 @@ struct Options {
     int host_blocking = 0;          /* 1: host seam with four blocking copies of the light field (rounds 1-4) */
     int band_mb = 0;                /* > 0: cap of the filt buffer in MiB (passes beyond it run band by band) */
     int bm3d_lanes = 3;             /* SAIs of LFBM3Ddenoising processed concurrently */
-    int scan_lds_cap = 0;           /* > 0: LDS bytes the first-generation table kernel may use */
+    int scan_lds_cap = 0;           /* accepted, without effect (it served a timing experiment of development builds) */
     int force_redo = 0;             /* test hook: treat the graph as incomplete once (exercises the sequential redo) */
     int spatial_bands = 1;          /* 0: chosen by lfbm5d_auto_bands; S > 1, several ranks, lfbm5d_denoise_*: S teams of ranks, each denoises a horizontal band of every SAI (+ halo) on its own
                                      * window graph; NOT bit-identical to one GPU, PSNR within 1e-3 dB (lfbm5d_steps.hip) */

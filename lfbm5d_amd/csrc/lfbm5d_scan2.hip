@@ -43,22 +43,10 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 typedef int v4i __attribute__((ext_vector_type(4)));
 
 constexpr unsigned kRsrcFlags = 0x00020000u;
-/* development builds (tools/build_variant.sh ... -DLFBM5D_S2_EXP=bits): timing experiments, results are garbage.
- * 1: table stores go nowhere; 2: no hand-off column traffic; 4: no ring loads; 8 / 16: no self / no disparity tables */
-#ifndef LFBM5D_S2_EXP
-#define LFBM5D_S2_EXP 0
-#endif
 /* cache policy of the (value, order) pairs: written once here, read once by the arg-min -- non-temporal on both sides (round 6:
  * block matching 1-2 % shorter per pass, profiles/r06_a_nt_knobs_ab.txt; the estimate rows every workgroup's loader re-reads stay in L2) */
-#ifndef LFBM5D_PAIR_STORE_AUX
-#define LFBM5D_PAIR_STORE_AUX 2
-#endif
-#ifndef LFBM5D_PAIR_LOAD_NT
-#define LFBM5D_PAIR_LOAD_NT 1
-#endif
-#ifndef LFBM5D_S2_HAND_AUX
-#define LFBM5D_S2_HAND_AUX 17   /* sc0 sc1 */
-#endif
+constexpr int kPairStoreAux = 2;   /* aux operand of the pair stores: nt (k_stereo_argmin3 reads them with non-temporal loads) */
+constexpr int kS2HandAux = 17;     /* ... of the hand-off column loads: sc0 sc1 */
 constexpr int kLeadBytes = 32;   /* the image resource starts 8 floats in front of the first plane (the estimate buffer has 64 of slack) */
 
 template <int K> struct S2Geom {
@@ -86,10 +74,7 @@ __device__ __forceinline__ void lds_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-#ifndef LFBM5D_S2_NW
-#define LFBM5D_S2_NW 11
-#endif
-constexpr int kS2NW = LFBM5D_S2_NW;         /* tables (table waves) of a workgroup */
+constexpr int kS2NW = 11;         /* tables (table waves) of a workgroup */
 constexpr int kS2NL = 1;          /* ... and its loader wave: twelve waves, three per SIMD (the loader's instruction count per chunk is about a
                                    * table wave's, so every SIMD carries the same load and no wave idles at the chunk barrier), one workgroup per CU */
 constexpr int kS2NI = 6;          /* 16-byte pieces of a block of eight ring rows per loader lane: 64 * kS2NI >= 2 (CW1 + CW2) */
@@ -182,7 +167,7 @@ __device__ __forceinline__ void scan2_loader(const ScanArgs& a, const Scan2Wg& g
         };
         auto hand_load = [&](int q, int c) -> float {
             /* sc0 sc1: served by L2, never by this CU's L1 (the values were stored by the table waves of this workgroup) */
-            return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rLA, hbase[q] >= 0 ? hbase[q] + 32 * c : -1, 0, LFBM5D_S2_HAND_AUX));
+            return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rLA, hbase[q] >= 0 ? hbase[q] + 32 * c : -1, 0, kS2HandAux));
         };
         /* blocks 0 .. lead of either ring, the hand-off values of chunk 0; then kS2LD blocks / chunks in flight */
         for (int j = 0; j <= LEADM; j++) {
@@ -211,11 +196,10 @@ __device__ __forceinline__ void scan2_loader(const ScanArgs& a, const Scan2Wg& g
 #endif
         /* chunk cc: block cc + lead + 1 goes into the ring, the loads of block cc + lead + 1 + kS2LD start */
         auto chunk = [&](const int d, const int cc) {
-            if (LFBM5D_S2_EXP & 32) { lds_barrier(); return; }   /* experiment: a loader that only keeps the barrier count */
 #pragma unroll
             for (int k = 0; k < kS2NI; k++) {
                 piece_write(k, stg[d][k]);
-                if (!(LFBM5D_S2_EXP & 4)) stg[d][k] = piece_load(k, cc + (p1[k] ? LEAD1 : LEAD2) + 1 + kS2LD);
+                stg[d][k] = piece_load(k, cc + (p1[k] ? LEAD1 : LEAD2) + 1 + kS2LD);
             }
 #pragma unroll
             for (int q = 0; q < 2; q++) {
@@ -292,7 +276,7 @@ __device__ __forceinline__ void scan2_table(const ScanArgs& a, const Scan2Wg& g,
     const __amdgpu_buffer_rsrc_t rL = __builtin_amdgcn_make_buffer_rsrc((void*)lcolT, 0, live ? (int)(a.lcol_stride * 4) : 0, kRsrcFlags);
     const size_t tstride = (STEREO && !COMB) ? stereo_table_stride2(a.W, a.H, a.k, a.nDisp) : 0;
     float* table = (STEREO && !COMB) ? a.tables + (size_t)(g.slot * ncand + tb) * tstride : nullptr;
-    const __amdgpu_buffer_rsrc_t rT = __builtin_amdgcn_make_buffer_rsrc((void*)table, 0, (STEREO && !COMB && live && !(LFBM5D_S2_EXP & 1)) ? (int)(tstride * 4) : 0, kRsrcFlags);
+    const __amdgpu_buffer_rsrc_t rT = __builtin_amdgcn_make_buffer_rsrc((void*)table, 0, (STEREO && !COMB && live) ? (int)(tstride * 4) : 0, kRsrcFlags);
     /* COMB: the workgroup's (value, order) pairs [strip][chunk][512] and this table's edge array [rows][strips] */
     const unsigned NCH = stereo_part_chunks(a.H, a.k, a.nDisp);
     const size_t pstride = COMB ? stereo_part_stride(a.W, a.H, a.k, a.nDisp) : 0;
@@ -300,7 +284,7 @@ __device__ __forceinline__ void scan2_table(const ScanArgs& a, const Scan2Wg& g,
     const unsigned n_slots = STEREO ? a.n_stereo / (unsigned)ncand : 0;
     float* part = COMB ? a.tables + ((size_t)g.slot * a.nwg_slot + g.wgj) * pstride * 2 : nullptr;
     float* edge = COMB ? a.tables + (size_t)n_slots * a.nwg_slot * pstride * 2 + (size_t)(g.slot * ncand + tb) * estride : nullptr;
-    const __amdgpu_buffer_rsrc_t rP = __builtin_amdgcn_make_buffer_rsrc((void*)part, 0, (COMB && !(LFBM5D_S2_EXP & 1)) ? (int)(pstride * 8) : 0, kRsrcFlags);
+    const __amdgpu_buffer_rsrc_t rP = __builtin_amdgcn_make_buffer_rsrc((void*)part, 0, COMB ? (int)(pstride * 8) : 0, kRsrcFlags);
     const __amdgpu_buffer_rsrc_t rEd = __builtin_amdgcn_make_buffer_rsrc((void*)edge, 0, (COMB && live) ? (int)(estride * 4) : 0, kRsrcFlags);
     /* COMB: the scan order dj * Ns + di of the workgroup's tables (packed from wave 0) comes with the descriptor: scalar loads
      * (an array computed here ends up in scratch, indexed by a chain of selects) */
@@ -522,7 +506,7 @@ __device__ __forceinline__ void scan2_table(const ScanArgs& a, const Scan2Wg& g,
             const int bo = __builtin_amdgcn_ds_bpermute(bq << 2, ordv);
             typedef int v2i __attribute__((ext_vector_type(2)));
             const v2i pr = {__float_as_int(best), bo};
-            __builtin_amdgcn_raw_buffer_store_b64(pr, rP, rok ? (int)(((strip * NCH + cprev) * 512 + rp) * 8) : -1, 0, LFBM5D_PAIR_STORE_AUX);
+            __builtin_amdgcn_raw_buffer_store_b64(pr, rP, rok ? (int)(((strip * NCH + cprev) * 512 + rp) * 8) : -1, 0, kPairStoreAux);
         };
 
         /* chain flavours: steady -- every lane active on every step, every row in the band; edge (ramp-up, ramp-down, short
@@ -632,7 +616,7 @@ __device__ __forceinline__ void scan2_table(const ScanArgs& a, const Scan2Wg& g,
                         }
                     }
                     /* hand-off column for the next strip: rows 1 + t - 63 of this strip's last column */
-                    if (!(LFBM5D_S2_EXP & 2)) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, out), rL, voffL, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, out), rL, voffL, 0, 0);
                     voffL += 16;
                     if (!EDGE) S2_QMARK(1 + gq);
                 }
@@ -657,20 +641,18 @@ __device__ __forceinline__ void scan2_table(const ScanArgs& a, const Scan2Wg& g,
         run();
         if (COMB && nsteps > 0) reduce_chunk(((nsteps + 15) >> 4) * 2 - 1);   /* the last chunk's values (the barrier behind it has been passed) */
         row0_left = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(S0), last_lane));
-#ifdef LFBM5D_PHASE_TIMING
-#if LFBM5D_PHASE_TIMING >= 2
+#if defined(LFBM5D_PHASE_TIMING) && LFBM5D_PHASE_TIMING >= 2
         if (lane == 0 && a.dbg && live && STEREO) {
             for (int i = 0; i < 4; i++) atomicAdd(&a.dbg[i], (unsigned long long)tk[i]);
             atomicAdd(&a.dbg[4], 1ull);
             for (int i = 0; i < 3; i++) atomicAdd(&a.dbg[6 + i], (unsigned long long)tq[i]);
         }
-#else
+#elif defined(LFBM5D_PHASE_TIMING)
         if (lane == 0 && a.dbg && live) {
             const int base = STEREO ? 0 : 6;
             for (int i = 0; i < 4; i++) atomicAdd(&a.dbg[base + i], (unsigned long long)tk[i]);
             atomicAdd(&a.dbg[base + 4], 1ull);
         }
-#endif
 #endif
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -703,16 +685,8 @@ template <int K, bool COMB>
 __global__ __launch_bounds__((kS2NW + kS2NL) * 64) void k_bm_scan2(ScanArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds2[];
     const Scan2Wg& g = a.wgs[blockIdx.x];
-    if ((LFBM5D_S2_EXP & 8) && g.slot < 0) return;     /* experiments: disparity tables only / self tables only */
-    if ((LFBM5D_S2_EXP & 16) && g.slot >= 0) return;
-#ifdef LFBM5D_SCAN2_ONLY_STEREO
-    scan2_body<K, true, kS2NW, kS2NL, COMB>(a, g, lds2);
-#elif defined(LFBM5D_SCAN2_ONLY_SELF)
-    scan2_body<K, false, kS2NW, kS2NL, false>(a, g, lds2);
-#else
     if (g.slot >= 0) scan2_body<K, true, kS2NW, kS2NL, COMB>(a, g, lds2);
     else scan2_body<K, false, kS2NW, kS2NL, false>(a, g, lds2);
-#endif
 }
 
 /* argmin over the (2 nDisp+1)^2 displacement tables (core:3581-3608) in the second-generation layout
@@ -919,11 +893,7 @@ __global__ __launch_bounds__(256) void k_stereo_argmin3(Argmin3Args a) {
             v4f w8[16];
 #pragma unroll
             for (int u = 0; u < 16; u++) {
-#if LFBM5D_PAIR_LOAD_NT
                 w8[u] = __builtin_nontemporal_load(src + (size_t)min(j0 + u, a.nwg_slot - 1) * (pstride >> 1));
-#else
-                w8[u] = src[(size_t)min(j0 + u, a.nwg_slot - 1) * (pstride >> 1)];
-#endif
             }
 #pragma unroll
             for (int u = 0; u < 16; u++) {
