@@ -44,7 +44,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((VEC4 && TW 
     __shared__ float kai[WINDOWED ? 256 : 1];   /* Kaiser windows exist for 8x8 and 12x12 patches only (bm3d.cpp:1101-1146) */
     const int lane = threadIdx.x;
     /* XCD-aware renumbering: hardware deals consecutive workgroup ids round-robin to the 8 XCDs */
-    const unsigned gx = (a.Wb + TW - 1) / TW, gy = (a.Hb + TH - 1) / TH, total_wg = gx * gy * a.A;
+    /* direct form (AggArgs::direct): the tiles cover the W x H interior of the padded frame, from (nHW, nHW) */
+    const unsigned org = a.direct ? a.nHW : 0u, Wt = a.Wb - 2 * org, Ht = a.Hb - 2 * org;
+    const unsigned gx = (Wt + TW - 1) / TW, gy = (Ht + TH - 1) / TH, total_wg = gx * gy * a.A;
     const unsigned per_xcd = gridDim.x / 8;          /* the launch is rounded up to a multiple of 8 workgroups */
     const unsigned lin2 = (blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
     if (lin2 >= total_wg) return;
@@ -52,12 +54,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((VEC4 && TW 
     const int tile_y = (int)((lin2 / gx) % gy), tile_x = (int)(lin2 % gx);
     if (a.proc_bits.test((unsigned)st)) return;      /* procSAI[st] != 0: skipped (core:486) */
     if (!a.mask_bits.test((unsigned)st)) return;
-    const int tx0 = tile_x * TW, ty0 = tile_y * TH;
+    const int tx0 = (int)org + tile_x * TW, ty0 = (int)org + tile_y * TH;   /* padded coordinates, like aggpos */
     const int x = tx0 + lane % TW, y = ty0 + lane / TW;
-    const bool inside = x < (int)a.Wb && y < (int)a.Hb;
+    const bool inside = x < (int)(org + Wt) && y < (int)(org + Ht);
     const int k = a.k, k2 = k * k, C = a.C, N = a.N, A = a.A;
     const int logN = 31 - __builtin_clz((unsigned)N);   /* N is a power of two (lfbm5d_api.hip validate) */
-    const size_t plane = (size_t)a.Wb * a.Hb;
+    const size_t plane = (size_t)Wt * Ht;   /* of num / den: the padded window's, or (direct form) the light field's */
     const int reach = (st == (int)a.pst) ? (int)a.nSim : (int)a.nHW;
     if (WINDOWED) for (int i = lane; i < k2; i += 64) kai[i] = a.tb->kaiser[i];
 
@@ -89,7 +91,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((VEC4 && TW 
     if (n_cand == 0) return;
 
     float accn[3] = {0, 0, 0}, accd[3] = {0, 0, 0};
-    const size_t pix = (size_t)st * C * plane + (size_t)y * a.Wb + x;
+    const size_t pix = (a.direct ? (size_t)a.sai.st[st] * a.lf_stride : (size_t)st * C * plane) + (size_t)(y - (int)org) * Wt + (size_t)(x - (int)org);
     if (inside) for (int c = 0; c < C; c++) { accn[c] = a.num[pix + c * plane]; accd[c] = a.den[pix + c * plane]; }
 
     /* rr / ncols_span by multiplication: exact while rr < 2^20 / ncols_span (rr is a few hundred) */
@@ -291,7 +293,8 @@ hipError_t launch_aggregate(hipStream_t s, const AggArgs& a) {
     const bool wide = a.k >= 12;
     constexpr int kAgg16TW = 16, kAgg16TH = 4, kAgg8TW = 8, kAgg8TH = 8;   /* tile of the 16 x 16 / 8 x 8 patches */
     const unsigned tw = wide ? (a.k == 12 ? 16 : kAgg16TW) : (a.k == 8 ? kAgg8TW : 8), th = wide ? (a.k == 12 ? 4 : kAgg16TH) : (a.k == 8 ? kAgg8TH : 8);
-    const unsigned tiles = ((a.Wb + tw - 1) / tw) * ((a.Hb + th - 1) / th) * a.A;
+    const unsigned org = a.direct ? a.nHW : 0u;   /* direct form: tiles over the interior only */
+    const unsigned tiles = ((a.Wb - 2 * org + tw - 1) / tw) * ((a.Hb - 2 * org + th - 1) / th) * a.A;
     const dim3 grid(((tiles + 7) / 8) * 8), block(64);
     const bool big = (a.filt_sai_stride ? a.filt_sai_stride * sizeof(float) : a.filt_bytes) > 0xfffff000ull || (a.opt & kOptAgg64Bit);   /* option agg_64bit: exercise the 64-bit path in tests */
     /* four candidates per lane and 16-byte position loads when a reference patch's N matches come in fours (option agg_scalar_scan: the

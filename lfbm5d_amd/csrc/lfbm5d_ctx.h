@@ -113,6 +113,9 @@ struct lfbm5d_ctx {
      * re-uploading (and without the stream synchronisation an upload from a stack object needs) */
     GeomCache gc[2]; int gslot = 0;
     bool est_ready = false;                /* the caller of pass_impl has formed the matching estimate in `est` already (graph form) */
+    /* direct sums (graph form, single-pass windows): the next pass_impl on this context aggregates straight into the light field's
+     * num / den (AggArgs::direct) and reads nothing of its d_num / d_den arguments; consumed by that call like est_ready */
+    struct DirectSums { bool on = false; float* num = nullptr; float* den = nullptr; size_t lf_stride = 0; lfbm5d::SaiList sai; } direct;
     DevBuf est, refmap, scores, tables, self_idx, self_cnt, best, shape, filt, wgt, aggpos, gpos, gofs, gok, sa_list, gshape, counters, small, t_num, t_den, d_mask;
     /* step-level buffers (g_num2 / g_den2 / n2: second step of a two-step job; e_basic: an emulated rank's own basic estimate) */
     DevBuf g_num, g_den, g_num2, g_den2, n2, e_basic, w_noisy, w_basic, w_num, w_den, h2d_noisy, h2d_basic, h2d_out, d_own, gscratch;

@@ -127,14 +127,21 @@ int run_graph(lfbm5d_ctx* c, const GraphJob& J, const plan::Graph& G, const unsi
 
     struct Lane { lfbm5d_ctx* x; float* w_noisy; float* w_basic; float* w_num; float* w_den; unsigned* d_small; };
     struct RankState { int rank; lfbm5d_ctx* x; float* g_num[2]; float* g_den[2]; float* basic; std::vector<Lane> lanes; };
+    /* Every window of the graph has exactly one pass, and the next window on its SAIs pads again from the light field: the mirror ring
+     * of a window's sums is never read.  So the aggregation works straight on the light field's num / den (AggArgs::direct), tiles over
+     * the interior only, and a window has no padded sums at all -- no copies in k_window_begin, no copy back in k_window_end, which is
+     * left with the coverage count.  Same sums, bit for bit.  Option window_sums_padded restores the padded copies (tests, A/B runs). */
+    const bool direct = !c->opt->window_sums_padded;
     auto lane_buffers = [&](lfbm5d_ctx* x, Lane& L) -> int {
         HIPCK(c, x->w_noisy.reserve(imgb_max * sizeof(float)));
         if (any_step2) HIPCK(c, x->w_basic.reserve(imgb_max * sizeof(float)));
-        HIPCK(c, x->w_num.reserve(imgb_max * sizeof(float)));
-        HIPCK(c, x->w_den.reserve(imgb_max * sizeof(float)));
+        if (!direct) {
+            HIPCK(c, x->w_num.reserve(imgb_max * sizeof(float)));
+            HIPCK(c, x->w_den.reserve(imgb_max * sizeof(float)));
+        }
         HIPCK(c, x->small.reserve((asize + 8 + kWinCounters) * sizeof(unsigned)));
         L.x = x; L.w_noisy = x->w_noisy.as<float>(); L.w_basic = x->w_basic.as<float>();
-        L.w_num = x->w_num.as<float>(); L.w_den = x->w_den.as<float>(); L.d_small = x->small.as<unsigned>();
+        L.w_num = direct ? nullptr : x->w_num.as<float>(); L.w_den = direct ? nullptr : x->w_den.as<float>(); L.d_small = x->small.as<unsigned>();
         return 0;
     };
     /* lanes the schedule actually uses (a 3x3 light field is one window: no extra lane, no extra buffers) */
@@ -387,12 +394,13 @@ int run_graph(lfbm5d_ctx* c, const GraphJob& J, const plan::Graph& G, const unsi
             Pw.tau_4D = nd.tau4;
             Lw.x->gslot = sl;
             Lw.x->est_ready = true;
+            if (direct) { Lw.x->direct.on = true; Lw.x->direct.num = S->g_num[sl]; Lw.x->direct.den = S->g_den[sl]; Lw.x->direct.lf_stride = img; Lw.x->direct.sai = wl; }
             const int prc = pass_impl(Lw.x, J.step[sl], &Pw, g.asw, g.asw, g.wb, g.hb, C, Lw.w_noisy, wien ? Lw.w_basic : nullptr, Lw.w_num, Lw.w_den,
                                       mask_w.data(), proc_w.data(), cst_w, cst_w);
             Lw.x->gslot = 0;
             if (prc) { if (Lw.x != c) c->err = Lw.x->err; return 1; }
-            /* the window's sums back into the light field, and the coverage count of the pass (LF_denoised_percent,
-             * utilities_LF.cpp:967-995) -> pinned memory */
+            /* the window's sums back into the light field (direct form: they are there already), and the coverage count of the pass
+             * (LF_denoised_percent, utilities_LF.cpp:967-995) -> pinned memory */
             HIPCK(c, launch_window_end(ls, S->g_num[sl], S->g_den[sl], img, Lw.w_num, Lw.w_den, g.imgb, wl, W, H, C, g.nHW, J.P[sl]->k, Lw.d_small));
             HIPCK(c, hipMemcpyAsync(c->h_counts + (size_t)n * kWinCounters, Lw.d_small, kWinCounters * sizeof(unsigned), hipMemcpyDeviceToHost, ls));
             if (!nd.fin.empty()) {   /* two-step jobs: these SAIs' first-step sums are final -> their basic estimate as the second step reads it */

@@ -156,8 +156,11 @@ __device__ __forceinline__ size_t filt_patch(const GroupArgs& a, unsigned g, uns
 }
 
 
+/* all SAIs of an angular window in one launch: slot i of the window <-> SAI L.st[i] of the light field */
+struct SaiList { unsigned st[kBigA]; unsigned n; };
+
 struct AggArgs {
-    float* num;
+    float* num;                 /* [A][C][Hb][Wb] the window's mirror-padded sums; direct form: the LIGHT FIELD's sums [SAI][C][H][W] */
     float* den;
     const float* filt;               /* the launch's groups only: [g - ref_begin][N][A][C][k2], or SAI-major [A][g - ref_begin][N][C][k2] */
     unsigned long long filt_sai_stride;   /* 0: group-major; > 0: SAI-major, floats per SAI (GroupArgs::filt_sai_stride) */
@@ -178,6 +181,13 @@ struct AggArgs {
     unsigned irregular;         /* reference list is not the regular grid (subset path): scan every reference */
     unsigned opt;               /* kOpt* bits (lfbm5d_options.h) */
     unsigned wchan0;            /* every channel uses channel 0's group weight (sd_weighting of bm3d.cpp:1345-1373) */
+    /* Direct form (single-pass windows of the graph form): num / den are the light field's sums, H = Hb - 2 nHW rows of W = Wb - 2 nHW
+     * pixels per channel, lf_stride floats per SAI, window slot st <-> SAI sai.st[st].  Tiles cover the interior only, from (nHW, nHW)
+     * of the padded frame -- the mirror ring of a window's sums is never read once the window has had its only pass --; every
+     * position (aggpos, the tile tests) stays in padded coordinates, so each pixel adds the same terms in the same order. */
+    unsigned direct;
+    unsigned long long lf_stride;
+    SaiList sai;
 };
 
 /* Disparity score tables are laid out strip-major and SKEWED -- [strip of 64 columns][table row + lane][64] -- so that
@@ -278,8 +288,6 @@ hipError_t launch_crop(hipStream_t s, float* dst, const float* src, unsigned W, 
 /* est = den ? num/den : sub on `n` elements */
 hipError_t launch_estimate(hipStream_t s, const float* num, const float* den, const float* sub,
                            float* est, size_t n);
-/* all SAIs of an angular window in one launch: slot i of the window <-> SAI L.st[i] of the light field */
-struct SaiList { unsigned st[kBigA]; unsigned n; };
 /* two-step jobs: basic[st] = forward(inverse(den ? num / den : sub)) for the light-field SAIs L.st[0 .. L.n) (colour = 0: no
  * colour round trip); light fields with three channels of n_px pixels */
 hipError_t launch_finalize_multi(hipStream_t s, const float* num, const float* den, const float* sub, float* basic, size_t sai_stride,
@@ -301,7 +309,9 @@ hipError_t launch_unsymetrize_multi(hipStream_t s, float* dst, size_t dst_stride
  * window's SAIs and the channel-0 matching estimate from the padded sums (= launch_symetrize_multi x 3..4 + launch_estimate_multi),
  * zero[0 .. kWinCounters) cleared;  end: the window's sums back into the light field and the pass's coverage count added to
  * count[0 .. kWinCounters) -- partial counters, the count is their sum -- (= launch_unsymetrize_multi x 2 + launch_count_denoised).
- * lf_stride / w_stride: floats per SAI of the light field / window. */
+ * lf_stride / w_stride: floats per SAI of the light field / window.
+ * Direct form (w_num == w_den == NULL; the aggregation works on the light field's sums, AggArgs::direct): begin reads channel 0 of
+ * num / den only, for the estimate, and writes no sums; end only counts, from the light field's den, and writes nothing but the counters. */
 constexpr unsigned kWinCounters = 32;
 hipError_t launch_window_begin(hipStream_t s, const float* noisy, const float* basic, const float* num, const float* den, size_t lf_stride,
                                float* w_noisy, float* w_basic, float* w_num, float* w_den, float* est, size_t w_stride, const SaiList& L,

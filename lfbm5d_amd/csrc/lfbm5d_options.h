@@ -54,6 +54,8 @@ struct Options {
     int spatial_bands = 1;          /* 0: chosen by lfbm5d_auto_bands; S > 1, several ranks, lfbm5d_denoise_*: S teams of ranks, each denoises a horizontal band of every SAI (+ halo) on its own
                                      * window graph; NOT bit-identical to one GPU, PSNR within 1e-3 dB (lfbm5d_steps.hip) */
     int band_halo = 0;              /* rows of halo of a band; 0: nSim + nDisp + k of the wider step */
+    int window_sums_padded = 0;     /* 1: the graph form's windows aggregate into mirror-padded copies of num / den and copy them back (rounds 1-7; tests, A/B runs)
+                                     * instead of straight into the light field's sums; an empty value means off */
     unsigned kernels = 0;           /* kOpt* bits: kernel-generation selectors */
 };
 
@@ -69,6 +71,7 @@ inline const OptionKey* option_keys(size_t* n) {
         {"bm3d_lanes", "LFBM5D_BM3D_LANES", &Options::bm3d_lanes, 0}, {"scan_lds_cap", "LFBM5D_SCAN_LDS_CAP", &Options::scan_lds_cap, 0},
         {"force_redo", "LFBM5D_FORCE_REDO", &Options::force_redo, 0}, {"spatial_bands", "LFBM5D_SPATIAL_BANDS", &Options::spatial_bands, 0},
         {"band_halo", "LFBM5D_BAND_HALO", &Options::band_halo, 0},
+        {"window_sums_padded", "LFBM5D_WINDOW_SUMS_PADDED", &Options::window_sums_padded, 0},
         {"scan_v1", "LFBM5D_SCAN_V1", nullptr, kOptScanV1}, {"scan_any", "LFBM5D_SCAN_ANY", nullptr, kOptScanAny},
         {"scan_full_tables", "LFBM5D_SCAN_FULL_TABLES", nullptr, kOptScanFullTables}, {"dct8w_v2", "LFBM5D_DCT8W_V2", nullptr, kOptDct8wV2},
         {"group_generic", "LFBM5D_GROUP_GENERIC", nullptr, kOptGroupGeneric}, {"no_sa_kernels", "LFBM5D_NO_SA_KERNELS", nullptr, kOptNoSaKernels},

@@ -180,6 +180,8 @@ int pass_impl(lfbm5d_ctx* c, int step, const lfbm5d_params* P, unsigned aw, unsi
      * error return cannot leave it set for the next pass on this context */
     const bool est_ready = c->est_ready;
     c->est_ready = false;
+    const bool direct = c->direct.on;   /* (likewise) */
+    c->direct.on = false;
     if (validate(c, step, P, aw, ah, C, bm3d)) return 1;
     if (step == 2 && !d_basic) return fail(c, "step 2 needs the basic estimate");
     const unsigned A = aw * ah, k = P->k, k2 = k * k, N = P->N, nHW = P->nSim + P->nDisp;
@@ -204,6 +206,8 @@ int pass_impl(lfbm5d_ctx* c, int step, const lfbm5d_params* P, unsigned aw, unsi
 
     /* reference grid (core:149-156); cached while the geometry is unchanged */
     const bool centre = pst == cst;
+    /* the direct form is the graph's: a window's only pass, unsharded, its estimate formed by k_window_begin -- nothing below reads d_num / d_den then */
+    if (direct && (!centre || !est_ready || bm3d || c->pass_world != 1 || c->pass_reduce)) return fail(c, "direct sums: not a single-pass window of the graph form");
     const unsigned key[5] = {Wb, Hb, k, nHW, P->p};
     if (centre && (std::memcmp(key, gc.grid_key, sizeof(key)) != 0 || gc.last_refs_host.empty())) {
         std::vector<unsigned> rows, cols;
@@ -485,6 +489,9 @@ int pass_impl(lfbm5d_ctx* c, int step, const lfbm5d_params* P, unsigned aw, unsi
     aa.mask_bits = mask_bits; aa.proc_bits = proc_bits; aa.tau4 = P->tau_4D; aa.irregular = centre ? 0u : 1u;
     aa.wchan0 = (bm3d && P->useSD) ? 1u : 0u;
     aa.opt = c->opt->kernels;
+    if (direct) {   /* bands too: each band's launch adds its rows' patches to the light field's sums, in raster order like the padded form's */
+        aa.num = c->direct.num; aa.den = c->direct.den; aa.direct = 1u; aa.lf_stride = c->direct.lf_stride; aa.sai = c->direct.sai;
+    }
     /* wide windows: filt SAI-major (kernels.h filt_patch) -- per SAI the launch's groups, [g][n][c][k2] */
     const bool sai_major = A >= kSaiMajorMinA && !(c->opt->kernels & kOptFiltGroupMajor);
     const size_t per_group_bias = sai_major ? per_group / A : per_group;   /* what one group takes in front of the patch the kernels address */

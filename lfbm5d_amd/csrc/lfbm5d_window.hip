@@ -306,9 +306,13 @@ __global__ __launch_bounds__(256) void k_window_begin(WinBeginArgs a) {
     const size_t d_o = (size_t)blockIdx.z * a.w_stride + (size_t)yy * w + xx;
     const size_t sp = (size_t)a.W * a.H, dp = (size_t)w * h;
     float n0 = 0.0f, u0 = 0.0f, d0 = 0.0f, b0 = 0.0f;
+    const bool sums = a.w_num != nullptr;   /* direct form: the aggregation starts from the light field's sums itself */
     for (int c = 0; c < a.C; c++) {
-        const float nv = a.noisy[so + c * sp], uv = a.num[so + c * sp], dv = a.den[so + c * sp];
-        a.w_noisy[d_o + c * dp] = nv; a.w_num[d_o + c * dp] = uv; a.w_den[d_o + c * dp] = dv;
+        const float nv = a.noisy[so + c * sp];
+        float uv = 0.0f, dv = 0.0f;
+        if (sums || c == 0) { uv = a.num[so + c * sp]; dv = a.den[so + c * sp]; }
+        a.w_noisy[d_o + c * dp] = nv;
+        if (sums) { a.w_num[d_o + c * dp] = uv; a.w_den[d_o + c * dp] = dv; }
         float bv = 0.0f;
         if (a.basic) { bv = a.basic[so + c * sp]; a.w_basic[d_o + c * dp] = bv; }
         if (c == 0) { n0 = nv; u0 = uv; d0 = dv; b0 = bv; }
@@ -318,9 +322,10 @@ __global__ __launch_bounds__(256) void k_window_begin(WinBeginArgs a) {
 
 /* end: the window's sums back into the light field (unsymetrize, utilities.cpp:265-298, bm5d.cpp:388-396) and the coverage
  * count of the pass (LF_denoised_percent, utilities_LF.cpp:985-992: (i, j, c) triples with den > 0 over the (H-k+1) x (W-k+1)
- * patch origins) -- k_unsymetrize_multi x 2 + k_count_denoised.  Thread = one pixel of one SAI, all channels. */
+ * patch origins) -- k_unsymetrize_multi x 2 + k_count_denoised.  Thread = one pixel of one SAI, all channels.
+ * Direct form (w_num == w_den == NULL): the count alone, read from the light field's den. */
 struct WinEndArgs {
-    float* num; float* den; const float* w_num; const float* w_den;
+    float* num; float* den; const float* w_num; const float* w_den;   /* (direct form: w_num = w_den = NULL, num / den are only read) */
     size_t lf_stride, w_stride;
     SaiList L;
     int W, H, C, N, k;
@@ -344,6 +349,10 @@ __global__ __launch_bounds__(256) void k_window_end(WinEndArgs a) {
             const size_t d_o = (size_t)st * a.lf_stride + (size_t)y * a.W + x;
             const size_t so = (size_t)blockIdx.z * a.w_stride + (size_t)(y + a.N) * w + x + a.N;
             const bool counted = x < a.W - a.k + 1 && y < a.H - a.k + 1;
+            if (!a.w_den) {   /* direct form: the sums are in the light field already */
+                if (counted) for (int c = 0; c < a.C; c++) cnt += a.den[d_o + c * dp] > 0.0f ? 1u : 0u;
+                continue;
+            }
             for (int c = 0; c < a.C; c++) {
                 const float dv = a.w_den[so + c * sp];
                 a.num[d_o + c * dp] = a.w_num[so + c * sp];
