@@ -352,6 +352,68 @@ int lfbm5d_noise_level_host_sai(lfbm5d_ctx* ctx, const float* const* h_lf, const
  * receives the eigenvalues ascending.  Returns 1 on bad arguments (no message: there is no context). */
 int lfbm5d_noise_level_statistic(unsigned d, const double* cov, double* sigma, unsigned* components, double* h_eigen);
 
+/* ---- light-field super-resolution: the scheme of SR-LFBM5D (Alain & Smolic, ICIP 2018; the reference's README points to its "SR
+ * branch") with the operators below -- NOT that branch's output, whose blur models and stopping rule are not reproduced.  Iterative
+ * back-projection regularised by the hard-thresholding step: with y the low-resolution light field (w x h per SAI), s = scale and
+ * W = s w, H = s h,
+ *   x_0 = U y;   for k = 1..K:  z = x_{k-1} + beta U (y - D x_{k-1}),  x_k = basic estimate of lfbm5d_step1_device on z with
+ *   P.sigma = sigma_k = sigma_start (sigma_end / sigma_start)^((k-1)/(K-1)) (double; K = 1: sigma_start);
+ *   close_projection != 0:  out = x_K + beta U (y - D x_K), else out = x_K.
+ * The step runs exactly as lfbm5d_step1_device runs it (colour space, window graph, lanes, every option).  One GPU.
+ * Operators: separable; a 1-D operator from n_in to n_out samples is a tap table first[n_out] (signed), w[n_out][T], built in double
+ * and rounded to float:  out[X] = sum_{t<T} w[X][t] in[clamp(first[X]+t, 0, n_in-1)], t ascending, float32 (clamped at read time,
+ * weights not merged); 2-D: rows' table * plane * columns' table^T, horizontal pass first.  keys = the Keys cubic with a = -0.5.
+ *   U  (LFBM5D_SR_UP, n_out = s n_in): u = (X+0.5)/s - 0.5, first = floor(u) - 1, T = 4, w_t = keys(u - (first+t)).
+ *   D  (LFBM5D_SR_DOWN, n_out = n_in / s, n_in a multiple of s): u = (x+0.5) s - 0.5;
+ *      LFBM5D_SR_BICUBIC  (antialiased): taps j in [ceil(u-2s), floor(u+2s)], w_j = keys((u-j)/s);
+ *      LFBM5D_SR_GAUSSIAN (blur_sigma in (0, 5]): R = ceil(3 blur_sigma), taps j in [ceil(u-R), floor(u+R)], w_j = exp(-(u-j)^2 / (2 blur_sigma^2));
+ *      both normalised to sum 1 in double; T = the largest tap count (<= 32), shorter rows padded with zero weights.
+ * No atomics, fixed summation order: repeated calls return the same bits.  Planes of empty SAIs are neither read nor written. */
+#define LFBM5D_SR_BICUBIC  0
+#define LFBM5D_SR_GAUSSIAN 1
+#define LFBM5D_SR_UP       0
+#define LFBM5D_SR_DOWN     1
+typedef struct {
+    unsigned scale;             /* 2, 3 or 4                                                         */
+    unsigned kernel;            /* of D: LFBM5D_SR_BICUBIC | LFBM5D_SR_GAUSSIAN                      */
+    float    blur_sigma;        /* of the Gaussian D, in high-resolution pixels (bicubic: ignored)   */
+    unsigned iterations;        /* K >= 1                                                            */
+    float    sigma_start;       /* sigma_1 > 0                                                       */
+    float    sigma_end;         /* sigma_K, 0 < sigma_end <= sigma_start                             */
+    float    beta;              /* back-projection step, (0, 2]                                      */
+    unsigned close_projection;  /* != 0: one more back-projection behind the last filtered iterate   */
+} lfbm5d_sr_params;
+/* Host only: K = 12, sigma_start = 15 s, sigma_end = 2 s, beta = 1, bicubic D (blur_sigma = 0.4 s for callers that switch to the Gaussian),
+ * closing projection on -- the best of a sweep on ONE light field (profiles/sr_defaults.txt), not optimal beyond it.  Returns 1 on a
+ * scale outside 2..4. */
+int lfbm5d_sr_defaults(unsigned scale, lfbm5d_sr_params* out);
+/* Host only, needs no GPU: the tap table of one 1-D operator for n_in input samples.  *T receives the taps per output sample; first
+ * [n_out] and w [n_out * T] are filled when both are given and `cap` (floats w can hold) >= n_out * T; both NULL = query T.  Returns
+ * 1 (no message: there is no context) on rejected parameters (scale, kernel, blur_sigma), n_in = 0, n_in no multiple of s for D, or a
+ * table that does not fit. */
+int lfbm5d_sr_taps(unsigned op, const lfbm5d_sr_params* sr, unsigned n_in, int* first, float* w, unsigned* T, unsigned cap);
+/* Device buffers: d_low [asize][C*h*w], d_high [asize][C*H*W]; h_mask [asize] host (0 = empty SAI); C = 1 or 3; w, h = the LOW-resolution
+ * size.  up: d_high = U d_low.  down: d_low = D d_high.  backproject: d_high_z = d_high_x + beta U (d_low_y - D d_high_x) in exactly two
+ * launches (d_high_z may be d_high_x).  Rejected inputs (see lfbm5d_sr_params; a NULL buffer; a mask without a non-empty SAI) return 1
+ * with a message. */
+int lfbm5d_sr_up_device(lfbm5d_ctx* ctx, const lfbm5d_sr_params* sr, const float* d_low, const unsigned* h_mask, float* d_high,
+                        unsigned asize, unsigned w, unsigned h, unsigned C);
+int lfbm5d_sr_down_device(lfbm5d_ctx* ctx, const lfbm5d_sr_params* sr, const float* d_high, const unsigned* h_mask, float* d_low,
+                          unsigned asize, unsigned w, unsigned h, unsigned C);
+int lfbm5d_sr_backproject_device(lfbm5d_ctx* ctx, const lfbm5d_sr_params* sr, const float* d_low_y, const float* d_high_x,
+                                 const unsigned* h_mask, float* d_high_z, unsigned asize, unsigned w, unsigned h, unsigned C);
+/* The loop above.  P = the hard-thresholding parameters (P->sigma is ignored), an = half size of its angular search window; d_low is only
+ * read, d_high receives the result.  Scratch (one high- and one low-resolution light field) belongs to the context and is reused.
+ * Contexts with a communicator return 1. */
+int lfbm5d_superres_device(lfbm5d_ctx* ctx, const lfbm5d_sr_params* sr, const lfbm5d_params* P, const float* d_low, const unsigned* h_mask,
+                           float* d_high, unsigned ang_major, unsigned awidth, unsigned aheight, unsigned an, unsigned w, unsigned h,
+                           unsigned C);
+/* The same on host light fields, one pointer per SAI (NULL allowed for empty SAIs), staged through HBM with blocking copies:
+ * bit-identical to the device form. */
+int lfbm5d_superres_host_sai(lfbm5d_ctx* ctx, const lfbm5d_sr_params* sr, const lfbm5d_params* P, const float* const* h_low,
+                             const unsigned* h_mask, float* const* h_high, unsigned ang_major, unsigned awidth, unsigned aheight,
+                             unsigned an, unsigned w, unsigned h, unsigned C);
+
 /* ---- inspection of the last pass's block matching (parity tests) ----
  * n_refs reference patches in raster order; h_refs[n_refs] flat index i*Wb+j;
  * h_self_idx[n_refs*N], h_self_cnt[n_refs] (precompute_BM, core:3301);

@@ -19,6 +19,9 @@ ROWMAJOR, COLMAJOR = 11, 12
 TAU = {"id": ID, "dct": DCT, "sadct": SADCT, "bior": BIOR, "hw": HADAMARD, "haar": HAAR}
 COLOR_SPACE = {"yuv": YUV, "ycbcr": YCBCR, "opp": OPP, "rgb": RGB}
 UNIQUE_ID_BYTES = 128
+SR_BICUBIC, SR_GAUSSIAN = 0, 1
+SR_UP, SR_DOWN = 0, 1
+SR_KERNEL = {"bicubic": SR_BICUBIC, "gaussian": SR_GAUSSIAN}
 
 
 class LfBm5dError(RuntimeError):
@@ -55,6 +58,12 @@ class NoiseLevelStruct(C.Structure):
     """lfbm5d_noise_level: the blind noise-level estimate (include/lfbm5d.h)."""
     _fields_ = [("sigma", C.c_double), ("sigma_channel", C.c_double * 3), ("components", C.c_uint), ("patch", C.c_uint),
                 ("patches", C.c_ulonglong)]
+
+
+class SrParams(C.Structure):
+    """lfbm5d_sr_params: operators and loop of the super-resolution (include/lfbm5d.h)."""
+    _fields_ = [("scale", C.c_uint), ("kernel", C.c_uint), ("blur_sigma", C.c_float), ("iterations", C.c_uint),
+                ("sigma_start", C.c_float), ("sigma_end", C.c_float), ("beta", C.c_float), ("close_projection", C.c_uint)]
 
 
 class NoiseLevel(NamedTuple):
@@ -161,6 +170,15 @@ def lib():
         L.lfbm5d_noise_level_device.argtypes = [vp, fp, up] + [C.c_uint] * 5 + [np_, dp, dp]
         L.lfbm5d_noise_level_host_sai.argtypes = [vp, fp, up] + [C.c_uint] * 5 + [np_, dp, dp]
         L.lfbm5d_noise_level_statistic.argtypes = [C.c_uint, dp, dp, up, dp]
+    if hasattr(L, "lfbm5d_superres_device"):   # (absent from older builds loaded through LFBM5D_HIP_LIB for A/B runs)
+        sp, pp = C.POINTER(SrParams), C.POINTER(Params)
+        L.lfbm5d_sr_defaults.argtypes = [C.c_uint, sp]
+        L.lfbm5d_sr_taps.argtypes = [C.c_uint, sp, C.c_uint, vp, vp, up, C.c_uint]
+        L.lfbm5d_sr_up_device.argtypes = [vp, sp, fp, up, fp] + [C.c_uint] * 4
+        L.lfbm5d_sr_down_device.argtypes = [vp, sp, fp, up, fp] + [C.c_uint] * 4
+        L.lfbm5d_sr_backproject_device.argtypes = [vp, sp, fp, fp, up, fp] + [C.c_uint] * 4
+        L.lfbm5d_superres_device.argtypes = [vp, sp, pp, fp, up, fp] + [C.c_uint] * 7
+        L.lfbm5d_superres_host_sai.argtypes = [vp, sp, pp, fp, up, fp] + [C.c_uint] * 7
     L.lfbm5d_malloc.argtypes = [C.POINTER(vp), C.c_size_t]
     L.lfbm5d_free.argtypes = [vp]
     L.lfbm5d_memcpy_h2d.argtypes = [vp, vp, C.c_size_t]
@@ -249,6 +267,35 @@ def noise_level_statistic(cov):
     if lib().lfbm5d_noise_level_statistic(d, cov.ctypes.data_as(dp), C.byref(sig), C.byref(m), lam.ctypes.data_as(dp)) != 0:
         raise LfBm5dError("lfbm5d_noise_level_statistic: bad arguments (d must be 1..64)")
     return sig.value, m.value, lam
+
+
+def sr_defaults(scale, /, **changes):
+    """lfbm5d_sr_defaults (host only): the SrParams the library starts from for `scale`; keyword arguments replace fields
+    (kernel may be "bicubic" / "gaussian")."""
+    sr = SrParams()
+    if lib().lfbm5d_sr_defaults(int(scale), C.byref(sr)) != 0:
+        raise LfBm5dError("lfbm5d_sr_defaults: scale must be 2, 3 or 4")
+    for k, v in changes.items():
+        if k == "kernel" and isinstance(v, str):
+            v = SR_KERNEL[v]
+        if k not in dict(SrParams._fields_):
+            raise LfBm5dError(f"SrParams has no field {k}")
+        setattr(sr, k, v)
+    return sr
+
+
+def sr_taps(op, sr, n_in):
+    """lfbm5d_sr_taps (host only, no GPU): (first int32 [n_out], w float32 [n_out][T]) of the 1-D operator `op` (SR_UP / SR_DOWN or
+    "up" / "down") for n_in input samples."""
+    op = {"up": SR_UP, "down": SR_DOWN}.get(op, op)
+    T = C.c_uint(0)
+    if lib().lfbm5d_sr_taps(int(op), C.byref(sr), int(n_in), None, None, C.byref(T), 0) != 0:
+        raise LfBm5dError("lfbm5d_sr_taps: rejected parameters (scale, kernel, blur_sigma, n_in)")
+    n_out = int(n_in) * sr.scale if op == SR_UP else int(n_in) // sr.scale
+    first, w = np.zeros(n_out, np.int32), np.zeros((n_out, T.value), np.float32)
+    if lib().lfbm5d_sr_taps(int(op), C.byref(sr), int(n_in), first.ctypes.data, w.ctypes.data, C.byref(T), w.size) != 0:
+        raise LfBm5dError("lfbm5d_sr_taps failed")
+    return first, w
 
 
 def shard_rows(n_rows, rank, world):
@@ -504,6 +551,40 @@ class Context:
         return NoiseLevel(res.sigma, tuple(res.sigma_channel[:C_]), int(res.components), int(res.patches), eig[:int(res.patch) ** 2],
                           sai[:asize] if per_sai else None)
 
+    # ---- super-resolution ----
+    def _sr_tail(self, mask, w, h, Cc):
+        m = _u32(mask)
+        return m, m.ctypes.data_as(C.POINTER(C.c_uint)), (m.size, int(w), int(h), int(Cc))
+
+    def sr_up(self, sr, low, mask, high, w, h, Cc):
+        """high = U low (lfbm5d_sr_up_device): CUDA float32 tensors [asize][C*h*w] -> [asize][C*sh*sw]; w, h = the low-resolution size."""
+        m, mp, tail = self._sr_tail(mask, w, h, Cc)
+        self._ck(self._L.lfbm5d_sr_up_device(self._h, C.byref(sr), _dev_ptr(low), mp, _dev_ptr(high), *tail))
+
+    def sr_down(self, sr, high, mask, low, w, h, Cc):
+        """low = D high (lfbm5d_sr_down_device)."""
+        m, mp, tail = self._sr_tail(mask, w, h, Cc)
+        self._ck(self._L.lfbm5d_sr_down_device(self._h, C.byref(sr), _dev_ptr(high), mp, _dev_ptr(low), *tail))
+
+    def sr_backproject(self, sr, low_y, high_x, mask, high_z, w, h, Cc):
+        """high_z = high_x + beta U (low_y - D high_x) in two launches (lfbm5d_sr_backproject_device); high_z may be high_x."""
+        m, mp, tail = self._sr_tail(mask, w, h, Cc)
+        self._ck(self._L.lfbm5d_sr_backproject_device(self._h, C.byref(sr), _dev_ptr(low_y), _dev_ptr(high_x), mp, _dev_ptr(high_z), *tail))
+
+    def superres(self, sr, P, low, mask, high, ang_major, awidth, aheight, an, w, h, Cc):
+        """Super-resolve `low` into `high` (lfbm5d_superres_*, include/lfbm5d.h): CUDA float32 tensors (device form), or float32 numpy
+        arrays / lists of per-SAI arrays (host form, staged through HBM; bit-identical).  P: the hard-thresholding parameters (sigma
+        ignored); w, h: the low-resolution size."""
+        m = _u32(mask)
+        mp = m.ctypes.data_as(C.POINTER(C.c_uint))
+        tail = (ang_major, awidth, aheight, an, int(w), int(h), int(Cc))
+        if isinstance(low, (list, tuple, np.ndarray)):
+            lo = list(low) if isinstance(low, (list, tuple)) else [a for a in low]
+            hi = list(high) if isinstance(high, (list, tuple)) else [a for a in high]
+            self._ck(self._L.lfbm5d_superres_host_sai(self._h, C.byref(sr), C.byref(P), _sai_ptrs(lo, m), mp, _sai_ptrs(hi, m), *tail))
+        else:
+            self._ck(self._L.lfbm5d_superres_device(self._h, C.byref(sr), C.byref(P), _dev_ptr(low), mp, _dev_ptr(high), *tail))
+
     def last_windows(self):
         """Processed SAI of every window the last step call ran, in order."""
         n = self._L.lfbm5d_last_windows(self._h, None, 0)
@@ -612,6 +693,12 @@ def noise_level(LF, LF_SAI_mask, width, height, chnls, patch=8, per_sai=False, c
     return (ctx or _ctx()).noise_level(LF, LF_SAI_mask, width, height, chnls, patch, per_sai)
 
 
+def superres(sr, P, low, mask, high, ang_major, awidth, aheight, an, w, h, chnls, ctx=None):
+    """Context.superres on the default context (device 0)."""
+    (ctx or _ctx()).superres(sr, P, low, mask, high, ang_major, awidth, aheight, an, w, h, chnls)
+    return 0
+
+
 _TAU = {"id": 4, "dct": 5, "sadct": 6, "bior": 7, "hw": 8, "hadamard": 8, "haar": 9}
 _CS = {"yuv": 0, "ycbcr": 1, "opp": 2, "rgb": 3}
 
@@ -643,3 +730,25 @@ def dropin_probe(noisy, mask, awidth, aheight, width, height, chnls, sigma, lamb
     if rc != 0:
         raise LfBm5dError("drop-in probe failed (message on stdout)")
     return ms, n_out, b_out, d_out
+
+
+def superres_probe(low, mask, awidth, aheight, width, height, chnls, sr, lambda_, hard, color_space="opp", ang_major=ROWMAJOR, an=1):
+    """The C++ drop-in's superres_LF (liblfbm5d_dropin.so, run_bm5d.h) on vector<vector<float>> light fields built from `low`
+    [asize][chnls*height*width]; hard = (N, nSim, nDisp, k, p, tau_2D, tau_4D, tau_5D[, useSD]).  Returns the high-resolution light field."""
+    path = os.path.join(os.path.dirname(library_path()), "liblfbm5d_dropin.so")
+    if not os.path.exists(path):
+        raise LfBm5dError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
+    D = C.CDLL(path)
+    D.lfbm5d_superres_probe.argtypes = [C.c_void_p] * 3 + [C.c_uint] * 7 + [C.c_void_p] * 3 + [C.c_uint]
+    t = tuple(hard)
+    hv = np.array([t[0], t[1], t[2], t[3], t[4], int(t[8]) if len(t) > 8 else 0, _TAU[t[5]], _TAU[t[6]], _TAU[t[7]]], np.uint32)
+    low = np.ascontiguousarray(low, np.float32)
+    m = _u32(mask)
+    out = np.zeros((low.shape[0], low[0].size * sr.scale * sr.scale), np.float32)
+    su = np.array([sr.scale, sr.kernel, sr.iterations], np.uint32)
+    sf = np.array([sr.blur_sigma, sr.sigma_start, sr.sigma_end, lambda_], np.float32)
+    rc = D.lfbm5d_superres_probe(low.ctypes.data, m.ctypes.data, out.ctypes.data, ang_major, awidth, aheight, an, width, height, chnls,
+                                 su.ctypes.data, sf.ctypes.data, hv.ctypes.data, _CS[color_space] if isinstance(color_space, str) else int(color_space))
+    if rc != 0:
+        raise LfBm5dError("superres_LF failed (message on stdout)")
+    return out

@@ -75,6 +75,7 @@ void lfbm5d_destroy(lfbm5d_ctx* c) {
                       &c->w_basic, &c->w_num, &c->w_den, &c->h2d_noisy, &c->h2d_basic, &c->h2d_out, &c->d_own, &c->gscratch, &c->scan_lcol};
     for (DevBuf* b : bufs) b->release();
     c->noise.sai.release(); c->noise.part.release(); c->noise.cells.release(); c->noise.m.release(); c->noise.pool.release();
+    c->sr.sai.release(); c->sr.tab.release(); c->sr.hi.release(); c->sr.lo.release();
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     if (c->h_small) (void)hipHostFree(c->h_small);
     if (c->stream) (void)hipStreamDestroy(c->stream);

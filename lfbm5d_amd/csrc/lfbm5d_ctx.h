@@ -143,6 +143,13 @@ struct lfbm5d_ctx {
     unsigned* h_small = nullptr; /* pinned, 64 uints */
     /* noise-level estimate (lfbm5d_noise.hip): non-empty SAI list, bulk partial sums, lag cells, centred scatters, pooled covariances */
     struct NoiseBufs { DevBuf sai, part, cells, m, pool; } noise;
+    /* super-resolution (lfbm5d_resample.hip): non-empty SAI list, the tap tables of U and D for the geometry in `key` (host copy, word
+     * offsets of first / w of Ux, Uy, Dx, Dy, their tap counts), the loop's scratch: one high- and one low-resolution light field */
+    struct SrBufs {
+        DevBuf sai, tab, hi, lo;
+        std::vector<unsigned> sai_host, host;
+        unsigned key[5] = {0, 0, 0, 0, 0}; size_t off[8] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned T[4] = {0, 0, 0, 0};
+    } sr;
     /* window lanes (run_step, pipelined form): extra contexts on the same device, each with its own stream, window
      * buffers and per-pass work buffers; owned by this context */
     std::vector<lfbm5d_ctx*> lanes;

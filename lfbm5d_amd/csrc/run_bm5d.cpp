@@ -206,6 +206,59 @@ int noise_level_LF(const std::vector<std::vector<float> >& LF, const std::vector
     return EXIT_SUCCESS;
 }
 
+/* super-resolution on the caller's vectors (one pointer per SAI, no flat copy) */
+int superres_LF(const std::vector<std::vector<float> >& LF_low, const std::vector<unsigned>& LF_SAI_mask, std::vector<std::vector<float> >& LF_high,
+                const unsigned ang_major, const unsigned awidth, const unsigned aheight, const unsigned anHard, const unsigned width,
+                const unsigned height, const unsigned chnls, const unsigned scale, const unsigned kernel, const float blurSigma,
+                const unsigned iterations, const float sigmaStart, const float sigmaEnd, const float lambdaHard5D, const unsigned NHard,
+                const unsigned nSim, const unsigned nDisp, const unsigned kHard, const unsigned pHard, const bool useSD, const unsigned tau_2D,
+                unsigned tau_4D, const unsigned tau_5D, const unsigned color_space) {
+    const unsigned asize = awidth * aheight;
+    if (LF_low.size() != asize || LF_SAI_mask.size() != asize) {
+        std::cout << "superres_LF: light field and mask must hold awidth*aheight SAIs" << std::endl;
+        return EXIT_FAILURE;
+    }
+    lfbm5d_sr_params sr;
+    if (lfbm5d_sr_defaults(scale, &sr) != 0) { std::cout << "superres_LF: scale must be 2, 3 or 4" << std::endl; return EXIT_FAILURE; }
+    sr.kernel = kernel;
+    if (kernel == LFBM5D_SR_GAUSSIAN) sr.blur_sigma = blurSigma;
+    if (iterations) sr.iterations = iterations;
+    if (sigmaStart != 0.0f) sr.sigma_start = sigmaStart;
+    if (sigmaEnd != 0.0f) sr.sigma_end = sigmaEnd;
+    lfbm5d_ctx* ctx = context();
+    if (!ctx) return EXIT_FAILURE;
+    if (LF_high.size() != asize) LF_high.resize(asize);
+    const size_t lo = (size_t)width * height * chnls, hi = lo * scale * scale;
+    std::vector<const float*> low(asize, nullptr);
+    for (size_t st = 0; st < asize; st++) if (LF_SAI_mask[st] && LF_low[st].size() == lo) low[st] = LF_low[st].data();
+    for (size_t st = 0; st < asize; st++)
+        if (LF_SAI_mask[st] && !low[st]) { std::cout << "superres_LF: a non-empty SAI does not hold width*height*chnls values" << std::endl; return EXIT_FAILURE; }
+    const std::vector<float*> high = sai_ptrs(LF_high, LF_SAI_mask, hi, true);
+    const lfbm5d_params P = make(0.0f, lambdaHard5D, NHard, nSim, nDisp, kHard, pHard, useSD, tau_2D, tau_4D, tau_5D, color_space);
+    if (lfbm5d_superres_host_sai(ctx, &sr, &P, low.data(), LF_SAI_mask.data(), high.data(), ang_major, awidth, aheight, anHard, width, height,
+                                 chnls) != 0) {
+        std::cout << "LFBM5D GPU backend: " << lfbm5d_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+    }
+    return EXIT_SUCCESS;
+}
+
+/* Test hook: superres_LF on vector<vector<float>> light fields built from a flat low-resolution copy [asize][chnls*height*width]; the
+ * result goes to high_out [asize][chnls*scale*height*scale*width].  sr = {scale, kernel, iterations}, srf = {blurSigma, sigmaStart,
+ * sigmaEnd, lambda}, hard = {N, nSim, nDisp, k, p, useSD, tau_2D, tau_4D, tau_5D}. */
+extern "C" int lfbm5d_superres_probe(const float* low_flat, const unsigned* mask, float* high_out, unsigned ang_major, unsigned awidth,
+                                     unsigned aheight, unsigned an, unsigned width, unsigned height, unsigned chnls, const unsigned* sr,
+                                     const float* srf, const unsigned* hard, unsigned color_space) {
+    const size_t asize = (size_t)awidth * aheight, lo = (size_t)width * height * chnls, hi = lo * sr[0] * sr[0];
+    std::vector<unsigned> m(mask, mask + asize);
+    std::vector<std::vector<float> > LF_low(asize), LF_high;
+    for (size_t st = 0; st < asize; st++) if (m[st]) LF_low[st].assign(low_flat + st * lo, low_flat + (st + 1) * lo);
+    if (superres_LF(LF_low, m, LF_high, ang_major, awidth, aheight, an, width, height, chnls, sr[0], sr[1], srf[0], sr[2], srf[1], srf[2], srf[3],
+                    hard[0], hard[1], hard[2], hard[3], hard[4], hard[5] != 0, hard[6], hard[7], hard[8], color_space) != EXIT_SUCCESS) return 1;
+    for (size_t st = 0; st < asize; st++) if (m[st]) std::memcpy(high_out + st * hi, LF_high[st].data(), hi * sizeof(float));
+    return 0;
+}
+
 /* run_bm3d_LF (src/bm3d_LF.h:10-35, bm3d_LF.cpp:75-125): BM3D on every SAI of the mask */
 #include "run_bm3d_lf.h"
 int run_bm3d_LF(const float sigma, std::vector<std::vector<float> >& LF_noisy, std::vector<unsigned>& LF_SAI_mask,

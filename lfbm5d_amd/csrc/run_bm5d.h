@@ -107,4 +107,39 @@ int noise_level_LF(
 ,   float &sigma
 );
 
+//! Super-resolution -- not in the reference's master branch: the scheme of SR-LFBM5D (iterative back-projection regularised by the
+//! hard-thresholding step above) with the operators of include/lfbm5d.h, on the GPU (lfbm5d_superres_host_sai).  LF_low holds
+//! width x height SAIs and is only read; LF_high is (re)sized to scale*width x scale*height SAIs and filled.  kernel: 0 = bicubic,
+//! 1 = Gaussian of blurSigma; iterations, sigmaStart, sigmaEnd: 0 = the library's defaults for `scale` (lfbm5d_sr_defaults).
+//! Returns EXIT_SUCCESS, or EXIT_FAILURE with the message on stdout.
+int superres_LF(
+    const std::vector<std::vector<float> > &LF_low
+,   const std::vector<unsigned> &LF_SAI_mask
+,   std::vector<std::vector<float> > &LF_high
+,   const unsigned ang_major
+,   const unsigned awidth
+,   const unsigned aheight
+,   const unsigned anHard
+,   const unsigned width
+,   const unsigned height
+,   const unsigned chnls
+,   const unsigned scale
+,   const unsigned kernel
+,   const float    blurSigma
+,   const unsigned iterations
+,   const float    sigmaStart
+,   const float    sigmaEnd
+,   const float    lambdaHard5D
+,   const unsigned NHard
+,   const unsigned nSim
+,   const unsigned nDisp
+,   const unsigned kHard
+,   const unsigned pHard
+,   const bool     useSD
+,   const unsigned tau_2D
+,         unsigned tau_4D
+,   const unsigned tau_5D
+,   const unsigned color_space
+);
+
 #endif
