@@ -414,6 +414,48 @@ int lfbm5d_superres_host_sai(lfbm5d_ctx* ctx, const lfbm5d_sr_params* sr, const 
                              const unsigned* h_mask, float* const* h_high, unsigned ang_major, unsigned awidth, unsigned aheight,
                              unsigned an, unsigned w, unsigned h, unsigned C);
 
+/* ---- quality of a light field against a reference: per-SAI PSNR, RMSE and SSIM, with the light fields resident in HBM ----
+ * ref and test are [asize][C*H*W] float32; channels are compared as stored (no colour transform); peak > 0 is the value range
+ * (0 = 255).  For every non-empty SAI, in double:
+ *   mse  = mean over all C*H*W values of (ref - test)^2;  rmse = sqrt(mse);  psnr = 10 log10(peak^2 / mse) (+inf when mse == 0)
+ *          -- the reference's compute_psnr / compute_psnr_LF (utilities_LF.cpp:639-692), which accumulate in float;
+ *   ssim = Wang, Bovik, Sheikh & Simoncelli (2004): window w = g g^T, 11 x 11, g_i = exp(-(i-5)^2 / (2 1.5^2)) normalised to sum 1;
+ *          per channel plane every valid window position, (H-10) x (W-10) of them, no padding; with mu_a = sum w a, mu_b,
+ *          s_a = sum w a^2 - mu_a^2, s_b, s_ab = sum w a b - mu_a mu_b, C1 = (0.01 peak)^2, C2 = (0.03 peak)^2 the map is
+ *          (2 mu_a mu_b + C1)(2 s_ab + C2) / ((mu_a^2 + mu_b^2 + C1)(s_a + s_b + C2)); the SAI's SSIM is the mean of the map over
+ *          channels and positions.  Needs W, H >= 11.
+ * The summary follows compute_psnr_LF: mean and population standard deviation (divide by the count) of psnr, rmse and ssim over
+ * the non-empty SAIs, the pooled mse over all values of all non-empty SAIs, and the count.  Non-finite entries follow IEEE
+ * arithmetic and are not special-cased: ONE SAI with mse == 0 makes psnr_mean +inf (and psnr_std NaN).  Entries of empty SAIs in
+ * the per-SAI arrays are 0.
+ * Every sum runs on the GPU in double and in a fixed order (no atomics): repeated calls, the device and host forms, and want_ssim
+ * on / off (for mse) return the same bits; only two doubles per SAI leave the device.  The inputs are only read; planes of empty
+ * SAIs are neither read nor written.  One GPU; works on any context. */
+typedef struct {
+    double   psnr_mean, psnr_std;   /* over the non-empty SAIs                                  */
+    double   rmse_mean, rmse_std;
+    double   ssim_mean, ssim_std;   /* 0 when SSIM was not asked for                            */
+    double   mse;                   /* pooled over all values of all non-empty SAIs             */
+    unsigned count;                 /* non-empty SAIs                                           */
+    unsigned has_ssim;              /* != 0: ssim_mean / ssim_std are filled                    */
+} lfbm5d_quality;
+/* d_ref, d_test [asize][C*H*W] in HBM, read only; h_mask [asize] (0 = empty SAI); C = 1 or 3; want_ssim != 0: SSIM too, in the same
+ * pass over the light fields.  h_mse_sai / h_ssim_sai [asize] or NULL: the per-SAI values (psnr and rmse follow from mse as above;
+ * h_ssim_sai is zero-filled without want_ssim).  Returns 1 with a message on a rejected input: a NULL required buffer, C not 1 or
+ * 3, a mask without a non-empty SAI, peak < 0 or not finite, W or H below 11 with want_ssim (or 0 at all). */
+int lfbm5d_quality_device(lfbm5d_ctx* ctx, const float* d_ref, const float* d_test, const unsigned* h_mask, unsigned asize, unsigned W,
+                          unsigned H, unsigned C, double peak, int want_ssim, lfbm5d_quality* out, double* h_mse_sai, double* h_ssim_sai);
+/* The same on host light fields, one pointer per SAI for each (NULL allowed for empty SAIs, rejected for non-empty ones), staged
+ * through HBM: bit-identical results. */
+int lfbm5d_quality_host_sai(lfbm5d_ctx* ctx, const float* const* h_ref, const float* const* h_test, const unsigned* h_mask, unsigned asize,
+                            unsigned W, unsigned H, unsigned C, double peak, int want_ssim, lfbm5d_quality* out, double* h_mse_sai,
+                            double* h_ssim_sai);
+/* Host only, needs no GPU: the summary above from per-SAI mse [asize] and ssim [asize] (or NULL: no SSIM); entries of empty SAIs are
+ * ignored.  The device forms call it.  Returns 1 on bad arguments (NULL mse / mask / out, no non-empty SAI, peak < 0 or not finite;
+ * no message: there is no context). */
+int lfbm5d_quality_summary(const double* h_mse_sai, const double* h_ssim_sai, const unsigned* h_mask, unsigned asize, double peak,
+                           lfbm5d_quality* out);
+
 /* ---- inspection of the last pass's block matching (parity tests) ----
  * n_refs reference patches in raster order; h_refs[n_refs] flat index i*Wb+j;
  * h_self_idx[n_refs*N], h_self_cnt[n_refs] (precompute_BM, core:3301);

@@ -60,6 +60,12 @@ class NoiseLevelStruct(C.Structure):
                 ("patches", C.c_ulonglong)]
 
 
+class QualityStruct(C.Structure):
+    """lfbm5d_quality: the summary of the quality metrics (include/lfbm5d.h)."""
+    _fields_ = [("psnr_mean", C.c_double), ("psnr_std", C.c_double), ("rmse_mean", C.c_double), ("rmse_std", C.c_double),
+                ("ssim_mean", C.c_double), ("ssim_std", C.c_double), ("mse", C.c_double), ("count", C.c_uint), ("has_ssim", C.c_uint)]
+
+
 class SrParams(C.Structure):
     """lfbm5d_sr_params: operators and loop of the super-resolution (include/lfbm5d.h)."""
     _fields_ = [("scale", C.c_uint), ("kernel", C.c_uint), ("blur_sigma", C.c_float), ("iterations", C.c_uint),
@@ -76,6 +82,23 @@ class NoiseLevel(NamedTuple):
     patches: int
     eigen: np.ndarray
     sigma_sai: Optional[np.ndarray]
+
+
+class Quality(NamedTuple):
+    """Result of Context.quality / quality / quality_summary: mean and population standard deviation of PSNR, RMSE and SSIM over the
+    non-empty SAIs, the pooled mse, the count of non-empty SAIs, and the per-SAI arrays (float64, 0 for empty SAIs).  The ssim
+    fields are None when SSIM was not asked for.  One SAI with mse == 0 makes psnr_mean +inf (IEEE arithmetic, not special-cased)."""
+    psnr_mean: float
+    psnr_std: float
+    rmse_mean: float
+    rmse_std: float
+    ssim_mean: Optional[float]
+    ssim_std: Optional[float]
+    mse: float
+    count: int
+    psnr_sai: np.ndarray
+    rmse_sai: np.ndarray
+    ssim_sai: Optional[np.ndarray]
 
 
 def library_path():
@@ -170,6 +193,11 @@ def lib():
         L.lfbm5d_noise_level_device.argtypes = [vp, fp, up] + [C.c_uint] * 5 + [np_, dp, dp]
         L.lfbm5d_noise_level_host_sai.argtypes = [vp, fp, up] + [C.c_uint] * 5 + [np_, dp, dp]
         L.lfbm5d_noise_level_statistic.argtypes = [C.c_uint, dp, dp, up, dp]
+    if hasattr(L, "lfbm5d_quality_device"):   # (absent from older builds loaded through LFBM5D_HIP_LIB for A/B runs)
+        dp, qp = C.POINTER(C.c_double), C.POINTER(QualityStruct)
+        L.lfbm5d_quality_device.argtypes = [vp, fp, fp, up] + [C.c_uint] * 4 + [C.c_double, C.c_int, qp, dp, dp]
+        L.lfbm5d_quality_host_sai.argtypes = [vp, fp, fp, up] + [C.c_uint] * 4 + [C.c_double, C.c_int, qp, dp, dp]
+        L.lfbm5d_quality_summary.argtypes = [dp, dp, up, C.c_uint, C.c_double, qp]
     if hasattr(L, "lfbm5d_superres_device"):   # (absent from older builds loaded through LFBM5D_HIP_LIB for A/B runs)
         sp, pp = C.POINTER(SrParams), C.POINTER(Params)
         L.lfbm5d_sr_defaults.argtypes = [C.c_uint, sp]
@@ -267,6 +295,38 @@ def noise_level_statistic(cov):
     if lib().lfbm5d_noise_level_statistic(d, cov.ctypes.data_as(dp), C.byref(sig), C.byref(m), lam.ctypes.data_as(dp)) != 0:
         raise LfBm5dError("lfbm5d_noise_level_statistic: bad arguments (d must be 1..64)")
     return sig.value, m.value, lam
+
+
+def _quality_result(res, mse, ssim, m, peak):
+    """Quality from the summary struct and the per-SAI mse / ssim arrays (psnr and rmse per SAI follow from mse)."""
+    pk = 255.0 if peak == 0 else float(peak)
+    on = m != 0
+    psnr, rmse = np.zeros(m.size, np.float64), np.zeros(m.size, np.float64)
+    with np.errstate(divide="ignore"):
+        psnr[on] = 10.0 * np.log10(pk * pk / mse[on])
+    rmse[on] = np.sqrt(mse[on])
+    has = bool(res.has_ssim)
+    return Quality(res.psnr_mean, res.psnr_std, res.rmse_mean, res.rmse_std, res.ssim_mean if has else None, res.ssim_std if has else None,
+                   res.mse, int(res.count), psnr, rmse, ssim if has else None)
+
+
+def quality_summary(mse_sai, ssim_sai, mask, peak=255.0):
+    """lfbm5d_quality_summary (host only, no GPU): the Quality of per-SAI mse and ssim (or None) under `mask`; entries of empty SAIs
+    are ignored (and 0 in the result's arrays)."""
+    m = _u32(mask)
+    mse = np.ascontiguousarray(mse_sai, np.float64).copy()
+    ssim = None if ssim_sai is None else np.ascontiguousarray(ssim_sai, np.float64).copy()
+    if mse.size != m.size or (ssim is not None and ssim.size != m.size):
+        raise LfBm5dError("lfbm5d_quality_summary: mse, ssim and mask must hold one entry per SAI")
+    dp = C.POINTER(C.c_double)
+    res = QualityStruct()
+    if lib().lfbm5d_quality_summary(mse.ctypes.data_as(dp), ssim.ctypes.data_as(dp) if ssim is not None else None,
+                                    m.ctypes.data_as(C.POINTER(C.c_uint)), m.size, float(peak), C.byref(res)) != 0:
+        raise LfBm5dError("lfbm5d_quality_summary: bad arguments (no non-empty SAI, or peak negative or not finite)")
+    mse[m == 0] = 0.0
+    if ssim is not None:
+        ssim[m == 0] = 0.0
+    return _quality_result(res, mse, ssim, m, peak)
 
 
 def sr_defaults(scale, /, **changes):
@@ -551,6 +611,32 @@ class Context:
         return NoiseLevel(res.sigma, tuple(res.sigma_channel[:C_]), int(res.components), int(res.patches), eig[:int(res.patch) ** 2],
                           sai[:asize] if per_sai else None)
 
+    # ---- quality metrics ----
+    def quality(self, ref, test, mask, width, height, chnls, peak=255.0, ssim=True):
+        """PSNR, RMSE and (ssim=True) SSIM of `test` against `ref`, per SAI and summarised (lfbm5d_quality_*, include/lfbm5d.h).  ref /
+        test: CUDA float32 tensors [asize][C*H*W] (device form, read only), or float32 numpy arrays of that shape / lists of per-SAI
+        float32 arrays (host form, staged through HBM; bit-identical).  Returns a Quality."""
+        m = _u32(mask)
+        asize = m.size
+        res = QualityStruct()
+        mse, ss = np.zeros(max(asize, 1), np.float64), np.zeros(max(asize, 1), np.float64)
+        dp = C.POINTER(C.c_double)
+        tail = (m.ctypes.data_as(C.POINTER(C.c_uint)), asize, int(width), int(height), int(chnls), float(peak), 1 if ssim else 0,
+                C.byref(res), mse.ctypes.data_as(dp), ss.ctypes.data_as(dp))
+        host = [isinstance(x, (list, tuple, np.ndarray)) for x in (ref, test)]
+        if host[0] != host[1]:
+            raise LfBm5dError("quality: ref and test must both be device tensors or both be host arrays")
+        if host[0]:
+            arrays = []
+            for x in (ref, test):
+                if isinstance(x, np.ndarray) and x.dtype != np.float32:
+                    raise LfBm5dError("host light fields must be float32")
+                arrays.append(list(x) if isinstance(x, (list, tuple)) else [np.ascontiguousarray(a) for a in x])
+            self._ck(self._L.lfbm5d_quality_host_sai(self._h, _sai_ptrs(arrays[0], m), _sai_ptrs(arrays[1], m), *tail))
+        else:
+            self._ck(self._L.lfbm5d_quality_device(self._h, _dev_ptr(ref), _dev_ptr(test), *tail))
+        return _quality_result(res, mse[:asize], ss[:asize], m, peak)
+
     # ---- super-resolution ----
     def _sr_tail(self, mask, w, h, Cc):
         m = _u32(mask)
@@ -691,6 +777,11 @@ def run_bm3d_LF(sigma, LF_noisy, LF_SAI_mask, LF_basic, LF_denoised, width, heig
 def noise_level(LF, LF_SAI_mask, width, height, chnls, patch=8, per_sai=False, ctx=None):
     """Context.noise_level on the default context (device 0): the blind estimate of the light field's noise sigma."""
     return (ctx or _ctx()).noise_level(LF, LF_SAI_mask, width, height, chnls, patch, per_sai)
+
+
+def quality(ref, test, mask, width, height, chnls, peak=255.0, ssim=True, ctx=None):
+    """Context.quality on the default context (device 0): per-SAI PSNR, RMSE and SSIM of `test` against `ref` and their summary."""
+    return (ctx or _ctx()).quality(ref, test, mask, width, height, chnls, peak, ssim)
 
 
 def superres(sr, P, low, mask, high, ang_major, awidth, aheight, an, w, h, chnls, ctx=None):

@@ -16,7 +16,10 @@
  *   LFBM5D_TILED=1    honour nbThreads > 1 the reference's way (tiles with a discarded halo, bm5d.cpp:411-708);
  *   LFBM5D_SIGMA=auto estimate sigma from the noisy light field (noise_level_LF, run_bm5d.h) once it exists -- loaded with
  *                     LFSourceDir = none, or made with the argument's sigma from a ground truth -- and use the estimate for both
- *                     steps and the diff images; any other value is an error.
+ *                     steps and the diff images; any other value is an error;
+ *   LFBM5D_REPORT_SSIM=1  the average SSIM next to every average PSNR on stdout and an SSIM block behind every PSNR block of the
+ *                     results file, computed on the GPU on the images as the files hold them (cli_quality.h); any other value is an
+ *                     error; unset, the output is unchanged.
  * Without LFBM5D_TILED nbThreads is parsed and ignored: the GPU path has the reference's untiled
  * (nb_threads == 1) semantics, half a dB better than its tiled mode.
  *
@@ -48,6 +51,7 @@
 #include "png_min.h"
 #include "run_bm5d.h"
 #include "run_bm3d_lf.h"
+#include "cli_quality.h"
 
 using namespace std;
 
@@ -305,6 +309,8 @@ int main(int argc, char** argv) {
     if (!ang_major || cs < 0) { cout << "Problem while reading parameters from command line !" << endl; return EXIT_FAILURE; }
     const int smode = sigma_mode();
     if (smode < 0) return EXIT_FAILURE;
+    const int qmode = cli_quality::ssim_mode();
+    if (qmode < 0) return EXIT_FAILURE;
 
     vector<vector<float> > LF, LF_noisy, LF_basic, LF_den, LF_diff;
     vector<unsigned> mask;
@@ -326,11 +332,15 @@ int main(int argc, char** argv) {
     if (smode == 1 && !estimate_sigma_LF(LF_noisy, mask, W, H, C, sigma)) return EXIT_FAILURE;
     LF_basic.assign(awh, vector<float>((size_t)W * H * C, 0.0f));
     LF_den = LF_basic; LF_diff = LF_basic;
-    vector<float> ps, rm; float ap_n = 0, sp = 0, ar = 0, sr = 0, ap_b = 0;
+    vector<float> ps, rm; float sp = 0, ar = 0, sr = 0;
+    cli_quality::Avg ap_n, ap_b, ap_d;
+    cli_quality::Block qb;
     if (gt) {
-        psnr_LF(LF, LF_noisy, mask, ps, ap_n, sp, rm, ar, sr);
+        psnr_LF(LF, LF_noisy, mask, ps, ap_n.psnr, sp, rm, ar, sr);
+        if (qmode && !cli_quality::compute(LF, LF_noisy, mask, W, H, C, ap_n, qb)) return EXIT_FAILURE;
         cout << endl << "Average PSNR:" << endl << "- Noisy light field: " << ap_n << endl;
-        write_psnr(results, "noisy", mask, ang_major, aw, ah, ps, ap_n, sp, rm, ar, sr);
+        write_psnr(results, "noisy", mask, ang_major, aw, ah, ps, ap_n.psnr, sp, rm, ar, sr);
+        if (qmode) cli_quality::write(results, "noisy", mask, ang_major, aw, ah, qb);
     }
     cout << endl << " ---> Running LFBM3D filter <--- " << endl << endl;
     const double tb = now_s();
@@ -339,17 +349,20 @@ int main(int argc, char** argv) {
                     t2[0], t2[1], lambda, cs, nb_threads, sub) != EXIT_SUCCESS) return EXIT_FAILURE;
     const double secs = now_s() - tb;
     if (gt) {
-        psnr_LF(LF, LF_basic, mask, ps, ap_b, sp, rm, ar, sr);
-        write_psnr(results, "basic", mask, ang_major, aw, ah, ps, ap_b, sp, rm, ar, sr);
+        psnr_LF(LF, LF_basic, mask, ps, ap_b.psnr, sp, rm, ar, sr);
+        if (qmode && !cli_quality::compute(LF, LF_basic, mask, W, H, C, ap_b, qb)) return EXIT_FAILURE;
+        write_psnr(results, "basic", mask, ang_major, aw, ah, ps, ap_b.psnr, sp, rm, ar, sr);
+        if (qmode) cli_quality::write(results, "basic", mask, ang_major, aw, ah, qb);
     }
     cout << endl << "Save basic light field..." << endl;
     if (save_LF(d_basic, name, sep, LF_basic, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
     if (gt) {
-        float ap_d;
-        psnr_LF(LF, LF_den, mask, ps, ap_d, sp, rm, ar, sr);
+        psnr_LF(LF, LF_den, mask, ps, ap_d.psnr, sp, rm, ar, sr);
+        if (qmode && !cli_quality::compute(LF, LF_den, mask, W, H, C, ap_d, qb)) return EXIT_FAILURE;
         cout << endl << "Average PSNR:" << endl << "- Noisy light field: " << ap_n << endl << "- Basic light field: " << ap_b << endl
              << "- Denoised light field: " << ap_d << endl << endl;
-        write_psnr(results, "denoised", mask, ang_major, aw, ah, ps, ap_d, sp, rm, ar, sr);
+        write_psnr(results, "denoised", mask, ang_major, aw, ah, ps, ap_d.psnr, sp, rm, ar, sr);
+        if (qmode) cli_quality::write(results, "denoised", mask, ang_major, aw, ah, qb);
         diff_LF(LF, LF_den, mask, LF_diff, sigma);
     }
     cout << endl << "Save denoised light field..." << endl;
@@ -402,6 +415,8 @@ int main(int argc, char** argv) {
     if (!ang_major || cs < 0) { cout << "Problem while reading parameters from command line !" << endl; usage(argv[0]); return EXIT_FAILURE; }
     const int smode = sigma_mode();
     if (smode < 0) return EXIT_FAILURE;
+    const int qmode = cli_quality::ssim_mode();
+    if (qmode < 0) return EXIT_FAILURE;
 
     vector<vector<float> > LF, LF_noisy, LF_basic, LF_den, LF_diff;
     vector<unsigned> mask;
@@ -423,11 +438,15 @@ int main(int argc, char** argv) {
     if (smode == 1 && !estimate_sigma_LF(LF_noisy, mask, W, H, C, sigma)) return EXIT_FAILURE;
     LF_basic.assign(awh, vector<float>((size_t)W * H * C, 0.0f));
     LF_den = LF_basic; LF_diff = LF_basic;
-    vector<float> ps, rm; float ap_n = 0, sp = 0, ar = 0, sr = 0, ap_b = 0;
+    vector<float> ps, rm; float sp = 0, ar = 0, sr = 0;
+    cli_quality::Avg ap_n, ap_b, ap_d;
+    cli_quality::Block qb;
     if (gt) {
-        psnr_LF(LF, LF_noisy, mask, ps, ap_n, sp, rm, ar, sr);
+        psnr_LF(LF, LF_noisy, mask, ps, ap_n.psnr, sp, rm, ar, sr);
+        if (qmode && !cli_quality::compute(LF, LF_noisy, mask, W, H, C, ap_n, qb)) return EXIT_FAILURE;
         cout << endl << "Average PSNR:" << endl << "- Noisy light field: " << ap_n << endl;
-        write_psnr(results, "noisy", mask, ang_major, aw, ah, ps, ap_n, sp, rm, ar, sr);
+        write_psnr(results, "noisy", mask, ang_major, aw, ah, ps, ap_n.psnr, sp, rm, ar, sr);
+        if (qmode) cli_quality::write(results, "noisy", mask, ang_major, aw, ah, qb);
     }
     /* LFBM5D_ONE_JOB=1 (not in the reference): both steps as one job (run_bm5d, run_bm5d.h) -- the same denoised files and PSNR, one time for
      * both.  The BASIC light field saved and reported in this mode is the one the job returns at its end, inverse(forward(inverse(estimate)))
@@ -452,9 +471,11 @@ int main(int argc, char** argv) {
     if (one_job) cout << endl << "Steps 1 and 2 done in " << job << " secs." << endl << endl;
     else cout << endl << "Step 1 done in " << step1 << " secs." << endl << endl;
     if (gt) {
-        psnr_LF(LF, LF_basic, mask, ps, ap_b, sp, rm, ar, sr);
+        psnr_LF(LF, LF_basic, mask, ps, ap_b.psnr, sp, rm, ar, sr);
+        if (qmode && !cli_quality::compute(LF, LF_basic, mask, W, H, C, ap_b, qb)) return EXIT_FAILURE;
         cout << endl << "Average PSNR:" << endl << "- Noisy light field: " << ap_n << endl << "- Basic light field: " << ap_b << endl;
-        write_psnr(results, "basic", mask, ang_major, aw, ah, ps, ap_b, sp, rm, ar, sr);
+        write_psnr(results, "basic", mask, ang_major, aw, ah, ps, ap_b.psnr, sp, rm, ar, sr);
+        if (qmode) cli_quality::write(results, "basic", mask, ang_major, aw, ah, qb);
         diff_LF(LF, LF_basic, mask, LF_diff, sigma);
     }
     cout << endl << "Save basic light field..." << endl;
@@ -466,11 +487,12 @@ int main(int argc, char** argv) {
     const double step2 = one_job ? 0.0 : now_s() - t1;
     if (!one_job) cout << endl << "Step 2 done in " << step2 << " secs." << endl << endl;
     if (gt) {
-        float ap_d;
-        psnr_LF(LF, LF_den, mask, ps, ap_d, sp, rm, ar, sr);
+        psnr_LF(LF, LF_den, mask, ps, ap_d.psnr, sp, rm, ar, sr);
+        if (qmode && !cli_quality::compute(LF, LF_den, mask, W, H, C, ap_d, qb)) return EXIT_FAILURE;
         cout << endl << "Average PSNR:" << endl << "- Noisy light field: " << ap_n << endl << "- Basic light field: " << ap_b << endl
              << "- Denoised light field: " << ap_d << endl << endl;
-        write_psnr(results, "denoised", mask, ang_major, aw, ah, ps, ap_d, sp, rm, ar, sr);
+        write_psnr(results, "denoised", mask, ang_major, aw, ah, ps, ap_d.psnr, sp, rm, ar, sr);
+        if (qmode) cli_quality::write(results, "denoised", mask, ang_major, aw, ah, qb);
         diff_LF(LF, LF_den, mask, LF_diff, sigma);
     }
     cout << endl << "Save denoised light field..." << endl;

@@ -143,6 +143,8 @@ struct lfbm5d_ctx {
     unsigned* h_small = nullptr; /* pinned, 64 uints */
     /* noise-level estimate (lfbm5d_noise.hip): non-empty SAI list, bulk partial sums, lag cells, centred scatters, pooled covariances */
     struct NoiseBufs { DevBuf sai, part, cells, m, pool; } noise;
+    /* quality metrics (lfbm5d_quality.hip): non-empty SAI list, the workgroups' partial sums, the two sums of every SAI */
+    struct QualityBufs { DevBuf sai, part, out; } quality;
     /* super-resolution (lfbm5d_resample.hip): non-empty SAI list, the tap tables of U and D for the geometry in `key` (host copy, word
      * offsets of first / w of Ux, Uy, Dx, Dy, their tap counts), the loop's scratch: one high- and one low-resolution light field */
     struct SrBufs {

@@ -9,7 +9,9 @@
  * Reads <LFLowDir>/<name><sep><ss><sep><tt>.png, writes SAIs of `scale` times the size to LFOutDir under the same names.  0 for
  * iterations / sigmaStart / sigmaEnd selects the library's defaults for the scale.  With LFSourceDir (the high-resolution ground
  * truth) it prints the PSNR of plain bicubic interpolation and of the result and appends both to resultsFile in the report format
- * of LFBM5Ddenoising.  Reads no environment of its own.
+ * of LFBM5Ddenoising.  Environment: LFBM5D_REPORT_SSIM=1 adds the average SSIM next to both average PSNRs and an SSIM block behind
+ * each PSNR block of resultsFile (cli_quality.h: on the images as the files hold them); any other value is an error; unset, the
+ * output is unchanged.
  */
 #include <cmath>
 #include <cstdlib>
@@ -24,6 +26,7 @@
 #include "../../include/lfbm5d.h"
 #include "png_min.h"
 #include "run_bm5d.h"
+#include "cli_quality.h"
 
 using namespace std;
 
@@ -197,6 +200,9 @@ int main(int argc, char** argv) {
         usage(argv[0]); cout << "Problem while reading parameters from command line !" << endl; return EXIT_FAILURE;
     }
 
+    const int qmode = cli_quality::ssim_mode();
+    if (qmode < 0) return EXIT_FAILURE;
+
     vector<vector<float> > LF_low, LF_high, LF_src, LF_bic;
     vector<unsigned> mask, mask_src;
     unsigned w = 0, h = 0, C = 0;
@@ -212,11 +218,15 @@ int main(int argc, char** argv) {
                     sd != 0, t2, t4, t5, cs) != EXIT_SUCCESS) return EXIT_FAILURE;
     if (d_src) {
         if (!bicubic_LF(LF_low, mask, LF_bic, scale, w, h, C)) { cout << "bicubic interpolation failed" << endl; return EXIT_FAILURE; }
-        vector<float> ps, rm; float ap_b = 0, ap_s = 0, sp = 0, ar = 0, sr = 0;
-        psnr_LF(LF_src, LF_bic, mask, ps, ap_b, sp, rm, ar, sr);
-        write_psnr(results, "bicubic", mask, ang_major, aw, ah, ps, ap_b, sp, rm, ar, sr);
-        psnr_LF(LF_src, LF_high, mask, ps, ap_s, sp, rm, ar, sr);
-        write_psnr(results, "super-resolved", mask, ang_major, aw, ah, ps, ap_s, sp, rm, ar, sr);
+        vector<float> ps, rm; float sp = 0, ar = 0, sr = 0;
+        cli_quality::Avg ap_b, ap_s;
+        cli_quality::Block qb;
+        psnr_LF(LF_src, LF_bic, mask, ps, ap_b.psnr, sp, rm, ar, sr);
+        write_psnr(results, "bicubic", mask, ang_major, aw, ah, ps, ap_b.psnr, sp, rm, ar, sr);
+        if (qmode) { if (!cli_quality::compute(LF_src, LF_bic, mask, W, H, C, ap_b, qb)) return EXIT_FAILURE; cli_quality::write(results, "bicubic", mask, ang_major, aw, ah, qb); }
+        psnr_LF(LF_src, LF_high, mask, ps, ap_s.psnr, sp, rm, ar, sr);
+        write_psnr(results, "super-resolved", mask, ang_major, aw, ah, ps, ap_s.psnr, sp, rm, ar, sr);
+        if (qmode) { if (!cli_quality::compute(LF_src, LF_high, mask, W, H, C, ap_s, qb)) return EXIT_FAILURE; cli_quality::write(results, "super-resolved", mask, ang_major, aw, ah, qb); }
         cout << endl << "Average PSNR:" << endl << "- Bicubic light field: " << ap_b << endl << "- Super-resolved light field: " << ap_s << endl << endl;
     }
     cout << "Save super-resolved light field..." << endl;

@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -203,6 +204,49 @@ int noise_level_LF(const std::vector<std::vector<float> >& LF, const std::vector
         return EXIT_FAILURE;
     }
     sigma = (float)r.sigma;
+    return EXIT_SUCCESS;
+}
+
+int report_ssim_mode() {
+    const char* e = std::getenv("LFBM5D_REPORT_SSIM");
+    if (!e) return 0;
+    if (!std::strcmp(e, "1")) return 1;
+    std::cout << "LFBM5D_REPORT_SSIM must be \"1\" (report SSIM next to PSNR) or unset; got \"" << e << "\"" << std::endl;
+    return -1;
+}
+
+/* quality metrics on the caller's vectors (one pointer per SAI, no flat copy) */
+int quality_LF(const std::vector<std::vector<float> >& LF_1, const std::vector<std::vector<float> >& LF_2, const std::vector<unsigned>& LF_SAI_mask,
+               unsigned width, unsigned height, unsigned chnls, std::vector<float>& psnr, float& avg_psnr, float& std_psnr, std::vector<float>& rmse,
+               float& avg_rmse, float& std_rmse, std::vector<float>& ssim, float& avg_ssim, float& std_ssim) {
+    const size_t asize = LF_SAI_mask.size();
+    if (LF_1.size() != asize || LF_2.size() != asize) {
+        std::cout << "quality_LF: light fields and mask must hold the same number of SAIs" << std::endl;
+        return EXIT_FAILURE;
+    }
+    lfbm5d_ctx* ctx = context();
+    if (!ctx) return EXIT_FAILURE;
+    const size_t img = (size_t)width * height * chnls;
+    std::vector<const float*> p1(asize, nullptr), p2(asize, nullptr);
+    for (size_t st = 0; st < asize; st++) {
+        if (!LF_SAI_mask[st]) continue;
+        if (LF_1[st].size() != img || LF_2[st].size() != img) { std::cout << "quality_LF: a non-empty SAI does not hold width*height*chnls values" << std::endl; return EXIT_FAILURE; }
+        p1[st] = LF_1[st].data(); p2[st] = LF_2[st].data();
+    }
+    lfbm5d_quality q;
+    std::vector<double> mse(asize, 0.0), ss(asize, 0.0);
+    if (lfbm5d_quality_host_sai(ctx, p1.data(), p2.data(), LF_SAI_mask.data(), (unsigned)asize, width, height, chnls, 255.0, 1, &q, mse.data(), ss.data()) != 0) {
+        std::cout << "LFBM5D GPU backend: " << lfbm5d_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+    }
+    psnr.assign(asize, 0.0f); rmse.assign(asize, 0.0f); ssim.assign(asize, 0.0f);
+    for (size_t st = 0; st < asize; st++) {
+        if (!LF_SAI_mask[st]) continue;
+        psnr[st] = (float)(10.0 * std::log10(255.0 * 255.0 / mse[st])); rmse[st] = (float)std::sqrt(mse[st]); ssim[st] = (float)ss[st];
+    }
+    avg_psnr = (float)q.psnr_mean; std_psnr = (float)q.psnr_std;
+    avg_rmse = (float)q.rmse_mean; std_rmse = (float)q.rmse_std;
+    avg_ssim = (float)q.ssim_mean; std_ssim = (float)q.ssim_std;
     return EXIT_SUCCESS;
 }
 

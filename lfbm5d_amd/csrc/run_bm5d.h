@@ -107,6 +107,33 @@ int noise_level_LF(
 ,   float &sigma
 );
 
+//! Quality of LF_2 against LF_1 on the GPU -- compute_psnr_LF (utilities_LF.cpp:639-692) with its argument order, the sizes and the
+//! SSIM triple added: per-SAI PSNR, RMSE and SSIM (0 for empty SAIs) with their mean and population standard deviation over the
+//! non-empty SAIs (lfbm5d_quality_host_sai, include/lfbm5d.h: double sums, peak 255, SSIM with the 11 x 11 Gaussian window over every
+//! valid position; width, height >= 11).  Both light fields are only read.  Returns EXIT_SUCCESS, or EXIT_FAILURE with the message
+//! on stdout.
+int quality_LF(
+    const std::vector<std::vector<float> > &LF_1
+,   const std::vector<std::vector<float> > &LF_2
+,   const std::vector<unsigned> &LF_SAI_mask
+,   unsigned width
+,   unsigned height
+,   unsigned chnls
+,   std::vector<float> &psnr
+,   float &avg_psnr
+,   float &std_psnr
+,   std::vector<float> &rmse
+,   float &avg_rmse
+,   float &std_rmse
+,   std::vector<float> &ssim
+,   float &avg_ssim
+,   float &std_ssim
+);
+
+//! LFBM5D_REPORT_SSIM of the command lines, read here with the drop-in's other program-level variables: 0 = unset, 1 = "1" (report
+//! SSIM through quality_LF next to every PSNR), -1 = any other value (the message is on stdout).
+int report_ssim_mode();
+
 //! Super-resolution -- not in the reference's master branch: the scheme of SR-LFBM5D (iterative back-projection regularised by the
 //! hard-thresholding step above) with the operators of include/lfbm5d.h, on the GPU (lfbm5d_superres_host_sai).  LF_low holds
 //! width x height SAIs and is only read; LF_high is (re)sized to scale*width x scale*height SAIs and filled.  kernel: 0 = bicubic,
