@@ -328,8 +328,9 @@ int lfbm5d_bm3d_lf_host(lfbm5d_ctx* ctx, const lfbm5d_bm3d_params* hard, const l
  * channel, over c for a SAI.  With the eigenvalues of Cov ascending, lambda_1 <= ... <= lambda_d, the statistic takes the first
  * m = d, d-1, ..., 1 at which as many of lambda_1..m lie above their mean mu_m as below it, and returns sqrt(max(mu_m, 0)) and m
  * (the size of the noise subspace found).  Units: grey levels of the channels as stored, i.e. lfbm5d_params.sigma.
- * The statistic assumes additive white Gaussian noise: signal-dependent (Poisson-Gaussian) or spatially correlated noise (e.g.
- * demosaicked raw data) is outside it, and values clipped to 0..255 (8-bit files) bias it low at large sigma.
+ * The statistic assumes additive white Gaussian noise: under signal-dependent (Poisson-Gaussian) noise it returns roughly the level of
+ * the darkest regions (lfbm5d_pg_* below model that case), spatially correlated noise (e.g. demosaicked raw data) is outside it, and
+ * values clipped to 0..255 (8-bit files) bias it low at large sigma.
  * The patch sums run on the GPU in double, every sum in a fixed order: repeated calls, and the device and host forms, return the
  * same bits; only the pooled d x d matrices leave the device; the eigenvalues are found on the host (double).  One GPU. */
 typedef struct {
@@ -455,6 +456,92 @@ int lfbm5d_quality_host_sai(lfbm5d_ctx* ctx, const float* const* h_ref, const fl
  * no message: there is no context). */
 int lfbm5d_quality_summary(const double* h_mse_sai, const double* h_ssim_sai, const unsigned* h_mask, unsigned asize, double peak,
                            lfbm5d_quality* out);
+
+/* ---- signal-dependent noise: Poisson-Gaussian model var(z | y) = a y + b, its estimate, and denoising through a variance-stabilising
+ * transform ----
+ * Not in the reference.  Every entry point above assumes additive white Gaussian noise of one sigma; the noise of a real capture
+ * (lenslet cameras, low light: the LFSourceDir = none case) grows with the intensity.  The remedy here leaves the filter alone:
+ * estimate (a, b), apply the generalised Anscombe transform (the noise becomes white Gaussian of a known sigma s), run the two-step job,
+ * return through the exact unbiased inverse (Makitalo & Foi, IEEE TIP 2013, closed-form approximation).  Light fields are [asize][C*H*W]
+ * float32, nominally 0..255, channels as stored (no colour transform); planes of empty SAIs are neither read nor written.  One GPU:
+ * contexts with a communicator or a shard return 1.
+ * Limits: the level bins and the scale s assume the 0..255 range; values clipped to 0..255 (8-bit files) lose part of their noise
+ * near black and white, which biases the dark and bright levels of the estimate; spatially correlated noise is outside the model.  At
+ * a <~ 1 (on the 0..255 scale) the path does not beat lfbm5d_denoise_* with a well-chosen single sigma (about 0.1-0.2 dB below the
+ * best one); the gain is at strong dependence, a >~ 4 (DESIGN.md 3f has the figures).
+ *
+ * Statistics (GPU, integers: independent of any summation order, equal to the model of tests/pg_model.py bit for bit).  L = 64 levels,
+ * E_MIN = -12, E_MAX = 8, Q = (E_MAX - E_MIN) 16 + 2 = 322 keys.  A block exists for every non-empty SAI, every channel plane I and every
+ * i < floor(H/2), j < floor(W/2) (odd W / H leave the last column / row unused): p00 = I[2i][2j], p01 = I[2i][2j+1], p10 = I[2i+1][2j],
+ * p11 = I[2i+1][2j+1]; in float32, in exactly this order,
+ *   m = ((p00 + p01) + (p10 + p11)) * 0.25f,    d = ((p00 - p01) - (p10 - p11)) * 0.5f
+ * (var d = the mean of the four pixels' noise variances = a mean(y) + b, plus a signal term the quantile below is robust to).  A block
+ * with non-finite m or d is skipped and counted.  mc = min(max(m, 0), 255); lev = min(63, (int)(mc * (float)(64.0/255.0)));
+ * key = clamp((bits(|d|) >> 19) - ((E_MIN + 127) << 4) + 1, 0, Q - 1): 16 bins per octave from the exponent and the top four mantissa
+ * bits; key 0 is [0, 2^-12), the lower edge e[k] of key k >= 1 is the float whose bits are (k - 1 + 1840) << 19, key 321 collects
+ * everything >= 2^8.  hist[c][lev][key] += 1, sum[c][lev] += (uint64) rint(mc * 256.0f).
+ * Fit (host, double) of one histogram h[64][322] with sum[64]: a level with n = sum_k h[l][k] < 256 is skipped; T = 0.25 n, k* = the
+ * first k whose cumulative count is >= T (k* = 0 or 321: level skipped); Qv = e[k*] + (e[k*+1] - e[k*]) (T - cum[k*-1]) / h[l][k*];
+ * v = (Qv / 0.31863936396437514)^2 (the 0.25 quantile of |N(0,1)|); x = sum[l] / (256 n); w = n / v^2.  Weighted least squares
+ * v = a x + b over the valid levels in level order; fewer than two valid levels or a determinant <= 1e-12 Sw Swxx: a = 0, b = Swv / Sw;
+ * a < 0: a = 0, b = Swv / Sw; otherwise b < 0: b = 0, a = Swxv / Swxx; no valid level: the fit fails.  The light field's model is the
+ * fit of the channels' histograms added together, a channel's model the fit of its own histogram.
+ * Transform.  A model is a_c >= 0, b_c per stored channel with c_c = 3/8 a_c^2 + b_c > 0 (anything else is rejected); the common scale
+ * s = mean over the channels of (sqrt(255 a_c + c_c) + sqrt(c_c)) / 2: after the forward transform every channel has noise standard
+ * deviation s and roughly the 0..255 range the filter's parameters are tuned for; a = 0 gives s = sqrt(b) and the identity.  In
+ * double, rounded once to float:
+ *   forward  w = a z + c (w < 0: w = 0, z = -c / a);  t = s 2z / (sqrt(w) + sqrt(c))      [= s (f(z) - f(0)), f(z) = (2/a) sqrt(a z + c)]
+ *   inverse  u = t / s;  q = a u + 2 sqrt(c);  q <= 0 -> 0;  g = a / q;  g > 0.816496580927726 -> 0;  else
+ *            y = a u^2 / 4 + u sqrt(c) + a / 4 + a (K1 g - 1.375 g^2 + K3 g^3), K1 = 0.30618621784789724, K3 = 0.7654655446197431;
+ *            the output is max(y, 0). */
+#define LFBM5D_PG_LEVELS 64
+#define LFBM5D_PG_KEYS   322
+typedef struct {
+    double a[3];   /* per stored channel (grey: [0] only) */
+    double b[3];
+} lfbm5d_pg_model;
+typedef struct {
+    double a, b;                         /* the light field's model: every non-empty SAI and channel pooled                   */
+    double a_channel[3], b_channel[3];   /* per stored channel (NaN for a channel whose own fit fails; grey: [0] only, rest 0) */
+    unsigned long long blocks;           /* 2 x 2 blocks visited                                                              */
+    unsigned long long skipped;          /* of those, skipped for a non-finite m or d                                         */
+} lfbm5d_pg_estimate;
+/* d_lf [asize][C*H*W] in HBM, read only; h_mask [asize] (0 = empty SAI); C = 1 or 3; W, H >= 2.  h_hist [C][64][322], h_sum [C][64]
+ * (host) receive the counts; blocks / skipped may be NULL.  Returns 1 with a message on a rejected input (a NULL required buffer, C, W /
+ * H, a mask without a non-empty SAI). */
+int lfbm5d_pg_histogram_device(lfbm5d_ctx* ctx, const float* d_lf, const unsigned* h_mask, unsigned asize, unsigned W, unsigned H, unsigned C,
+                               unsigned long long* h_hist, unsigned long long* h_sum, unsigned long long* blocks, unsigned long long* skipped);
+/* Host only, needs no GPU: the fit above of one histogram hist [64][322], sum [64].  Returns 1 when no level is valid (or on a NULL
+ * pointer; no message: there is no context). */
+int lfbm5d_pg_fit(const unsigned long long* hist, const unsigned long long* sum, double* a, double* b);
+/* Histogram + fits.  h_hist / h_sum as above or NULL.  Returns 1 with a message when the pooled fit fails (too few blocks). */
+int lfbm5d_pg_estimate_device(lfbm5d_ctx* ctx, const float* d_lf, const unsigned* h_mask, unsigned asize, unsigned W, unsigned H, unsigned C,
+                              lfbm5d_pg_estimate* out, unsigned long long* h_hist, unsigned long long* h_sum);
+/* The same on host light fields, one pointer per SAI (NULL allowed for empty SAIs), staged through HBM: identical results. */
+int lfbm5d_pg_estimate_host_sai(lfbm5d_ctx* ctx, const float* const* h_lf, const unsigned* h_mask, unsigned asize, unsigned W, unsigned H,
+                                unsigned C, lfbm5d_pg_estimate* out, unsigned long long* h_hist, unsigned long long* h_sum);
+/* Host only, needs no GPU: the common scale s of a model for C = 1 or 3 channels -- the sigma of the transformed light field.  Returns 1
+ * on a rejected model (a < 0, 3/8 a^2 + b <= 0, anything not finite) or C. */
+int lfbm5d_pg_scale(const lfbm5d_pg_model* model, unsigned C, double* s);
+/* d_out = forward / inverse transform of d_in, both [asize][C*H*W] in HBM; d_out may be d_in. */
+int lfbm5d_pg_forward_device(lfbm5d_ctx* ctx, const lfbm5d_pg_model* model, const float* d_in, const unsigned* h_mask, float* d_out,
+                             unsigned asize, unsigned W, unsigned H, unsigned C);
+int lfbm5d_pg_inverse_device(lfbm5d_ctx* ctx, const lfbm5d_pg_model* model, const float* d_in, const unsigned* h_mask, float* d_out,
+                             unsigned asize, unsigned W, unsigned H, unsigned C);
+/* The job: (1) forward transform of d_noisy -- which is only read -- into a light field of scratch the context owns, (2)
+ * lfbm5d_denoise_device on it with P1->sigma = P2->sigma = (float)s (the sigmas passed are ignored; every option and fallback of that
+ * call applies), (3) inverse transform in place on d_basic and d_denoised.  Bit-identical to the three calls made by hand.  model NULL:
+ * the pooled model (a, b for every channel) is estimated from d_noisy first; `used` (may be NULL) receives the model that was applied. */
+int lfbm5d_denoise_pg_device(lfbm5d_ctx* ctx, const lfbm5d_pg_model* model, lfbm5d_pg_model* used, const lfbm5d_params* P1,
+                             const lfbm5d_params* P2, const float* d_noisy, const unsigned* h_mask, float* d_basic, float* d_denoised,
+                             unsigned ang_major, unsigned awidth, unsigned aheight, unsigned an1, unsigned an2, unsigned W, unsigned H,
+                             unsigned C);
+/* The same on host light fields, one pointer per SAI (NULL allowed for empty SAIs), staged through HBM with blocking copies:
+ * bit-identical to the device form.  h_noisy is only read. */
+int lfbm5d_denoise_pg_host_sai(lfbm5d_ctx* ctx, const lfbm5d_pg_model* model, lfbm5d_pg_model* used, const lfbm5d_params* P1,
+                               const lfbm5d_params* P2, const float* const* h_noisy, const unsigned* h_mask, float* const* h_basic,
+                               float* const* h_denoised, unsigned ang_major, unsigned awidth, unsigned aheight, unsigned an1, unsigned an2,
+                               unsigned W, unsigned H, unsigned C);
 
 /* ---- inspection of the last pass's block matching (parity tests) ----
  * n_refs reference patches in raster order; h_refs[n_refs] flat index i*Wb+j;

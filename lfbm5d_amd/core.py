@@ -72,6 +72,34 @@ class SrParams(C.Structure):
                 ("sigma_start", C.c_float), ("sigma_end", C.c_float), ("beta", C.c_float), ("close_projection", C.c_uint)]
 
 
+class PgModelStruct(C.Structure):
+    """lfbm5d_pg_model: a, b of var(z | y) = a y + b per stored channel (include/lfbm5d.h)."""
+    _fields_ = [("a", C.c_double * 3), ("b", C.c_double * 3)]
+
+
+class PgEstimateStruct(C.Structure):
+    """lfbm5d_pg_estimate: the fitted Poisson-Gaussian models of a light field (include/lfbm5d.h)."""
+    _fields_ = [("a", C.c_double), ("b", C.c_double), ("a_channel", C.c_double * 3), ("b_channel", C.c_double * 3),
+                ("blocks", C.c_ulonglong), ("skipped", C.c_ulonglong)]
+
+
+PG_LEVELS, PG_KEYS = 64, 322
+
+
+class PgEstimate(NamedTuple):
+    """Result of Context.pg_estimate / pg_estimate: the light field's model var(z | y) = a y + b (all non-empty SAIs and channels
+    pooled), the per-channel models (NaN where a channel's own fit fails), the 2 x 2 blocks visited and skipped (non-finite), and
+    the statistics the fits came from: hist uint64 [C][64][322], sum_m uint64 [C][64]."""
+    a: float
+    b: float
+    a_channel: tuple
+    b_channel: tuple
+    blocks: int
+    skipped: int
+    hist: np.ndarray
+    sum_m: np.ndarray
+
+
 class NoiseLevel(NamedTuple):
     """Result of Context.noise_level / noise_level: sigma of the whole light field (what to pass as `sigma`), per stored channel
     (grey: [0] only), the size m of the noise subspace, the patches pooled, the eigenvalues of the pooled covariance (ascending)
@@ -207,6 +235,18 @@ def lib():
         L.lfbm5d_sr_backproject_device.argtypes = [vp, sp, fp, fp, up, fp] + [C.c_uint] * 4
         L.lfbm5d_superres_device.argtypes = [vp, sp, pp, fp, up, fp] + [C.c_uint] * 7
         L.lfbm5d_superres_host_sai.argtypes = [vp, sp, pp, fp, up, fp] + [C.c_uint] * 7
+    if hasattr(L, "lfbm5d_denoise_pg_device"):   # (absent from older builds loaded through LFBM5D_HIP_LIB for A/B runs)
+        dp, ullp, mp_, ep = C.POINTER(C.c_double), C.POINTER(C.c_ulonglong), C.POINTER(PgModelStruct), C.POINTER(PgEstimateStruct)
+        pp = C.POINTER(Params)
+        L.lfbm5d_pg_histogram_device.argtypes = [vp, fp, up] + [C.c_uint] * 4 + [ullp, ullp, ullp, ullp]
+        L.lfbm5d_pg_fit.argtypes = [ullp, ullp, dp, dp]
+        L.lfbm5d_pg_estimate_device.argtypes = [vp, fp, up] + [C.c_uint] * 4 + [ep, ullp, ullp]
+        L.lfbm5d_pg_estimate_host_sai.argtypes = [vp, fp, up] + [C.c_uint] * 4 + [ep, ullp, ullp]
+        L.lfbm5d_pg_scale.argtypes = [mp_, C.c_uint, dp]
+        L.lfbm5d_pg_forward_device.argtypes = [vp, mp_, fp, up, fp] + [C.c_uint] * 4
+        L.lfbm5d_pg_inverse_device.argtypes = [vp, mp_, fp, up, fp] + [C.c_uint] * 4
+        L.lfbm5d_denoise_pg_device.argtypes = [vp, mp_, mp_, pp, pp, fp, up, fp, fp] + [C.c_uint] * 8
+        L.lfbm5d_denoise_pg_host_sai.argtypes = [vp, mp_, mp_, pp, pp, fp, up, fp, fp] + [C.c_uint] * 8
     L.lfbm5d_malloc.argtypes = [C.POINTER(vp), C.c_size_t]
     L.lfbm5d_free.argtypes = [vp]
     L.lfbm5d_memcpy_h2d.argtypes = [vp, vp, C.c_size_t]
@@ -327,6 +367,54 @@ def quality_summary(mse_sai, ssim_sai, mask, peak=255.0):
     if ssim is not None:
         ssim[m == 0] = 0.0
     return _quality_result(res, mse, ssim, m, peak)
+
+
+def pg_fit(hist, sum_m):
+    """lfbm5d_pg_fit (host only, no GPU): (a, b) of one histogram hist uint64 [64][322] with sum_m uint64 [64] (include/lfbm5d.h has
+    the definition).  Raises when no level is valid."""
+    h = np.ascontiguousarray(hist, np.uint64)
+    sm = np.ascontiguousarray(sum_m, np.uint64)
+    if h.shape != (PG_LEVELS, PG_KEYS) or sm.shape != (PG_LEVELS,):
+        raise LfBm5dError("lfbm5d_pg_fit: hist must be [64][322] and sum_m [64]")
+    a, b = C.c_double(), C.c_double()
+    ullp = C.POINTER(C.c_ulonglong)
+    if lib().lfbm5d_pg_fit(h.ctypes.data_as(ullp), sm.ctypes.data_as(ullp), C.byref(a), C.byref(b)) != 0:
+        raise LfBm5dError("lfbm5d_pg_fit: no valid level (every level holds fewer than 256 blocks, or its quantile fell into an end bin)")
+    return a.value, b.value
+
+
+def pg_model(a, b, chnls=3):
+    """lfbm5d_pg_model from scalars (the same model for every channel) or per-channel sequences."""
+    a = [float(a)] * chnls if np.isscalar(a) else [float(v) for v in a]
+    b = [float(b)] * chnls if np.isscalar(b) else [float(v) for v in b]
+    if len(a) != chnls or len(b) != chnls or chnls not in (1, 3):
+        raise LfBm5dError("a Poisson-Gaussian model holds one (a, b) per stored channel, 1 or 3 of them")
+    m = PgModelStruct()
+    for i in range(3):
+        j = i if chnls == 3 else 0
+        m.a[i], m.b[i] = a[j], b[j]
+    return m
+
+
+def _as_pg_model(model, chnls):
+    if model is None or isinstance(model, PgModelStruct):
+        return model
+    if isinstance(model, PgEstimate):
+        return pg_model(model.a, model.b, chnls)
+    return pg_model(model[0], model[1], chnls)
+
+
+def pg_scale(model, chnls=3):
+    """lfbm5d_pg_scale (host only, no GPU): the sigma of the light field after the forward transform of `model` (a PgModelStruct, a
+    PgEstimate or a pair (a, b) of scalars or per-channel sequences).  Raises on a rejected model."""
+    s = C.c_double()
+    try:
+        m = _as_pg_model(model, chnls)
+    except (TypeError, ValueError) as e:
+        raise LfBm5dError(f"lfbm5d_pg_scale: {e}")
+    if m is None or lib().lfbm5d_pg_scale(C.byref(m), int(chnls), C.byref(s)) != 0:
+        raise LfBm5dError("lfbm5d_pg_scale: bad model (every channel needs a >= 0 and 3/8 a^2 + b > 0, finite; chnls 1 or 3)")
+    return s.value
 
 
 def sr_defaults(scale, /, **changes):
@@ -637,6 +725,77 @@ class Context:
             self._ck(self._L.lfbm5d_quality_device(self._h, _dev_ptr(ref), _dev_ptr(test), *tail))
         return _quality_result(res, mse[:asize], ss[:asize], m, peak)
 
+    # ---- Poisson-Gaussian noise ----
+    @staticmethod
+    def _host_sais(LF):
+        if isinstance(LF, np.ndarray) and LF.dtype != np.float32:
+            raise LfBm5dError("host light fields must be float32")
+        return list(LF) if isinstance(LF, (list, tuple)) else [np.ascontiguousarray(a) for a in LF]
+
+    def pg_histogram(self, LF, LF_SAI_mask, width, height, chnls):
+        """The block statistics of lfbm5d_pg_histogram_device on a CUDA float32 tensor [asize][C*H*W]: (hist uint64 [C][64][322],
+        sum_m uint64 [C][64], blocks, skipped)."""
+        m = _u32(LF_SAI_mask)
+        C_ = int(chnls)
+        hist, sm = np.zeros((max(C_, 1), PG_LEVELS, PG_KEYS), np.uint64), np.zeros((max(C_, 1), PG_LEVELS), np.uint64)
+        blocks, skipped = C.c_ulonglong(), C.c_ulonglong()
+        ullp = C.POINTER(C.c_ulonglong)
+        self._ck(self._L.lfbm5d_pg_histogram_device(self._h, _dev_ptr(LF), m.ctypes.data_as(C.POINTER(C.c_uint)), m.size, int(width),
+                                                    int(height), C_, hist.ctypes.data_as(ullp), sm.ctypes.data_as(ullp),
+                                                    C.byref(blocks), C.byref(skipped)))
+        return hist, sm, blocks.value, skipped.value
+
+    def pg_estimate(self, LF, LF_SAI_mask, width, height, chnls):
+        """Estimate the Poisson-Gaussian model var(z | y) = a y + b of a noisy light field (lfbm5d_pg_estimate_*, include/lfbm5d.h).
+        LF: a CUDA float32 tensor [asize][C*H*W] (device form, read only), a float32 numpy array of that shape or a list of per-SAI
+        float32 arrays (host form, staged through HBM; identical results).  Returns a PgEstimate."""
+        m = _u32(LF_SAI_mask)
+        C_ = int(chnls)
+        res = PgEstimateStruct()
+        hist, sm = np.zeros((max(C_, 1), PG_LEVELS, PG_KEYS), np.uint64), np.zeros((max(C_, 1), PG_LEVELS), np.uint64)
+        ullp = C.POINTER(C.c_ulonglong)
+        tail = (m.ctypes.data_as(C.POINTER(C.c_uint)), m.size, int(width), int(height), C_, C.byref(res), hist.ctypes.data_as(ullp),
+                sm.ctypes.data_as(ullp))
+        if isinstance(LF, (list, tuple, np.ndarray)):
+            self._ck(self._L.lfbm5d_pg_estimate_host_sai(self._h, _sai_ptrs(self._host_sais(LF), m), *tail))
+        else:
+            self._ck(self._L.lfbm5d_pg_estimate_device(self._h, _dev_ptr(LF), *tail))
+        return PgEstimate(res.a, res.b, tuple(res.a_channel[:C_]), tuple(res.b_channel[:C_]), int(res.blocks), int(res.skipped), hist, sm)
+
+    def pg_forward(self, model, LF, mask, out, width, height, chnls):
+        """out = generalised Anscombe transform of LF under `model` (lfbm5d_pg_forward_device): CUDA float32 tensors [asize][C*H*W];
+        out may be LF.  Returns the sigma of `out` (pg_scale)."""
+        mdl = _as_pg_model(model, int(chnls))
+        m = _u32(mask)
+        self._ck(self._L.lfbm5d_pg_forward_device(self._h, C.byref(mdl), _dev_ptr(LF), m.ctypes.data_as(C.POINTER(C.c_uint)), _dev_ptr(out),
+                                                  m.size, int(width), int(height), int(chnls)))
+        return pg_scale(mdl, chnls)
+
+    def pg_inverse(self, model, LF, mask, out, width, height, chnls):
+        """out = exact unbiased inverse of pg_forward (lfbm5d_pg_inverse_device); out may be LF."""
+        mdl = _as_pg_model(model, int(chnls))
+        m = _u32(mask)
+        self._ck(self._L.lfbm5d_pg_inverse_device(self._h, C.byref(mdl), _dev_ptr(LF), m.ctypes.data_as(C.POINTER(C.c_uint)), _dev_ptr(out),
+                                                  m.size, int(width), int(height), int(chnls)))
+
+    def denoise_pg(self, model, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, Cc):
+        """The two-step job under Poisson-Gaussian noise (lfbm5d_denoise_pg_*): forward transform, denoise() with sigma = the model's
+        scale (P1.sigma / P2.sigma are ignored), inverse transform.  model: a PgModelStruct, a PgEstimate, a pair (a, b), or None =
+        estimate the pooled model from `noisy`.  noisy is only read.  CUDA float32 tensors (device form), or float32 numpy arrays /
+        lists of per-SAI arrays (host form; bit-identical).  Returns the model that was used (PgModelStruct)."""
+        mdl = _as_pg_model(model, int(Cc))
+        used = PgModelStruct()
+        m = _u32(mask)
+        mp = m.ctypes.data_as(C.POINTER(C.c_uint))
+        head = (self._h, C.byref(mdl) if mdl is not None else None, C.byref(used), C.byref(P1), C.byref(P2))
+        tail = (ang_major, awidth, aheight, an1, an2, int(W), int(H), int(Cc))
+        if isinstance(noisy, (list, tuple, np.ndarray)):
+            n, b, d = (self._host_sais(x) for x in (noisy, basic, denoised))
+            self._ck(self._L.lfbm5d_denoise_pg_host_sai(*head, _sai_ptrs(n, m), mp, _sai_ptrs(b, m), _sai_ptrs(d, m), *tail))
+        else:
+            self._ck(self._L.lfbm5d_denoise_pg_device(*head, _dev_ptr(noisy), mp, _dev_ptr(basic), _dev_ptr(denoised), *tail))
+        return used
+
     # ---- super-resolution ----
     def _sr_tail(self, mask, w, h, Cc):
         m = _u32(mask)
@@ -782,6 +941,16 @@ def noise_level(LF, LF_SAI_mask, width, height, chnls, patch=8, per_sai=False, c
 def quality(ref, test, mask, width, height, chnls, peak=255.0, ssim=True, ctx=None):
     """Context.quality on the default context (device 0): per-SAI PSNR, RMSE and SSIM of `test` against `ref` and their summary."""
     return (ctx or _ctx()).quality(ref, test, mask, width, height, chnls, peak, ssim)
+
+
+def pg_estimate(LF, LF_SAI_mask, width, height, chnls, ctx=None):
+    """Context.pg_estimate on the default context (device 0): the Poisson-Gaussian noise model of a noisy light field."""
+    return (ctx or _ctx()).pg_estimate(LF, LF_SAI_mask, width, height, chnls)
+
+
+def denoise_pg(model, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls, ctx=None):
+    """Context.denoise_pg on the default context (device 0); returns the model that was used."""
+    return (ctx or _ctx()).denoise_pg(model, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls)
 
 
 def superres(sr, P, low, mask, high, ang_major, awidth, aheight, an, w, h, chnls, ctx=None):

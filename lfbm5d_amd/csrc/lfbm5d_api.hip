@@ -77,6 +77,7 @@ void lfbm5d_destroy(lfbm5d_ctx* c) {
     c->noise.sai.release(); c->noise.part.release(); c->noise.cells.release(); c->noise.m.release(); c->noise.pool.release();
     c->sr.sai.release(); c->sr.tab.release(); c->sr.hi.release(); c->sr.lo.release();
     c->quality.sai.release(); c->quality.part.release(); c->quality.out.release();
+    c->pg.sai.release(); c->pg.stats.release(); c->pg.lf.release();
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     if (c->h_small) (void)hipHostFree(c->h_small);
     if (c->stream) (void)hipStreamDestroy(c->stream);

@@ -16,7 +16,13 @@
  *   LFBM5D_TILED=1    honour nbThreads > 1 the reference's way (tiles with a discarded halo, bm5d.cpp:411-708);
  *   LFBM5D_SIGMA=auto estimate sigma from the noisy light field (noise_level_LF, run_bm5d.h) once it exists -- loaded with
  *                     LFSourceDir = none, or made with the argument's sigma from a ground truth -- and use the estimate for both
- *                     steps and the diff images; any other value is an error;
+ *                     steps and the diff images;
+ *   LFBM5D_SIGMA=poisson | poisson:<a>,<b>   signal-dependent noise var(z | y) = a y + b (0..255 scale; a >= 0, 3/8 a^2 + b > 0): the
+ *                     model is estimated from the noisy light field (pg_estimate_LF, run_bm5d.h), or given; both steps then run as one
+ *                     job between the variance-stabilising transform and its exact unbiased inverse (denoise_pg_LF; LFBM3Ddenoising:
+ *                     pg_forward_LF, run_bm3d_LF, pg_inverse_LF), with the sigma the transform leaves (also used for the diff images).
+ *                     With a ground truth and poisson:<a>,<b> the noise added is Poisson-Gaussian with those parameters (<random>,
+ *                     seeded from LFBM5D_SEED; the argument's sigma is unused); any other value is an error;
  *   LFBM5D_REPORT_SSIM=1  the average SSIM next to every average PSNR on stdout and an SSIM block behind every PSNR block of the
  *                     results file, computed on the GPU on the images as the files hold them (cli_quality.h); any other value is an
  *                     error; unset, the output is unchanged.
@@ -33,6 +39,7 @@
 #include <sys/time.h>
 #include <unistd.h>
 
+#include <cctype>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -202,8 +209,26 @@ void diff_LF(const vector<vector<float> >& A, const vector<vector<float> >& B, c
  * and the process id: the SAIs' streams are independent and are drawn by the I/O thread pool (the SAI's index added to the seed:
  * threads that start within one millisecond must not share one).  LFBM5D_SEED (tests, benchmarks) is ONE stream through the SAIs
  * in order: its uniforms are drawn in order, SAI by SAI, and only their Box-Muller transform is spread over the threads. */
-void add_noise_LF(const vector<vector<float> >& LF, const vector<unsigned>& mask, vector<vector<float> >& LF_noisy, float sigma) {
+void add_noise_LF(const vector<vector<float> >& LF, const vector<unsigned>& mask, vector<vector<float> >& LF_noisy, float sigma,
+                  const double* pg = nullptr) {
     const char* seed = getenv("LFBM5D_SEED");
+    if (pg) {   /* Poisson-Gaussian noise {a, b}: a * Poisson(y / a) + N(0, b), one <random> stream through the SAIs in order */
+        timeval tp; gettimeofday(&tp, nullptr);
+        std::mt19937_64 g(seed ? strtoull(seed, nullptr, 10) : (unsigned long long)(tp.tv_sec * 1000 + tp.tv_usec / 1000 + getpid()));
+        const double a = pg[0], sd = sqrt(std::max(pg[1], 0.0));
+        std::normal_distribution<double> gauss(0.0, 1.0);
+        for (size_t st = 0; st < LF.size(); st++) {
+            if (!mask[st]) continue;
+            for (size_t q = 0; q < LF[st].size(); q++) {
+                const double y = LF[st][q];
+                double z = y;
+                if (a > 0.0) z = y > 0.0 ? a * (double)std::poisson_distribution<long long>(y / a)(g) : 0.0;
+                if (sd > 0.0) z += sd * gauss(g);
+                LF_noisy[st][q] = (float)z;
+            }
+        }
+        return;
+    }
     auto gauss = [sigma](double x, double y) { return (float)((double)sigma * sqrt(-2.0 * log(x)) * cos(2.0 * M_PI * y)); };
     if (!seed) {
         parallel_sais((unsigned)LF.size(), [&](unsigned st) {
@@ -233,13 +258,35 @@ void add_noise_LF(const vector<vector<float> >& LF, const vector<unsigned>& mask
     }
 }
 
-/* LFBM5D_SIGMA: unset -> 0 (the argument's sigma), "auto" -> 1 (estimate it), anything else -> -1 (error, message printed) */
-int sigma_mode() {
+/* LFBM5D_SIGMA: unset -> 0 (the argument's sigma), "auto" -> 1 (estimate it), "poisson" -> 2 (Poisson-Gaussian model, estimated),
+ * "poisson:<a>,<b>" -> 3 (that model: pg = {a, b}), anything else -> -1 (error, message printed) */
+int sigma_mode(double* pg) {
     const char* e = getenv("LFBM5D_SIGMA");
     if (!e) return 0;
     if (!strcmp(e, "auto")) return 1;
-    cout << "LFBM5D_SIGMA must be \"auto\" (estimate sigma from the noisy light field) or unset; got \"" << e << "\"" << endl;
+    if (!strcmp(e, "poisson")) return 2;
+    if (!strncmp(e, "poisson:", 8)) {
+        const char* p = e + 8;
+        char *q = nullptr, *r = nullptr;
+        const double a = strtod(p, &q);
+        if (q != p && *q == ',' && q[1] && !isspace((unsigned char)q[1])) {
+            const double b = strtod(q + 1, &r);
+            if (r != q + 1 && !*r && std::isfinite(a) && std::isfinite(b) && a >= 0.0 && 0.375 * a * a + b > 0.0) { pg[0] = a; pg[1] = b; return 3; }
+        }
+    }
+    cout << "LFBM5D_SIGMA must be \"auto\" (estimate sigma from the noisy light field), \"poisson\" (estimate a Poisson-Gaussian noise model "
+            "var = a y + b) or \"poisson:<a>,<b>\" (that model; a >= 0, 3/8 a^2 + b > 0), or unset; got \"" << e << "\"" << endl;
     return -1;
+}
+
+/* LFBM5D_SIGMA=poisson: the model of the noisy light field */
+[[maybe_unused]] bool estimate_pg_LF(const vector<vector<float> >& LF_noisy, const vector<unsigned>& mask, unsigned W, unsigned H, unsigned C, double* pg) {
+    return pg_estimate_LF(LF_noisy, mask, W, H, C, pg[0], pg[1]) == EXIT_SUCCESS;
+}
+
+void print_pg_model(bool estimated, const double* pg, float s) {
+    cout << endl << (estimated ? "Estimated" : "Given") << " noise model: a = " << setprecision(8) << pg[0] << ", b = " << pg[1]
+         << " (sigma after stabilisation = " << s << ")" << setprecision(6) << endl;
 }
 
 /* LFBM5D_SIGMA=auto: replace `sigma` with the estimate on the noisy light field */
@@ -307,7 +354,8 @@ int main(int argc, char** argv) {
     const unsigned nb_threads = atoi(argv[a++]);
     const char* results = argv[a++];
     if (!ang_major || cs < 0) { cout << "Problem while reading parameters from command line !" << endl; return EXIT_FAILURE; }
-    const int smode = sigma_mode();
+    double pg[2] = {0.0, 0.0};
+    const int smode = sigma_mode(pg);
     if (smode < 0) return EXIT_FAILURE;
     const int qmode = cli_quality::ssim_mode();
     if (qmode < 0) return EXIT_FAILURE;
@@ -321,9 +369,10 @@ int main(int argc, char** argv) {
         if (load_LF(src, name, sep, LF, mask, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
         cout << "Loading LF elapsed time = " << now_s() - t << "s." << endl;
         LF_noisy.assign(awh, vector<float>((size_t)W * H * C, 0.0f));
-        cout << endl << "Add noise [sigma = " << sigma << "] ... " << flush;
+        if (smode == 3) cout << endl << "Add noise [Poisson-Gaussian, a = " << pg[0] << ", b = " << pg[1] << "] ... " << flush;
+        else cout << endl << "Add noise [sigma = " << sigma << "] ... " << flush;
         t = now_s();
-        add_noise_LF(LF, mask, LF_noisy, sigma);
+        add_noise_LF(LF, mask, LF_noisy, sigma, smode == 3 ? pg : nullptr);
         cout << "done in " << now_s() - t << "s." << endl << endl << "Save noisy light field..." << endl;
         if (save_LF(d_noisy, name, sep, LF_noisy, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
     } else {
@@ -345,6 +394,16 @@ int main(int argc, char** argv) {
     cout << endl << " ---> Running LFBM3D filter <--- " << endl << endl;
     const double tb = now_s();
     char sub[] = "SAI";
+    if (smode >= 2) {   /* Poisson-Gaussian noise: stabilise a copy, filter it with the sigma that leaves, invert the results */
+        if (smode == 2 && !estimate_pg_LF(LF_noisy, mask, W, H, C, pg)) return EXIT_FAILURE;
+        vector<vector<float> > LF_t = LF_noisy;
+        if (pg_forward_LF(pg[0], pg[1], LF_t, mask, W, H, C, sigma) != EXIT_SUCCESS) return EXIT_FAILURE;
+        print_pg_model(smode == 2, pg, sigma);
+        if (run_bm3d_LF(sigma, LF_t, mask, LF_basic, LF_den, W, H, C, n[0], n[1], k[0], k[1], N[0], N[1], p[0], p[1], sd[0] != 0, sd[1] != 0,
+                        t2[0], t2[1], lambda, cs, nb_threads, sub) != EXIT_SUCCESS) return EXIT_FAILURE;
+        if (pg_inverse_LF(pg[0], pg[1], LF_basic, mask, W, H, C) != EXIT_SUCCESS || pg_inverse_LF(pg[0], pg[1], LF_den, mask, W, H, C) != EXIT_SUCCESS)
+            return EXIT_FAILURE;
+    } else
     if (run_bm3d_LF(sigma, LF_noisy, mask, LF_basic, LF_den, W, H, C, n[0], n[1], k[0], k[1], N[0], N[1], p[0], p[1], sd[0] != 0, sd[1] != 0,
                     t2[0], t2[1], lambda, cs, nb_threads, sub) != EXIT_SUCCESS) return EXIT_FAILURE;
     const double secs = now_s() - tb;
@@ -413,7 +472,8 @@ int main(int argc, char** argv) {
     const unsigned nb_threads = atoi(argv[a++]);
     const char* results = argv[a++];
     if (!ang_major || cs < 0) { cout << "Problem while reading parameters from command line !" << endl; usage(argv[0]); return EXIT_FAILURE; }
-    const int smode = sigma_mode();
+    double pg[2] = {0.0, 0.0};
+    const int smode = sigma_mode(pg);
     if (smode < 0) return EXIT_FAILURE;
     const int qmode = cli_quality::ssim_mode();
     if (qmode < 0) return EXIT_FAILURE;
@@ -427,9 +487,10 @@ int main(int argc, char** argv) {
         if (load_LF(src, name, sep, LF, mask, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
         cout << "Loading LF elapsed time = " << now_s() - t << "s." << endl;
         LF_noisy.assign(awh, vector<float>((size_t)W * H * C, 0.0f));
-        cout << endl << "Add noise [sigma = " << sigma << "] ... " << flush;
+        if (smode == 3) cout << endl << "Add noise [Poisson-Gaussian, a = " << pg[0] << ", b = " << pg[1] << "] ... " << flush;
+        else cout << endl << "Add noise [sigma = " << sigma << "] ... " << flush;
         t = now_s();
-        add_noise_LF(LF, mask, LF_noisy, sigma);
+        add_noise_LF(LF, mask, LF_noisy, sigma, smode == 3 ? pg : nullptr);
         cout << "done in " << now_s() - t << "s." << endl << endl << "Save noisy light field..." << endl;
         if (save_LF(d_noisy, name, sep, LF_noisy, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
     } else {
@@ -454,12 +515,18 @@ int main(int argc, char** argv) {
      * inverse(estimate) between the calls: the two differ (0.015 dB on the test light field) because the reference's colour matrices are not
      * inverses of each other */
     const char* one_job_s = getenv("LFBM5D_ONE_JOB");
-    const bool one_job = one_job_s && *one_job_s && *one_job_s != '0';
+    const bool one_job = smode >= 2 || (one_job_s && *one_job_s && *one_job_s != '0');   /* the Poisson-Gaussian path is one job */
     cout << endl << " ---> Running LFBM5D filter <--- " << endl << endl << (one_job ? "Steps 1 and 2 running as one job..." : "Step 1 running...") << endl;
     const double tb = now_s();
     double t1 = now_s();
     double job = 0.0;
-    if (one_job) {
+    if (smode >= 2) {
+        if (denoise_pg_LF(pg[0], pg[1], smode == 2, sigma, lambda, LF_noisy, mask, LF_basic, LF_den, ang_major, aw, ah, anH, anW, W, H, C, N[0],
+                          nSim[0], nDisp[0], k[0], p[0], sd[0] != 0, t2[0], t4[0], t5[0], N[1], nSim[1], nDisp[1], k[1], p[1], sd[1] != 0, t2[1],
+                          t4[1], t5[1], cs, nb_threads) != EXIT_SUCCESS) return EXIT_FAILURE;
+        job = now_s() - t1;
+        print_pg_model(smode == 2, pg, sigma);
+    } else if (one_job) {
         if (run_bm5d(sigma, lambda, LF_noisy, mask, LF_basic, LF_den, ang_major, aw, ah, anH, anW, W, H, C, N[0], nSim[0], nDisp[0], k[0], p[0],
                      sd[0] != 0, t2[0], t4[0], t5[0], N[1], nSim[1], nDisp[1], k[1], p[1], sd[1] != 0, t2[1], t4[1], t5[1], cs, nb_threads) != EXIT_SUCCESS)
             return EXIT_FAILURE;

@@ -152,6 +152,8 @@ struct lfbm5d_ctx {
         std::vector<unsigned> sai_host, host;
         unsigned key[5] = {0, 0, 0, 0, 0}; size_t off[8] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned T[4] = {0, 0, 0, 0};
     } sr;
+    /* Poisson-Gaussian noise (lfbm5d_pg.hip): non-empty SAI list, the statistics kernel's counters, the job's stabilised light field */
+    struct PgBufs { DevBuf sai, stats, lf; } pg;
     /* window lanes (run_step, pipelined form): extra contexts on the same device, each with its own stream, window
      * buffers and per-pass work buffers; owned by this context */
     std::vector<lfbm5d_ctx*> lanes;

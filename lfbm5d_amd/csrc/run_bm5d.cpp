@@ -207,6 +207,121 @@ int noise_level_LF(const std::vector<std::vector<float> >& LF, const std::vector
     return EXIT_SUCCESS;
 }
 
+/* Poisson-Gaussian noise model on the caller's vectors (one pointer per SAI, no flat copy) */
+int pg_estimate_LF(const std::vector<std::vector<float> >& LF, const std::vector<unsigned>& LF_SAI_mask, unsigned width, unsigned height,
+                   unsigned chnls, double& a, double& b) {
+    if (LF.size() != LF_SAI_mask.size()) {
+        std::cout << "pg_estimate_LF: light field and mask must hold the same number of SAIs" << std::endl;
+        return EXIT_FAILURE;
+    }
+    lfbm5d_ctx* ctx = context();
+    if (!ctx) return EXIT_FAILURE;
+    const size_t img = (size_t)width * height * chnls;
+    std::vector<const float*> p(LF.size(), nullptr);
+    for (size_t st = 0; st < LF.size(); st++) if (LF_SAI_mask[st] && LF[st].size() == img) p[st] = LF[st].data();
+    for (size_t st = 0; st < LF.size(); st++)
+        if (LF_SAI_mask[st] && !p[st]) { std::cout << "pg_estimate_LF: a non-empty SAI does not hold width*height*chnls values" << std::endl; return EXIT_FAILURE; }
+    lfbm5d_pg_estimate r;
+    if (lfbm5d_pg_estimate_host_sai(ctx, p.data(), LF_SAI_mask.data(), (unsigned)LF.size(), width, height, chnls, &r, nullptr, nullptr) != 0) {
+        std::cout << "LFBM5D GPU backend: " << lfbm5d_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+    }
+    a = r.a; b = r.b;
+    return EXIT_SUCCESS;
+}
+
+namespace {
+
+lfbm5d_pg_model pg_model_of(double a, double b) {
+    lfbm5d_pg_model m;
+    for (int c = 0; c < 3; c++) { m.a[c] = a; m.b[c] = b; }
+    return m;
+}
+
+/* the transforms have device forms only: the light field goes through a device buffer of this call */
+int pg_transform_LF(const char* who, bool inverse, double a, double b, std::vector<std::vector<float> >& LF, const std::vector<unsigned>& mask,
+                    unsigned width, unsigned height, unsigned chnls, float* sigma) {
+    if (LF.size() != mask.size()) { std::cout << who << ": light field and mask must hold the same number of SAIs" << std::endl; return EXIT_FAILURE; }
+    const lfbm5d_pg_model m = pg_model_of(a, b);
+    double s = 0.0;
+    if (lfbm5d_pg_scale(&m, chnls, &s) != 0) {
+        std::cout << who << ": bad noise model (needs a >= 0 and 3/8 a^2 + b > 0; chnls 1 or 3)" << std::endl;
+        return EXIT_FAILURE;
+    }
+    lfbm5d_ctx* ctx = context();
+    if (!ctx) return EXIT_FAILURE;
+    const size_t img = (size_t)width * height * chnls, asize = LF.size();
+    for (size_t st = 0; st < asize; st++)
+        if (mask[st] && LF[st].size() != img) { std::cout << who << ": a non-empty SAI does not hold width*height*chnls values" << std::endl; return EXIT_FAILURE; }
+    Flat flat;
+    flatten(LF, mask, img, flat);
+    void* d = nullptr;
+    const size_t bytes = std::max<size_t>(1, asize * img) * sizeof(float);
+    if (lfbm5d_malloc(&d, bytes) != 0) { std::cout << who << ": out of device memory" << std::endl; return EXIT_FAILURE; }
+    int rc = lfbm5d_memcpy_h2d(d, flat.get(), asize * img * sizeof(float));
+    if (!rc) rc = inverse ? lfbm5d_pg_inverse_device(ctx, &m, (const float*)d, mask.data(), (float*)d, (unsigned)asize, width, height, chnls)
+                          : lfbm5d_pg_forward_device(ctx, &m, (const float*)d, mask.data(), (float*)d, (unsigned)asize, width, height, chnls);
+    if (rc) std::cout << "LFBM5D GPU backend: " << lfbm5d_last_error(ctx) << std::endl;
+    if (!rc) rc = lfbm5d_memcpy_d2h(flat.get(), d, asize * img * sizeof(float));
+    lfbm5d_free(d);
+    if (rc) return EXIT_FAILURE;
+    unflatten(LF, mask, img, flat);
+    if (sigma) *sigma = (float)s;
+    return EXIT_SUCCESS;
+}
+
+} // namespace
+
+int pg_forward_LF(double a, double b, std::vector<std::vector<float> >& LF, const std::vector<unsigned>& LF_SAI_mask, unsigned width,
+                  unsigned height, unsigned chnls, float& sigma) {
+    return pg_transform_LF("pg_forward_LF", false, a, b, LF, LF_SAI_mask, width, height, chnls, &sigma);
+}
+
+int pg_inverse_LF(double a, double b, std::vector<std::vector<float> >& LF, const std::vector<unsigned>& LF_SAI_mask, unsigned width,
+                  unsigned height, unsigned chnls) {
+    return pg_transform_LF("pg_inverse_LF", true, a, b, LF, LF_SAI_mask, width, height, chnls, nullptr);
+}
+
+int denoise_pg_LF(double& a, double& b, const bool estimate, float& sigma, const float lambdaHard5D, const std::vector<std::vector<float> >& LF_noisy,
+                  std::vector<unsigned>& LF_SAI_mask, std::vector<std::vector<float> >& LF_basic, std::vector<std::vector<float> >& LF_denoised,
+                  const unsigned ang_major, const unsigned awidth, const unsigned aheight, const unsigned anHard, const unsigned anWien,
+                  const unsigned width, const unsigned height, const unsigned chnls, const unsigned NHard, const unsigned nSimHard,
+                  const unsigned nDispHard, const unsigned kHard, const unsigned pHard, const bool useSDHard, const unsigned tau_2D_hard,
+                  unsigned tau_4D_hard, const unsigned tau_5D_hard, const unsigned NWien, const unsigned nSimWien, const unsigned nDispWien,
+                  const unsigned kWien, const unsigned pWien, const bool useSDWien, const unsigned tau_2D_wien, unsigned tau_4D_wien,
+                  const unsigned tau_5D_wien, const unsigned color_space, const unsigned nb_threads) {
+    const unsigned asize = awidth * aheight;
+    if (LF_noisy.size() != asize || LF_SAI_mask.size() != asize) {
+        std::cout << "denoise_pg_LF: light field and mask must hold awidth*aheight SAIs" << std::endl;
+        return EXIT_FAILURE;
+    }
+    lfbm5d_ctx* ctx = context();
+    if (!ctx) return EXIT_FAILURE;
+    lfbm5d_set_tiles(ctx, tiles_for(nb_threads));
+    if (LF_basic.size() != asize) LF_basic.resize(asize);
+    if (LF_denoised.size() != asize) LF_denoised.resize(asize);
+    const size_t img = (size_t)width * height * chnls;
+    std::vector<const float*> noisy(asize, nullptr);
+    for (size_t st = 0; st < asize; st++) if (LF_SAI_mask[st] && LF_noisy[st].size() == img) noisy[st] = LF_noisy[st].data();
+    for (size_t st = 0; st < asize; st++)
+        if (LF_SAI_mask[st] && !noisy[st]) { std::cout << "denoise_pg_LF: a non-empty SAI does not hold width*height*chnls values" << std::endl; return EXIT_FAILURE; }
+    const std::vector<float*> basic = sai_ptrs(LF_basic, LF_SAI_mask, img, true), den = sai_ptrs(LF_denoised, LF_SAI_mask, img, true);
+    const lfbm5d_params P1 = make(0.0f, lambdaHard5D, NHard, nSimHard, nDispHard, kHard, pHard, useSDHard, tau_2D_hard, tau_4D_hard, tau_5D_hard, color_space);
+    const lfbm5d_params P2 = make(0.0f, 0.0f, NWien, nSimWien, nDispWien, kWien, pWien, useSDWien, tau_2D_wien, tau_4D_wien, tau_5D_wien, color_space);
+    const lfbm5d_pg_model given = pg_model_of(a, b);
+    lfbm5d_pg_model used;
+    double s = 0.0;
+    if (lfbm5d_denoise_pg_host_sai(ctx, estimate ? nullptr : &given, &used, &P1, &P2, noisy.data(), LF_SAI_mask.data(), basic.data(), den.data(),
+                                   ang_major, awidth, aheight, anHard, anWien, width, height, chnls) != 0 ||
+        lfbm5d_pg_scale(&used, chnls, &s) != 0) {
+        std::cout << "LFBM5D GPU backend: " << lfbm5d_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+    }
+    a = used.a[0]; b = used.b[0];
+    sigma = (float)s;
+    return EXIT_SUCCESS;
+}
+
 int report_ssim_mode() {
     const char* e = std::getenv("LFBM5D_REPORT_SSIM");
     if (!e) return 0;

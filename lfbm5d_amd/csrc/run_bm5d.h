@@ -107,6 +107,72 @@ int noise_level_LF(
 ,   float &sigma
 );
 
+//! Signal-dependent noise -- not in the reference: the Poisson-Gaussian model var(z | y) = a y + b (grey levels of the channels as stored,
+//! 0..255 scale) of a noisy light field, estimated on the GPU with every non-empty SAI and channel pooled (lfbm5d_pg_estimate_host_sai,
+//! include/lfbm5d.h).  LF is only read.  Returns EXIT_SUCCESS, or EXIT_FAILURE with the message on stdout.
+int pg_estimate_LF(
+    const std::vector<std::vector<float> > &LF
+,   const std::vector<unsigned> &LF_SAI_mask
+,   unsigned width
+,   unsigned height
+,   unsigned chnls
+,   double &a
+,   double &b
+);
+
+//! The generalised Anscombe transform of LF under the model (a, b) of every channel, in place, on the GPU (lfbm5d_pg_forward_device):
+//! afterwards the noise is white Gaussian of standard deviation `sigma` (returned; lfbm5d_pg_scale) and any denoiser for such noise
+//! applies -- run_bm5d_*, run_bm3d_LF.  pg_inverse_LF is the exact unbiased inverse for the denoised result.  A rejected model (a < 0,
+//! 3/8 a^2 + b <= 0) returns EXIT_FAILURE with the message on stdout.
+int pg_forward_LF(
+    double a
+,   double b
+,   std::vector<std::vector<float> > &LF
+,   const std::vector<unsigned> &LF_SAI_mask
+,   unsigned width
+,   unsigned height
+,   unsigned chnls
+,   float &sigma
+);
+int pg_inverse_LF(
+    double a
+,   double b
+,   std::vector<std::vector<float> > &LF
+,   const std::vector<unsigned> &LF_SAI_mask
+,   unsigned width
+,   unsigned height
+,   unsigned chnls
+);
+
+//! run_bm5d under Poisson-Gaussian noise (lfbm5d_denoise_pg_host_sai): forward transform, both steps as one job with sigma = the
+//! model's scale, inverse transform of LF_basic and LF_denoised.  estimate = true: (a, b) are estimated from LF_noisy first and
+//! returned; otherwise they are the model to use.  LF_noisy is only read; `sigma` receives the sigma the job ran with.
+int denoise_pg_LF(
+    double &a
+,   double &b
+,   const bool estimate
+,   float &sigma
+,   const float lambdaHard5D
+,   const std::vector<std::vector<float> > &LF_noisy
+,   std::vector<unsigned> &LF_SAI_mask
+,   std::vector<std::vector<float> > &LF_basic
+,   std::vector<std::vector<float> > &LF_denoised
+,   const unsigned ang_major
+,   const unsigned awidth
+,   const unsigned aheight
+,   const unsigned anHard
+,   const unsigned anWien
+,   const unsigned width
+,   const unsigned height
+,   const unsigned chnls
+,   const unsigned NHard, const unsigned nSimHard, const unsigned nDispHard, const unsigned kHard, const unsigned pHard
+,   const bool useSDHard, const unsigned tau_2D_hard, unsigned tau_4D_hard, const unsigned tau_5D_hard
+,   const unsigned NWien, const unsigned nSimWien, const unsigned nDispWien, const unsigned kWien, const unsigned pWien
+,   const bool useSDWien, const unsigned tau_2D_wien, unsigned tau_4D_wien, const unsigned tau_5D_wien
+,   const unsigned color_space
+,   const unsigned nb_threads
+);
+
 //! Quality of LF_2 against LF_1 on the GPU -- compute_psnr_LF (utilities_LF.cpp:639-692) with its argument order, the sizes and the
 //! SSIM triple added: per-SAI PSNR, RMSE and SSIM (0 for empty SAIs) with their mean and population standard deviation over the
 //! non-empty SAIs (lfbm5d_quality_host_sai, include/lfbm5d.h: double sums, peak 255, SSIM with the 11 x 11 Gaussian window over every

@@ -110,3 +110,15 @@ def add_noise_mt19937(clean, sigma, seed=1, out=None):
             jobs = [(u[2 * j:2 * min(j + piece, n0)], i0 + j, min(piece, n0 - j)) for j in range(0, n0, piece)]
             list(pool.map(box_muller, jobs))
     return res
+
+
+def add_poisson_gaussian(clean, a, b, seed=1):
+    """Poisson-Gaussian noise var(z | y) = a y + b on `clean` (any shape, nominally 0..255) from numpy's default_rng(seed):
+    a * poisson(clean / a) + normal(0, sqrt(b)); a = 0 gives the Gaussian part alone.  Negative values of `clean` count as 0 for the
+    Poisson part.  Returns float32."""
+    clean = np.asarray(clean, dtype=np.float64)
+    rng = np.random.default_rng(seed)
+    z = float(a) * rng.poisson(np.maximum(clean, 0.0) / float(a)) if a > 0 else clean.copy()
+    if b > 0:
+        z = z + rng.normal(0.0, np.sqrt(float(b)), clean.shape)
+    return z.astype(np.float32)
