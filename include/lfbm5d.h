@@ -543,6 +543,82 @@ int lfbm5d_denoise_pg_host_sai(lfbm5d_ctx* ctx, const lfbm5d_pg_model* model, lf
                                float* const* h_denoised, unsigned ang_major, unsigned awidth, unsigned aheight, unsigned an1, unsigned an2,
                                unsigned W, unsigned H, unsigned C);
 
+/* ---- impulse-noise repair: outlier detection and replacement ahead of the denoiser ----
+ * Not in the reference (its authors run such a stage in front of it: README [4]).  The estimators above and the filter assume that every
+ * pixel carries Gaussian-like noise; hot and dead pixels, salt and pepper and drop-outs written as 0, 255 or NaN count as noise for the
+ * blind sigma, as structure for the block matching, and survive the hard threshold.  This stage finds and replaces them; it is opt-in.
+ * Light fields are [asize][C*H*W] float32, channels as stored; h_mask marks empty SAIs, whose planes are neither read nor written; C = 1 or
+ * 3; W, H >= 2.  One GPU: contexts with a communicator or a shard return 1.  Everything below is stated in float32 operations without a
+ * product, integer counts and order statistics: the GPU equals the numpy model of tests/impulse_model.py bit for bit.
+ * Limits: an impulse smeared by demosaicking into a blob, or a cluster that fills a 3 x 3, is not found (its neighbours agree with it);
+ * detection is spatial only (no cross-SAI test); on nearly noise-free, textured data about 0.4 % of the sound values are touched
+ * (DESIGN.md 3g has the table); k = 8 is the cheapest row of that table on sound data, a default and not a law.
+ *
+ * Neighbours.  For a pixel c of a plane I the neighbours q are the eight positions of the 3 x 3 around it; coordinates outside the plane
+ * are mirrored without repeating the edge (-1 -> 1, W -> W - 2), so every neighbour is another real pixel, at the corners too (a pixel
+ * may appear twice).
+ * ROAD (rank-ordered absolute differences, Garnett et al., IEEE TIP 2005), float32: d_q = |c - q|; a non-finite q or c gives d_q = +inf;
+ * with d sorted ascending R = ((d0 + d1) + d2) + d3.
+ * Extremeness.  lt = the finite neighbours q < c, gt = the finite neighbours q > c; the pixel is extreme when min(lt, gt) = 0 (not a
+ * strict test: two adjacent impulses of one value both qualify).  Without it texture, whose R is large, is flagged 10-70 times as often.
+ * Scale.  Per channel a histogram of R over every pixel of every non-empty SAI: E_MIN = -12, E_MAX = 12, Q = (E_MAX - E_MIN) 16 + 2 = 386
+ * keys, key = clamp((bits(R) >> 19) - ((E_MIN + 127) << 4) + 1, 0, Q - 1): key 0 is [0, 2^-12), the lower edge e[k] of key k >= 1 is the
+ * float whose bits are (k - 1 + 1840) << 19, key 385 collects everything >= 2^12 (R reaches 1020 on 0..255 data).  A non-finite R is
+ * skipped and counted.  scale = the 0.5 quantile: n = sum_k h[k], T = 0.5 n, k* = the first k whose cumulative count is >= T,
+ * scale = e[k*] + (e[k*+1] - e[k*]) (T - cum[k*-1]) / h[k*] in double (k* = 385 has no upper edge: scale = e[385]); n = 0 fails.  A
+ * channel's scale comes from its own histogram, the pooled scale from the channels' histograms added; inside the repair an empty
+ * histogram counts as scale 0.
+ * Threshold.  T_c = (float) max(k scale_c, min_threshold); a caller-given threshold[c] > 0 replaces it: T_c = (float) threshold[c]; when
+ * every channel's is given the statistics pass is skipped (scales 0, skipped 0).
+ * Flag.  A pixel is flagged when c is not finite, or when R > T_c and the pixel is extreme.
+ * Repair.  The unflagged finite neighbours of a flagged pixel, n of them, sorted ascending (-0 before +0): the pixel becomes element
+ * (n - 1) / 2, the lower median -- always an existing pixel value, no arithmetic; n = 0: the pixel is left as it is.  Unflagged pixels are
+ * copied unchanged.  Flag plane (optional, uint8 [asize][C*H*W]): 0 = sound, 1 = flagged and repaired, 2 = flagged and left. */
+#define LFBM5D_IMPULSE_KEYS 386
+typedef struct {
+    double k;              /* threshold = k x the channel's median ROAD; >= 0                       */
+    double min_threshold;  /* floor of that threshold; >= 0                                         */
+    double threshold[3];   /* > 0: this channel's threshold outright (grey: [0] only)               */
+} lfbm5d_impulse_params;
+typedef struct {
+    double scale;                  /* median ROAD of all channels pooled (0 when the statistics pass did not run) */
+    double scale_channel[3];       /* per stored channel                                                          */
+    double threshold[3];           /* the float32 thresholds that were applied                                    */
+    unsigned long long flagged[3]; /* per stored channel: repaired + left                                         */
+    unsigned long long repaired[3];
+    unsigned long long left[3];    /* flagged pixels without a sound neighbour, left as they were                 */
+    unsigned long long pixels;     /* values of the non-empty SAIs                                                */
+    unsigned long long skipped;    /* of those, the statistics pass skipped for a non-finite R                    */
+} lfbm5d_impulse_result;
+/* Host only: k = 8, min_threshold = 0, no given threshold. */
+void lfbm5d_impulse_defaults(lfbm5d_impulse_params* out);
+/* d_lf [asize][C*H*W] in HBM, read only; h_hist [C][386] (host) receives the counts; pixels / skipped may be NULL.  Returns 1 with a
+ * message on a rejected input (a NULL required buffer, C, W / H, a mask without a non-empty SAI, a context with a communicator or shard). */
+int lfbm5d_impulse_histogram_device(lfbm5d_ctx* ctx, const float* d_lf, const unsigned* h_mask, unsigned asize, unsigned W, unsigned H,
+                                    unsigned C, unsigned long long* h_hist, unsigned long long* pixels, unsigned long long* skipped);
+/* Host only, needs no GPU: the scale above of one histogram hist [386].  Returns 1 on an empty histogram (or a NULL pointer; no message:
+ * there is no context). */
+int lfbm5d_impulse_scale(const unsigned long long* hist, double* scale);
+/* Detect and repair: d_out = repaired d_in, both [asize][C*H*W] in HBM.  d_out must not overlap d_in (neighbours are read across tile
+ * edges): that returns 1 with a message.  d_flags (uint8 [asize][C*H*W] in HBM) or NULL; out or NULL; h_counts_sai (host,
+ * [asize][C][3] = flagged, repaired, left; zeros for empty SAIs) or NULL.  Integer atomics only: repeated calls return the same bits. */
+int lfbm5d_impulse_repair_device(lfbm5d_ctx* ctx, const lfbm5d_impulse_params* params, const float* d_in, const unsigned* h_mask, float* d_out,
+                                 unsigned char* d_flags, unsigned asize, unsigned W, unsigned H, unsigned C, lfbm5d_impulse_result* out,
+                                 unsigned long long* h_counts_sai);
+/* Repair under the caller's flags (a camera's fixed defect map): d_flags_in uint8 [asize][C*H*W] in HBM, non-zero = defective; no
+ * detection, no statistics (scales and thresholds of `out` are 0); an unflagged non-finite pixel is copied like any other and is no
+ * candidate for a neighbour's repair.  d_flags (the codes above) or NULL; it must not overlap d_flags_in. */
+int lfbm5d_impulse_repair_flags_device(lfbm5d_ctx* ctx, const float* d_in, const unsigned char* d_flags_in, const unsigned* h_mask,
+                                       float* d_out, unsigned char* d_flags, unsigned asize, unsigned W, unsigned H, unsigned C,
+                                       lfbm5d_impulse_result* out, unsigned long long* h_counts_sai);
+/* The same on host light fields, one pointer per SAI (NULL allowed for empty SAIs), staged through HBM with blocking copies: identical
+ * results.  h_flags_in NULL: detect and repair (params required); otherwise the given-flags form (params ignored).  h_flags or NULL.
+ * h_out[st] may be h_in[st]: the staging buffers are distinct. */
+int lfbm5d_impulse_repair_host_sai(lfbm5d_ctx* ctx, const lfbm5d_impulse_params* params, const float* const* h_in,
+                                   const unsigned char* const* h_flags_in, const unsigned* h_mask, float* const* h_out,
+                                   unsigned char* const* h_flags, unsigned asize, unsigned W, unsigned H, unsigned C,
+                                   lfbm5d_impulse_result* out, unsigned long long* h_counts_sai);
+
 /* ---- inspection of the last pass's block matching (parity tests) ----
  * n_refs reference patches in raster order; h_refs[n_refs] flat index i*Wb+j;
  * h_self_idx[n_refs*N], h_self_cnt[n_refs] (precompute_BM, core:3301);

@@ -11,11 +11,12 @@ from .core import (Context, Params, Bm3dParams, Stats, run_bm5d_1st_step, run_bm
                    TAU, COLOR_SPACE, LfBm5dError, library_path, build_library, NoiseLevel, noise_level,
                    noise_level_statistic, Quality, quality, quality_summary, SrParams, sr_defaults, sr_taps, superres,
                    SR_BICUBIC, SR_GAUSSIAN, SR_UP, SR_DOWN, PgModelStruct, PgEstimate, pg_model, pg_fit, pg_scale, pg_estimate,
-                   denoise_pg)
+                   denoise_pg, ImpulseParamsStruct, ImpulseResultStruct, ImpulseRepair, impulse_params, impulse_scale, impulse_repair)
 
 __all__ = ["Context", "Params", "Bm3dParams", "Stats", "run_bm5d_1st_step", "run_bm5d_2nd_step", "run_bm3d_LF", "shard_rows",
            "YUV", "YCBCR", "OPP", "RGB", "ID", "DCT", "SADCT", "BIOR", "HADAMARD", "HAAR",
            "ROWMAJOR", "COLMAJOR", "TAU", "COLOR_SPACE", "LfBm5dError", "library_path",
            "build_library", "NoiseLevel", "noise_level", "noise_level_statistic", "Quality", "quality", "quality_summary",
            "SrParams", "sr_defaults", "sr_taps", "superres", "SR_BICUBIC", "SR_GAUSSIAN", "SR_UP", "SR_DOWN",
-           "PgModelStruct", "PgEstimate", "pg_model", "pg_fit", "pg_scale", "pg_estimate", "denoise_pg"]
+           "PgModelStruct", "PgEstimate", "pg_model", "pg_fit", "pg_scale", "pg_estimate", "denoise_pg",
+           "ImpulseParamsStruct", "ImpulseResultStruct", "ImpulseRepair", "impulse_params", "impulse_scale", "impulse_repair"]

@@ -86,6 +86,39 @@ class PgEstimateStruct(C.Structure):
 PG_LEVELS, PG_KEYS = 64, 322
 
 
+class ImpulseParamsStruct(C.Structure):
+    """lfbm5d_impulse_params: threshold factor, floor and given thresholds of the impulse repair (include/lfbm5d.h)."""
+    _fields_ = [("k", C.c_double), ("min_threshold", C.c_double), ("threshold", C.c_double * 3)]
+
+
+class ImpulseResultStruct(C.Structure):
+    """lfbm5d_impulse_result: scales, thresholds and counts of one impulse repair (include/lfbm5d.h)."""
+    _fields_ = [("scale", C.c_double), ("scale_channel", C.c_double * 3), ("threshold", C.c_double * 3),
+                ("flagged", C.c_ulonglong * 3), ("repaired", C.c_ulonglong * 3), ("left", C.c_ulonglong * 3),
+                ("pixels", C.c_ulonglong), ("skipped", C.c_ulonglong)]
+
+
+IMPULSE_KEYS = 386
+
+
+class ImpulseRepair(NamedTuple):
+    """Result of Context.impulse_repair / impulse_repair: the repaired light field (a tensor or an array like the input), the flag plane
+    (uint8, 0 = sound, 1 = flagged and repaired, 2 = flagged and left; None unless asked for), the pooled and per-channel median ROAD
+    (0 when every threshold was given, and with given flags), the float32 thresholds applied, the counts per stored channel and per
+    (SAI, channel) -- counts_sai int64 [asize][C][3] = flagged, repaired, left -- and the values visited / skipped by the statistics."""
+    out: object
+    flags: object
+    scale: float
+    scale_channel: tuple
+    threshold: tuple
+    flagged: tuple
+    repaired: tuple
+    left: tuple
+    pixels: int
+    skipped: int
+    counts_sai: np.ndarray
+
+
 class PgEstimate(NamedTuple):
     """Result of Context.pg_estimate / pg_estimate: the light field's model var(z | y) = a y + b (all non-empty SAIs and channels
     pooled), the per-channel models (NaN where a channel's own fit fails), the 2 x 2 blocks visited and skipped (non-finite), and
@@ -247,6 +280,16 @@ def lib():
         L.lfbm5d_pg_inverse_device.argtypes = [vp, mp_, fp, up, fp] + [C.c_uint] * 4
         L.lfbm5d_denoise_pg_device.argtypes = [vp, mp_, mp_, pp, pp, fp, up, fp, fp] + [C.c_uint] * 8
         L.lfbm5d_denoise_pg_host_sai.argtypes = [vp, mp_, mp_, pp, pp, fp, up, fp, fp] + [C.c_uint] * 8
+    if hasattr(L, "lfbm5d_impulse_repair_device"):   # (absent from older builds loaded through LFBM5D_HIP_LIB for A/B runs)
+        dp, ullp = C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)
+        ip, rp = C.POINTER(ImpulseParamsStruct), C.POINTER(ImpulseResultStruct)
+        L.lfbm5d_impulse_defaults.argtypes = [ip]
+        L.lfbm5d_impulse_defaults.restype = None
+        L.lfbm5d_impulse_histogram_device.argtypes = [vp, fp, up] + [C.c_uint] * 4 + [ullp, ullp, ullp]
+        L.lfbm5d_impulse_scale.argtypes = [ullp, dp]
+        L.lfbm5d_impulse_repair_device.argtypes = [vp, ip, fp, up, fp, vp] + [C.c_uint] * 4 + [rp, ullp]
+        L.lfbm5d_impulse_repair_flags_device.argtypes = [vp, fp, vp, up, fp, vp] + [C.c_uint] * 4 + [rp, ullp]
+        L.lfbm5d_impulse_repair_host_sai.argtypes = [vp, ip, fp, vp, up, fp, vp] + [C.c_uint] * 4 + [rp, ullp]
     L.lfbm5d_malloc.argtypes = [C.POINTER(vp), C.c_size_t]
     L.lfbm5d_free.argtypes = [vp]
     L.lfbm5d_memcpy_h2d.argtypes = [vp, vp, C.c_size_t]
@@ -417,6 +460,32 @@ def pg_scale(model, chnls=3):
     return s.value
 
 
+def impulse_scale(hist):
+    """lfbm5d_impulse_scale (host only, no GPU): the 0.5 quantile of one ROAD histogram hist uint64 [386], interpolated inside its bin
+    (include/lfbm5d.h has the definition).  Raises LfBm5dError on an empty histogram."""
+    h = np.ascontiguousarray(hist, dtype=np.uint64)
+    if h.shape != (IMPULSE_KEYS,):
+        raise LfBm5dError("lfbm5d_impulse_scale: hist must be [386]")
+    s = C.c_double()
+    if lib().lfbm5d_impulse_scale(h.ctypes.data_as(C.POINTER(C.c_ulonglong)), C.byref(s)) != 0:
+        raise LfBm5dError("lfbm5d_impulse_scale: the histogram is empty")
+    return s.value
+
+
+def impulse_params(k=8.0, min_threshold=0.0, threshold=None):
+    """lfbm5d_impulse_params from the defaults of the library; threshold: a scalar (every channel) or a per-channel sequence."""
+    P = ImpulseParamsStruct()
+    lib().lfbm5d_impulse_defaults(C.byref(P))
+    P.k, P.min_threshold = float(k), float(min_threshold)
+    if threshold is not None:
+        t = np.atleast_1d(np.asarray(threshold, np.float64))
+        if t.size not in (1, 3):
+            raise LfBm5dError("impulse repair: threshold must be a scalar or hold one value per channel")
+        for c in range(3):
+            P.threshold[c] = float(t[c if t.size == 3 else 0])
+    return P
+
+
 def sr_defaults(scale, /, **changes):
     """lfbm5d_sr_defaults (host only): the SrParams the library starts from for `scale`; keyword arguments replace fields
     (kernel may be "bicubic" / "gaussian")."""
@@ -479,6 +548,27 @@ def _dev_ptr(t):
         raise LfBm5dError("device entry points need contiguous float32 CUDA tensors")
     torch.cuda.current_stream(t.device).synchronize()
     return C.c_void_p(t.data_ptr())
+
+
+def _dev_ptr_u8(t):
+    """Raw device pointer of a contiguous uint8 CUDA tensor (flag planes); see _dev_ptr."""
+    import torch
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+        raise LfBm5dError("flag planes on the device must be contiguous uint8 CUDA tensors")
+    torch.cuda.current_stream(t.device).synchronize()
+    return C.c_void_p(t.data_ptr())
+
+
+def _sai_ptrs_u8(arrays, mask):
+    """unsigned char*[asize] over a list of per-SAI uint8 arrays."""
+    out = (C.c_void_p * len(arrays))()
+    for i, a in enumerate(arrays):
+        if a is None or not mask[i]:
+            continue
+        if not (isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.flags.c_contiguous):
+            raise LfBm5dError("per-SAI host flag planes must be contiguous uint8 numpy arrays")
+        out[i] = a.ctypes.data
+    return out
 
 
 def _sai_ptrs(arrays, mask):
@@ -796,6 +886,67 @@ class Context:
             self._ck(self._L.lfbm5d_denoise_pg_device(*head, _dev_ptr(noisy), mp, _dev_ptr(basic), _dev_ptr(denoised), *tail))
         return used
 
+    # ---- impulse repair ----
+    def impulse_histogram(self, LF, LF_SAI_mask, width, height, chnls):
+        """The ROAD histogram of lfbm5d_impulse_histogram_device on a CUDA float32 tensor [asize][C*H*W]: (hist uint64 [C][386], pixels,
+        skipped)."""
+        m = _u32(LF_SAI_mask)
+        C_ = int(chnls)
+        hist = np.zeros((max(C_, 1), IMPULSE_KEYS), np.uint64)
+        pixels, skipped = C.c_ulonglong(), C.c_ulonglong()
+        self._ck(self._L.lfbm5d_impulse_histogram_device(self._h, _dev_ptr(LF), m.ctypes.data_as(C.POINTER(C.c_uint)), m.size, int(width),
+                                                         int(height), C_, hist.ctypes.data_as(C.POINTER(C.c_ulonglong)),
+                                                         C.byref(pixels), C.byref(skipped)))
+        return hist, pixels.value, skipped.value
+
+    def impulse_repair(self, noisy, mask, width, height, chnls, k=8.0, threshold=None, flags=None, return_flags=False, min_threshold=0.0,
+                       out=None, flags_out=None):
+        """Impulse repair (lfbm5d_impulse_repair_*, include/lfbm5d.h): pixels that are not finite, or whose rank-ordered absolute
+        difference exceeds max(k x the channel's median, min_threshold) -- or `threshold`, a scalar or per-channel sequence, outright --
+        while no neighbour lies on one side of them, are replaced by the lower median of their sound neighbours.  flags (uint8, like
+        noisy, non-zero = defective): repair exactly those instead; no detection.  noisy: a CUDA float32 tensor [asize][C*H*W] (device
+        form; out / flags_out: optional tensors to write into, distinct from the inputs) or a float32 numpy array of that shape / a list
+        of per-SAI arrays (host form, staged through HBM; identical results).  noisy is only read; planes of empty SAIs of the result
+        are copies of the input's (of `out` when given: untouched).  Returns an ImpulseRepair."""
+        m = _u32(mask)
+        asize, C_ = m.size, int(chnls)
+        P = impulse_params(k, min_threshold, threshold)
+        res = ImpulseResultStruct()
+        cs = np.zeros((max(asize, 1), max(C_, 1), 3), np.uint64)
+        mp = m.ctypes.data_as(C.POINTER(C.c_uint))
+        tail = (asize, int(width), int(height), C_, C.byref(res), cs.ctypes.data_as(C.POINTER(C.c_ulonglong)))
+        if isinstance(noisy, (list, tuple, np.ndarray)):
+            arrays = self._host_sais(noisy)
+            if out is None:
+                out = [None if a is None else np.array(a, np.float32, copy=True) for a in arrays]
+            outs = self._host_sais(out)
+            fin = None
+            if flags is not None:
+                fin = [None if a is None else np.ascontiguousarray(a, np.uint8) for a in flags]
+            fo = None
+            if return_flags or flags_out is not None:
+                fo = [None if a is None else np.zeros(a.shape, np.uint8) for a in arrays] if flags_out is None else list(flags_out)
+            self._ck(self._L.lfbm5d_impulse_repair_host_sai(self._h, C.byref(P), _sai_ptrs(arrays, m), None if fin is None else _sai_ptrs_u8(fin, m),
+                                                            mp, _sai_ptrs(outs, m), None if fo is None else _sai_ptrs_u8(fo, m), *tail))
+            if isinstance(noisy, np.ndarray):
+                out = out if isinstance(out, np.ndarray) else np.stack(outs).reshape(noisy.shape)
+                fo = fo if fo is None or isinstance(fo, np.ndarray) else np.stack(fo).reshape(noisy.shape)
+        else:
+            import torch
+            if out is None:
+                out = noisy.clone() if not m.all() else torch.empty_like(noisy)
+            fo = flags_out
+            if fo is None and return_flags:
+                fo = torch.zeros(noisy.shape, dtype=torch.uint8, device=noisy.device)
+            fop = None if fo is None else _dev_ptr_u8(fo)
+            if flags is None:
+                self._ck(self._L.lfbm5d_impulse_repair_device(self._h, C.byref(P), _dev_ptr(noisy), mp, _dev_ptr(out), fop, *tail))
+            else:
+                self._ck(self._L.lfbm5d_impulse_repair_flags_device(self._h, _dev_ptr(noisy), _dev_ptr_u8(flags), mp, _dev_ptr(out), fop, *tail))
+        return ImpulseRepair(out, fo, res.scale, tuple(res.scale_channel[:C_]), tuple(res.threshold[:C_]), tuple(res.flagged[:C_]),
+                             tuple(res.repaired[:C_]), tuple(res.left[:C_]), int(res.pixels), int(res.skipped),
+                             cs[:asize, :C_].astype(np.int64))
+
     # ---- super-resolution ----
     def _sr_tail(self, mask, w, h, Cc):
         m = _u32(mask)
@@ -946,6 +1097,12 @@ def quality(ref, test, mask, width, height, chnls, peak=255.0, ssim=True, ctx=No
 def pg_estimate(LF, LF_SAI_mask, width, height, chnls, ctx=None):
     """Context.pg_estimate on the default context (device 0): the Poisson-Gaussian noise model of a noisy light field."""
     return (ctx or _ctx()).pg_estimate(LF, LF_SAI_mask, width, height, chnls)
+
+
+def impulse_repair(noisy, mask, width, height, chnls, k=8.0, threshold=None, flags=None, return_flags=False, ctx=None, **more):
+    """Context.impulse_repair on the default context (device 0): detection and repair of impulses ahead of the denoiser."""
+    return (ctx or _ctx()).impulse_repair(noisy, mask, width, height, chnls, k=k, threshold=threshold, flags=flags,
+                                          return_flags=return_flags, **more)
 
 
 def denoise_pg(model, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls, ctx=None):

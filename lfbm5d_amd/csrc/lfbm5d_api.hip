@@ -78,6 +78,7 @@ void lfbm5d_destroy(lfbm5d_ctx* c) {
     c->sr.sai.release(); c->sr.tab.release(); c->sr.hi.release(); c->sr.lo.release();
     c->quality.sai.release(); c->quality.part.release(); c->quality.out.release();
     c->pg.sai.release(); c->pg.stats.release(); c->pg.lf.release();
+    c->imp.sai.release(); c->imp.stats.release(); c->imp.flags.release();
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     if (c->h_small) (void)hipHostFree(c->h_small);
     if (c->stream) (void)hipStreamDestroy(c->stream);

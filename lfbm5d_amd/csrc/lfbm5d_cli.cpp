@@ -23,6 +23,13 @@
  *                     pg_forward_LF, run_bm3d_LF, pg_inverse_LF), with the sigma the transform leaves (also used for the diff images).
  *                     With a ground truth and poisson:<a>,<b> the noise added is Poisson-Gaussian with those parameters (<random>,
  *                     seeded from LFBM5D_SEED; the argument's sigma is unused); any other value is an error;
+ *   LFBM5D_IMPULSE=auto | <k>   impulse repair (impulse_repair_LF, run_bm5d.h) of the noisy light field once it exists, loaded or
+ *                     synthesised, before LFBM5D_SIGMA=auto / poisson look at it and before the filter: hot and dead pixels, salt and
+ *                     pepper and values that are not finite are replaced by the lower median of their sound neighbours; auto = the
+ *                     default threshold factor k = 8, <k> = that factor (finite, >= 0); prints `Impulse repair: <n> of <N> values flagged
+ *                     (<pct> %), <m> left; thresholds <T0> <T1> <T2>`.  With a ground truth LFBM5D_IMPULSE_ADD=<p> (0 <= p <= 1) first
+ *                     replaces that fraction of the synthesised noisy values by 0 or 255 (<random>, seeded from LFBM5D_SEED); the noisy
+ *                     files are saved before the repair.  Any other value of either is an error; unset, the output is unchanged;
  *   LFBM5D_REPORT_SSIM=1  the average SSIM next to every average PSNR on stdout and an SSIM block behind every PSNR block of the
  *                     results file, computed on the GPU on the images as the files hold them (cli_quality.h); any other value is an
  *                     error; unset, the output is unchanged.
@@ -66,6 +73,9 @@ namespace {
 
 double now_s() { timeval tp; gettimeofday(&tp, nullptr); return tp.tv_sec + tp.tv_usec * 1e-6; }
 
+/* the program-level variables of the header comment, read where they are used */
+const char* env(const char* name) { return getenv(name); }
+
 /* mt19937ar genrand_res53 on std::mt19937 (identical generator and seeding recurrence) */
 struct Mt {
     std::mt19937 g;
@@ -77,7 +87,7 @@ struct Mt {
  * filter runs on a GPU: 18 ms per 512 x 512 colour image and thread).  LFBM5D_IO_THREADS (default: the machine's cores, at most
  * 16; 1: one after the other like the reference).  fn(i) -> false stops the loop and fails it. */
 template <class F> bool parallel_sais(unsigned n, F fn) {
-    const char* e = getenv("LFBM5D_IO_THREADS");
+    const char* e = env("LFBM5D_IO_THREADS");
     unsigned nt = e && *e ? (unsigned)std::max(1, atoi(e)) : std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
     nt = std::min(nt, std::max(1u, n));
     std::atomic<unsigned> next(0);
@@ -211,7 +221,7 @@ void diff_LF(const vector<vector<float> >& A, const vector<vector<float> >& B, c
  * in order: its uniforms are drawn in order, SAI by SAI, and only their Box-Muller transform is spread over the threads. */
 void add_noise_LF(const vector<vector<float> >& LF, const vector<unsigned>& mask, vector<vector<float> >& LF_noisy, float sigma,
                   const double* pg = nullptr) {
-    const char* seed = getenv("LFBM5D_SEED");
+    const char* seed = env("LFBM5D_SEED");
     if (pg) {   /* Poisson-Gaussian noise {a, b}: a * Poisson(y / a) + N(0, b), one <random> stream through the SAIs in order */
         timeval tp; gettimeofday(&tp, nullptr);
         std::mt19937_64 g(seed ? strtoull(seed, nullptr, 10) : (unsigned long long)(tp.tv_sec * 1000 + tp.tv_usec / 1000 + getpid()));
@@ -261,7 +271,7 @@ void add_noise_LF(const vector<vector<float> >& LF, const vector<unsigned>& mask
 /* LFBM5D_SIGMA: unset -> 0 (the argument's sigma), "auto" -> 1 (estimate it), "poisson" -> 2 (Poisson-Gaussian model, estimated),
  * "poisson:<a>,<b>" -> 3 (that model: pg = {a, b}), anything else -> -1 (error, message printed) */
 int sigma_mode(double* pg) {
-    const char* e = getenv("LFBM5D_SIGMA");
+    const char* e = env("LFBM5D_SIGMA");
     if (!e) return 0;
     if (!strcmp(e, "auto")) return 1;
     if (!strcmp(e, "poisson")) return 2;
@@ -277,6 +287,59 @@ int sigma_mode(double* pg) {
     cout << "LFBM5D_SIGMA must be \"auto\" (estimate sigma from the noisy light field), \"poisson\" (estimate a Poisson-Gaussian noise model "
             "var = a y + b) or \"poisson:<a>,<b>\" (that model; a >= 0, 3/8 a^2 + b > 0), or unset; got \"" << e << "\"" << endl;
     return -1;
+}
+
+/* LFBM5D_IMPULSE / LFBM5D_IMPULSE_ADD: k < 0 = no repair, add = 0 = no impulses added; false (message printed) on anything else */
+bool impulse_mode(double& k, double& add) {
+    k = -1.0; add = 0.0;
+    if (const char* e = env("LFBM5D_IMPULSE")) {
+        char* q = nullptr;
+        const double v = strcmp(e, "auto") ? strtod(e, &q) : 8.0;
+        if (strcmp(e, "auto") && (q == e || *q || isspace((unsigned char)*e) || !std::isfinite(v) || v < 0.0)) {
+            cout << "LFBM5D_IMPULSE must be \"auto\" (impulse repair with the default threshold factor k = 8) or a factor k >= 0, or unset; got \""
+                 << e << "\"" << endl;
+            return false;
+        }
+        k = v;
+    }
+    if (const char* e = env("LFBM5D_IMPULSE_ADD")) {
+        char* q = nullptr;
+        const double v = strtod(e, &q);
+        if (q == e || *q || isspace((unsigned char)*e) || !(v >= 0.0 && v <= 1.0)) {
+            cout << "LFBM5D_IMPULSE_ADD must be a fraction 0 <= p <= 1 of the values to replace by 0 or 255, or unset; got \"" << e << "\"" << endl;
+            return false;
+        }
+        add = v;
+    }
+    return true;
+}
+
+/* LFBM5D_IMPULSE_ADD: salt and pepper on the synthesised noisy light field, one <random> stream through the SAIs in order */
+void add_impulses_LF(vector<vector<float> >& LF_noisy, const vector<unsigned>& mask, double p) {
+    const char* seed = env("LFBM5D_SEED");
+    timeval tp; gettimeofday(&tp, nullptr);
+    std::mt19937_64 g(seed ? strtoull(seed, nullptr, 10) + 0x9e3779b97f4a7c15ull : (unsigned long long)(tp.tv_sec * 1000 + tp.tv_usec / 1000 + getpid()));
+    std::uniform_real_distribution<double> u(0.0, 1.0);
+    unsigned long long hit = 0, all = 0;
+    for (size_t st = 0; st < LF_noisy.size(); st++) {
+        if (!mask[st]) continue;
+        for (float& v : LF_noisy[st]) {
+            all++;
+            if (u(g) < p) { v = (g() & 1ull) ? 255.0f : 0.0f; hit++; }
+        }
+    }
+    cout << "Add impulses [p = " << p << "]: " << hit << " of " << all << " values replaced by 0 or 255" << endl;
+}
+
+/* LFBM5D_IMPULSE: repair the noisy light field in place */
+bool repair_impulses_LF(vector<vector<float> >& LF_noisy, const vector<unsigned>& mask, unsigned W, unsigned H, unsigned C, double k) {
+    unsigned long long flagged = 0, left = 0, all = 0;
+    double T[3] = {0.0, 0.0, 0.0};
+    if (impulse_repair_LF(LF_noisy, mask, W, H, C, k, flagged, left, T) != EXIT_SUCCESS) return false;
+    for (size_t st = 0; st < mask.size(); st++) if (mask[st]) all += (unsigned long long)W * H * C;
+    cout << endl << "Impulse repair: " << flagged << " of " << all << " values flagged (" << 100.0 * (double)flagged / (double)all << " %), " << left
+         << " left; thresholds " << T[0] << " " << T[1] << " " << T[2] << endl;
+    return true;
 }
 
 /* LFBM5D_SIGMA=poisson: the model of the noisy light field */
@@ -359,6 +422,8 @@ int main(int argc, char** argv) {
     if (smode < 0) return EXIT_FAILURE;
     const int qmode = cli_quality::ssim_mode();
     if (qmode < 0) return EXIT_FAILURE;
+    double imp_k = -1.0, imp_add = 0.0;
+    if (!impulse_mode(imp_k, imp_add)) return EXIT_FAILURE;
 
     vector<vector<float> > LF, LF_noisy, LF_basic, LF_den, LF_diff;
     vector<unsigned> mask;
@@ -373,11 +438,14 @@ int main(int argc, char** argv) {
         else cout << endl << "Add noise [sigma = " << sigma << "] ... " << flush;
         t = now_s();
         add_noise_LF(LF, mask, LF_noisy, sigma, smode == 3 ? pg : nullptr);
-        cout << "done in " << now_s() - t << "s." << endl << endl << "Save noisy light field..." << endl;
+        cout << "done in " << now_s() - t << "s." << endl;
+        if (imp_add > 0.0) add_impulses_LF(LF_noisy, mask, imp_add);
+        cout << endl << "Save noisy light field..." << endl;
         if (save_LF(d_noisy, name, sep, LF_noisy, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
     } else {
         if (load_LF(d_noisy, name, sep, LF_noisy, mask, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
     }
+    if (imp_k >= 0.0 && !repair_impulses_LF(LF_noisy, mask, W, H, C, imp_k)) return EXIT_FAILURE;
     if (smode == 1 && !estimate_sigma_LF(LF_noisy, mask, W, H, C, sigma)) return EXIT_FAILURE;
     LF_basic.assign(awh, vector<float>((size_t)W * H * C, 0.0f));
     LF_den = LF_basic; LF_diff = LF_basic;
@@ -477,6 +545,8 @@ int main(int argc, char** argv) {
     if (smode < 0) return EXIT_FAILURE;
     const int qmode = cli_quality::ssim_mode();
     if (qmode < 0) return EXIT_FAILURE;
+    double imp_k = -1.0, imp_add = 0.0;
+    if (!impulse_mode(imp_k, imp_add)) return EXIT_FAILURE;
 
     vector<vector<float> > LF, LF_noisy, LF_basic, LF_den, LF_diff;
     vector<unsigned> mask;
@@ -491,11 +561,14 @@ int main(int argc, char** argv) {
         else cout << endl << "Add noise [sigma = " << sigma << "] ... " << flush;
         t = now_s();
         add_noise_LF(LF, mask, LF_noisy, sigma, smode == 3 ? pg : nullptr);
-        cout << "done in " << now_s() - t << "s." << endl << endl << "Save noisy light field..." << endl;
+        cout << "done in " << now_s() - t << "s." << endl;
+        if (imp_add > 0.0) add_impulses_LF(LF_noisy, mask, imp_add);
+        cout << endl << "Save noisy light field..." << endl;
         if (save_LF(d_noisy, name, sep, LF_noisy, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
     } else {
         if (load_LF(d_noisy, name, sep, LF_noisy, mask, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
     }
+    if (imp_k >= 0.0 && !repair_impulses_LF(LF_noisy, mask, W, H, C, imp_k)) return EXIT_FAILURE;
     if (smode == 1 && !estimate_sigma_LF(LF_noisy, mask, W, H, C, sigma)) return EXIT_FAILURE;
     LF_basic.assign(awh, vector<float>((size_t)W * H * C, 0.0f));
     LF_den = LF_basic; LF_diff = LF_basic;
@@ -514,7 +587,7 @@ int main(int argc, char** argv) {
      * -- what LF_basic holds after run_bm5d_2nd_step's lossy colour round trip (bm5d.cpp:829, :1416) -- where the two-call form saves
      * inverse(estimate) between the calls: the two differ (0.015 dB on the test light field) because the reference's colour matrices are not
      * inverses of each other */
-    const char* one_job_s = getenv("LFBM5D_ONE_JOB");
+    const char* one_job_s = env("LFBM5D_ONE_JOB");
     const bool one_job = smode >= 2 || (one_job_s && *one_job_s && *one_job_s != '0');   /* the Poisson-Gaussian path is one job */
     cout << endl << " ---> Running LFBM5D filter <--- " << endl << endl << (one_job ? "Steps 1 and 2 running as one job..." : "Step 1 running...") << endl;
     const double tb = now_s();

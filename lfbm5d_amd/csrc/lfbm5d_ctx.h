@@ -154,6 +154,8 @@ struct lfbm5d_ctx {
     } sr;
     /* Poisson-Gaussian noise (lfbm5d_pg.hip): non-empty SAI list, the statistics kernel's counters, the job's stabilised light field */
     struct PgBufs { DevBuf sai, stats, lf; } pg;
+    /* impulse repair (lfbm5d_impulse.hip): non-empty SAI list, the kernels' counters, the host form's flag planes (in, out) */
+    struct ImpulseBufs { DevBuf sai, stats, flags; } imp;
     /* window lanes (run_step, pipelined form): extra contexts on the same device, each with its own stream, window
      * buffers and per-pass work buffers; owned by this context */
     std::vector<lfbm5d_ctx*> lanes;

@@ -230,6 +230,34 @@ int pg_estimate_LF(const std::vector<std::vector<float> >& LF, const std::vector
     return EXIT_SUCCESS;
 }
 
+/* impulse repair on the caller's vectors, in place for the caller (one pointer per SAI; the library stages in and out apart) */
+int impulse_repair_LF(std::vector<std::vector<float> >& LF, const std::vector<unsigned>& LF_SAI_mask, unsigned width, unsigned height,
+                      unsigned chnls, double k, unsigned long long& flagged, unsigned long long& left, double thresholds[3]) {
+    if (LF.size() != LF_SAI_mask.size()) {
+        std::cout << "impulse_repair_LF: light field and mask must hold the same number of SAIs" << std::endl;
+        return EXIT_FAILURE;
+    }
+    lfbm5d_ctx* ctx = context();
+    if (!ctx) return EXIT_FAILURE;
+    const size_t img = (size_t)width * height * chnls;
+    std::vector<float*> p(LF.size(), nullptr);
+    for (size_t st = 0; st < LF.size(); st++) if (LF_SAI_mask[st] && LF[st].size() == img) p[st] = LF[st].data();
+    for (size_t st = 0; st < LF.size(); st++)
+        if (LF_SAI_mask[st] && !p[st]) { std::cout << "impulse_repair_LF: a non-empty SAI does not hold width*height*chnls values" << std::endl; return EXIT_FAILURE; }
+    lfbm5d_impulse_params P;
+    lfbm5d_impulse_defaults(&P);
+    P.k = k;
+    lfbm5d_impulse_result r;
+    if (lfbm5d_impulse_repair_host_sai(ctx, &P, p.data(), nullptr, LF_SAI_mask.data(), p.data(), nullptr, (unsigned)LF.size(), width, height, chnls,
+                                       &r, nullptr) != 0) {
+        std::cout << "LFBM5D GPU backend: " << lfbm5d_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+    }
+    flagged = left = 0;
+    for (unsigned c = 0; c < 3; c++) { flagged += r.flagged[c]; left += r.left[c]; thresholds[c] = r.threshold[c]; }
+    return EXIT_SUCCESS;
+}
+
 namespace {
 
 lfbm5d_pg_model pg_model_of(double a, double b) {

@@ -107,6 +107,23 @@ int noise_level_LF(
 ,   float &sigma
 );
 
+//! Impulse repair -- not in the reference, whose authors run such a stage in front of it: hot and dead pixels, salt and pepper and values
+//! that are not finite are detected on the GPU (rank-ordered absolute differences against k x the channel's median, include/lfbm5d.h) and
+//! replaced in LF by the lower median of their sound neighbours, before noise_level_LF / pg_estimate_LF and the filter see them.  k = 8 is
+//! the default of the C-ABI.  `flagged` and `left` (flagged, but without a sound neighbour: unchanged) count values over all channels;
+//! thresholds[3] receives what was applied per stored channel.  Returns EXIT_SUCCESS, or EXIT_FAILURE with the message on stdout.
+int impulse_repair_LF(
+    std::vector<std::vector<float> > &LF
+,   const std::vector<unsigned> &LF_SAI_mask
+,   unsigned width
+,   unsigned height
+,   unsigned chnls
+,   double k
+,   unsigned long long &flagged
+,   unsigned long long &left
+,   double thresholds[3]
+);
+
 //! Signal-dependent noise -- not in the reference: the Poisson-Gaussian model var(z | y) = a y + b (grey levels of the channels as stored,
 //! 0..255 scale) of a noisy light field, estimated on the GPU with every non-empty SAI and channel pooled (lfbm5d_pg_estimate_host_sai,
 //! include/lfbm5d.h).  LF is only read.  Returns EXIT_SUCCESS, or EXIT_FAILURE with the message on stdout.

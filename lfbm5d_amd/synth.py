@@ -122,3 +122,24 @@ def add_poisson_gaussian(clean, a, b, seed=1):
     if b > 0:
         z = z + rng.normal(0.0, np.sqrt(float(b)), clean.shape)
     return z.astype(np.float32)
+
+
+def add_impulse(lf, p, seed=1, kind="salt_pepper"):
+    """Impulse noise on `lf` (any shape, nominally 0..255) from numpy's default_rng(seed): every value is hit with probability p and
+    replaced -- "salt_pepper": by 0 or 255 with equal probability, "random": by a uniform value of [0, 255), "hot": by 255.  The draws
+    are one array of uniforms for the hits, then (not for "hot") one for the values, both of lf's shape.  Returns (damaged float32
+    array, boolean hit mask); a hit may leave a value unchanged (a 255 replaced by 255)."""
+    lf = np.asarray(lf, dtype=np.float32)
+    if not 0.0 <= float(p) <= 1.0:
+        raise ValueError("add_impulse: p must lie in [0, 1]")
+    rng = np.random.default_rng(seed)
+    hit = rng.random(lf.shape) < float(p)
+    if kind == "salt_pepper":
+        val = np.where(rng.random(lf.shape) < 0.5, np.float32(0.0), np.float32(255.0))
+    elif kind == "random":
+        val = (rng.random(lf.shape) * 255.0).astype(np.float32)
+    elif kind == "hot":
+        val = np.float32(255.0)
+    else:
+        raise ValueError('add_impulse: kind must be "salt_pepper", "random" or "hot"')
+    return np.where(hit, val, lf).astype(np.float32), hit
