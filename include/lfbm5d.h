@@ -619,6 +619,72 @@ int lfbm5d_impulse_repair_host_sai(lfbm5d_ctx* ctx, const lfbm5d_impulse_params*
                                    unsigned char* const* h_flags, unsigned asize, unsigned W, unsigned H, unsigned C,
                                    lfbm5d_impulse_result* out, unsigned long long* h_counts_sai);
 
+/* ---- defect inpainting: region fill under a defect map, refined by the hard-thresholding step ----
+ * Not in the reference.  The impulse repair above sees a 3 x 3: a dead column pair, a dust shadow on the microlens array, a hot cluster,
+ * a hole of non-finite values left by rectification or a region the user masks out is larger than that, is structure to the block
+ * matching and survives the threshold.  This stage fills such regions from their rim inwards and then refines the fill with what the
+ * other sub-aperture images show of it: super-resolution's loop (above) with a mask as the operator.  Opt-in.
+ * Data.  Light fields are [asize][C*H*W] float32, channels as stored; h_mask marks empty SAIs, whose planes are neither read nor written;
+ * C = 1 or 3; W, H >= 2.  Flags: uint8 [asize][C*H*W], non-zero = defective.  A value that is not finite counts as flagged whether or not
+ * the map names it: nothing non-finite reaches the filter.  One GPU: contexts with a communicator or a shard return 1.
+ * Fill (onion peel), per channel plane, in passes.  Neighbours are the eight positions of the 3 x 3, mirrored without repeating the edge
+ * (-1 -> 1, W -> W - 2) exactly as in the impulse repair; a mirrored neighbour may appear twice and then counts twice.  In pass t every
+ * value that was flagged before the pass and has n >= 1 unflagged neighbours becomes s r[n] (float32): s starts at +0.0f and adds the
+ * unflagged neighbours in raster order of the 3 x 3 (rows outer, centre skipped); r[n] = (float)(1.0 / n) is a table.  From pass t + 1 on
+ * the value counts as sound (Jacobi: a pass reads only the state before it).  Passes repeat until nothing is flagged or a pass fills
+ * nothing; the second case is a plane without one sound value, whose values stay as they are.  Unflagged values are copied unchanged.
+ * Flag plane (optional): 0 = sound, 1 = flagged and filled, 2 = flagged and left.  Sums in a fixed order, one product, integer counts: the
+ * GPU equals the numpy model of tests/inpaint_model.py bit for bit, and the result does not depend on how the passes fall into launches
+ * (LFBM5D_INPAINT_PASSES_PER_LAUNCH of them run in one; a region deeper than that takes another launch).
+ * Projection.  out = flag ? x : y, elementwise.
+ * Loop.  x_0 = fill(y, f); for k = 1..K: b = the basic estimate of lfbm5d_step1_device on a scratch copy of x_{k-1} with
+ * P.sigma = max(tau_k, sigma_noise), tau_k = sigma_start (sigma_end / sigma_start)^((k-1)/(K-1)) (double; K = 1: sigma_start);
+ * x_k = f ? b : y; the result is x_K, and K = 0 is the fill alone.  f is "flagged" as above (the map or a non-finite value).  The step
+ * runs exactly as lfbm5d_step1_device runs it (colour space, window graph, lanes, every option); every step filters the whole light field,
+ * not only the windows that hold defects.  K >= 1 with a value left (a plane without one sound value) returns 1 with a message: such a
+ * plane belongs to an SAI that should have been masked as empty.
+ * Limits: the map is given (or comes from the impulse repair: the code-2 values of its flag plane can be passed on as a map); blobs are
+ * not detected here; a whole missing SAI is not reconstructed; the defaults are the best of a sweep on one light field
+ * (profiles/inpaint_defaults.txt) and claim nothing beyond it. */
+#define LFBM5D_INPAINT_PASSES_PER_LAUNCH 8
+typedef struct {
+    unsigned iterations;   /* K refinement steps; 0 = the fill alone                                                  */
+    float sigma_start;     /* tau_1 > 0                                                                               */
+    float sigma_end;       /* tau_K, 0 < sigma_end <= sigma_start                                                     */
+    float sigma_noise;     /* the noise level of the sound data: a floor under the schedule; >= 0                     */
+} lfbm5d_inpaint_params;
+typedef struct {
+    unsigned long long flagged[3]; /* per stored channel: filled + left                                               */
+    unsigned long long filled[3];
+    unsigned long long left[3];    /* flagged values of planes without one sound value, left as they were             */
+    unsigned long long pixels;     /* values of the non-empty SAIs                                                    */
+    unsigned passes;               /* the largest pass number that filled something (the depth of the deepest region) */
+    unsigned launches;             /* launches of the fill kernel                                                     */
+} lfbm5d_inpaint_result;
+/* Host only: K = 8, sigma 30 -> 5, sigma_noise = 0 (the best of the sweep in profiles/inpaint_defaults.txt). */
+void lfbm5d_inpaint_defaults(lfbm5d_inpaint_params* out);
+/* The fill alone: d_out = filled d_in under d_flags_in, all in HBM; d_in and d_flags_in are only read.  d_out must not overlap d_in, and
+ * d_flags (the codes above, or NULL) must not overlap d_flags_in (neighbours are read across tile edges): 1 with a message, as for a NULL
+ * required buffer, C, W / H, a mask without a non-empty SAI and a context with a communicator or shard.  out or NULL.  Integer atomics
+ * only: repeated calls return the same bits. */
+int lfbm5d_inpaint_fill_device(lfbm5d_ctx* ctx, const float* d_in, const unsigned char* d_flags_in, const unsigned* h_mask, float* d_out,
+                               unsigned char* d_flags, unsigned asize, unsigned W, unsigned H, unsigned C, lfbm5d_inpaint_result* out);
+/* The projection: d_out = d_flags ? d_x : d_y on the non-empty SAIs.  d_out may be d_x or d_y. */
+int lfbm5d_inpaint_project_device(lfbm5d_ctx* ctx, const unsigned char* d_flags, const float* d_x, const float* d_y, const unsigned* h_mask,
+                                  float* d_out, unsigned asize, unsigned W, unsigned H, unsigned C);
+/* The loop: d_out = x_K.  P = the hard-thresholding step's parameters (its sigma is replaced step by step), an = its angular search
+ * window; buffers as for the fill; d_flags receives the fill's codes.  `out` (or NULL) is filled in before a K >= 1 call fails for
+ * values left. */
+int lfbm5d_inpaint_device(lfbm5d_ctx* ctx, const lfbm5d_inpaint_params* params, const lfbm5d_params* P, const float* d_in,
+                          const unsigned char* d_flags_in, const unsigned* h_mask, float* d_out, unsigned char* d_flags, unsigned ang_major,
+                          unsigned awidth, unsigned aheight, unsigned an, unsigned W, unsigned H, unsigned C, lfbm5d_inpaint_result* out);
+/* The same on host light fields, one pointer per SAI (NULL allowed for empty SAIs), staged through HBM with blocking copies:
+ * bit-identical to the device form.  h_flags or NULL.  h_out[st] may be h_in[st]: the staging buffers are distinct. */
+int lfbm5d_inpaint_host_sai(lfbm5d_ctx* ctx, const lfbm5d_inpaint_params* params, const lfbm5d_params* P, const float* const* h_in,
+                            const unsigned char* const* h_flags_in, const unsigned* h_mask, float* const* h_out,
+                            unsigned char* const* h_flags, unsigned ang_major, unsigned awidth, unsigned aheight, unsigned an, unsigned W,
+                            unsigned H, unsigned C, lfbm5d_inpaint_result* out);
+
 /* ---- inspection of the last pass's block matching (parity tests) ----
  * n_refs reference patches in raster order; h_refs[n_refs] flat index i*Wb+j;
  * h_self_idx[n_refs*N], h_self_cnt[n_refs] (precompute_BM, core:3301);

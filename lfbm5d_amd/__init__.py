@@ -11,7 +11,8 @@ from .core import (Context, Params, Bm3dParams, Stats, run_bm5d_1st_step, run_bm
                    TAU, COLOR_SPACE, LfBm5dError, library_path, build_library, NoiseLevel, noise_level,
                    noise_level_statistic, Quality, quality, quality_summary, SrParams, sr_defaults, sr_taps, superres,
                    SR_BICUBIC, SR_GAUSSIAN, SR_UP, SR_DOWN, PgModelStruct, PgEstimate, pg_model, pg_fit, pg_scale, pg_estimate,
-                   denoise_pg, ImpulseParamsStruct, ImpulseResultStruct, ImpulseRepair, impulse_params, impulse_scale, impulse_repair)
+                   denoise_pg, ImpulseParamsStruct, ImpulseResultStruct, ImpulseRepair, impulse_params, impulse_scale, impulse_repair,
+                   InpaintParamsStruct, InpaintResultStruct, Inpaint, inpaint_params, inpaint)
 
 __all__ = ["Context", "Params", "Bm3dParams", "Stats", "run_bm5d_1st_step", "run_bm5d_2nd_step", "run_bm3d_LF", "shard_rows",
            "YUV", "YCBCR", "OPP", "RGB", "ID", "DCT", "SADCT", "BIOR", "HADAMARD", "HAAR",
@@ -19,4 +20,5 @@ __all__ = ["Context", "Params", "Bm3dParams", "Stats", "run_bm5d_1st_step", "run
            "build_library", "NoiseLevel", "noise_level", "noise_level_statistic", "Quality", "quality", "quality_summary",
            "SrParams", "sr_defaults", "sr_taps", "superres", "SR_BICUBIC", "SR_GAUSSIAN", "SR_UP", "SR_DOWN",
            "PgModelStruct", "PgEstimate", "pg_model", "pg_fit", "pg_scale", "pg_estimate", "denoise_pg",
-           "ImpulseParamsStruct", "ImpulseResultStruct", "ImpulseRepair", "impulse_params", "impulse_scale", "impulse_repair"]
+           "ImpulseParamsStruct", "ImpulseResultStruct", "ImpulseRepair", "impulse_params", "impulse_scale", "impulse_repair",
+           "InpaintParamsStruct", "InpaintResultStruct", "Inpaint", "inpaint_params", "inpaint"]

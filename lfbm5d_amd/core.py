@@ -101,6 +101,34 @@ class ImpulseResultStruct(C.Structure):
 IMPULSE_KEYS = 386
 
 
+class InpaintParamsStruct(C.Structure):
+    """lfbm5d_inpaint_params: refinement steps and sigma schedule of the defect inpainting (include/lfbm5d.h)."""
+    _fields_ = [("iterations", C.c_uint), ("sigma_start", C.c_float), ("sigma_end", C.c_float), ("sigma_noise", C.c_float)]
+
+
+class InpaintResultStruct(C.Structure):
+    """lfbm5d_inpaint_result: counts of one fill (include/lfbm5d.h)."""
+    _fields_ = [("flagged", C.c_ulonglong * 3), ("filled", C.c_ulonglong * 3), ("left", C.c_ulonglong * 3), ("pixels", C.c_ulonglong),
+                ("passes", C.c_uint), ("launches", C.c_uint)]
+
+
+INPAINT_PASSES_PER_LAUNCH = 8
+
+
+class Inpaint(NamedTuple):
+    """Result of Context.inpaint_fill / Context.inpaint / inpaint: the repaired light field (a tensor or an array like the input), the
+    flag plane (uint8, 0 = sound, 1 = flagged and filled, 2 = flagged and left; None unless asked for), the counts per stored channel,
+    the values of the non-empty SAIs, the largest pass number that filled something and the launches of the fill kernel."""
+    out: object
+    flags: object
+    flagged: tuple
+    filled: tuple
+    left: tuple
+    pixels: int
+    passes: int
+    launches: int
+
+
 class ImpulseRepair(NamedTuple):
     """Result of Context.impulse_repair / impulse_repair: the repaired light field (a tensor or an array like the input), the flag plane
     (uint8, 0 = sound, 1 = flagged and repaired, 2 = flagged and left; None unless asked for), the pooled and per-channel median ROAD
@@ -290,6 +318,14 @@ def lib():
         L.lfbm5d_impulse_repair_device.argtypes = [vp, ip, fp, up, fp, vp] + [C.c_uint] * 4 + [rp, ullp]
         L.lfbm5d_impulse_repair_flags_device.argtypes = [vp, fp, vp, up, fp, vp] + [C.c_uint] * 4 + [rp, ullp]
         L.lfbm5d_impulse_repair_host_sai.argtypes = [vp, ip, fp, vp, up, fp, vp] + [C.c_uint] * 4 + [rp, ullp]
+    if hasattr(L, "lfbm5d_inpaint_device"):   # (absent from older builds loaded through LFBM5D_HIP_LIB for A/B runs)
+        np_, nr, pp = C.POINTER(InpaintParamsStruct), C.POINTER(InpaintResultStruct), C.POINTER(Params)
+        L.lfbm5d_inpaint_defaults.argtypes = [np_]
+        L.lfbm5d_inpaint_defaults.restype = None
+        L.lfbm5d_inpaint_fill_device.argtypes = [vp, fp, vp, up, fp, vp] + [C.c_uint] * 4 + [nr]
+        L.lfbm5d_inpaint_project_device.argtypes = [vp, vp, fp, fp, up, fp] + [C.c_uint] * 4
+        L.lfbm5d_inpaint_device.argtypes = [vp, np_, pp, fp, vp, up, fp, vp] + [C.c_uint] * 7 + [nr]
+        L.lfbm5d_inpaint_host_sai.argtypes = [vp, np_, pp, fp, vp, up, fp, vp] + [C.c_uint] * 7 + [nr]
     L.lfbm5d_malloc.argtypes = [C.POINTER(vp), C.c_size_t]
     L.lfbm5d_free.argtypes = [vp]
     L.lfbm5d_memcpy_h2d.argtypes = [vp, vp, C.c_size_t]
@@ -483,6 +519,21 @@ def impulse_params(k=8.0, min_threshold=0.0, threshold=None):
             raise LfBm5dError("impulse repair: threshold must be a scalar or hold one value per channel")
         for c in range(3):
             P.threshold[c] = float(t[c if t.size == 3 else 0])
+    return P
+
+
+def inpaint_params(iterations=None, sigma_start=None, sigma_end=None, sigma_noise=None):
+    """lfbm5d_inpaint_params from the defaults of the library (lfbm5d_inpaint_defaults); None keeps a default."""
+    P = InpaintParamsStruct()
+    lib().lfbm5d_inpaint_defaults(C.byref(P))
+    if iterations is not None:
+        P.iterations = int(iterations)
+    if sigma_start is not None:
+        P.sigma_start = float(sigma_start)
+    if sigma_end is not None:
+        P.sigma_end = float(sigma_end)
+    if sigma_noise is not None:
+        P.sigma_noise = float(sigma_noise)
     return P
 
 
@@ -947,6 +998,76 @@ class Context:
                              tuple(res.repaired[:C_]), tuple(res.left[:C_]), int(res.pixels), int(res.skipped),
                              cs[:asize, :C_].astype(np.int64))
 
+    # ---- defect inpainting ----
+    @staticmethod
+    def _inpaint_result(out, fo, res, C_):
+        return Inpaint(out, fo, tuple(res.flagged[:C_]), tuple(res.filled[:C_]), tuple(res.left[:C_]), int(res.pixels), int(res.passes),
+                       int(res.launches))
+
+    def inpaint_fill(self, noisy, flags, mask, width, height, chnls, return_flags=False, out=None, flags_out=None):
+        """The onion-peel fill of lfbm5d_inpaint_fill_device on CUDA tensors: noisy float32 [asize][C*H*W], flags uint8 of that shape
+        (non-zero = defective; a value that is not finite is flagged too).  Both are only read; out / flags_out: optional tensors to
+        write into, distinct from the inputs; planes of empty SAIs of a fresh result are copies of the input's.  Returns an Inpaint."""
+        import torch
+        m = _u32(mask)
+        C_ = int(chnls)
+        res = InpaintResultStruct()
+        if out is None:
+            out = noisy.clone() if not m.all() else torch.empty_like(noisy)
+        fo = flags_out
+        if fo is None and return_flags:
+            fo = torch.zeros(noisy.shape, dtype=torch.uint8, device=noisy.device)
+        self._ck(self._L.lfbm5d_inpaint_fill_device(self._h, _dev_ptr(noisy), _dev_ptr_u8(flags), m.ctypes.data_as(C.POINTER(C.c_uint)),
+                                                    _dev_ptr(out), None if fo is None else _dev_ptr_u8(fo), m.size, int(width), int(height),
+                                                    C_, C.byref(res)))
+        return self._inpaint_result(out, fo, res, C_)
+
+    def inpaint_project(self, flags, x, y, mask, out, width, height, chnls):
+        """out = flags ? x : y on the non-empty SAIs (lfbm5d_inpaint_project_device); CUDA tensors, out may be x or y."""
+        m = _u32(mask)
+        self._ck(self._L.lfbm5d_inpaint_project_device(self._h, _dev_ptr_u8(flags), _dev_ptr(x), _dev_ptr(y),
+                                                       m.ctypes.data_as(C.POINTER(C.c_uint)), _dev_ptr(out), m.size, int(width), int(height),
+                                                       int(chnls)))
+
+    def inpaint(self, noisy, flags, mask, P, ang_major, awidth, aheight, an, width, height, chnls, iterations=None, sigma_start=None,
+                sigma_end=None, sigma_noise=None, return_flags=False, out=None, flags_out=None):
+        """Defect inpainting (lfbm5d_inpaint_*, include/lfbm5d.h): the values `flags` names (uint8 like noisy, non-zero = defective) and
+        every value that is not finite are filled from their rim inwards, then refined by `iterations` hard-thresholding steps (P, its
+        sigma replaced by the schedule sigma_start -> sigma_end, not below sigma_noise) with the sound data put back after every step;
+        iterations = 0 is the fill alone, None the library's defaults.  noisy: a CUDA float32 tensor [asize][C*H*W] with a uint8 CUDA
+        tensor of flags (device form), or float32 / uint8 numpy arrays of that shape or lists of per-SAI arrays (host form, staged
+        through HBM; identical results).  The inputs are only read.  Returns an Inpaint."""
+        m = _u32(mask)
+        asize, C_ = m.size, int(chnls)
+        ip = inpaint_params(iterations, sigma_start, sigma_end, sigma_noise)
+        res = InpaintResultStruct()
+        mp = m.ctypes.data_as(C.POINTER(C.c_uint))
+        tail = (ang_major, awidth, aheight, an, int(width), int(height), C_, C.byref(res))
+        if isinstance(noisy, (list, tuple, np.ndarray)):
+            arrays = self._host_sais(noisy)
+            if out is None:
+                out = [None if a is None else np.array(a, np.float32, copy=True) for a in arrays]
+            outs = self._host_sais(out)
+            fin = [None if a is None else np.ascontiguousarray(a, np.uint8) for a in flags]
+            fo = None
+            if return_flags or flags_out is not None:
+                fo = [None if a is None else np.zeros(a.shape, np.uint8) for a in arrays] if flags_out is None else list(flags_out)
+            self._ck(self._L.lfbm5d_inpaint_host_sai(self._h, C.byref(ip), C.byref(P), _sai_ptrs(arrays, m), _sai_ptrs_u8(fin, m), mp,
+                                                     _sai_ptrs(outs, m), None if fo is None else _sai_ptrs_u8(fo, m), *tail))
+            if isinstance(noisy, np.ndarray):
+                out = out if isinstance(out, np.ndarray) else np.stack(outs).reshape(noisy.shape)
+                fo = fo if fo is None or isinstance(fo, np.ndarray) else np.stack(fo).reshape(noisy.shape)
+        else:
+            import torch
+            if out is None:
+                out = noisy.clone() if not m.all() else torch.empty_like(noisy)
+            fo = flags_out
+            if fo is None and return_flags:
+                fo = torch.zeros(noisy.shape, dtype=torch.uint8, device=noisy.device)
+            self._ck(self._L.lfbm5d_inpaint_device(self._h, C.byref(ip), C.byref(P), _dev_ptr(noisy), _dev_ptr_u8(flags), mp, _dev_ptr(out),
+                                                   None if fo is None else _dev_ptr_u8(fo), *tail))
+        return self._inpaint_result(out, fo, res, C_)
+
     # ---- super-resolution ----
     def _sr_tail(self, mask, w, h, Cc):
         m = _u32(mask)
@@ -1105,6 +1226,11 @@ def impulse_repair(noisy, mask, width, height, chnls, k=8.0, threshold=None, fla
                                           return_flags=return_flags, **more)
 
 
+def inpaint(noisy, flags, mask, P, ang_major, awidth, aheight, an, width, height, chnls, ctx=None, **more):
+    """Context.inpaint on the default context (device 0): defect inpainting under a given map, refined by the hard-thresholding step."""
+    return (ctx or _ctx()).inpaint(noisy, flags, mask, P, ang_major, awidth, aheight, an, width, height, chnls, **more)
+
+
 def denoise_pg(model, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls, ctx=None):
     """Context.denoise_pg on the default context (device 0); returns the model that was used."""
     return (ctx or _ctx()).denoise_pg(model, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls)
@@ -1169,3 +1295,30 @@ def superres_probe(low, mask, awidth, aheight, width, height, chnls, sr, lambda_
     if rc != 0:
         raise LfBm5dError("superres_LF failed (message on stdout)")
     return out
+
+
+
+def inpaint_probe(noisy, flags, mask, awidth, aheight, width, height, chnls, lambda_, hard, iterations=-1, sigma_start=0.0, sigma_end=0.0,
+                  sigma_noise=0.0, color_space="opp", ang_major=ROWMAJOR, an=1):
+    """The C++ drop-in's inpaint_LF (liblfbm5d_dropin.so, run_bm5d.h) on vector<vector<float>> light fields built from `noisy` and `flags`
+    [asize][chnls*height*width]; hard = (N, nSim, nDisp, k, p, tau_2D, tau_4D, tau_5D[, useSD]).  Returns (the repaired light field,
+    flagged, left, passes)."""
+    path = os.path.join(os.path.dirname(library_path()), "liblfbm5d_dropin.so")
+    if not os.path.exists(path):
+        raise LfBm5dError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
+    D = C.CDLL(path)
+    D.lfbm5d_inpaint_probe.argtypes = [C.c_void_p] * 4 + [C.c_uint] * 7 + [C.c_int] + [C.c_void_p] * 2 + [C.c_uint, C.c_void_p]
+    t = tuple(hard)
+    hv = np.array([t[0], t[1], t[2], t[3], t[4], int(t[8]) if len(t) > 8 else 0, _TAU[t[5]], _TAU[t[6]], _TAU[t[7]]], np.uint32)
+    noisy = np.ascontiguousarray(noisy, np.float32)
+    fl = np.ascontiguousarray(flags, np.uint8)
+    m = _u32(mask)
+    out = noisy.copy()
+    ipf = np.array([sigma_start, sigma_end, sigma_noise, lambda_], np.float32)
+    counts = np.zeros(3, np.uint64)
+    rc = D.lfbm5d_inpaint_probe(noisy.ctypes.data, fl.ctypes.data, m.ctypes.data, out.ctypes.data, ang_major, awidth, aheight, an, width, height,
+                                chnls, int(iterations), ipf.ctypes.data, hv.ctypes.data,
+                                _CS[color_space] if isinstance(color_space, str) else int(color_space), counts.ctypes.data)
+    if rc != 0:
+        raise LfBm5dError("inpaint_LF failed (message on stdout)")
+    return out, int(counts[0]), int(counts[1]), int(counts[2])

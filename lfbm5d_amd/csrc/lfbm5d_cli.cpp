@@ -30,6 +30,14 @@
  *                     (<pct> %), <m> left; thresholds <T0> <T1> <T2>`.  With a ground truth LFBM5D_IMPULSE_ADD=<p> (0 <= p <= 1) first
  *                     replaces that fraction of the synthesised noisy values by 0 or 255 (<random>, seeded from LFBM5D_SEED); the noisy
  *                     files are saved before the repair.  Any other value of either is an error; unset, the output is unchanged;
+ *   LFBM5D_DEFECTS=<dir>   defect inpainting (inpaint_LF, run_bm5d.h) of the noisy light field once it exists: <dir> holds 8-bit PNGs
+ *                     named like the SAIs, non-zero = defective (a grey file applies to every channel; a missing file = no defects in
+ *                     that SAI).  Order: the fill; LFBM5D_IMPULSE if set; the sigma estimate of LFBM5D_SIGMA=auto; the refinement loop
+ *                     with this command's hard-thresholding parameters and sigma_noise = sigma; the job.  LFBM5D_DEFECTS_ITER=<K>
+ *                     replaces the library's number of refinement steps (0 = the fill alone).  With LFBM5D_SIGMA=poisson, and in
+ *                     LFBM3Ddenoising (which has no 5-D parameters), only the fill runs, and the command says so.  Prints `Defect
+ *                     inpainting: <n> of <N> values flagged (<pct> %), <m> left; <passes> fill passes, <K> refinement steps`.  The
+ *                     noisy files are saved before the fill.  Unset, the output is unchanged;
  *   LFBM5D_REPORT_SSIM=1  the average SSIM next to every average PSNR on stdout and an SSIM block behind every PSNR block of the
  *                     results file, computed on the GPU on the images as the files hold them (cli_quality.h); any other value is an
  *                     error; unset, the output is unchanged.
@@ -342,6 +350,68 @@ bool repair_impulses_LF(vector<vector<float> >& LF_noisy, const vector<unsigned>
     return true;
 }
 
+/* LFBM5D_DEFECTS / LFBM5D_DEFECTS_ITER: dir = NULL: no inpainting; iter < 0: the library's number of steps; false (message printed) on a
+ * malformed value */
+bool defects_mode(const char*& dir, int& iter) {
+    dir = env("LFBM5D_DEFECTS"); iter = -1;
+    if (dir && !*dir) { cout << "LFBM5D_DEFECTS must name a directory of defect maps (PNG files named like the SAIs), or be unset" << endl; return false; }
+    if (const char* e = env("LFBM5D_DEFECTS_ITER")) {
+        char* q = nullptr;
+        const long v = strtol(e, &q, 10);
+        if (q == e || *q || isspace((unsigned char)*e) || v < 0 || v > 1000) {
+            cout << "LFBM5D_DEFECTS_ITER must be a number of refinement steps 0 <= K <= 1000, or unset; got \"" << e << "\"" << endl;
+            return false;
+        }
+        iter = (int)v;
+    }
+    return true;
+}
+
+/* the defect maps of LFBM5D_DEFECTS: one uint8 plane set per non-empty SAI, non-zero = defective */
+bool load_defects(const char* dir, const char* name, const char* sep, vector<vector<unsigned char> >& flags, const vector<unsigned>& mask,
+                  unsigned ang_major, unsigned aw, unsigned ah, unsigned s0, unsigned t0, unsigned W, unsigned H, unsigned C) {
+    flags.assign(aw * ah, vector<unsigned char>());
+    const size_t plane = (size_t)W * H;
+    for (unsigned s = 0; s < ah; s++)
+        for (unsigned t = 0; t < aw; t++) {
+            const unsigned st = ang_major == LFBM5D_ROWMAJOR ? s * aw + t : s + t * ah;
+            if (!mask[st]) continue;
+            flags[st].assign(plane * C, 0);
+            const string p = sai_path(dir, name, sep, s + s0, t + t0);
+            if (!ifstream(p)) continue;   /* no file: no defects in this SAI */
+            vector<float> img; size_t w, h, c;
+            if (!png_read_planar_f32(p, img, w, h, c) || w != W || h != H) {
+                cout << "error :: defect map " << p << " is not a png image of the SAIs' size." << endl;
+                return false;
+            }
+            const size_t colours = c >= 3 ? 3 : 1;   /* alpha is dropped */
+            for (unsigned ch = 0; ch < C; ch++)
+                for (size_t k = 0; k < plane; k++) {
+                    bool f;
+                    if (colours == 1) f = img[k] != 0.0f;
+                    else if (C == 3) f = img[ch * plane + k] != 0.0f;
+                    else f = img[k] != 0.0f || img[plane + k] != 0.0f || img[2 * plane + k] != 0.0f;
+                    flags[st][ch * plane + k] = f ? 1 : 0;
+                }
+        }
+    return true;
+}
+
+/* LFBM5D_DEFECTS: the fill (steps = 0) or the fill and the refinement loop, in place; hard = N, nSim, nDisp, k, p, useSD, tau_2D, tau_4D,
+ * tau_5D of the hard-thresholding step.  report: print the line of the header comment, with the steps that are still to come. */
+bool inpaint_defects_LF(vector<vector<float> >& LF_noisy, const vector<vector<unsigned char> >& flags, const vector<unsigned>& mask,
+                        unsigned ang_major, unsigned aw, unsigned ah, unsigned an, unsigned W, unsigned H, unsigned C, unsigned steps,
+                        unsigned steps_to_come, float sigma_noise, float lambda, const unsigned* hard, unsigned cs, bool report) {
+    unsigned long long flagged = 0, left = 0, all = 0; unsigned passes = 0;
+    if (inpaint_LF(LF_noisy, flags, mask, ang_major, aw, ah, an, W, H, C, (int)steps, 0.0f, 0.0f, sigma_noise, lambda, hard[0], hard[1], hard[2],
+                   hard[3], hard[4], hard[5] != 0, hard[6], hard[7], hard[8], cs, flagged, left, passes) != EXIT_SUCCESS) return false;
+    for (size_t st = 0; st < mask.size(); st++) if (mask[st]) all += (unsigned long long)W * H * C;
+    if (report)
+        cout << endl << "Defect inpainting: " << flagged << " of " << all << " values flagged (" << 100.0 * (double)flagged / (double)all << " %), "
+             << left << " left; " << passes << " fill passes, " << steps_to_come << " refinement steps" << endl;
+    return true;
+}
+
 /* LFBM5D_SIGMA=poisson: the model of the noisy light field */
 [[maybe_unused]] bool estimate_pg_LF(const vector<vector<float> >& LF_noisy, const vector<unsigned>& mask, unsigned W, unsigned H, unsigned C, double* pg) {
     return pg_estimate_LF(LF_noisy, mask, W, H, C, pg[0], pg[1]) == EXIT_SUCCESS;
@@ -424,6 +494,8 @@ int main(int argc, char** argv) {
     if (qmode < 0) return EXIT_FAILURE;
     double imp_k = -1.0, imp_add = 0.0;
     if (!impulse_mode(imp_k, imp_add)) return EXIT_FAILURE;
+    const char* def_dir = nullptr; int def_iter = -1;
+    if (!defects_mode(def_dir, def_iter)) return EXIT_FAILURE;
 
     vector<vector<float> > LF, LF_noisy, LF_basic, LF_den, LF_diff;
     vector<unsigned> mask;
@@ -444,6 +516,13 @@ int main(int argc, char** argv) {
         if (save_LF(d_noisy, name, sep, LF_noisy, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
     } else {
         if (load_LF(d_noisy, name, sep, LF_noisy, mask, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
+    }
+    if (def_dir) {   /* the fill alone: the refinement loop needs the 5-D step's parameters, which this command does not have */
+        vector<vector<unsigned char> > defects;
+        const unsigned hard[9] = {8, 8, 3, 8, 3, 0, LFBM5D_DCT, LFBM5D_SADCT, LFBM5D_HAAR};
+        if (!load_defects(def_dir, name, sep, defects, mask, ang_major, aw, ah, s0, t0, W, H, C)) return EXIT_FAILURE;
+        if (!inpaint_defects_LF(LF_noisy, defects, mask, ang_major, aw, ah, 1, W, H, C, 0, 0, 0.0f, lambda, hard, (unsigned)cs, true)) return EXIT_FAILURE;
+        cout << "Defect inpainting: the fill alone (the refinement steps run in LFBM5Ddenoising)" << endl;
     }
     if (imp_k >= 0.0 && !repair_impulses_LF(LF_noisy, mask, W, H, C, imp_k)) return EXIT_FAILURE;
     if (smode == 1 && !estimate_sigma_LF(LF_noisy, mask, W, H, C, sigma)) return EXIT_FAILURE;
@@ -547,6 +626,8 @@ int main(int argc, char** argv) {
     if (qmode < 0) return EXIT_FAILURE;
     double imp_k = -1.0, imp_add = 0.0;
     if (!impulse_mode(imp_k, imp_add)) return EXIT_FAILURE;
+    const char* def_dir = nullptr; int def_iter = -1;
+    if (!defects_mode(def_dir, def_iter)) return EXIT_FAILURE;
 
     vector<vector<float> > LF, LF_noisy, LF_basic, LF_den, LF_diff;
     vector<unsigned> mask;
@@ -568,8 +649,22 @@ int main(int argc, char** argv) {
     } else {
         if (load_LF(d_noisy, name, sep, LF_noisy, mask, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
     }
+    vector<vector<unsigned char> > defects;
+    const unsigned def_hard[9] = {N[0], nSim[0], nDisp[0], k[0], p[0], sd[0], (unsigned)t2[0], (unsigned)t4[0], (unsigned)t5[0]};
+    unsigned def_steps = 0;
+    if (def_dir) {
+        lfbm5d_inpaint_params ip;
+        lfbm5d_inpaint_defaults(&ip);
+        def_steps = smode >= 2 ? 0u : def_iter >= 0 ? (unsigned)def_iter : ip.iterations;
+        if (!load_defects(def_dir, name, sep, defects, mask, ang_major, aw, ah, s0, t0, W, H, C)) return EXIT_FAILURE;
+        if (!inpaint_defects_LF(LF_noisy, defects, mask, ang_major, aw, ah, anH, W, H, C, 0, def_steps, 0.0f, lambda, def_hard, (unsigned)cs, true))
+            return EXIT_FAILURE;
+        if (smode >= 2) cout << "Defect inpainting: the fill alone (LFBM5D_SIGMA=poisson: the refinement steps assume one sigma)" << endl;
+    }
     if (imp_k >= 0.0 && !repair_impulses_LF(LF_noisy, mask, W, H, C, imp_k)) return EXIT_FAILURE;
     if (smode == 1 && !estimate_sigma_LF(LF_noisy, mask, W, H, C, sigma)) return EXIT_FAILURE;
+    if (def_steps && !inpaint_defects_LF(LF_noisy, defects, mask, ang_major, aw, ah, anH, W, H, C, def_steps, def_steps, sigma, lambda, def_hard,
+                                         (unsigned)cs, false)) return EXIT_FAILURE;
     LF_basic.assign(awh, vector<float>((size_t)W * H * C, 0.0f));
     LF_den = LF_basic; LF_diff = LF_basic;
     vector<float> ps, rm; float sp = 0, ar = 0, sr = 0;

@@ -446,6 +446,73 @@ extern "C" int lfbm5d_superres_probe(const float* low_flat, const unsigned* mask
     return 0;
 }
 
+/* defect inpainting on the caller's vectors, in place for the caller (one pointer per SAI; the library stages in and out apart) */
+int inpaint_LF(std::vector<std::vector<float> >& LF, const std::vector<std::vector<unsigned char> >& flags, const std::vector<unsigned>& LF_SAI_mask,
+               const unsigned ang_major, const unsigned awidth, const unsigned aheight, const unsigned anHard, const unsigned width,
+               const unsigned height, const unsigned chnls, const int iterations, const float sigmaStart, const float sigmaEnd,
+               const float sigmaNoise, const float lambdaHard5D, const unsigned NHard, const unsigned nSim, const unsigned nDisp,
+               const unsigned kHard, const unsigned pHard, const bool useSD, const unsigned tau_2D, unsigned tau_4D, const unsigned tau_5D,
+               const unsigned color_space, unsigned long long& flagged, unsigned long long& left, unsigned& passes) {
+    const unsigned asize = awidth * aheight;
+    if (LF.size() != asize || flags.size() != asize || LF_SAI_mask.size() != asize) {
+        std::cout << "inpaint_LF: light field, flags and mask must hold awidth*aheight SAIs" << std::endl;
+        return EXIT_FAILURE;
+    }
+    lfbm5d_inpaint_params ip;
+    lfbm5d_inpaint_defaults(&ip);
+    if (iterations >= 0) ip.iterations = (unsigned)iterations;
+    if (sigmaStart != 0.0f) ip.sigma_start = sigmaStart;
+    if (sigmaEnd != 0.0f) ip.sigma_end = sigmaEnd;
+    ip.sigma_noise = sigmaNoise;
+    lfbm5d_ctx* ctx = context();
+    if (!ctx) return EXIT_FAILURE;
+    const size_t img = (size_t)width * height * chnls;
+    std::vector<float*> p(asize, nullptr);
+    std::vector<const unsigned char*> f(asize, nullptr);
+    for (size_t st = 0; st < asize; st++)
+        if (LF_SAI_mask[st]) {
+            if (LF[st].size() != img || flags[st].size() != img) {
+                std::cout << "inpaint_LF: a non-empty SAI does not hold width*height*chnls values and flags" << std::endl;
+                return EXIT_FAILURE;
+            }
+            p[st] = LF[st].data(); f[st] = flags[st].data();
+        }
+    const lfbm5d_params P = make(0.0f, lambdaHard5D, NHard, nSim, nDisp, kHard, pHard, useSD, tau_2D, tau_4D, tau_5D, color_space);
+    lfbm5d_inpaint_result r;
+    std::memset(&r, 0, sizeof(r));
+    const int rc = lfbm5d_inpaint_host_sai(ctx, &ip, &P, p.data(), f.data(), LF_SAI_mask.data(), p.data(), nullptr, ang_major, awidth, aheight,
+                                           anHard, width, height, chnls, &r);
+    flagged = left = 0;
+    for (unsigned c = 0; c < 3; c++) { flagged += r.flagged[c]; left += r.left[c]; }
+    passes = r.passes;
+    if (rc != 0) {
+        std::cout << "LFBM5D GPU backend: " << lfbm5d_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+    }
+    return EXIT_SUCCESS;
+}
+
+/* Test hook: inpaint_LF on vector<vector<float>> light fields built from flat copies [asize][chnls*height*width]; the result goes to
+ * out_flat.  ipf = {sigmaStart, sigmaEnd, sigmaNoise, lambda}, hard = {N, nSim, nDisp, k, p, useSD, tau_2D, tau_4D, tau_5D},
+ * counts = {flagged, left, passes}. */
+extern "C" int lfbm5d_inpaint_probe(const float* in_flat, const unsigned char* flags_flat, const unsigned* mask, float* out_flat,
+                                    unsigned ang_major, unsigned awidth, unsigned aheight, unsigned an, unsigned width, unsigned height,
+                                    unsigned chnls, int iterations, const float* ipf, const unsigned* hard, unsigned color_space,
+                                    unsigned long long* counts) {
+    const size_t asize = (size_t)awidth * aheight, img = (size_t)width * height * chnls;
+    std::vector<unsigned> m(mask, mask + asize);
+    std::vector<std::vector<float> > LF(asize);
+    std::vector<std::vector<unsigned char> > fl(asize);
+    for (size_t st = 0; st < asize; st++)
+        if (m[st]) { LF[st].assign(in_flat + st * img, in_flat + (st + 1) * img); fl[st].assign(flags_flat + st * img, flags_flat + (st + 1) * img); }
+    unsigned long long flagged = 0, left = 0; unsigned passes = 0;
+    if (inpaint_LF(LF, fl, m, ang_major, awidth, aheight, an, width, height, chnls, iterations, ipf[0], ipf[1], ipf[2], ipf[3], hard[0], hard[1],
+                   hard[2], hard[3], hard[4], hard[5] != 0, hard[6], hard[7], hard[8], color_space, flagged, left, passes) != EXIT_SUCCESS) return 1;
+    for (size_t st = 0; st < asize; st++) if (m[st]) std::memcpy(out_flat + st * img, LF[st].data(), img * sizeof(float));
+    if (counts) { counts[0] = flagged; counts[1] = left; counts[2] = passes; }
+    return 0;
+}
+
 /* run_bm3d_LF (src/bm3d_LF.h:10-35, bm3d_LF.cpp:75-125): BM3D on every SAI of the mask */
 #include "run_bm3d_lf.h"
 int run_bm3d_LF(const float sigma, std::vector<std::vector<float> >& LF_noisy, std::vector<unsigned>& LF_SAI_mask,

@@ -217,6 +217,43 @@ int quality_LF(
 //! SSIM through quality_LF next to every PSNR), -1 = any other value (the message is on stdout).
 int report_ssim_mode();
 
+//! Defect inpainting -- not in the reference: the values that `flags` names (one uint8 plane per SAI, non-zero = defective) and every value
+//! that is not finite are filled on the GPU from their rim inwards and refined by `iterations` hard-thresholding steps whose sigma falls
+//! from sigmaStart to sigmaEnd but not below sigmaNoise, the sound data being put back after every step (lfbm5d_inpaint_host_sai,
+//! include/lfbm5d.h).  LF is repaired in place.  iterations < 0, sigmaStart = 0, sigmaEnd = 0: the library's defaults
+//! (lfbm5d_inpaint_defaults); iterations = 0: the fill alone.  `flagged` and `left` (values of a plane without one sound value, unchanged)
+//! count over all channels; `passes` is the depth of the deepest region.  Returns EXIT_SUCCESS, or EXIT_FAILURE with the message on stdout.
+int inpaint_LF(
+    std::vector<std::vector<float> > &LF
+,   const std::vector<std::vector<unsigned char> > &flags
+,   const std::vector<unsigned> &LF_SAI_mask
+,   const unsigned ang_major
+,   const unsigned awidth
+,   const unsigned aheight
+,   const unsigned anHard
+,   const unsigned width
+,   const unsigned height
+,   const unsigned chnls
+,   const int      iterations
+,   const float    sigmaStart
+,   const float    sigmaEnd
+,   const float    sigmaNoise
+,   const float    lambdaHard5D
+,   const unsigned NHard
+,   const unsigned nSim
+,   const unsigned nDisp
+,   const unsigned kHard
+,   const unsigned pHard
+,   const bool     useSD
+,   const unsigned tau_2D
+,         unsigned tau_4D
+,   const unsigned tau_5D
+,   const unsigned color_space
+,   unsigned long long &flagged
+,   unsigned long long &left
+,   unsigned &passes
+);
+
 //! Super-resolution -- not in the reference's master branch: the scheme of SR-LFBM5D (iterative back-projection regularised by the
 //! hard-thresholding step above) with the operators of include/lfbm5d.h, on the GPU (lfbm5d_superres_host_sai).  LF_low holds
 //! width x height SAIs and is only read; LF_high is (re)sized to scale*width x scale*height SAIs and filled.  kernel: 0 = bicubic,

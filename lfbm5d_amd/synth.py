@@ -143,3 +143,28 @@ def add_impulse(lf, p, seed=1, kind="salt_pepper"):
     else:
         raise ValueError('add_impulse: kind must be "salt_pepper", "random" or "hot"')
     return np.where(hit, val, lf).astype(np.float32), hit
+
+
+def add_defects(shape, seed=1):
+    """Defect map for a light field of `shape` = (A, C, n, n), n >= 17, from numpy's default_rng(seed): per SAI three squares of side
+    3..7, one full-height pair of columns and one disc of radius 4 (centre at least 8 from the edges), the same in every channel.  The
+    draws per SAI, in this order: for each square its side, row and column; the column pair's first column; the disc's centre (row,
+    column) in one call.  Returns a boolean array of `shape`; about 6 % of the values are flagged at n = 64."""
+    A, C, H, W = (int(v) for v in shape)
+    if H != W or H < 17:
+        raise ValueError("add_defects: shape must be (A, C, n, n) with n >= 17")
+    n = H
+    rng = np.random.default_rng(seed)
+    fl = np.zeros((A, 1, n, n), bool)
+    yy, xx = np.mgrid[:n, :n]
+    for st in range(A):
+        for _ in range(3):
+            s = rng.integers(3, 8)
+            i = rng.integers(0, n - s + 1)
+            j = rng.integers(0, n - s + 1)
+            fl[st, 0, i:i + s, j:j + s] = True
+        j = rng.integers(0, n - 2)
+        fl[st, 0, :, j:j + 2] = True
+        ci, cj = rng.integers(8, n - 8, 2)
+        fl[st, 0][(yy - ci) ** 2 + (xx - cj) ** 2 <= 16] = True
+    return np.ascontiguousarray(np.broadcast_to(fl, (A, C, n, n)))
