@@ -644,7 +644,7 @@ int lfbm5d_impulse_repair_host_sai(lfbm5d_ctx* ctx, const lfbm5d_impulse_params*
  * not only the windows that hold defects.  K >= 1 with a value left (a plane without one sound value) returns 1 with a message: such a
  * plane belongs to an SAI that should have been masked as empty.
  * Limits: the map is given (or comes from the impulse repair: the code-2 values of its flag plane can be passed on as a map); blobs are
- * not detected here; a whole missing SAI is not reconstructed; the defaults are the best of a sweep on one light field
+ * not detected here; a whole missing SAI is reconstructed by the view synthesis below, not here; the defaults are the best of a sweep on one light field
  * (profiles/inpaint_defaults.txt) and claim nothing beyond it. */
 #define LFBM5D_INPAINT_PASSES_PER_LAUNCH 8
 typedef struct {
@@ -684,6 +684,72 @@ int lfbm5d_inpaint_host_sai(lfbm5d_ctx* ctx, const lfbm5d_inpaint_params* params
                             const unsigned char* const* h_flags_in, const unsigned* h_mask, float* const* h_out,
                             unsigned char* const* h_flags, unsigned ang_major, unsigned awidth, unsigned aheight, unsigned an, unsigned W,
                             unsigned H, unsigned C, lfbm5d_inpaint_result* out);
+
+/* ---- view synthesis: whole missing sub-aperture images from their angular neighbours, refined by the hard-thresholding step ----
+ * Not in the reference.  The stages above repair values; an SAI that is lost, corrupt or too dark, a failed member of a camera array, or the
+ * views an angular up-sampling asks for (3 x 3 in, 5 x 5 out) have no sound value at all.  A point seen at x in SAI (s, t) is seen at
+ * x + d (ds, dt) in SAI (s + ds, t + dt) with one scalar disparity d: a plane sweep over integer d synthesises the view from its sound
+ * neighbours, and the loop of the defect inpainting refines it.  Opt-in.
+ * Data.  Light fields are [asize][C*H*W] float32, channels as stored; C = 1 or 3; W, H >= 2.  h_mask marks non-empty SAIs as everywhere;
+ * h_missing is unsigned [asize], non-zero = to be reconstructed.  A missing SAI must be non-empty in h_mask (the filter processes it).  The
+ * planes of a missing SAI in d_in are never read.  (s, t) of index st: ROWMAJOR st = s awidth + t, COLMAJOR st = s + t aheight; s moves along
+ * image rows (y), t along columns (x).  One GPU: contexts with a communicator or a shard return 1.  Source values are assumed finite (the
+ * impulse and defect stages run ahead of this one).
+ * Sources of a missing SAI m: the SAIs q that are non-empty, not missing, with max(|s_q - s_m|, |t_q - t_m|) <= ang_radius, in increasing
+ * index order; n of them.  n = 0: the SAI is left (its planes of d_out are not written; counted in `left`).
+ * Warp, for a hypothesis d: w_{q,d}(c, y, x) = I_q(c, rho_H(y - d (s_q - s_m)), rho_W(x - d (t_q - t_m))); rho_n is the reflection of
+ * period 2n - 2 that does not repeat the edge (-1 -> 1, n -> n - 2), for any argument (a shift can exceed a narrow plane).
+ * Mean: mu_d = (((+0.0f + w_1) + w_2) + ... + w_n) r[n], r[n] = (float)(1.0 / n) from a table; float32.
+ * Error: e_d(y, x) = sum_c sum_q (w_{q,d} - mu_d)^2 from +0.0f, c outer, q inner; every difference, product and sum rounded on its own
+ * (no fused multiply-add).
+ * Box: h_d(y, x) = sum_{k=-r..r} e_d(y, rho_W(x + k)), E_d(y, x) = sum_{k=-r..r} h_d(rho_H(y + k), x), both from +0.0f in that order.
+ * Decision: hypotheses in the order 0, -1, +1, -2, +2, ..., -D, +D; one replaces the best so far only if E_d < E_best (ties keep the
+ * smaller |d|; n = 1 gives E = 0 everywhere: d = 0, a copy of the source).  The view is mu_{d*} for all C channels.
+ * d_disp (optional): int8 [asize][H*W], d* of the synthesised SAIs; other planes are not written.
+ * Sums in a fixed order, integer counts: the GPU equals the numpy model of tests/view_model.py bit for bit, values and disparities, and
+ * repeated calls return the same bits.
+ * Loop.  f = every value of the synthesised SAIs; x_0 = the input with those SAIs replaced; for k = 1..K: b = the basic estimate of
+ * lfbm5d_step1_device on a scratch copy of x_{k-1} with P.sigma = max(tau_k, sigma_noise), tau_k on the schedule of the defect inpainting;
+ * x_k = f ? b : y.  K = 0 is the synthesis alone.  K >= 1 with an SAI left returns 1 with a message, after `out` is filled in.
+ * Limits: integer disparities; occlusions are not modelled; one scalar d per pixel; sources only within ang_radius; one GPU; every step of
+ * the loop filters the whole light field; the defaults are the best row of a sweep on one light field (profiles/view_defaults.txt). */
+typedef struct {
+    unsigned max_disparity; /* D, 0..8: hypotheses -D..D                                                               */
+    unsigned box_radius;    /* r, 0..7: the (2r + 1)^2 aggregation box                                                 */
+    unsigned ang_radius;    /* 1 or 2: how far (Chebyshev, in views) a source may be                                   */
+    unsigned iterations;    /* K refinement steps; 0 = the synthesis alone                                             */
+    float sigma_start;      /* tau_1 > 0                                                                               */
+    float sigma_end;        /* tau_K, 0 < sigma_end <= sigma_start                                                     */
+    float sigma_noise;      /* the noise level of the sound SAIs: a floor under the schedule; >= 0                     */
+} lfbm5d_view_params;
+typedef struct {
+    unsigned missing;       /* SAIs marked missing: synthesised + left                                                 */
+    unsigned synthesised;
+    unsigned left;          /* missing SAIs without a source, not written                                              */
+    unsigned long long pixels;             /* positions of the synthesised SAIs (synthesised * W * H)                  */
+    unsigned long long disparity_hist[17]; /* positions per d*, index d + 8                                            */
+} lfbm5d_view_result;
+/* Host only: D = 4, r = 3, ang_radius = 1, K = 4, sigma 30 -> 5, sigma_noise = 0 (the best row of the sweep in
+ * profiles/view_defaults.txt). */
+void lfbm5d_view_defaults(lfbm5d_view_params* out);
+/* The synthesis alone: the planes of the synthesised SAIs of d_out (and of d_disp, or NULL) are written, nothing else; d_in is only read.
+ * 1 with a message: a NULL required buffer, C, W / H, max_disparity, box_radius, ang_radius, ang_major, a missing SAI masked empty, no
+ * missing SAI, d_out overlapping d_in, a context with a communicator or shard.  The loop's fields of params are not looked at.  out or
+ * NULL.  Integer atomics only: repeated calls return the same bits. */
+int lfbm5d_view_fill_device(lfbm5d_ctx* ctx, const lfbm5d_view_params* params, const float* d_in, const unsigned* h_mask,
+                            const unsigned* h_missing, float* d_out, signed char* d_disp, unsigned ang_major, unsigned awidth,
+                            unsigned aheight, unsigned W, unsigned H, unsigned C, lfbm5d_view_result* out);
+/* The loop: d_out = x_K on every non-empty SAI (the sound SAIs are copies of d_in's; an SAI that is left is not written).  P = the
+ * hard-thresholding step's parameters (its sigma is replaced step by step), an = its angular search window. */
+int lfbm5d_view_device(lfbm5d_ctx* ctx, const lfbm5d_view_params* params, const lfbm5d_params* P, const float* d_in, const unsigned* h_mask,
+                       const unsigned* h_missing, float* d_out, signed char* d_disp, unsigned ang_major, unsigned awidth, unsigned aheight,
+                       unsigned an, unsigned W, unsigned H, unsigned C, lfbm5d_view_result* out);
+/* The same on host light fields, one pointer per SAI (NULL allowed for empty SAIs, and in h_in for missing ones), staged through HBM with
+ * blocking copies: bit-identical to the device form.  h_disp or NULL: one int8 plane per missing SAI.  h_out[st] may be h_in[st]. */
+int lfbm5d_view_host_sai(lfbm5d_ctx* ctx, const lfbm5d_view_params* params, const lfbm5d_params* P, const float* const* h_in,
+                         const unsigned* h_mask, const unsigned* h_missing, float* const* h_out, signed char* const* h_disp,
+                         unsigned ang_major, unsigned awidth, unsigned aheight, unsigned an, unsigned W, unsigned H, unsigned C,
+                         lfbm5d_view_result* out);
 
 /* ---- inspection of the last pass's block matching (parity tests) ----
  * n_refs reference patches in raster order; h_refs[n_refs] flat index i*Wb+j;

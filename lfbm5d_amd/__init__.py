@@ -12,7 +12,8 @@ from .core import (Context, Params, Bm3dParams, Stats, run_bm5d_1st_step, run_bm
                    noise_level_statistic, Quality, quality, quality_summary, SrParams, sr_defaults, sr_taps, superres,
                    SR_BICUBIC, SR_GAUSSIAN, SR_UP, SR_DOWN, PgModelStruct, PgEstimate, pg_model, pg_fit, pg_scale, pg_estimate,
                    denoise_pg, ImpulseParamsStruct, ImpulseResultStruct, ImpulseRepair, impulse_params, impulse_scale, impulse_repair,
-                   InpaintParamsStruct, InpaintResultStruct, Inpaint, inpaint_params, inpaint)
+                   InpaintParamsStruct, InpaintResultStruct, Inpaint, inpaint_params, inpaint,
+                   ViewParamsStruct, ViewResultStruct, ViewSynth, view_params, view_synth)
 
 __all__ = ["Context", "Params", "Bm3dParams", "Stats", "run_bm5d_1st_step", "run_bm5d_2nd_step", "run_bm3d_LF", "shard_rows",
            "YUV", "YCBCR", "OPP", "RGB", "ID", "DCT", "SADCT", "BIOR", "HADAMARD", "HAAR",
@@ -21,4 +22,5 @@ __all__ = ["Context", "Params", "Bm3dParams", "Stats", "run_bm5d_1st_step", "run
            "SrParams", "sr_defaults", "sr_taps", "superres", "SR_BICUBIC", "SR_GAUSSIAN", "SR_UP", "SR_DOWN",
            "PgModelStruct", "PgEstimate", "pg_model", "pg_fit", "pg_scale", "pg_estimate", "denoise_pg",
            "ImpulseParamsStruct", "ImpulseResultStruct", "ImpulseRepair", "impulse_params", "impulse_scale", "impulse_repair",
-           "InpaintParamsStruct", "InpaintResultStruct", "Inpaint", "inpaint_params", "inpaint"]
+           "InpaintParamsStruct", "InpaintResultStruct", "Inpaint", "inpaint_params", "inpaint",
+           "ViewParamsStruct", "ViewResultStruct", "ViewSynth", "view_params", "view_synth"]

@@ -115,6 +115,32 @@ class InpaintResultStruct(C.Structure):
 INPAINT_PASSES_PER_LAUNCH = 8
 
 
+class ViewParamsStruct(C.Structure):
+    """lfbm5d_view_params: hypotheses, box, sources and the refinement schedule of the view synthesis (include/lfbm5d.h)."""
+    _fields_ = [("max_disparity", C.c_uint), ("box_radius", C.c_uint), ("ang_radius", C.c_uint), ("iterations", C.c_uint),
+                ("sigma_start", C.c_float), ("sigma_end", C.c_float), ("sigma_noise", C.c_float)]
+
+
+class ViewResultStruct(C.Structure):
+    """lfbm5d_view_result: counts of one synthesis (include/lfbm5d.h)."""
+    _fields_ = [("missing", C.c_uint), ("synthesised", C.c_uint), ("left", C.c_uint), ("pixels", C.c_ulonglong),
+                ("disparity_hist", C.c_ulonglong * 17)]
+
+
+class ViewSynth(NamedTuple):
+    """Result of Context.view_fill / Context.view_synth / view_synth: the light field with the missing SAIs reconstructed (a tensor or
+    an array like the input), the disparity planes (int8 [asize][H*W], written for the synthesised SAIs; None unless asked for), the
+    SAIs marked missing, synthesised and left (no source within ang_radius), the positions of the synthesised SAIs and the positions
+    per disparity (index d + 8)."""
+    out: object
+    disparity: object
+    missing: int
+    synthesised: int
+    left: int
+    pixels: int
+    disparity_hist: tuple
+
+
 class Inpaint(NamedTuple):
     """Result of Context.inpaint_fill / Context.inpaint / inpaint: the repaired light field (a tensor or an array like the input), the
     flag plane (uint8, 0 = sound, 1 = flagged and filled, 2 = flagged and left; None unless asked for), the counts per stored channel,
@@ -326,6 +352,13 @@ def lib():
         L.lfbm5d_inpaint_project_device.argtypes = [vp, vp, fp, fp, up, fp] + [C.c_uint] * 4
         L.lfbm5d_inpaint_device.argtypes = [vp, np_, pp, fp, vp, up, fp, vp] + [C.c_uint] * 7 + [nr]
         L.lfbm5d_inpaint_host_sai.argtypes = [vp, np_, pp, fp, vp, up, fp, vp] + [C.c_uint] * 7 + [nr]
+    if hasattr(L, "lfbm5d_view_device"):   # (absent from older builds loaded through LFBM5D_HIP_LIB for A/B runs)
+        wp, wr, pp = C.POINTER(ViewParamsStruct), C.POINTER(ViewResultStruct), C.POINTER(Params)
+        L.lfbm5d_view_defaults.argtypes = [wp]
+        L.lfbm5d_view_defaults.restype = None
+        L.lfbm5d_view_fill_device.argtypes = [vp, wp, fp, up, up, fp, vp] + [C.c_uint] * 6 + [wr]
+        L.lfbm5d_view_device.argtypes = [vp, wp, pp, fp, up, up, fp, vp] + [C.c_uint] * 7 + [wr]
+        L.lfbm5d_view_host_sai.argtypes = [vp, wp, pp, vp, up, up, vp, vp] + [C.c_uint] * 7 + [wr]
     L.lfbm5d_malloc.argtypes = [C.POINTER(vp), C.c_size_t]
     L.lfbm5d_free.argtypes = [vp]
     L.lfbm5d_memcpy_h2d.argtypes = [vp, vp, C.c_size_t]
@@ -537,6 +570,20 @@ def inpaint_params(iterations=None, sigma_start=None, sigma_end=None, sigma_nois
     return P
 
 
+def view_params(max_disparity=None, box_radius=None, ang_radius=None, iterations=None, sigma_start=None, sigma_end=None,
+                sigma_noise=None):
+    """lfbm5d_view_params from the defaults of the library (lfbm5d_view_defaults, host only); None keeps a default."""
+    P = ViewParamsStruct()
+    lib().lfbm5d_view_defaults(C.byref(P))
+    for name, v in (("max_disparity", max_disparity), ("box_radius", box_radius), ("ang_radius", ang_radius), ("iterations", iterations)):
+        if v is not None:
+            setattr(P, name, int(v))
+    for name, v in (("sigma_start", sigma_start), ("sigma_end", sigma_end), ("sigma_noise", sigma_noise)):
+        if v is not None:
+            setattr(P, name, float(v))
+    return P
+
+
 def sr_defaults(scale, /, **changes):
     """lfbm5d_sr_defaults (host only): the SrParams the library starts from for `scale`; keyword arguments replace fields
     (kernel may be "bicubic" / "gaussian")."""
@@ -608,6 +655,27 @@ def _dev_ptr_u8(t):
         raise LfBm5dError("flag planes on the device must be contiguous uint8 CUDA tensors")
     torch.cuda.current_stream(t.device).synchronize()
     return C.c_void_p(t.data_ptr())
+
+
+def _dev_ptr_i8(t):
+    """Raw device pointer of a contiguous int8 CUDA tensor (disparity planes); see _dev_ptr."""
+    import torch
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int8 and t.is_contiguous()):
+        raise LfBm5dError("disparity planes on the device must be contiguous int8 CUDA tensors")
+    torch.cuda.current_stream(t.device).synchronize()
+    return C.c_void_p(t.data_ptr())
+
+
+def _sai_ptrs_i8(arrays, mask):
+    """signed char*[asize] over a list of per-SAI int8 arrays."""
+    out = (C.c_void_p * len(arrays))()
+    for i, a in enumerate(arrays):
+        if a is None or not mask[i]:
+            continue
+        if not (isinstance(a, np.ndarray) and a.dtype == np.int8 and a.flags.c_contiguous):
+            raise LfBm5dError("per-SAI host disparity planes must be contiguous int8 numpy arrays")
+        out[i] = a.ctypes.data
+    return out
 
 
 def _sai_ptrs_u8(arrays, mask):
@@ -1068,6 +1136,76 @@ class Context:
                                                    None if fo is None else _dev_ptr_u8(fo), *tail))
         return self._inpaint_result(out, fo, res, C_)
 
+    # ---- view synthesis ----
+    @staticmethod
+    def _view_result(out, disp, res):
+        return ViewSynth(out, disp, int(res.missing), int(res.synthesised), int(res.left), int(res.pixels), tuple(res.disparity_hist))
+
+    @staticmethod
+    def _view_disp(noisy, asize, width, height, disparity_out, return_disparity):
+        import torch
+        if disparity_out is None and return_disparity:
+            return torch.zeros((asize, int(width) * int(height)), dtype=torch.int8, device=noisy.device)
+        return disparity_out
+
+    def view_fill(self, noisy, mask, missing, ang_major, awidth, aheight, width, height, chnls, max_disparity=None, box_radius=None,
+                  ang_radius=None, return_disparity=False, out=None, disparity_out=None):
+        """The plane-sweep synthesis of lfbm5d_view_fill_device on CUDA tensors: noisy float32 [asize][C*H*W] (only read; the planes of
+        the SAIs `missing` marks are never read).  out / disparity_out (int8 [asize][H*W]): optional tensors to write into, distinct
+        from the input; only the planes of the synthesised SAIs are written, a fresh `out` is a copy of the input elsewhere.  Returns a
+        ViewSynth."""
+        m, ms = _u32(mask), _u32(missing)
+        vp = view_params(max_disparity, box_radius, ang_radius)
+        res = ViewResultStruct()
+        if out is None:
+            out = noisy.clone()
+        dp = self._view_disp(noisy, m.size, width, height, disparity_out, return_disparity)
+        up = C.POINTER(C.c_uint)
+        self._ck(self._L.lfbm5d_view_fill_device(self._h, C.byref(vp), _dev_ptr(noisy), m.ctypes.data_as(up), ms.ctypes.data_as(up),
+                                                 _dev_ptr(out), None if dp is None else _dev_ptr_i8(dp), ang_major, awidth, aheight,
+                                                 int(width), int(height), int(chnls), C.byref(res)))
+        return self._view_result(out, dp, res)
+
+    def view_synth(self, noisy, mask, missing, P, ang_major, awidth, aheight, an, width, height, chnls, max_disparity=None,
+                   box_radius=None, ang_radius=None, iterations=None, sigma_start=None, sigma_end=None, sigma_noise=None,
+                   return_disparity=False, out=None, disparity_out=None):
+        """View synthesis (lfbm5d_view_*, include/lfbm5d.h): the SAIs `missing` marks (non-zero; they must be non-empty in `mask`) are
+        synthesised from their sound angular neighbours by a plane sweep over the integer disparities -max_disparity..max_disparity
+        and refined by `iterations` hard-thresholding steps (P, its sigma replaced by the schedule sigma_start -> sigma_end, not below
+        sigma_noise) with the sound SAIs put back after every step; iterations = 0 is the synthesis alone, None the library's
+        defaults.  noisy: a CUDA float32 tensor [asize][C*H*W] (device form), or a float32 numpy array of that shape or a list of
+        per-SAI arrays, None allowed for missing SAIs (host form, staged through HBM; identical results).  The input is only read.
+        return_disparity: the int8 planes [asize][H*W] of d*.  Returns a ViewSynth."""
+        m, ms = _u32(mask), _u32(missing)
+        asize = m.size
+        vp = view_params(max_disparity, box_radius, ang_radius, iterations, sigma_start, sigma_end, sigma_noise)
+        res = ViewResultStruct()
+        up = C.POINTER(C.c_uint)
+        mp, msp = m.ctypes.data_as(up), ms.ctypes.data_as(up)
+        tail = (ang_major, awidth, aheight, an, int(width), int(height), int(chnls), C.byref(res))
+        if isinstance(noisy, (list, tuple, np.ndarray)):
+            arrays = self._host_sais(noisy)
+            img = int(chnls) * int(width) * int(height)
+            if out is None:
+                out = [(np.zeros(img, np.float32) if m[i] else None) if a is None else np.array(a, np.float32, copy=True)
+                       for i, a in enumerate(arrays)]
+            outs = self._host_sais(out)
+            dp = None
+            if return_disparity or disparity_out is not None:
+                dp = [np.zeros(int(width) * int(height), np.int8) for _ in arrays] if disparity_out is None else list(disparity_out)
+            self._ck(self._L.lfbm5d_view_host_sai(self._h, C.byref(vp), C.byref(P), _sai_ptrs(arrays, m), mp, msp, _sai_ptrs(outs, m),
+                                                  None if dp is None else _sai_ptrs_i8(dp, m), *tail))
+            if isinstance(noisy, np.ndarray):
+                out = out if isinstance(out, np.ndarray) else np.stack(outs).reshape(noisy.shape)
+                dp = dp if dp is None or isinstance(dp, np.ndarray) else np.stack(dp)
+        else:
+            if out is None:
+                out = noisy.clone()
+            dp = self._view_disp(noisy, asize, width, height, disparity_out, return_disparity)
+            self._ck(self._L.lfbm5d_view_device(self._h, C.byref(vp), C.byref(P), _dev_ptr(noisy), mp, msp, _dev_ptr(out),
+                                                None if dp is None else _dev_ptr_i8(dp), *tail))
+        return self._view_result(out, dp, res)
+
     # ---- super-resolution ----
     def _sr_tail(self, mask, w, h, Cc):
         m = _u32(mask)
@@ -1231,6 +1369,12 @@ def inpaint(noisy, flags, mask, P, ang_major, awidth, aheight, an, width, height
     return (ctx or _ctx()).inpaint(noisy, flags, mask, P, ang_major, awidth, aheight, an, width, height, chnls, **more)
 
 
+def view_synth(noisy, mask, missing, P, ang_major, awidth, aheight, an, width, height, chnls, ctx=None, **more):
+    """Context.view_synth on the default context (device 0): missing SAIs synthesised from their angular neighbours, refined by the
+    hard-thresholding step."""
+    return (ctx or _ctx()).view_synth(noisy, mask, missing, P, ang_major, awidth, aheight, an, width, height, chnls, **more)
+
+
 def denoise_pg(model, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls, ctx=None):
     """Context.denoise_pg on the default context (device 0); returns the model that was used."""
     return (ctx or _ctx()).denoise_pg(model, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls)
@@ -1322,3 +1466,29 @@ def inpaint_probe(noisy, flags, mask, awidth, aheight, width, height, chnls, lam
     if rc != 0:
         raise LfBm5dError("inpaint_LF failed (message on stdout)")
     return out, int(counts[0]), int(counts[1]), int(counts[2])
+
+
+def view_synth_probe(noisy, mask, missing, awidth, aheight, width, height, chnls, lambda_, hard, max_disparity=-1, box_radius=-1, ang_radius=-1,
+                     iterations=-1, sigma_start=0.0, sigma_end=0.0, sigma_noise=0.0, color_space="opp", ang_major=ROWMAJOR, an=1):
+    """The C++ drop-in's view_synth_LF (liblfbm5d_dropin.so, run_bm5d.h) on a vector<vector<float>> light field built from `noisy`
+    [asize][chnls*height*width] (the vectors of missing SAIs are left empty); hard = (N, nSim, nDisp, k, p, tau_2D, tau_4D, tau_5D[, useSD]).
+    Returns (the completed light field, synthesised, left, dmin, dmax)."""
+    path = os.path.join(os.path.dirname(library_path()), "liblfbm5d_dropin.so")
+    if not os.path.exists(path):
+        raise LfBm5dError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
+    D = C.CDLL(path)
+    D.lfbm5d_view_synth_probe.argtypes = [C.c_void_p] * 4 + [C.c_uint] * 7 + [C.c_void_p] * 3 + [C.c_uint, C.c_void_p]
+    t = tuple(hard)
+    hv = np.array([t[0], t[1], t[2], t[3], t[4], int(t[8]) if len(t) > 8 else 0, _TAU[t[5]], _TAU[t[6]], _TAU[t[7]]], np.uint32)
+    noisy = np.ascontiguousarray(noisy, np.float32)
+    m, ms = _u32(mask), _u32(missing)
+    out = noisy.copy()
+    vpi = np.array([max_disparity, box_radius, ang_radius, iterations], np.int32)
+    vpf = np.array([sigma_start, sigma_end, sigma_noise, lambda_], np.float32)
+    counts = np.zeros(4, np.int32)
+    rc = D.lfbm5d_view_synth_probe(noisy.ctypes.data, m.ctypes.data, ms.ctypes.data, out.ctypes.data, ang_major, awidth, aheight, an, width,
+                                   height, chnls, vpi.ctypes.data, vpf.ctypes.data, hv.ctypes.data,
+                                   _CS[color_space] if isinstance(color_space, str) else int(color_space), counts.ctypes.data)
+    if rc != 0:
+        raise LfBm5dError("view_synth_LF failed (message on stdout)")
+    return out, int(counts[0]), int(counts[1]), int(counts[2]), int(counts[3])

@@ -38,6 +38,16 @@
  *                     LFBM3Ddenoising (which has no 5-D parameters), only the fill runs, and the command says so.  Prints `Defect
  *                     inpainting: <n> of <N> values flagged (<pct> %), <m> left; <passes> fill passes, <K> refinement steps`.  The
  *                     noisy files are saved before the fill.  Unset, the output is unchanged;
+ *   LFBM5D_MISSING=<s>_<t>[,<s>_<t>...]   view synthesis (view_synth_LF, run_bm5d.h): the SAIs named, in the indices the file names carry,
+ *                     are reconstructed from their sound angular neighbours.  With LFSourceDir = none their files need not exist and
+ *                     are not read; with a ground truth they are dropped (zeroed) from the noisy light field once it is made, before
+ *                     it is saved.  Order: the synthesis; LFBM5D_IMPULSE if set; the sigma estimate of LFBM5D_SIGMA=auto, on a mask with
+ *                     the missing SAIs marked empty (a mean of n sources carries less noise than a real SAI); the synthesis again (the
+ *                     sources may have been repaired) and the refinement loop with this command's hard-thresholding parameters and
+ *                     sigma_noise = sigma; the job.  LFBM5D_MISSING_ITER=<K> replaces the library's number of refinement steps.  With
+ *                     LFBM5D_SIGMA=poisson, and in LFBM3Ddenoising (which has no 5-D parameters), only the synthesis runs, and the
+ *                     command says so.  Prints `View synthesis: <n> of <A> SAIs missing, <m> left; disparities <dmin>..<dmax>, <K>
+ *                     refinement steps`.  Combining it with LFBM5D_DEFECTS is an error.  Unset, the output is unchanged;
  *   LFBM5D_REPORT_SSIM=1  the average SSIM next to every average PSNR on stdout and an SSIM block behind every PSNR block of the
  *                     results file, computed on the GPU on the images as the files hold them (cli_quality.h); any other value is an
  *                     error; unset, the output is unchanged.
@@ -116,7 +126,8 @@ string sai_path(const char* dir, const char* name, const char* sep, unsigned s, 
 
 /* load_LF, utilities_LF.cpp:72-167 */
 int load_LF(const char* dir, const char* name, const char* sep, vector<vector<float> >& LF, vector<unsigned>& mask,
-            unsigned ang_major, unsigned aw, unsigned ah, unsigned s0, unsigned t0, unsigned& W, unsigned& H, unsigned& C) {
+            unsigned ang_major, unsigned aw, unsigned ah, unsigned s0, unsigned t0, unsigned& W, unsigned& H, unsigned& C,
+            const vector<unsigned>* skip = nullptr) {   /* skip (LFBM5D_MISSING): SAIs whose files are not read; zeros, marked non-empty */
     mask.assign(aw * ah, 0u);
     LF.assign(aw * ah, vector<float>());
     cout << endl;
@@ -125,6 +136,7 @@ int load_LF(const char* dir, const char* name, const char* sep, vector<vector<fl
     string bad;
     const bool ok = parallel_sais(aw * ah, [&](unsigned i) {
         const unsigned s = i / aw, t = i % aw;
+        if (skip && (*skip)[ang_major == LFBM5D_ROWMAJOR ? s * aw + t : s + t * ah]) return true;
         const string p = sai_path(dir, name, sep, s + s0, t + t0);
         { std::lock_guard<std::mutex> g(out); cout << "\rRead input image " << p << flush; }
         vector<float> img;
@@ -144,10 +156,21 @@ int load_LF(const char* dir, const char* name, const char* sep, vector<vector<fl
     });
     if (!ok) { cout << endl << "error :: " << bad << " not found or not a correct png image." << endl; return EXIT_FAILURE; }
     {   /* all SAIs of the first one's size (the first in the reference's reading order: s, t = 0, 0) */
-        const unsigned st0 = 0;
+        unsigned st0 = 0;
+        if (skip) {   /* the first SAI in reading order that has a file */
+            unsigned i = 0;
+            for (; i < aw * ah; i++) {
+                const unsigned s = i / aw, t = i % aw;
+                st0 = ang_major == LFBM5D_ROWMAJOR ? s * aw + t : s + t * ah;
+                if (!(*skip)[st0]) break;
+            }
+            if (i == aw * ah) { cout << endl << "error :: every SAI is missing" << endl; return EXIT_FAILURE; }
+        }
         W = (unsigned)ws[st0]; H = (unsigned)hs[st0]; C = (unsigned)cs[st0];
-        for (unsigned st = 0; st < aw * ah; st++)
+        for (unsigned st = 0; st < aw * ah; st++) {
+            if (skip && (*skip)[st]) { LF[st].assign((size_t)W * H * C, 0.0f); mask[st] = 1; continue; }
             if (ws[st] != W || hs[st] != H || cs[st] != C) { cout << endl << "error :: SAIs of different sizes" << endl; return EXIT_FAILURE; }
+        }
     }
     cout << endl << " Light field size :" << endl << " - awidth         = " << aw << endl << " - aheight        = " << ah << endl
          << " - width          = " << W << endl << " - height         = " << H << endl << " - nb of channels = " << C << endl;
@@ -412,6 +435,62 @@ bool inpaint_defects_LF(vector<vector<float> >& LF_noisy, const vector<vector<un
     return true;
 }
 
+/* LFBM5D_MISSING / LFBM5D_MISSING_ITER: missing stays empty when unset, else one entry per SAI (non-zero = to be reconstructed);
+ * iter < 0: the library's number of steps; false (message printed) on a malformed value or together with LFBM5D_DEFECTS */
+bool missing_mode(vector<unsigned>& missing, int& iter, unsigned ang_major, unsigned aw, unsigned ah, unsigned s0, unsigned t0) {
+    missing.clear(); iter = -1;
+    if (const char* e = env("LFBM5D_MISSING_ITER")) {
+        char* q = nullptr;
+        const long v = strtol(e, &q, 10);
+        if (q == e || *q || isspace((unsigned char)*e) || v < 0 || v > 1000) {
+            cout << "LFBM5D_MISSING_ITER must be a number of refinement steps 0 <= K <= 1000, or unset; got \"" << e << "\"" << endl;
+            return false;
+        }
+        iter = (int)v;
+    }
+    const char* e = env("LFBM5D_MISSING");
+    if (!e) return true;
+    if (env("LFBM5D_DEFECTS")) { cout << "LFBM5D_MISSING cannot be combined with LFBM5D_DEFECTS (there is no combined loop): run them one after the other" << endl; return false; }
+    missing.assign((size_t)aw * ah, 0u);
+    const char* p = e;
+    bool ok = *p != 0;
+    while (ok) {
+        char *q = nullptr, *r = nullptr;
+        ok = isdigit((unsigned char)*p) != 0;
+        const long s = ok ? strtol(p, &q, 10) : 0;
+        ok = ok && *q == '_' && isdigit((unsigned char)q[1]);
+        const long t = ok ? strtol(q + 1, &r, 10) : 0;
+        ok = ok && s >= (long)s0 && s < (long)(s0 + ah) && t >= (long)t0 && t < (long)(t0 + aw);
+        if (!ok) break;
+        const unsigned ss = (unsigned)s - s0, tt = (unsigned)t - t0;
+        missing[ang_major == LFBM5D_ROWMAJOR ? ss * aw + tt : ss + tt * ah] = 1;
+        if (!*r) break;
+        ok = *r == ',';
+        p = r + 1;
+    }
+    if (!ok) {
+        cout << "LFBM5D_MISSING must be a list <s>_<t>[,<s>_<t>...] of SAIs of the light field, in the indices the file names carry, or unset; got \""
+             << e << "\"" << endl;
+        return false;
+    }
+    return true;
+}
+
+/* LFBM5D_MISSING: the synthesis (steps = 0) or the synthesis and the refinement loop, in place; hard as for inpaint_defects_LF.  report:
+ * print the line of the header comment, with the steps that are still to come. */
+bool synthesise_missing_LF(vector<vector<float> >& LF_noisy, const vector<unsigned>& mask, const vector<unsigned>& missing, unsigned ang_major,
+                           unsigned aw, unsigned ah, unsigned an, unsigned W, unsigned H, unsigned C, unsigned steps, unsigned steps_to_come,
+                           float sigma_noise, float lambda, const unsigned* hard, unsigned cs, bool report) {
+    unsigned done = 0, left = 0, all = 0, n = 0; int dmin = 0, dmax = 0;
+    if (view_synth_LF(LF_noisy, mask, missing, ang_major, aw, ah, an, W, H, C, -1, -1, -1, (int)steps, 0.0f, 0.0f, sigma_noise, lambda, hard[0],
+                      hard[1], hard[2], hard[3], hard[4], hard[5] != 0, hard[6], hard[7], hard[8], cs, done, left, dmin, dmax) != EXIT_SUCCESS) return false;
+    for (size_t st = 0; st < mask.size(); st++) { if (mask[st]) all++; if (missing[st]) n++; }
+    if (report)
+        cout << endl << "View synthesis: " << n << " of " << all << " SAIs missing, " << left << " left; disparities " << dmin << ".." << dmax << ", "
+             << steps_to_come << " refinement steps" << endl;
+    return true;
+}
+
 /* LFBM5D_SIGMA=poisson: the model of the noisy light field */
 [[maybe_unused]] bool estimate_pg_LF(const vector<vector<float> >& LF_noisy, const vector<unsigned>& mask, unsigned W, unsigned H, unsigned C, double* pg) {
     return pg_estimate_LF(LF_noisy, mask, W, H, C, pg[0], pg[1]) == EXIT_SUCCESS;
@@ -496,6 +575,8 @@ int main(int argc, char** argv) {
     if (!impulse_mode(imp_k, imp_add)) return EXIT_FAILURE;
     const char* def_dir = nullptr; int def_iter = -1;
     if (!defects_mode(def_dir, def_iter)) return EXIT_FAILURE;
+    vector<unsigned> missing; int miss_iter = -1;
+    if (!missing_mode(missing, miss_iter, ang_major, aw, ah, s0, t0)) return EXIT_FAILURE;
 
     vector<vector<float> > LF, LF_noisy, LF_basic, LF_den, LF_diff;
     vector<unsigned> mask;
@@ -512,10 +593,19 @@ int main(int argc, char** argv) {
         add_noise_LF(LF, mask, LF_noisy, sigma, smode == 3 ? pg : nullptr);
         cout << "done in " << now_s() - t << "s." << endl;
         if (imp_add > 0.0) add_impulses_LF(LF_noisy, mask, imp_add);
+        for (size_t st = 0; st < missing.size(); st++) if (missing[st]) LF_noisy[st].assign(LF_noisy[st].size(), 0.0f);   /* dropped */
         cout << endl << "Save noisy light field..." << endl;
         if (save_LF(d_noisy, name, sep, LF_noisy, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
     } else {
-        if (load_LF(d_noisy, name, sep, LF_noisy, mask, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
+        if (load_LF(d_noisy, name, sep, LF_noisy, mask, ang_major, aw, ah, s0, t0, W, H, C, missing.empty() ? nullptr : &missing) != EXIT_SUCCESS)
+            return EXIT_FAILURE;
+    }
+    vector<unsigned> est_mask = mask;   /* the sigma estimate does not look at reconstructed SAIs */
+    if (!missing.empty()) {   /* the synthesis alone, for the same reason as the fill alone below */
+        const unsigned hard[9] = {8, 8, 3, 8, 3, 0, LFBM5D_DCT, LFBM5D_SADCT, LFBM5D_HAAR};
+        if (!synthesise_missing_LF(LF_noisy, mask, missing, ang_major, aw, ah, 1, W, H, C, 0, 0, 0.0f, lambda, hard, (unsigned)cs, true)) return EXIT_FAILURE;
+        cout << "View synthesis: the synthesis alone (the refinement steps run in LFBM5Ddenoising)" << endl;
+        for (size_t st = 0; st < missing.size(); st++) if (missing[st]) est_mask[st] = 0;
     }
     if (def_dir) {   /* the fill alone: the refinement loop needs the 5-D step's parameters, which this command does not have */
         vector<vector<unsigned char> > defects;
@@ -525,7 +615,7 @@ int main(int argc, char** argv) {
         cout << "Defect inpainting: the fill alone (the refinement steps run in LFBM5Ddenoising)" << endl;
     }
     if (imp_k >= 0.0 && !repair_impulses_LF(LF_noisy, mask, W, H, C, imp_k)) return EXIT_FAILURE;
-    if (smode == 1 && !estimate_sigma_LF(LF_noisy, mask, W, H, C, sigma)) return EXIT_FAILURE;
+    if (smode == 1 && !estimate_sigma_LF(LF_noisy, est_mask, W, H, C, sigma)) return EXIT_FAILURE;
     LF_basic.assign(awh, vector<float>((size_t)W * H * C, 0.0f));
     LF_den = LF_basic; LF_diff = LF_basic;
     vector<float> ps, rm; float sp = 0, ar = 0, sr = 0;
@@ -628,6 +718,8 @@ int main(int argc, char** argv) {
     if (!impulse_mode(imp_k, imp_add)) return EXIT_FAILURE;
     const char* def_dir = nullptr; int def_iter = -1;
     if (!defects_mode(def_dir, def_iter)) return EXIT_FAILURE;
+    vector<unsigned> missing; int miss_iter = -1;
+    if (!missing_mode(missing, miss_iter, ang_major, aw, ah, s0, t0)) return EXIT_FAILURE;
 
     vector<vector<float> > LF, LF_noisy, LF_basic, LF_den, LF_diff;
     vector<unsigned> mask;
@@ -644,14 +736,27 @@ int main(int argc, char** argv) {
         add_noise_LF(LF, mask, LF_noisy, sigma, smode == 3 ? pg : nullptr);
         cout << "done in " << now_s() - t << "s." << endl;
         if (imp_add > 0.0) add_impulses_LF(LF_noisy, mask, imp_add);
+        for (size_t st = 0; st < missing.size(); st++) if (missing[st]) LF_noisy[st].assign(LF_noisy[st].size(), 0.0f);   /* dropped */
         cout << endl << "Save noisy light field..." << endl;
         if (save_LF(d_noisy, name, sep, LF_noisy, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
     } else {
-        if (load_LF(d_noisy, name, sep, LF_noisy, mask, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
+        if (load_LF(d_noisy, name, sep, LF_noisy, mask, ang_major, aw, ah, s0, t0, W, H, C, missing.empty() ? nullptr : &missing) != EXIT_SUCCESS)
+            return EXIT_FAILURE;
     }
     vector<vector<unsigned char> > defects;
     const unsigned def_hard[9] = {N[0], nSim[0], nDisp[0], k[0], p[0], sd[0], (unsigned)t2[0], (unsigned)t4[0], (unsigned)t5[0]};
     unsigned def_steps = 0;
+    vector<unsigned> est_mask = mask;   /* the sigma estimate does not look at reconstructed SAIs */
+    unsigned view_steps = 0;
+    if (!missing.empty()) {
+        lfbm5d_view_params vp;
+        lfbm5d_view_defaults(&vp);
+        view_steps = smode >= 2 ? 0u : miss_iter >= 0 ? (unsigned)miss_iter : vp.iterations;
+        if (!synthesise_missing_LF(LF_noisy, mask, missing, ang_major, aw, ah, anH, W, H, C, 0, view_steps, 0.0f, lambda, def_hard, (unsigned)cs, true))
+            return EXIT_FAILURE;
+        if (smode >= 2) cout << "View synthesis: the synthesis alone (LFBM5D_SIGMA=poisson: the refinement steps assume one sigma)" << endl;
+        for (size_t st = 0; st < missing.size(); st++) if (missing[st]) est_mask[st] = 0;
+    }
     if (def_dir) {
         lfbm5d_inpaint_params ip;
         lfbm5d_inpaint_defaults(&ip);
@@ -662,7 +767,9 @@ int main(int argc, char** argv) {
         if (smode >= 2) cout << "Defect inpainting: the fill alone (LFBM5D_SIGMA=poisson: the refinement steps assume one sigma)" << endl;
     }
     if (imp_k >= 0.0 && !repair_impulses_LF(LF_noisy, mask, W, H, C, imp_k)) return EXIT_FAILURE;
-    if (smode == 1 && !estimate_sigma_LF(LF_noisy, mask, W, H, C, sigma)) return EXIT_FAILURE;
+    if (smode == 1 && !estimate_sigma_LF(LF_noisy, est_mask, W, H, C, sigma)) return EXIT_FAILURE;
+    if (view_steps && !synthesise_missing_LF(LF_noisy, mask, missing, ang_major, aw, ah, anH, W, H, C, view_steps, view_steps, sigma, lambda, def_hard,
+                                             (unsigned)cs, false)) return EXIT_FAILURE;
     if (def_steps && !inpaint_defects_LF(LF_noisy, defects, mask, ang_major, aw, ah, anH, W, H, C, def_steps, def_steps, sigma, lambda, def_hard,
                                          (unsigned)cs, false)) return EXIT_FAILURE;
     LF_basic.assign(awh, vector<float>((size_t)W * H * C, 0.0f));

@@ -159,6 +159,9 @@ struct lfbm5d_ctx {
     /* defect inpainting (lfbm5d_inpaint.hip): non-empty SAI list, the fill's counters, its state planes and second value plane (also the
      * loop's scratch input of the step), the host form's flag planes (in, out) */
     struct InpaintBufs { DevBuf sai, stats, state[2], tmp, flags; } inp;
+    /* view synthesis (lfbm5d_view.hip): the source lists, the disparity histogram, the loop's scratch input of the step, the host form's
+     * disparity planes */
+    struct ViewBufs { DevBuf table, stats, tmp, disp; } view;
     /* window lanes (run_step, pipelined form): extra contexts on the same device, each with its own stream, window
      * buffers and per-pass work buffers; owned by this context */
     std::vector<lfbm5d_ctx*> lanes;

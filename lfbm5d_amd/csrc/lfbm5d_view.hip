@@ -1,0 +1,373 @@
+/*
+ * lfbm5d_view.hip -- reconstruction of whole missing sub-aperture images (lfbm5d_view_*, include/lfbm5d.h): a missing SAI is synthesised
+ * from its sound angular neighbours by a plane sweep over integer disparities (per hypothesis the neighbours are warped by d times their
+ * angular offset, the squared deviations from their mean are summed over a box, the smallest sum wins per pixel), and the synthesis is
+ * refined by the loop "regularise with the hard-thresholding step, put the sound SAIs back, lower sigma" of the defect inpainting
+ * (lfbm5d_inpaint.hip) with "every value of the synthesised SAIs" as the mask.  Not in the reference.
+ *
+ * Kernel (256 threads):
+ *   k_view_sweep   grid (tiles, synthesised SAIs); a tile is 64 x 32 positions, a thread owns 8 of them (one column, every fourth row).
+ *                  Per hypothesis: the per-pixel error of the tile plus a halo of r goes into LDS (a cell outside the plane is computed at
+ *                  the position it mirrors: the same operands, the same bits), barrier, horizontal box sums into a second LDS plane,
+ *                  barrier, vertical box sums into registers and the running (E_best, d*) update.  After the last hypothesis the mean at
+ *                  d* is recomputed from the sources and stored with the disparity.  Lanes run along x in every phase: global loads are
+ *                  rows shifted by a uniform amount, LDS reads of both box passes are consecutive words (no bank conflict).
+ * Sums in a fixed order from +0, no fused multiply-add, one product with a table entry, integer atomics for the histogram (LDS, then
+ * global): the GPU equals tests/view_model.py bit for bit.
+ */
+#include "lfbm5d_ctx.h"
+
+#include <cstdint>
+
+using namespace lfbm5d_host;
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kTW = 64, kTH = 32, kThreads = 256;
+constexpr int kRMax = 7, kDMax = 8, kSrcMax = 24;                /* box radius, disparity, sources at ang_radius 2 */
+constexpr int kEW = kTW + 2 * kRMax, kEH = kTH + 2 * kRMax;      /* the error plane: tile + halo, 78 x 46 */
+constexpr int kPer = kTW * kTH / kThreads;                       /* 8 positions per thread */
+constexpr int kHist = 2 * kDMax + 1;
+constexpr int kTabStride = 2 + 3 * kSrcMax;                      /* per synthesised SAI: its index, n, n x (source index, ds, dt) */
+static_assert(kTW * kTH % kThreads == 0 && kThreads % kTW == 0, "a thread owns one column");
+
+/* r[n] = (float)(1.0 / n) */
+__constant__ float kRecip[kSrcMax + 1] = {
+    0.0f, 1.0f, 0.5f, (float)(1.0 / 3.0), 0.25f, (float)(1.0 / 5.0), (float)(1.0 / 6.0), (float)(1.0 / 7.0), 0.125f, (float)(1.0 / 9.0),
+    (float)(1.0 / 10.0), (float)(1.0 / 11.0), (float)(1.0 / 12.0), (float)(1.0 / 13.0), (float)(1.0 / 14.0), (float)(1.0 / 15.0), 0.0625f,
+    (float)(1.0 / 17.0), (float)(1.0 / 18.0), (float)(1.0 / 19.0), (float)(1.0 / 20.0), (float)(1.0 / 21.0), (float)(1.0 / 22.0),
+    (float)(1.0 / 23.0), (float)(1.0 / 24.0)};
+
+/* coordinate g of the mirrored plane (period 2 (n - 1), no edge repeated) -> 0..n-1; n >= 2; any g (a shift can exceed a narrow plane) */
+__device__ __forceinline__ int mirror(int g, int n) {
+    if ((unsigned)g < (unsigned)n) return g;
+    const int P = 2 * (n - 1);
+    g %= P;
+    if (g < 0) g += P;
+    return g < n ? g : P - g;
+}
+
+/* the sum of the n sources of channel plane c, warped by hypothesis d, at the in-plane position (y, x): ((+0 + w_1) + w_2) + ... */
+__device__ __forceinline__ float warped_sum(const float* __restrict__ in, const int* __restrict__ tab, int n, int d, int c, int C, int y,
+                                            int x, int W, int H) {
+    const size_t plane = (size_t)W * H;
+    float s = 0.0f;
+    for (int q = 0; q < n; q++) {
+        const int sy = mirror(y - d * tab[3 + 3 * q], H), sx = mirror(x - d * tab[4 + 3 * q], W);
+        s = s + in[((size_t)tab[2 + 3 * q] * C + c) * plane + (size_t)sy * W + sx];
+    }
+    return s;
+}
+
+/* e_d(y, x) = sum_c sum_q (w_{q,d} - mu_d)^2, c outer, q inner, from +0 */
+__device__ __forceinline__ float pixel_error(const float* __restrict__ in, const int* __restrict__ tab, int n, float rn, int d, int C, int y,
+                                             int x, int W, int H) {
+    const size_t plane = (size_t)W * H;
+    float e = 0.0f;
+    for (int c = 0; c < C; c++) {
+        const float mu = warped_sum(in, tab, n, d, c, C, y, x, W, H) * rn;
+        for (int q = 0; q < n; q++) {
+            const int sy = mirror(y - d * tab[3 + 3 * q], H), sx = mirror(x - d * tab[4 + 3 * q], W);
+            const float diff = in[((size_t)tab[2 + 3 * q] * C + c) * plane + (size_t)sy * W + sx] - mu;
+            const float sq = diff * diff;
+            e = e + sq;
+        }
+    }
+    return e;
+}
+
+/* grid (tx_n * ty_n, synthesised SAIs), 256 threads.  table: kTabStride ints per synthesised SAI.  cnt[kHist]: positions per d* + 8. */
+__global__ __launch_bounds__(kThreads) void k_view_sweep(const float* __restrict__ in, float* __restrict__ out, signed char* __restrict__ disp,
+                                                         const int* __restrict__ table, int C, int W, int H, unsigned tx_n, int D, int r,
+                                                         unsigned long long* __restrict__ cnt) {
+    __shared__ float e[kEH * kEW];
+    __shared__ float h[kEH * kTW];
+    __shared__ unsigned hist[kHist];
+    const int tid = (int)threadIdx.x;
+    const int* __restrict__ tab = table + (size_t)blockIdx.y * kTabStride;
+    const int m = tab[0], n = tab[1];
+    const float rn = kRecip[n];
+    const unsigned ty = blockIdx.x / tx_n, tx = blockIdx.x - ty * tx_n;
+    const int x0 = (int)(tx * kTW), y0 = (int)(ty * kTH);
+    const int ew = kTW + 2 * r, eh = kTH + 2 * r;
+    const int lx = tid & (kTW - 1), ly0 = tid / kTW;              /* this thread's column and first row of the tile */
+    if (tid < kHist) hist[tid] = 0u;
+
+    float best[kPer];
+    int dstar[kPer];
+#pragma unroll
+    for (int k = 0; k < kPer; k++) { best[k] = 0.0f; dstar[k] = 0; }
+
+    for (int j = 0; j <= 2 * D; j++) {
+        const int d = (j & 1) ? -((j + 1) >> 1) : (j >> 1);       /* 0, -1, +1, -2, +2, ... */
+        for (int i = tid; i < ew * eh; i += kThreads) {
+            const int wy = i / ew, wx = i - wy * ew;
+            e[wy * kEW + wx] = pixel_error(in, tab, n, rn, d, C, mirror(y0 - r + wy, H), mirror(x0 - r + wx, W), W, H);
+        }
+        __syncthreads();
+        for (int i = tid; i < eh * kTW; i += kThreads) {          /* h(row, x) = sum_k e(row, x + k): window columns x .. x + 2r */
+            const float* row = e + (i / kTW) * kEW + (i & (kTW - 1));
+            float s = 0.0f;
+            for (int k = 0; k <= 2 * r; k++) s = s + row[k];
+            h[i] = s;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < kPer; k++) {                          /* E(y, x) = sum_k h(y + k, x): window rows y .. y + 2r */
+            const float* col = h + (ly0 + k * (kThreads / kTW)) * kTW + lx;
+            float s = 0.0f;
+            for (int kk = 0; kk <= 2 * r; kk++) s = s + col[kk * kTW];
+            if (j == 0 || s < best[k]) { best[k] = s; dstar[k] = d; }
+        }
+        /* the next hypothesis writes e at once (its readers passed the second barrier) and h only behind its first barrier */
+    }
+
+    const size_t plane = (size_t)W * H;
+    const int gx = x0 + lx;
+#pragma unroll
+    for (int k = 0; k < kPer; k++) {
+        const int gy = y0 + ly0 + k * (kThreads / kTW);
+        if (gx >= W || gy >= H) continue;
+        const size_t at = (size_t)gy * W + gx;
+        for (int c = 0; c < C; c++) out[((size_t)m * C + c) * plane + at] = warped_sum(in, tab, n, dstar[k], c, C, gy, gx, W, H) * rn;
+        if (disp) disp[(size_t)m * plane + at] = (signed char)dstar[k];
+        atomicAdd(&hist[dstar[k] + kDMax], 1u);
+    }
+    __syncthreads();
+    if (tid < kHist && hist[tid]) atomicAdd(&cnt[tid], (unsigned long long)hist[tid]);
+}
+
+bool overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + nb && y < x + na;
+}
+
+struct Plan {
+    std::vector<int> table;            /* kTabStride ints per synthesised SAI */
+    std::vector<unsigned> synth, left; /* indices, increasing */
+    unsigned nne = 0;
+};
+
+void coords(unsigned st, unsigned ang_major, unsigned aw, unsigned ah, int& s, int& t) {
+    if (ang_major == LFBM5D_ROWMAJOR) { s = (int)(st / aw); t = (int)(st % aw); }
+    else { s = (int)(st % ah); t = (int)(st / ah); }
+}
+
+const char* check_params(const lfbm5d_view_params* vp) {
+    if (vp->max_disparity > (unsigned)kDMax) return "max_disparity must be 0..8";
+    if (vp->box_radius > (unsigned)kRMax) return "box_radius must be 0..7";
+    if (vp->ang_radius < 1 || vp->ang_radius > 2) return "ang_radius must be 1 or 2";
+    return nullptr;
+}
+
+const char* check_loop(const lfbm5d_view_params* vp) {
+    if (!vp->iterations) return nullptr;
+    if (vp->iterations > 1000) return "iterations must be at most 1000";
+    if (!(vp->sigma_start > 0.0f) || !(vp->sigma_end > 0.0f) || !std::isfinite(vp->sigma_start)) return "sigma_start and sigma_end must be positive";
+    if (vp->sigma_end > vp->sigma_start) return "sigma_end must not exceed sigma_start";
+    if (!(vp->sigma_noise >= 0.0f) || !std::isfinite(vp->sigma_noise)) return "sigma_noise must be finite and not negative";
+    return nullptr;
+}
+
+/* the checks on the host arguments every entry shares, and the source lists; 1 with a message */
+int plan_sources(lfbm5d_ctx* c, const std::string& who, const lfbm5d_view_params* vp, const unsigned* h_mask, const unsigned* h_missing,
+         unsigned ang_major, unsigned aw, unsigned ah, unsigned W, unsigned H, unsigned C, Plan& p) {
+    if (!vp || !h_mask || !h_missing) return fail(c, who + "NULL pointer for a required buffer");
+    if (C != 1 && C != 3) return fail(c, who + "chnls must be 1 or 3");
+    if (W < 2 || H < 2) return fail(c, who + "width and height must be at least 2");
+    if (ang_major != LFBM5D_ROWMAJOR && ang_major != LFBM5D_COLMAJOR) return fail(c, who + "ang_major must be LFBM5D_ROWMAJOR or LFBM5D_COLMAJOR");
+    if (!aw || !ah) return fail(c, who + "awidth and aheight must be at least 1");
+    if (const char* msg = check_params(vp)) return fail(c, who + msg);
+    if (c->world > 1 || c->comm || c->ipc) return fail(c, who + "the view synthesis runs on one GPU (this context has a communicator or a shard)");
+    const unsigned asize = aw * ah;
+    unsigned n_missing = 0;
+    for (unsigned st = 0; st < asize; st++) {
+        if (h_mask[st]) p.nne++;
+        if (!h_missing[st]) continue;
+        n_missing++;
+        if (!h_mask[st]) return fail(c, who + "a missing SAI is masked empty (the filter processes a reconstructed SAI: mark it non-empty)");
+    }
+    if (!n_missing) return fail(c, who + "no SAI is marked missing");
+    if ((unsigned long long)W * H > 0x3fffffffull || (unsigned long long)((W + kTW - 1) / kTW) * ((H + kTH - 1) / kTH) > 0x7fffffffull || asize > 65535)
+        return fail(c, who + "light field too large");
+    const int R = (int)vp->ang_radius;
+    for (unsigned m = 0; m < asize; m++) {
+        if (!h_missing[m]) continue;
+        int sm, tm;
+        coords(m, ang_major, aw, ah, sm, tm);
+        int row[kTabStride] = {(int)m, 0};
+        for (unsigned q = 0; q < asize; q++) {
+            if (!h_mask[q] || h_missing[q]) continue;
+            int s, t;
+            coords(q, ang_major, aw, ah, s, t);
+            if (std::abs(s - sm) > R || std::abs(t - tm) > R) continue;
+            int* at = row + 2 + 3 * row[1]++;
+            at[0] = (int)q; at[1] = s - sm; at[2] = t - tm;
+        }
+        if (!row[1]) { p.left.push_back(m); continue; }
+        p.synth.push_back(m);
+        p.table.insert(p.table.end(), row, row + kTabStride);
+    }
+    return 0;
+}
+
+int check_buffers(lfbm5d_ctx* c, const std::string& who, const float* d_in, float* d_out, unsigned asize, unsigned W, unsigned H, unsigned C) {
+    if (!d_in || !d_out) return fail(c, who + "NULL pointer for a required buffer");
+    if (C != 1 && C != 3) return fail(c, who + "chnls must be 1 or 3");
+    const size_t bytes = (size_t)asize * C * W * H * sizeof(float);
+    if (overlap(d_in, bytes, d_out, bytes)) return fail(c, who + "d_out must not overlap d_in (sources are read across tile edges)");
+    return 0;
+}
+
+/* the synthesis; after plan_sources().  On return the stream is idle and the planes of the synthesised SAIs of d_out (and d_disp) are written. */
+int sweep(lfbm5d_ctx* c, const Plan& p, const lfbm5d_view_params* vp, const float* d_in, float* d_out, signed char* d_disp, unsigned W,
+          unsigned H, unsigned C, lfbm5d_view_result& r) {
+    std::memset(&r, 0, sizeof(r));
+    r.missing = (unsigned)(p.synth.size() + p.left.size());
+    r.synthesised = (unsigned)p.synth.size();
+    r.left = (unsigned)p.left.size();
+    r.pixels = (unsigned long long)p.synth.size() * W * H;
+    if (p.synth.empty()) return 0;
+    (void)hipSetDevice(c->device);
+    HIPCK(c, c->view.table.reserve(p.table.size() * sizeof(int)));
+    HIPCK(c, c->view.stats.reserve(kHist * sizeof(unsigned long long)));
+    unsigned long long* d_cnt = c->view.stats.as<unsigned long long>();
+    HIPCK(c, hipMemcpyAsync(c->view.table.p, p.table.data(), p.table.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemsetAsync(d_cnt, 0, kHist * sizeof(unsigned long long), c->stream));
+    const unsigned tx_n = (W + kTW - 1) / kTW, ty_n = (H + kTH - 1) / kTH;
+    hipLaunchKernelGGL(k_view_sweep, dim3(tx_n * ty_n, (unsigned)p.synth.size()), dim3(kThreads), 0, c->stream, d_in, d_out, d_disp,
+                       c->view.table.as<int>(), (int)C, (int)W, (int)H, tx_n, (int)vp->max_disparity, (int)vp->box_radius, d_cnt);
+    HIPCK(c, hipGetLastError());
+    HIPCK(c, hipMemcpyAsync(r.disparity_hist, d_cnt, kHist * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));   /* the table leaves a caller's object; the histogram is read */
+    return 0;
+}
+
+/* planes of the SAIs with keep(st) of src -> dst (device to device) */
+template <class F>
+int copy_sais(lfbm5d_ctx* c, unsigned asize, float* dst, const float* src, size_t img, F keep) {
+    for (unsigned st = 0; st < asize; st++)
+        if (keep(st))
+            HIPCK(c, hipMemcpyAsync(dst + (size_t)st * img, src + (size_t)st * img, img * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+}
+
+/* include/lfbm5d.h, lfbm5d_view_device */
+int view(lfbm5d_ctx* c, const std::string& who, const lfbm5d_view_params* vp, const lfbm5d_params* P, const float* d_in, const unsigned* h_mask,
+         const unsigned* h_missing, float* d_out, signed char* d_disp, unsigned ang_major, unsigned aw, unsigned ah, unsigned an, unsigned W,
+         unsigned H, unsigned C, lfbm5d_view_result* res) {
+    if (!vp || !P) return fail(c, who + "NULL pointer for a required buffer");
+    const unsigned asize = aw * ah;
+    if (check_buffers(c, who, d_in, d_out, asize, W, H, C)) return 1;
+    if (const char* msg = check_loop(vp)) return fail(c, who + msg);
+    Plan p;
+    if (plan_sources(c, who, vp, h_mask, h_missing, ang_major, aw, ah, W, H, C, p)) return 1;
+    lfbm5d_view_result r;
+    if (sweep(c, p, vp, d_in, d_out, d_disp, W, H, C, r)) return 1;
+    if (res) *res = r;
+    const size_t img = (size_t)C * W * H;
+    const auto sound = [&](unsigned st) { return h_mask[st] && !h_missing[st]; };
+    if (copy_sais(c, asize, d_out, d_in, img, sound)) return 1;             /* x_0: the input with the synthesised SAIs replaced */
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    const unsigned K = vp->iterations;
+    if (!K) return 0;
+    if (r.left) return fail(c, who + "a missing SAI without a source within ang_radius cannot be refined (run the synthesis alone, or widen ang_radius)");
+    const size_t bytes = (size_t)asize * img * sizeof(float);
+    HIPCK(c, c->view.tmp.reserve(bytes));
+    float* z = c->view.tmp.as<float>();
+    if (p.nne < asize) HIPCK(c, hipMemsetAsync(z, 0, bytes, c->stream));   /* the step is handed defined values in empty SAIs too */
+    const double s0 = (double)vp->sigma_start, s1 = (double)vp->sigma_end;
+    for (unsigned k = 1; k <= K; k++) {
+        if (copy_sais(c, asize, z, d_out, img, [&](unsigned st) { return h_mask[st] != 0; })) return 1;   /* x_{k-1}, into the scratch the step may mutate */
+        HIPCK(c, hipStreamSynchronize(c->stream));                          /* the step's contract: its buffers are ready on entry */
+        lfbm5d_params Pk = *P;
+        const double tau = K == 1 ? s0 : s0 * std::pow(s1 / s0, (double)(k - 1) / (double)(K - 1));
+        Pk.sigma = (float)std::max(tau, (double)vp->sigma_noise);
+        if (run_step(c, 1, &Pk, z, h_mask, nullptr, d_out, ang_major, aw, ah, an, W, H, C)) return 1;   /* b_k */
+        if (copy_sais(c, asize, d_out, d_in, img, sound)) return 1;         /* x_k = f ? b_k : y: a selection moves bits, so a copy is one */
+        HIPCK(c, hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+
+} /* namespace */
+
+extern "C" {
+
+void lfbm5d_view_defaults(lfbm5d_view_params* out) {
+    if (!out) return;
+    out->max_disparity = 4;                  /* the best row of the sweep in profiles/view_defaults.txt */
+    out->box_radius = 3;
+    out->ang_radius = 1;
+    out->iterations = 4;
+    out->sigma_start = 30.0f;
+    out->sigma_end = 5.0f;
+    out->sigma_noise = 0.0f;
+}
+
+int lfbm5d_view_fill_device(lfbm5d_ctx* c, const lfbm5d_view_params* vp, const float* d_in, const unsigned* h_mask, const unsigned* h_missing,
+                            float* d_out, signed char* d_disp, unsigned ang_major, unsigned awidth, unsigned aheight, unsigned W, unsigned H,
+                            unsigned C, lfbm5d_view_result* out) {
+    if (!c) return 1;
+    const std::string who = "lfbm5d_view_fill_device: ";
+    if (check_buffers(c, who, d_in, d_out, awidth * aheight, W, H, C)) return 1;
+    Plan p;
+    if (plan_sources(c, who, vp, h_mask, h_missing, ang_major, awidth, aheight, W, H, C, p)) return 1;
+    lfbm5d_view_result r;
+    if (sweep(c, p, vp, d_in, d_out, d_disp, W, H, C, r)) return 1;
+    if (out) *out = r;
+    return 0;
+}
+
+int lfbm5d_view_device(lfbm5d_ctx* c, const lfbm5d_view_params* vp, const lfbm5d_params* P, const float* d_in, const unsigned* h_mask,
+                       const unsigned* h_missing, float* d_out, signed char* d_disp, unsigned ang_major, unsigned awidth, unsigned aheight,
+                       unsigned an, unsigned W, unsigned H, unsigned C, lfbm5d_view_result* out) {
+    if (!c) return 1;
+    return view(c, "lfbm5d_view_device: ", vp, P, d_in, h_mask, h_missing, d_out, d_disp, ang_major, awidth, aheight, an, W, H, C, out);
+}
+
+int lfbm5d_view_host_sai(lfbm5d_ctx* c, const lfbm5d_view_params* vp, const lfbm5d_params* P, const float* const* h_in, const unsigned* h_mask,
+                         const unsigned* h_missing, float* const* h_out, signed char* const* h_disp, unsigned ang_major, unsigned awidth,
+                         unsigned aheight, unsigned an, unsigned W, unsigned H, unsigned C, lfbm5d_view_result* out) {
+    if (!c) return 1;
+    const std::string who = "lfbm5d_view_host_sai: ";
+    if (!vp || !P || !h_in || !h_out || !h_mask || !h_missing) return fail(c, who + "NULL pointer for a required buffer");
+    if (C != 1 && C != 3) return fail(c, who + "chnls must be 1 or 3");
+    const unsigned asize = awidth * aheight;
+    const size_t img = (size_t)C * W * H, plane = (size_t)W * H, all = std::max<size_t>(1, (size_t)asize * img);
+    for (unsigned st = 0; st < asize; st++) {
+        if (!h_mask[st]) continue;
+        if (!h_out[st] || (!h_missing[st] && !h_in[st]) || (h_missing[st] && h_disp && !h_disp[st]))
+            return fail(c, who + "NULL pointer for a non-empty SAI");
+    }
+    (void)hipSetDevice(c->device);
+    HIPCK(c, c->h2d_noisy.reserve(all * sizeof(float)));
+    HIPCK(c, c->h2d_out.reserve(all * sizeof(float)));
+    if (h_disp) HIPCK(c, c->view.disp.reserve(std::max<size_t>(1, (size_t)asize * plane)));
+    float* const din = c->h2d_noisy.as<float>(); float* const dout = c->h2d_out.as<float>();
+    signed char* const ddisp = h_disp ? c->view.disp.as<signed char>() : nullptr;
+    for (unsigned st = 0; st < asize; st++)
+        if (h_mask[st] && !h_missing[st])
+            HIPCK(c, hipMemcpyAsync(din + (size_t)st * img, h_in[st], img * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    lfbm5d_view_result r;
+    std::memset(&r, 0, sizeof(r));
+    const int rc = view(c, who, vp, P, din, h_mask, h_missing, dout, ddisp, ang_major, awidth, aheight, an, W, H, C, &r);
+    if (out) *out = r;
+    if (rc) return 1;
+    /* an SAI that was left (K = 0 only) was not written on the device: its host planes stay as they are */
+    Plan p;
+    if (r.left && plan_sources(c, who, vp, h_mask, h_missing, ang_major, awidth, aheight, W, H, C, p)) return 1;
+    for (unsigned st = 0; st < asize; st++) {
+        if (!h_mask[st]) continue;
+        if (h_missing[st] && r.left && std::find(p.left.begin(), p.left.end(), st) != p.left.end()) continue;
+        HIPCK(c, hipMemcpyAsync(h_out[st], dout + (size_t)st * img, img * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        if (h_disp && h_missing[st]) HIPCK(c, hipMemcpyAsync(h_disp[st], ddisp + (size_t)st * plane, plane, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+} /* extern "C" */

@@ -513,6 +513,80 @@ extern "C" int lfbm5d_inpaint_probe(const float* in_flat, const unsigned char* f
     return 0;
 }
 
+/* view synthesis on the caller's vectors, in place for the caller (one pointer per SAI; the library stages in and out apart) */
+int view_synth_LF(std::vector<std::vector<float> >& LF, const std::vector<unsigned>& LF_SAI_mask, const std::vector<unsigned>& missing,
+                  const unsigned ang_major, const unsigned awidth, const unsigned aheight, const unsigned anHard, const unsigned width,
+                  const unsigned height, const unsigned chnls, const int maxDisparity, const int boxRadius, const int angRadius,
+                  const int iterations, const float sigmaStart, const float sigmaEnd, const float sigmaNoise, const float lambdaHard5D,
+                  const unsigned NHard, const unsigned nSim, const unsigned nDisp, const unsigned kHard, const unsigned pHard, const bool useSD,
+                  const unsigned tau_2D, unsigned tau_4D, const unsigned tau_5D, const unsigned color_space, unsigned& synthesised,
+                  unsigned& left, int& dmin, int& dmax) {
+    const unsigned asize = awidth * aheight;
+    synthesised = left = 0; dmin = dmax = 0;
+    if (LF.size() != asize || LF_SAI_mask.size() != asize || missing.size() != asize) {
+        std::cout << "view_synth_LF: light field, mask and missing must hold awidth*aheight SAIs" << std::endl;
+        return EXIT_FAILURE;
+    }
+    lfbm5d_view_params vp;
+    lfbm5d_view_defaults(&vp);
+    if (maxDisparity >= 0) vp.max_disparity = (unsigned)maxDisparity;
+    if (boxRadius >= 0) vp.box_radius = (unsigned)boxRadius;
+    if (angRadius >= 0) vp.ang_radius = (unsigned)angRadius;
+    if (iterations >= 0) vp.iterations = (unsigned)iterations;
+    if (sigmaStart != 0.0f) vp.sigma_start = sigmaStart;
+    if (sigmaEnd != 0.0f) vp.sigma_end = sigmaEnd;
+    vp.sigma_noise = sigmaNoise;
+    lfbm5d_ctx* ctx = context();
+    if (!ctx) return EXIT_FAILURE;
+    const size_t img = (size_t)width * height * chnls;
+    std::vector<float*> p(asize, nullptr);
+    for (size_t st = 0; st < asize; st++)
+        if (LF_SAI_mask[st]) {
+            if (missing[st]) LF[st].resize(img);
+            else if (LF[st].size() != img) {
+                std::cout << "view_synth_LF: a sound SAI does not hold width*height*chnls values" << std::endl;
+                return EXIT_FAILURE;
+            }
+            p[st] = LF[st].data();
+        }
+    const lfbm5d_params P = make(0.0f, lambdaHard5D, NHard, nSim, nDisp, kHard, pHard, useSD, tau_2D, tau_4D, tau_5D, color_space);
+    lfbm5d_view_result r;
+    std::memset(&r, 0, sizeof(r));
+    const int rc = lfbm5d_view_host_sai(ctx, &vp, &P, p.data(), LF_SAI_mask.data(), missing.data(), p.data(), nullptr, ang_major, awidth,
+                                        aheight, anHard, width, height, chnls, &r);
+    synthesised = r.synthesised; left = r.left;
+    bool any = false;
+    for (int d = -8; d <= 8; d++)
+        if (r.disparity_hist[d + 8]) { if (!any) dmin = d; dmax = d; any = true; }
+    if (rc != 0) {
+        std::cout << "LFBM5D GPU backend: " << lfbm5d_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+    }
+    return EXIT_SUCCESS;
+}
+
+/* Test hook: view_synth_LF on a vector<vector<float>> light field built from a flat copy [asize][chnls*height*width] (the vectors of
+ * missing SAIs stay empty); the result goes to out_flat.  vpi = {maxDisparity, boxRadius, angRadius, iterations},
+ * vpf = {sigmaStart, sigmaEnd, sigmaNoise, lambda}, hard = {N, nSim, nDisp, k, p, useSD, tau_2D, tau_4D, tau_5D},
+ * counts = {synthesised, left, dmin, dmax}. */
+extern "C" int lfbm5d_view_synth_probe(const float* in_flat, const unsigned* mask, const unsigned* missing, float* out_flat, unsigned ang_major,
+                                       unsigned awidth, unsigned aheight, unsigned an, unsigned width, unsigned height, unsigned chnls,
+                                       const int* vpi, const float* vpf, const unsigned* hard, unsigned color_space, int* counts) {
+    const size_t asize = (size_t)awidth * aheight, img = (size_t)width * height * chnls;
+    std::vector<unsigned> m(mask, mask + asize), ms(missing, missing + asize);
+    std::vector<std::vector<float> > LF(asize);
+    for (size_t st = 0; st < asize; st++)
+        if (m[st] && !ms[st]) LF[st].assign(in_flat + st * img, in_flat + (st + 1) * img);
+    unsigned synthesised = 0, left = 0; int dmin = 0, dmax = 0;
+    const int rc = view_synth_LF(LF, m, ms, ang_major, awidth, aheight, an, width, height, chnls, vpi[0], vpi[1], vpi[2], vpi[3], vpf[0], vpf[1],
+                                 vpf[2], vpf[3], hard[0], hard[1], hard[2], hard[3], hard[4], hard[5] != 0, hard[6], hard[7], hard[8], color_space,
+                                 synthesised, left, dmin, dmax);
+    if (counts) { counts[0] = (int)synthesised; counts[1] = (int)left; counts[2] = dmin; counts[3] = dmax; }
+    if (rc != EXIT_SUCCESS) return 1;
+    for (size_t st = 0; st < asize; st++) if (m[st] && LF[st].size() == img) std::memcpy(out_flat + st * img, LF[st].data(), img * sizeof(float));
+    return 0;
+}
+
 /* run_bm3d_LF (src/bm3d_LF.h:10-35, bm3d_LF.cpp:75-125): BM3D on every SAI of the mask */
 #include "run_bm3d_lf.h"
 int run_bm3d_LF(const float sigma, std::vector<std::vector<float> >& LF_noisy, std::vector<unsigned>& LF_SAI_mask,

@@ -254,6 +254,49 @@ int inpaint_LF(
 ,   unsigned &passes
 );
 
+//! View synthesis -- not in the reference: the SAIs that `missing` marks (non-zero; they must be non-empty in LF_SAI_mask; their vectors
+//! are not read and are resized) are synthesised on the GPU from their sound angular neighbours by a plane sweep over the integer
+//! disparities -maxDisparity..maxDisparity with a (2 boxRadius + 1)^2 box, sources within angRadius views, and refined by `iterations`
+//! hard-thresholding steps whose sigma falls from sigmaStart to sigmaEnd but not below sigmaNoise, the sound SAIs being put back after
+//! every step (lfbm5d_view_host_sai, include/lfbm5d.h).  LF is completed in place.  maxDisparity, boxRadius, angRadius, iterations < 0,
+//! sigmaStart = 0, sigmaEnd = 0: the library's defaults (lfbm5d_view_defaults); iterations = 0: the synthesis alone.  `left` counts the
+//! missing SAIs without a source (unchanged); dmin..dmax is the range of the disparities chosen (0..0 when nothing was synthesised).
+//! Returns EXIT_SUCCESS, or EXIT_FAILURE with the message on stdout.
+int view_synth_LF(
+    std::vector<std::vector<float> > &LF
+,   const std::vector<unsigned> &LF_SAI_mask
+,   const std::vector<unsigned> &missing
+,   const unsigned ang_major
+,   const unsigned awidth
+,   const unsigned aheight
+,   const unsigned anHard
+,   const unsigned width
+,   const unsigned height
+,   const unsigned chnls
+,   const int      maxDisparity
+,   const int      boxRadius
+,   const int      angRadius
+,   const int      iterations
+,   const float    sigmaStart
+,   const float    sigmaEnd
+,   const float    sigmaNoise
+,   const float    lambdaHard5D
+,   const unsigned NHard
+,   const unsigned nSim
+,   const unsigned nDisp
+,   const unsigned kHard
+,   const unsigned pHard
+,   const bool     useSD
+,   const unsigned tau_2D
+,         unsigned tau_4D
+,   const unsigned tau_5D
+,   const unsigned color_space
+,   unsigned &synthesised
+,   unsigned &left
+,   int &dmin
+,   int &dmax
+);
+
 //! Super-resolution -- not in the reference's master branch: the scheme of SR-LFBM5D (iterative back-projection regularised by the
 //! hard-thresholding step above) with the operators of include/lfbm5d.h, on the GPU (lfbm5d_superres_host_sai).  LF_low holds
 //! width x height SAIs and is only read; LF_high is (re)sized to scale*width x scale*height SAIs and filled.  kernel: 0 = bicubic,
