@@ -6,7 +6,6 @@
 #include "lfbm5d_graph.h"
 
 using namespace lfbm5d_host;
-using lfbm5d::plan::search_window;
 using lfbm5d::plan::plan_windows;
 
 namespace { std::string g_create_error; }
@@ -150,7 +149,7 @@ int lfbm5d_plan_windows(unsigned awidth, unsigned aheight, unsigned an, unsigned
     if (!mask || !awidth || !aheight || 2 * an + 1 > awidth || 2 * an + 1 > aheight) return -1;
     if (ang_major != LFBM5D_ROWMAJOR && ang_major != LFBM5D_COLMAJOR) return -1;
     std::vector<unsigned> plan;
-    plan_windows(mask, awidth, aheight, an, ang_major, plan);
+    plan_windows(mask, plan::Grid{awidth, aheight, ang_major}, an, plan);
     for (size_t i = 0; i < plan.size() && i < cap && out_sai; i++) out_sai[i] = plan[i];
     return (int)plan.size();
 }
@@ -161,7 +160,7 @@ int lfbm5d_plan_graph(unsigned awidth, unsigned aheight, unsigned an, unsigned a
     if (ang_major != LFBM5D_ROWMAJOR && ang_major != LFBM5D_COLMAJOR) return -1;
     plan::Graph G;
     const plan::StepDesc sd = {an, LFBM5D_SADCT, 1u};
-    plan::build(mask, awidth, aheight, ang_major, &sd, 1, world, lanes, 0, G);
+    plan::build(mask, plan::Grid{awidth, aheight, ang_major}, &sd, 1, world, lanes, 0, G);
     for (size_t i = 0; i < G.nodes.size() && i < cap; i++) {
         if (out_rank) out_rank[i] = (unsigned)G.nodes[i].rank;
         if (out_lane) out_lane[i] = (unsigned)G.nodes[i].lane;
@@ -176,7 +175,7 @@ int lfbm5d_plan_messages(unsigned awidth, unsigned aheight, unsigned an, unsigne
     if (ang_major != LFBM5D_ROWMAJOR && ang_major != LFBM5D_COLMAJOR) return -1;
     plan::Graph G;
     const plan::StepDesc sd = {an, LFBM5D_SADCT, 1u};
-    plan::build(mask, awidth, aheight, ang_major, &sd, 1, world, 1, 0, G);
+    plan::build(mask, plan::Grid{awidth, aheight, ang_major}, &sd, 1, world, 1, 0, G);
     for (size_t i = 0; i < G.xfers.size() && i < cap && out; i++) {
         out[4 * i] = G.xfers[i].from; out[4 * i + 1] = (unsigned)G.xfers[i].to_node; out[4 * i + 2] = G.xfers[i].sai; out[4 * i + 3] = (unsigned)G.xfers[i].channel;
     }
@@ -194,7 +193,7 @@ int lfbm5d_plan_job(unsigned awidth, unsigned aheight, unsigned ang_major, const
         sd[i] = {an[i], LFBM5D_SADCT, cost ? cost[i] : (n_steps == 2 ? (i == 0 ? 10u : 9u) : 1u)};
     }
     plan::Graph G;
-    plan::build(mask, awidth, aheight, ang_major, sd, n_steps, world, lanes, 0, G);
+    plan::build(mask, plan::Grid{awidth, aheight, ang_major}, sd, n_steps, world, lanes, 0, G);
     std::vector<unsigned> pos(G.nodes.size(), 0);
     for (size_t i = 0; i < G.order.size(); i++) pos[G.order[i]] = (unsigned)i;
     for (size_t i = 0; i < G.nodes.size() && i < node_cap && out_nodes; i++) {
@@ -542,10 +541,7 @@ int run_bm3d_lf(lfbm5d_ctx* c, const lfbm5d_bm3d_params* Hd, const lfbm5d_bm3d_p
     for (unsigned l = 1; l < n_l; l++) {
         lfbm5d_ctx* const x = c->lanes[l - 1];
         if (bm3d_fold(x, Wn, C, 2)) { c->err = x->err; return 1; }
-        c->stats.passes += x->stats.passes; c->stats.groups += x->stats.groups; c->stats.stack_patches += x->stats.stack_patches;
-        c->stats.sadct_groups += x->stats.sadct_groups; c->stats.algorithmic_bytes += x->stats.algorithmic_bytes;
-        c->stats.ms_bm += x->stats.ms_bm; c->stats.ms_group += x->stats.ms_group; c->stats.ms_aggregate += x->stats.ms_aggregate;
-        c->stats.launches_group += x->stats.launches_group; c->stats.launches_aggregate += x->stats.launches_aggregate;
+        add_stats(c->stats, x->stats);
         std::memset(&x->stats, 0, sizeof(x->stats));
     }
     drain_guard.armed = false;   /* every lane has been synchronised above */

@@ -162,11 +162,10 @@ struct lfbm5d_ctx {
     /* view synthesis (lfbm5d_view.hip): the source lists, the disparity histogram, the loop's scratch input of the step, the host form's
      * disparity planes */
     struct ViewBufs { DevBuf table, stats, tmp, disp; } view;
-    /* window lanes (run_step, pipelined form): extra contexts on the same device, each with its own stream, window
+    /* window lanes (run_graph; the per-SAI BM3D steps): extra contexts on the same device, each with its own stream, window
      * buffers and per-pass work buffers; owned by this context */
     std::vector<lfbm5d_ctx*> lanes;
     unsigned* h_counts = nullptr; size_t h_counts_cap = 0;   /* pinned: coverage count of every window of a step */
-    unsigned long long lane_windows = 0;   /* windows of the last step that ran on a lane other than the first */
     std::vector<hipEvent_t> ev_pool; size_t ev_used = 0;
     std::vector<PassEvents> pending;
     /* last pass (inspection) */
@@ -197,6 +196,16 @@ void build_tables(GroupTables& t, unsigned k, unsigned aw, unsigned ah);
 bool is_pow2(unsigned n);
 int validate(lfbm5d_ctx* c, int step, const lfbm5d_params* P, unsigned aw, unsigned ah, unsigned C, bool bm3d = false);
 int fold_counters(lfbm5d_ctx* c, const lfbm5d_params* P, unsigned A, unsigned C, int step, int slot = 0);
+/* A lane's (or an emulated rank's) counters and event times into the job's context: every field a pass adds to.  Not added:
+ * windows, messages, lane_windows -- the job counts those on its own context as it enqueues, a lane's are zero; ms_comm -- the
+ * job's exchange is timed on its own stream, a lane's pass is never sharded; ms_other -- nothing accumulates it. */
+inline void add_stats(lfbm5d_stats& dst, const lfbm5d_stats& src) {
+    static_assert(sizeof(lfbm5d_stats) == 15 * 8, "lfbm5d_stats has a new field: add it below or name it above");
+    dst.passes += src.passes; dst.groups += src.groups; dst.stack_patches += src.stack_patches; dst.sadct_groups += src.sadct_groups;
+    dst.algorithmic_bytes += src.algorithmic_bytes;
+    dst.ms_bm += src.ms_bm; dst.ms_group += src.ms_group; dst.ms_aggregate += src.ms_aggregate;
+    dst.launches_group += src.launches_group; dst.launches_aggregate += src.launches_aggregate;
+}
 /* lfbm5d_pass.hip */
 int pass_impl(lfbm5d_ctx* c, int step, const lfbm5d_params* P, unsigned aw, unsigned ah, unsigned Wb,
               unsigned Hb, unsigned C, const float* d_noisy, const float* d_basic, float* d_num,

@@ -1,5 +1,7 @@
 /*
- * lfbm5d_graph.h -- a JOB of the window graph (run_graph, lfbm5d_graph.hip) as the step functions hand it over.  Internal.
+ * lfbm5d_graph.h -- a JOB of the window graph (run_graph, lfbm5d_graph.hip) as the step functions hand it over, and what the window
+ * engines of lfbm5d_graph.hip and lfbm5d_steps.hip share: a window's masked geometry, a lane's buffers, the transports' teardown and
+ * the timer of a collective.  Internal.
  */
 #ifndef LFBM5D_GRAPH_H
 #define LFBM5D_GRAPH_H
@@ -28,8 +30,48 @@ struct GraphJob {
     unsigned color_space = LFBM5D_RGB;
 };
 
-int run_graph(lfbm5d_ctx* c, const GraphJob& J, const plan::Graph& G, const unsigned* h_mask, unsigned awidth, unsigned aheight,
-              unsigned ang_major, unsigned W, unsigned H, unsigned C, int nranks, bool emulate, int* complete_out);
+int run_graph(lfbm5d_ctx* c, const GraphJob& J, const plan::Graph& G, const unsigned* h_mask, const plan::Grid& grid,
+              unsigned W, unsigned H, unsigned C, int nranks, bool emulate, int* complete_out);
+
+/* The mask applied to a window, per slot: which slots hold a SAI (mask_w, bits; sl = their light-field indices, 0xffffffff for an
+ * empty slot), which are processed already (proc_w: the empty ones), and how many SAIs the window holds. */
+struct MaskedWindow { std::vector<unsigned> mask_w, proc_w; SaiList sl; SaiMask bits = sai_mask_none(); unsigned n_in = 0; };
+inline MaskedWindow mask_window(const plan::Window& w, const unsigned* h_mask) {
+    const unsigned Aw = w.slots.size();
+    MaskedWindow m;
+    m.mask_w.assign(Aw, 0); m.proc_w.assign(Aw, 0);
+    m.sl.n = Aw;
+    for (unsigned i = 0; i < Aw; i++) {
+        m.mask_w[i] = h_mask[w.st[i]];
+        m.proc_w[i] = !m.mask_w[i];
+        m.sl.st[i] = m.mask_w[i] ? w.st[i] : 0xffffffffu;
+        if (m.mask_w[i]) { m.bits.set(i); m.n_in++; }
+    }
+    return m;
+}
+
+/* A lane = a context with its stream, per-pass work buffers and these window buffers (lane 0 is the job's own context).
+ * lane_buffers sizes them for windows of win_floats floats; the padded sums only where the form keeps them. */
+struct Lane { lfbm5d_ctx* x; float* w_noisy; float* w_basic; float* w_num; float* w_den; unsigned* d_small; };
+int lane_buffers(lfbm5d_ctx* c, lfbm5d_ctx* x, size_t win_floats, bool with_basic, bool with_sums, unsigned asize, Lane& L);
+
+/* The light-field sums of the first n_slots step slots (floats each) in context x's buffers, zeroed on stream xs. */
+int zeroed_sums(lfbm5d_ctx* c, lfbm5d_ctx* x, int n_slots, size_t floats, hipStream_t xs, float* g_num[2], float* g_den[2]);
+
+/* Teardown of a transport after a failed job.  abort_comms: peers wait in operations this rank will never match, so both
+ * communicators are aborted (comm2 first: it was split from comm) and `c->err` says on behalf of what; close_ipc_peers unmaps
+ * every buffer of a peer this process has opened. */
+void abort_comms(lfbm5d_ctx* c, const char* what);
+void close_ipc_peers(lfbm5d_ctx* c);
+
+/* HIP-event time of what is enqueued on `s` between begin() and end(), added to stats.ms_comm when the timer goes out of scope --
+ * by then the caller has synchronised the stream.  The events are the context's pooled ones: nothing to release on an error return. */
+struct CommTimer {
+    lfbm5d_ctx* c; hipStream_t s; hipEvent_t e0 = nullptr, e1 = nullptr; bool closed = false;
+    hipError_t begin() { e0 = get_event(c); e1 = get_event(c); return hipEventRecord(e0, s); }
+    hipError_t end() { closed = true; return hipEventRecord(e1, s); }
+    ~CommTimer() { float ms = 0.0f; if (closed && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) c->stats.ms_comm += ms; }
+};
 
 } /* namespace lfbm5d_host */
 #endif

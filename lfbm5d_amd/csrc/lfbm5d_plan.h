@@ -38,14 +38,47 @@ inline void search_window(int aidx, unsigned asize, unsigned an, int& cc, int& m
     mn += shift; mx += shift; cc -= shift;
 }
 
+/* An angular grid -- the light field's SAIs, or the slots of a window -- in the caller's major order: SAI (s, t), row s of
+ * aheight and column t of awidth, <-> its index.  The only place that knows the two orders. */
+struct Grid {
+    unsigned awidth, aheight, ang_major;
+    unsigned size() const { return awidth * aheight; }
+    unsigned index(unsigned s, unsigned t) const { return ang_major == kRowMajor ? s * awidth + t : s + t * aheight; }
+    void coords(unsigned st, unsigned& s, unsigned& t) const {
+        if (ang_major == kRowMajor) { s = st / awidth; t = st % awidth; }
+        else { s = st % aheight; t = st / aheight; }
+    }
+};
+
+/* The angular window of half size `an` around SAI (ps, pt), shifted into the light field (bm5d.cpp:215-232): its slots form a grid
+ * of their own in the same major order. */
+struct Window {
+    Grid slots;                   /* asw x asw */
+    int mins = 0, mint = 0;       /* light-field row / column of slot (0, 0) */
+    unsigned cst_w = 0;           /* slot of (ps, pt) */
+    std::vector<unsigned> st;     /* light-field index of every slot, in slot order */
+    unsigned at(unsigned si, unsigned ti) const { return st[slots.index(si, ti)]; }
+};
+inline Window window_at(const Grid& g, unsigned ps, unsigned pt, unsigned an) {
+    const unsigned asw = 2 * an + 1;
+    Window w;
+    w.slots = Grid{asw, asw, g.ang_major};
+    int cs_w, maxs, ct_w, maxt;
+    search_window((int)ps, g.aheight, an, cs_w, w.mins, maxs);
+    search_window((int)pt, g.awidth, an, ct_w, w.mint, maxt);
+    w.cst_w = w.slots.index((unsigned)cs_w, (unsigned)ct_w);
+    w.st.resize(w.slots.size());
+    for (unsigned si = 0; si < asw; si++)
+        for (unsigned ti = 0; ti < asw; ti++) w.st[w.slots.index(si, ti)] = g.index(si + (unsigned)w.mins, ti + (unsigned)w.mint);
+    return w;
+}
+
 /* The sequence of windows a step processes, as the processed SAI of each: first the centre SAI if it is not empty, then
  * always the last unprocessed SAI; every SAI of a window is processed when the window is done (bm5d.cpp:165-402 -- all
  * candidates of the reference's arg-max tie, see lfbm5d_plan_windows in include/lfbm5d.h). */
-inline void plan_windows(const unsigned* h_mask, unsigned awidth, unsigned aheight, unsigned an, unsigned ang_major,
-                         std::vector<unsigned>& out) {
-    const unsigned asize = awidth * aheight, asw = 2 * an + 1;
-    const unsigned cs = aheight / 2, ct = awidth / 2;
-    const unsigned cst = ang_major == kRowMajor ? cs * awidth + ct : cs + ct * aheight;
+inline void plan_windows(const unsigned* h_mask, const Grid& grid, unsigned an, std::vector<unsigned>& out) {
+    const unsigned asize = grid.size();
+    const unsigned cst = grid.index(grid.aheight / 2, grid.awidth / 2);
     std::vector<unsigned> proc(asize);
     for (unsigned st = 0; st < asize; st++) proc[st] = !h_mask[st];
     unsigned remaining = (unsigned)std::count(proc.begin(), proc.end(), 0u);
@@ -55,17 +88,10 @@ inline void plan_windows(const unsigned* h_mask, unsigned awidth, unsigned aheig
         unsigned pst = 0;
         if (remaining == total && h_mask[cst]) pst = cst;
         else for (unsigned st = 0; st < asize; st++) if (!proc[st]) pst = st;
-        const unsigned ps = ang_major == kRowMajor ? pst / awidth : pst % aheight;
-        const unsigned pt = ang_major == kRowMajor ? pst % awidth : pst / aheight;
-        int cs_w, mins, maxs, ct_w, mint, maxt;
-        search_window((int)ps, aheight, an, cs_w, mins, maxs);
-        search_window((int)pt, awidth, an, ct_w, mint, maxt);
-        for (unsigned si = 0; si < asw; si++)
-            for (unsigned ti = 0; ti < asw; ti++) {
-                const unsigned S = si + mins, T = ti + mint;
-                const unsigned st = ang_major == kRowMajor ? S * awidth + T : S + T * aheight;
-                if (h_mask[st]) proc[st] = 1;
-            }
+        unsigned ps, pt;
+        grid.coords(pst, ps, pt);
+        for (unsigned st : window_at(grid, ps, pt, an).st)
+            if (h_mask[st]) proc[st] = 1;
         out.push_back(pst);
         remaining = (unsigned)std::count(proc.begin(), proc.end(), 0u);
     }
@@ -103,9 +129,9 @@ struct Graph {
     unsigned makespan = 0;                /* of the simulated execution (lanes as parallel servers) */
 };
 
-inline void build(const unsigned* h_mask, unsigned awidth, unsigned aheight, unsigned ang_major, const StepDesc* steps, int n_steps,
+inline void build(const unsigned* h_mask, const Grid& grid, const StepDesc* steps, int n_steps,
                   int world, int n_lanes, int max_windows, Graph& G) {
-    const unsigned asize = awidth * aheight;
+    const unsigned asize = grid.size();
     const int Gn = std::max(1, world);
     n_lanes = std::max(1, n_lanes);
     G.nodes.clear(); G.order.clear(); G.xfers.clear(); G.centre_ok = true; G.n_first = 0; G.makespan = 0;
@@ -113,7 +139,7 @@ inline void build(const unsigned* h_mask, unsigned awidth, unsigned aheight, uns
     for (int s = 0; s < n_steps; s++) {
         const unsigned an = steps[s].an, asw = 2 * an + 1, Aw = asw * asw;
         std::vector<unsigned> pl;
-        plan_windows(h_mask, awidth, aheight, an, ang_major, pl);
+        plan_windows(h_mask, grid, an, pl);
         if (max_windows > 0 && pl.size() > (size_t)max_windows) pl.resize((size_t)max_windows);
         G.last_touch[s].assign(asize, -1);
         unsigned t4 = steps[s].tau4;
@@ -121,21 +147,14 @@ inline void build(const unsigned* h_mask, unsigned awidth, unsigned aheight, uns
         for (size_t w = 0; w < pl.size(); w++) {
             Node nd;
             nd.s = s; nd.w = (unsigned)w; nd.pst = pl[w]; nd.cost = std::max(1u, steps[s].cost);
-            nd.ps = ang_major == kRowMajor ? pl[w] / awidth : pl[w] % aheight;
-            nd.pt = ang_major == kRowMajor ? pl[w] % awidth : pl[w] / aheight;
-            int cs_w, mins, maxs, ct_w, mint, maxt;
-            search_window((int)nd.ps, aheight, an, cs_w, mins, maxs);
-            search_window((int)nd.pt, awidth, an, ct_w, mint, maxt);
-            for (unsigned si = 0; si < asw; si++)
-                for (unsigned ti = 0; ti < asw; ti++) {
-                    const unsigned st = ang_major == kRowMajor ? (si + mins) * awidth + (ti + mint) : (si + mins) + (ti + mint) * aheight;
-                    if (h_mask[st]) nd.sai.push_back(st);
-                }
+            grid.coords(pl[w], nd.ps, nd.pt);
+            const Window win = window_at(grid, nd.ps, nd.pt, an);
+            for (unsigned si = 0; si < asw; si++)   /* (rows first in either major order: the order of a node's SAIs is the messages') */
+                for (unsigned ti = 0; ti < asw; ti++)
+                    if (h_mask[win.at(si, ti)]) nd.sai.push_back(win.at(si, ti));
             if (nd.sai.size() != Aw && t4 == 5u /* LFBM5D_DCT */) t4 = 6u /* LFBM5D_SADCT */;
             nd.tau4 = t4;
-            const unsigned cst_lf = ang_major == kRowMajor ? (unsigned)(mins + cs_w) * awidth + (unsigned)(mint + ct_w)
-                                                           : (unsigned)(mins + cs_w) + (unsigned)(mint + ct_w) * aheight;
-            if (!h_mask[cst_lf]) G.centre_ok = false;
+            if (!h_mask[win.st[win.cst_w]]) G.centre_ok = false;
             if (w > 0 && nd.ps != G.nodes.back().ps) chain++;
             else if (w == 0 && base > 0) chain++;
             nd.chain = chain;

@@ -76,6 +76,27 @@ def _window_cover(aw, ah, pst):
     return [(s0 + s) * aw + (t0 + t) for s in range(3) for t in range(3)], (ps - s0) * 3 + (pt - t0)
 
 
+def _masked_cover(aw, ah, an, colmajor, mask, pst):
+    """The non-empty SAIs of the window of half size `an` around SAI pst, in either major order."""
+    idx = (lambda s_, t_: s_ + t_ * ah) if colmajor else (lambda s_, t_: s_ * aw + t_)
+    ps, pt = (int(pst) % ah, int(pst) // ah) if colmajor else (int(pst) // aw, int(pst) % aw)
+    n = 2 * an + 1
+    s0, t0 = min(max(ps - an, 0), ah - n), min(max(pt - an, 0), aw - n)
+    return {idx(s0 + s_, t0 + t_) for s_ in range(n) for t_ in range(n) if mask[idx(s0 + s_, t0 + t_)]}
+
+
+# (ah, aw, an, column-major, empty SAIs as (s, t)): the last case has an = 2, column-major order and holes off the centre
+_PLAN_CASES = ((17, 17, 1, False, ()), (9, 9, 1, False, ()), (15, 15, 1, False, ()), (5, 7, 1, False, ()), (3, 3, 1, False, ()),
+               (7, 9, 2, True, ((0, 0), (6, 7), (1, 8))))
+
+
+def _plan_case_mask(ah, aw, colmajor, holes):
+    mask = np.ones(ah * aw, np.uint32)
+    for (s_, t_) in holes:
+        mask[s_ + t_ * ah if colmajor else s_ * aw + t_] = 0
+    return mask
+
+
 def _graph_job(noisy, ah, aw, H, W, pks, team, me, group):
     """One rank's part of the graph form of a job on the light field `noisy` (A x C*H*W): the oracle's core pass stands in for the
     device kernels and gloo send / recv for RCCL's.  `team` = the global ranks that share the job (plan rank i = team[i]), `me` =
@@ -340,13 +361,16 @@ def test_graph_plan_properties():
     and messages connect exactly the consecutive touchers of an SAI that live on different ranks (+ one basic estimate per SAI
     and reading rank in two-step jobs)."""
     from lfbm5d_amd import core
-    for (ah, aw) in ((17, 17), (9, 9), (15, 15), (5, 7), (3, 3)):
-        plan = core.plan_windows(aw, ah, 1)
-        cover = [set(_window_cover(aw, ah, pst)[0]) for pst in plan]
+    for (ah, aw, an, colmajor, holes) in _PLAN_CASES:
+        major, mask = core.COLMAJOR if colmajor else core.ROWMAJOR, _plan_case_mask(ah, aw, colmajor, holes)
+        plan = core.plan_windows(aw, ah, an, major, mask)
+        cover = [_masked_cover(aw, ah, an, colmajor, mask, pst) for pst in plan]
+        if not holes and not colmajor and an == 1:
+            assert cover == [set(_window_cover(aw, ah, pst)[0]) for pst in plan]
         NW = len(plan)
         for world in (1, 2, 3, 4, 8):
             for lanes in (1, 3):
-                ranks, lane, start = core.plan_graph(aw, ah, world, lanes)
+                ranks, lane, start = core.plan_graph(aw, ah, world, lanes, an, major, mask)
                 assert len(ranks) == NW and ranks.max() < world and lane.max() < lanes
                 for w in range(NW):
                     for p in range(w):
@@ -354,8 +378,8 @@ def test_graph_plan_properties():
                             assert start[p] < start[w], (ah, aw, world, lanes, p, w)
                 # no two windows at once on one lane
                 assert len({(int(ranks[w]), int(lane[w]), int(start[w])) for w in range(NW)}) == NW
-            msgs = core.plan_messages(aw, ah, world)
-            ranks, _, start = core.plan_graph(aw, ah, world)
+            msgs = core.plan_messages(aw, ah, world, an, major, mask)
+            ranks, _, start = core.plan_graph(aw, ah, world, 1, an, major, mask)
             expect = []
             for w in range(NW):
                 for st in sorted(cover[w]):
@@ -369,7 +393,7 @@ def test_graph_plan_properties():
                 assert len(msgs) == 0
             # the two-step job
             for lanes in (1, 3):
-                nodes, jm, info = core.plan_job(aw, ah, world, lanes, an=(1, 1))
+                nodes, jm, info = core.plan_job(aw, ah, world, lanes, an=(an, an), ang_major=major, mask=mask)
                 assert len(nodes) == 2 * NW and info["centre_ok"]
                 pos = nodes[:, 6].astype(int)
                 assert sorted(pos.tolist()) == list(range(2 * NW))
@@ -429,6 +453,15 @@ def test_plan_windows_matches_the_reference_rule():
     assert core.plan_windows(5, 5, 1, mask=mask)[0] == 24
     for st in core.plan_windows(5, 5, 1, mask=mask):
         assert mask[st]
+    # the rule replayed for every case of the graph test, among them an = 2 in column-major order with holes
+    for (ah, aw, an, colmajor, holes) in _PLAN_CASES:
+        mask = _plan_case_mask(ah, aw, colmajor, holes)
+        cst = ah // 2 + (aw // 2) * ah if colmajor else (ah // 2) * aw + aw // 2
+        todo, expect = {st for st in range(ah * aw) if mask[st]}, []
+        while todo:
+            expect.append(cst if not expect and mask[cst] else max(todo))
+            todo -= _masked_cover(aw, ah, an, colmajor, mask, expect[-1])
+        assert core.plan_windows(aw, ah, an, core.COLMAJOR if colmajor else core.ROWMAJOR, mask).tolist() == expect, (ah, aw, an, colmajor)
 
 
 def _simulate_exchange(aw, ah, world, lanes, single_channel=False, perturb=False, n_steps=1):
