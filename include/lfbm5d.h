@@ -551,7 +551,7 @@ int lfbm5d_denoise_pg_host_sai(lfbm5d_ctx* ctx, const lfbm5d_pg_model* model, lf
  * 3; W, H >= 2.  One GPU: contexts with a communicator or a shard return 1.  Everything below is stated in float32 operations without a
  * product, integer counts and order statistics: the GPU equals the numpy model of tests/impulse_model.py bit for bit.
  * Limits: an impulse smeared by demosaicking into a blob, or a cluster that fills a 3 x 3, is not found (its neighbours agree with it);
- * detection is spatial only (no cross-SAI test); on nearly noise-free, textured data about 0.4 % of the sound values are touched
+ * detection here is spatial only (the cross-SAI test is the consistency check below, lfbm5d_consist_*); on nearly noise-free, textured data about 0.4 % of the sound values are touched
  * (DESIGN.md 3g has the table); k = 8 is the cheapest row of that table on sound data, a default and not a law.
  *
  * Neighbours.  For a pixel c of a plane I the neighbours q are the eight positions of the 3 x 3 around it; coordinates outside the plane
@@ -643,8 +643,8 @@ int lfbm5d_impulse_repair_host_sai(lfbm5d_ctx* ctx, const lfbm5d_impulse_params*
  * runs exactly as lfbm5d_step1_device runs it (colour space, window graph, lanes, every option); every step filters the whole light field,
  * not only the windows that hold defects.  K >= 1 with a value left (a plane without one sound value) returns 1 with a message: such a
  * plane belongs to an SAI that should have been masked as empty.
- * Limits: the map is given (or comes from the impulse repair: the code-2 values of its flag plane can be passed on as a map); blobs are
- * not detected here; a whole missing SAI is reconstructed by the view synthesis below, not here; the defaults are the best of a sweep on one light field
+ * Limits: the map is given (it comes from the consistency check below, lfbm5d_consist_*, or from the impulse repair: the code-2 values of
+ * its flag plane can be passed on as a map); blobs are not detected here; a whole missing SAI is reconstructed by the view synthesis below, not here; the defaults are the best of a sweep on one light field
  * (profiles/inpaint_defaults.txt) and claim nothing beyond it. */
 #define LFBM5D_INPAINT_PASSES_PER_LAUNCH 8
 typedef struct {
@@ -711,7 +711,8 @@ int lfbm5d_inpaint_host_sai(lfbm5d_ctx* ctx, const lfbm5d_inpaint_params* params
  * Loop.  f = every value of the synthesised SAIs; x_0 = the input with those SAIs replaced; for k = 1..K: b = the basic estimate of
  * lfbm5d_step1_device on a scratch copy of x_{k-1} with P.sigma = max(tau_k, sigma_noise), tau_k on the schedule of the defect inpainting;
  * x_k = f ? b : y.  K = 0 is the synthesis alone.  K >= 1 with an SAI left returns 1 with a message, after `out` is filled in.
- * Limits: integer disparities; occlusions are not modelled; one scalar d per pixel; sources only within ang_radius; one GPU; every step of
+ * Limits: integer disparities; occlusions are not modelled; one scalar d per pixel; sources only within ang_radius; which SAIs are bad is
+ * not decided here (the consistency check below does that); one GPU; every step of
  * the loop filters the whole light field; the defaults are the best row of a sweep on one light field (profiles/view_defaults.txt). */
 typedef struct {
     unsigned max_disparity; /* D, 0..8: hypotheses -D..D                                                               */
@@ -750,6 +751,86 @@ int lfbm5d_view_host_sai(lfbm5d_ctx* ctx, const lfbm5d_view_params* params, cons
                          const unsigned* h_mask, const unsigned* h_missing, float* const* h_out, signed char* const* h_disp,
                          unsigned ang_major, unsigned awidth, unsigned aheight, unsigned an, unsigned W, unsigned H, unsigned C,
                          lfbm5d_view_result* out);
+
+/* ---- consistency check: defective values and bad sub-aperture images found by what the other views say ----
+ * Not in the reference.  The three stages above repair what they are told about (a defect map, a list of missing SAIs) or what a 3 x 3
+ * shows (single-pixel impulses).  A light field says more: a sound value is predicted by its angular neighbours, a defective one is
+ * not.  This stage predicts every SAI from its neighbours with the view synthesis' plane sweep, the SAI itself left out, and tests the
+ * residual.  Its flag planes can be handed to lfbm5d_inpaint_* as the map, its bad SAIs to lfbm5d_view_* as the missing list.  Opt-in.
+ * Data.  As for the view synthesis: [asize][C*H*W] float32, h_mask, (s, t) by ang_major, C = 1 or 3, W, H >= 2.  h_exclude (optional,
+ * unsigned [asize], non-zero = known bad): neither tested nor used as a source.  One GPU: contexts with a communicator or a shard
+ * return 1.
+ * Tested SAIs.  An SAI m is tested if it is non-empty and not excluded.  Its sources are the view synthesis' sources with "missing" =
+ * the exclude set and m: every other usable SAI within ang_radius, in increasing index order, n of them.  n < min_sources (>= 2): the
+ * SAI is untested (reported; its flag plane is all 0).
+ * Prediction.  Exactly the view synthesis' sweep at (max_disparity, box_radius): d*(y, x) and mu = mu_{d*}(c, y, x).  The tested SAI
+ * does not take part, so a defect in it cannot steer d*.
+ * Residual and spread, float32, every operation rounded on its own (no fused multiply-add): rho = I_m - mu; a = |rho|;
+ * v = sum_q (w_{q,d*} - mu)^2 from +0.0f in source order, per channel.
+ * Scale.  Per tested SAI and channel a histogram of a with the impulse repair's keys (LFBM5D_IMPULSE_KEYS, the same key function; a NaN
+ * a, from a non-finite source, lands in the last key); a value whose I_m is not finite is skipped and counted.  Medians by
+ * lfbm5d_impulse_scale: scale_c of the channel's histogram pooled over the tested SAIs, s_m of SAI m's histogram pooled over channels.
+ * Pixel decision.  T_c = (float) max(k scale_c, min_threshold); g = (float)(spread^2), formed in double.  Code 2: I_m is not finite.
+ * Code 1: a > T_c and (rho rho) (float)(n - 1) > g v.  The second test keeps depth edges and occlusions out (there the sources
+ * disagree among themselves) and rejects the shadow a neighbour's defect delta throws on m: then rho = -delta / n and
+ * v = delta^2 (n - 1) / n, the ratio of the two sides is 1 / (n spread^2), so no spread >= 1 flags it.
+ * Bad-SAI decision, on the host in double.  ref = the lower median of s_m over the tested SAIs with a non-empty histogram; m exceeds
+ * when s_m > sai_factor max(ref, min_scale); m is bad when it exceeds and no tested neighbour q within ang_radius exceeds with
+ * s_q > s_m, or with s_q = s_m and q < m (a bad view raises its neighbours' residuals by about delta / n: only the local maximum is
+ * bad).  A tested SAI whose histogram is empty (nothing finite) is bad.  sai_factor = 0 switches the decision off.
+ * Rounds.  Sweep and statistics run with the current exclude set; new bad SAIs join it and the round repeats; at most max_rounds
+ * decisions are made; if the last allowed decision still found one, one more sweep runs without a decision.  Flags, scales, histograms
+ * and d* come from the final sweep; `rounds` counts the sweeps.
+ * Non-finite source values: decisions within max_disparity ang_radius + box_radius of one are deterministic (comparisons with a NaN are
+ * false) but meaningless; fill such values first (lfbm5d_inpaint_fill_device under an empty map), as the Python wrapper does.
+ * Sums in a fixed order, integer atomics, quantiles on integer histograms: the GPU equals the numpy model of tests/consist_model.py bit
+ * for bit in every integer and float it returns, and repeated calls return the same bits.
+ * Limits: integer disparities and no occlusion reasoning (the view synthesis'); a defect at the same position with zero disparity in
+ * every view is consistent, hence invisible; one noise level for the whole field (no per-SAI noise model); one GPU; the defaults are
+ * one row of a sweep on one light field (profiles/consist_defaults.txt). */
+typedef struct {
+    unsigned max_disparity; /* D, 0..8, and                                                                            */
+    unsigned box_radius;    /* r, 0..7, and                                                                            */
+    unsigned ang_radius;    /* 1 or 2: the sweep's, as in lfbm5d_view_params                                           */
+    unsigned min_sources;   /* 2..24: an SAI with fewer sources is untested                                            */
+    unsigned max_rounds;    /* 1..64: bad-SAI decisions at most                                                        */
+    double k;               /* threshold = k x the channel's median |residual|; >= 0                                   */
+    double min_threshold;   /* floor of that threshold; >= 0                                                           */
+    double spread;          /* the residual must exceed spread x the sources' standard deviation; >= 0                 */
+    double sai_factor;      /* an SAI exceeds at sai_factor x the median SAI scale; 0 = no bad-SAI decision            */
+    double min_scale;       /* floor under that median; >= 0                                                           */
+} lfbm5d_consist_params;
+typedef struct {
+    double scale_channel[3];          /* median |residual| per stored channel over the tested SAIs (0: nothing finite)  */
+    double threshold[3];              /* the float32 thresholds that were applied                                       */
+    unsigned long long flagged[3][2]; /* per stored channel: values with code 1, with code 2                            */
+    unsigned long long pixels;        /* values of the tested SAIs                                                      */
+    unsigned long long skipped;       /* of those, not finite (code 2)                                                  */
+    unsigned bad;                     /* SAIs found bad                                                                 */
+    unsigned untested;                /* SAIs with fewer than min_sources sources                                       */
+    unsigned tested;
+    unsigned rounds;                  /* sweeps                                                                         */
+} lfbm5d_consist_result;
+/* Host only: D = 4, r = 3, ang_radius = 1 (the view synthesis'), min_sources = 3, max_rounds = 3, k = 8, min_threshold = 0, spread = 4,
+ * sai_factor = 1.5, min_scale = 0.5 (the row picked by the sweep in profiles/consist_defaults.txt, which rests on one light field). */
+void lfbm5d_consist_defaults(lfbm5d_consist_params* out);
+/* d_in is only read.  d_flags: uint8 [asize][C*H*W] in HBM, fully written for non-empty SAIs (0 for untested, bad and excluded ones),
+ * untouched for empty ones.  h_state [asize] (host): 0 empty, 1 tested, 2 bad, 3 untested, 4 excluded.  Optional (NULL): h_exclude;
+ * d_disp int8 [asize][H*W] in HBM, d* of the tested SAIs (other planes are not written); h_scale_sai [asize] (host), s_m of the tested
+ * SAIs and, for a bad one, the s_m it was judged by (0 otherwise); h_hist [asize][C][386] (host); out.  1 with a message: a NULL
+ * required buffer, C, W / H, ang_major, awidth / aheight, each parameter out of range, a mask without a non-empty SAI, a light field
+ * too large, a context with a communicator or shard. */
+int lfbm5d_consist_device(lfbm5d_ctx* ctx, const lfbm5d_consist_params* params, const float* d_in, const unsigned* h_mask,
+                          const unsigned* h_exclude, unsigned char* d_flags, unsigned* h_state, signed char* d_disp, double* h_scale_sai,
+                          unsigned long long* h_hist, unsigned ang_major, unsigned awidth, unsigned aheight, unsigned W, unsigned H,
+                          unsigned C, lfbm5d_consist_result* out);
+/* The same on host light fields, one pointer per SAI (NULL allowed for empty SAIs), staged through HBM with blocking copies:
+ * bit-identical to the device form.  h_flags: one uint8 plane set per non-empty SAI; h_disp or NULL: one int8 plane per non-empty SAI,
+ * written for tested ones. */
+int lfbm5d_consist_host_sai(lfbm5d_ctx* ctx, const lfbm5d_consist_params* params, const float* const* h_in, const unsigned* h_mask,
+                            const unsigned* h_exclude, unsigned char* const* h_flags, unsigned* h_state, signed char* const* h_disp,
+                            double* h_scale_sai, unsigned long long* h_hist, unsigned ang_major, unsigned awidth, unsigned aheight,
+                            unsigned W, unsigned H, unsigned C, lfbm5d_consist_result* out);
 
 /* ---- inspection of the last pass's block matching (parity tests) ----
  * n_refs reference patches in raster order; h_refs[n_refs] flat index i*Wb+j;

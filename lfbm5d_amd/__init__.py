@@ -13,7 +13,8 @@ from .core import (Context, Params, Bm3dParams, Stats, run_bm5d_1st_step, run_bm
                    SR_BICUBIC, SR_GAUSSIAN, SR_UP, SR_DOWN, PgModelStruct, PgEstimate, pg_model, pg_fit, pg_scale, pg_estimate,
                    denoise_pg, ImpulseParamsStruct, ImpulseResultStruct, ImpulseRepair, impulse_params, impulse_scale, impulse_repair,
                    InpaintParamsStruct, InpaintResultStruct, Inpaint, inpaint_params, inpaint,
-                   ViewParamsStruct, ViewResultStruct, ViewSynth, view_params, view_synth)
+                   ViewParamsStruct, ViewResultStruct, ViewSynth, view_params, view_synth,
+                   ConsistParamsStruct, ConsistResultStruct, Consist, consist_params, consist)
 
 __all__ = ["Context", "Params", "Bm3dParams", "Stats", "run_bm5d_1st_step", "run_bm5d_2nd_step", "run_bm3d_LF", "shard_rows",
            "YUV", "YCBCR", "OPP", "RGB", "ID", "DCT", "SADCT", "BIOR", "HADAMARD", "HAAR",
@@ -23,4 +24,5 @@ __all__ = ["Context", "Params", "Bm3dParams", "Stats", "run_bm5d_1st_step", "run
            "PgModelStruct", "PgEstimate", "pg_model", "pg_fit", "pg_scale", "pg_estimate", "denoise_pg",
            "ImpulseParamsStruct", "ImpulseResultStruct", "ImpulseRepair", "impulse_params", "impulse_scale", "impulse_repair",
            "InpaintParamsStruct", "InpaintResultStruct", "Inpaint", "inpaint_params", "inpaint",
-           "ViewParamsStruct", "ViewResultStruct", "ViewSynth", "view_params", "view_synth"]
+           "ViewParamsStruct", "ViewResultStruct", "ViewSynth", "view_params", "view_synth",
+           "ConsistParamsStruct", "ConsistResultStruct", "Consist", "consist_params", "consist"]

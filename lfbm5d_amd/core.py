@@ -127,6 +127,51 @@ class ViewResultStruct(C.Structure):
                 ("disparity_hist", C.c_ulonglong * 17)]
 
 
+class ConsistParamsStruct(C.Structure):
+    """lfbm5d_consist_params: the sweep, the two pixel tests and the bad-SAI decision of the consistency check (include/lfbm5d.h)."""
+    _fields_ = [("max_disparity", C.c_uint), ("box_radius", C.c_uint), ("ang_radius", C.c_uint), ("min_sources", C.c_uint),
+                ("max_rounds", C.c_uint), ("k", C.c_double), ("min_threshold", C.c_double), ("spread", C.c_double),
+                ("sai_factor", C.c_double), ("min_scale", C.c_double)]
+
+
+class ConsistResultStruct(C.Structure):
+    """lfbm5d_consist_result: scales, thresholds and counts of one consistency check (include/lfbm5d.h)."""
+    _fields_ = [("scale_channel", C.c_double * 3), ("threshold", C.c_double * 3), ("flagged", (C.c_ulonglong * 2) * 3),
+                ("pixels", C.c_ulonglong), ("skipped", C.c_ulonglong), ("bad", C.c_uint), ("untested", C.c_uint), ("tested", C.c_uint),
+                ("rounds", C.c_uint)]
+
+
+CONSIST_EMPTY, CONSIST_TESTED, CONSIST_BAD, CONSIST_UNTESTED, CONSIST_EXCLUDED = 0, 1, 2, 3, 4
+
+
+class Consist(NamedTuple):
+    """Result of Context.consist / consist: the flag planes (uint8 like the input: 0 sound, 1 inconsistent with the other views, 2 not
+    finite; a tensor or an array like the input), the state of every SAI (int64 [asize]: 0 empty, 1 tested, 2 bad, 3 untested,
+    4 excluded), the disparity planes (int8 [asize][H*W], written for tested SAIs; None unless asked for), the median |residual| per
+    stored channel and the float32 thresholds, s_m per SAI (float64 [asize]), the histograms (uint64 [asize][C][386]), the counts per
+    stored channel of code 1 and of code 2, the indices of the bad and of the untested SAIs, the sweeps, the values of the tested SAIs
+    and how many of them are not finite."""
+    flags: object
+    state: object
+    disparity: object
+    scale_channel: tuple
+    threshold: tuple
+    scale_sai: object
+    hist: object
+    flagged: tuple
+    nonfinite: tuple
+    bad: tuple
+    untested: tuple
+    rounds: int
+    pixels: int
+    skipped: int
+
+    @property
+    def missing(self):
+        """uint32 [asize], 1 on the bad SAIs: the `missing` argument of view_synth."""
+        return (np.asarray(self.state) == CONSIST_BAD).astype(np.uint32)
+
+
 class ViewSynth(NamedTuple):
     """Result of Context.view_fill / Context.view_synth / view_synth: the light field with the missing SAIs reconstructed (a tensor or
     an array like the input), the disparity planes (int8 [asize][H*W], written for the synthesised SAIs; None unless asked for), the
@@ -359,6 +404,13 @@ def lib():
         L.lfbm5d_view_fill_device.argtypes = [vp, wp, fp, up, up, fp, vp] + [C.c_uint] * 6 + [wr]
         L.lfbm5d_view_device.argtypes = [vp, wp, pp, fp, up, up, fp, vp] + [C.c_uint] * 7 + [wr]
         L.lfbm5d_view_host_sai.argtypes = [vp, wp, pp, vp, up, up, vp, vp] + [C.c_uint] * 7 + [wr]
+    if hasattr(L, "lfbm5d_consist_device"):   # (absent from older builds loaded through LFBM5D_HIP_LIB for A/B runs)
+        cp, cr = C.POINTER(ConsistParamsStruct), C.POINTER(ConsistResultStruct)
+        dp, ullp = C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)
+        L.lfbm5d_consist_defaults.argtypes = [cp]
+        L.lfbm5d_consist_defaults.restype = None
+        L.lfbm5d_consist_device.argtypes = [vp, cp, fp, up, up, vp, up, vp, dp, ullp] + [C.c_uint] * 6 + [cr]
+        L.lfbm5d_consist_host_sai.argtypes = [vp, cp, vp, up, up, vp, up, vp, dp, ullp] + [C.c_uint] * 6 + [cr]
     L.lfbm5d_malloc.argtypes = [C.POINTER(vp), C.c_size_t]
     L.lfbm5d_free.argtypes = [vp]
     L.lfbm5d_memcpy_h2d.argtypes = [vp, vp, C.c_size_t]
@@ -579,6 +631,21 @@ def view_params(max_disparity=None, box_radius=None, ang_radius=None, iterations
         if v is not None:
             setattr(P, name, int(v))
     for name, v in (("sigma_start", sigma_start), ("sigma_end", sigma_end), ("sigma_noise", sigma_noise)):
+        if v is not None:
+            setattr(P, name, float(v))
+    return P
+
+
+def consist_params(max_disparity=None, box_radius=None, ang_radius=None, min_sources=None, max_rounds=None, k=None, min_threshold=None,
+                   spread=None, sai_factor=None, min_scale=None):
+    """lfbm5d_consist_params from the defaults of the library (lfbm5d_consist_defaults, host only); None keeps a default."""
+    P = ConsistParamsStruct()
+    lib().lfbm5d_consist_defaults(C.byref(P))
+    for name, v in (("max_disparity", max_disparity), ("box_radius", box_radius), ("ang_radius", ang_radius), ("min_sources", min_sources),
+                    ("max_rounds", max_rounds)):
+        if v is not None:
+            setattr(P, name, int(v))
+    for name, v in (("k", k), ("min_threshold", min_threshold), ("spread", spread), ("sai_factor", sai_factor), ("min_scale", min_scale)):
         if v is not None:
             setattr(P, name, float(v))
     return P
@@ -1206,6 +1273,75 @@ class Context:
                                                 None if dp is None else _dev_ptr_i8(dp), *tail))
         return self._view_result(out, dp, res)
 
+    # ---- consistency check ----
+    def consist(self, noisy, mask, ang_major, awidth, aheight, width, height, chnls, exclude=None, return_disparity=False,
+                flags_out=None, disparity_out=None, fill_nonfinite=True, **params):
+        """Consistency check (lfbm5d_consist_*, include/lfbm5d.h): every usable SAI is predicted from its angular neighbours by the view
+        synthesis' plane sweep with the SAI itself left out; a value is flagged when its residual exceeds k x the light field's median
+        residual and spread x the sources' own disagreement, an SAI is bad when its median residual stands out among its neighbours'.
+        noisy: a CUDA float32 tensor [asize][C*H*W] (device form), or a float32 numpy array of that shape or a list of per-SAI arrays
+        (host form, staged through HBM; identical results).  The input is only read.  exclude: SAIs known bad (non-zero), neither
+        tested nor used.  params: the fields of consist_params.  fill_nonfinite: when the input holds a value that is not finite, the
+        check runs on a copy with those values filled (inpaint_fill under an empty map) and they are reported with code 2 on top of
+        the library's flags (the counts are the library's).  Returns a Consist, whose flags go to inpaint(...) as the map and whose
+        .missing goes to view_synth(...)."""
+        m = _u32(mask)
+        asize, C_, W_, H_ = m.size, int(chnls), int(width), int(height)
+        P = consist_params(**params)
+        res = ConsistResultStruct()
+        up = C.POINTER(C.c_uint)
+        ex = None if exclude is None else _u32(exclude)
+        state = np.zeros(asize, np.uint32)
+        ssai = np.zeros(asize, np.float64)
+        hist = np.zeros((asize, max(C_, 1), IMPULSE_KEYS), np.uint64)
+        head = (self._h, C.byref(P))
+        mid = (m.ctypes.data_as(up), None if ex is None else ex.ctypes.data_as(up))
+        tail = (ssai.ctypes.data_as(C.POINTER(C.c_double)), hist.ctypes.data_as(C.POINTER(C.c_ulonglong)), ang_major, awidth, aheight,
+                W_, H_, C_, C.byref(res))
+        if isinstance(noisy, (list, tuple, np.ndarray)):
+            arrays = self._host_sais(noisy)
+            live = [i for i in range(asize) if m[i] and arrays[i] is not None]
+            holes = {i: ~np.isfinite(arrays[i]) for i in live} if fill_nonfinite else {}
+            holes = {i: h for i, h in holes.items() if h.any()}
+            if holes:
+                import torch
+                full = np.zeros((asize, C_ * W_ * H_), np.float32)
+                for i in live:
+                    full[i] = np.asarray(arrays[i]).reshape(-1)
+                d = torch.from_numpy(full).cuda()
+                filled = self.inpaint_fill(d, torch.zeros(d.shape, dtype=torch.uint8, device=d.device), m, W_, H_, C_).out.cpu().numpy()
+                arrays = [np.ascontiguousarray(filled[i].reshape(np.shape(arrays[i]))) if i in holes else arrays[i] for i in range(asize)]
+            fo = [None if a is None else np.zeros(np.shape(a), np.uint8) for a in arrays] if flags_out is None else list(flags_out)
+            dp = None
+            if return_disparity or disparity_out is not None:
+                dp = [np.zeros(W_ * H_, np.int8) for _ in arrays] if disparity_out is None else list(disparity_out)
+            self._ck(self._L.lfbm5d_consist_host_sai(*head, _sai_ptrs(arrays, m), *mid, _sai_ptrs_u8(fo, m), state.ctypes.data_as(up),
+                                                     None if dp is None else _sai_ptrs_i8(dp, m), *tail))
+            for i, h in holes.items():
+                fo[i][h] = 2
+            if isinstance(noisy, np.ndarray):
+                fo = fo if isinstance(fo, np.ndarray) else np.stack(fo).reshape(noisy.shape)
+                dp = dp if dp is None or isinstance(dp, np.ndarray) else np.stack(dp)
+        else:
+            import torch
+            src, hole = noisy, None
+            live = torch.from_numpy(m != 0).to(noisy.device)
+            if fill_nonfinite and not bool(torch.isfinite(noisy[live]).all().item()):
+                hole = ~torch.isfinite(noisy)
+                hole[~live] = False
+                src = self.inpaint_fill(noisy, torch.zeros(noisy.shape, dtype=torch.uint8, device=noisy.device), m, W_, H_, C_).out
+            fo = flags_out if flags_out is not None else torch.zeros(noisy.shape, dtype=torch.uint8, device=noisy.device)
+            dp = self._view_disp(noisy, asize, W_, H_, disparity_out, return_disparity)
+            self._ck(self._L.lfbm5d_consist_device(*head, _dev_ptr(src), *mid, _dev_ptr_u8(fo), state.ctypes.data_as(up),
+                                                   None if dp is None else _dev_ptr_i8(dp), *tail))
+            if hole is not None:
+                fo[hole] = 2
+        st = state.astype(np.int64)
+        return Consist(fo, st, dp, tuple(res.scale_channel[:C_]), tuple(res.threshold[:C_]), ssai, hist[:, :C_],
+                       tuple(int(res.flagged[c][0]) for c in range(C_)), tuple(int(res.flagged[c][1]) for c in range(C_)),
+                       tuple(int(i) for i in np.nonzero(st == CONSIST_BAD)[0]), tuple(int(i) for i in np.nonzero(st == CONSIST_UNTESTED)[0]),
+                       int(res.rounds), int(res.pixels), int(res.skipped))
+
     # ---- super-resolution ----
     def _sr_tail(self, mask, w, h, Cc):
         m = _u32(mask)
@@ -1375,6 +1511,11 @@ def view_synth(noisy, mask, missing, P, ang_major, awidth, aheight, an, width, h
     return (ctx or _ctx()).view_synth(noisy, mask, missing, P, ang_major, awidth, aheight, an, width, height, chnls, **more)
 
 
+def consist(noisy, mask, ang_major, awidth, aheight, width, height, chnls, ctx=None, **more):
+    """Context.consist on the default context (device 0): defective values and bad SAIs found by cross-view consistency."""
+    return (ctx or _ctx()).consist(noisy, mask, ang_major, awidth, aheight, width, height, chnls, **more)
+
+
 def denoise_pg(model, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls, ctx=None):
     """Context.denoise_pg on the default context (device 0); returns the model that was used."""
     return (ctx or _ctx()).denoise_pg(model, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls)
@@ -1492,3 +1633,29 @@ def view_synth_probe(noisy, mask, missing, awidth, aheight, width, height, chnls
     if rc != 0:
         raise LfBm5dError("view_synth_LF failed (message on stdout)")
     return out, int(counts[0]), int(counts[1]), int(counts[2]), int(counts[3])
+
+
+def consist_probe(noisy, mask, awidth, aheight, width, height, chnls, exclude=None, max_disparity=-1, box_radius=-1, ang_radius=-1,
+                  min_sources=-1, max_rounds=-1, k=-1.0, spread=-1.0, sai_factor=-1.0, ang_major=ROWMAJOR):
+    """The C++ drop-in's consist_LF (liblfbm5d_dropin.so, run_bm5d.h) on a vector<vector<float>> light field built from `noisy`
+    [asize][chnls*height*width].  Returns (flags uint8 like noisy, state int64 [asize], flagged, nonfinite, bad, untested, rounds,
+    the three channel scales)."""
+    path = os.path.join(os.path.dirname(library_path()), "liblfbm5d_dropin.so")
+    if not os.path.exists(path):
+        raise LfBm5dError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
+    D = C.CDLL(path)
+    D.lfbm5d_consist_probe.argtypes = [C.c_void_p] * 5 + [C.c_uint] * 6 + [C.c_void_p] * 4
+    noisy = np.ascontiguousarray(noisy, np.float32)
+    m = _u32(mask)
+    ex = None if exclude is None else _u32(exclude)
+    flags = np.zeros(noisy.shape, np.uint8)
+    state = np.zeros(m.size, np.uint32)
+    cpi = np.array([max_disparity, box_radius, ang_radius, min_sources, max_rounds], np.int32)
+    cpd = np.array([k, spread, sai_factor], np.float64)
+    counts, scales = np.zeros(5, np.uint64), np.zeros(3, np.float64)
+    rc = D.lfbm5d_consist_probe(noisy.ctypes.data, m.ctypes.data, None if ex is None else ex.ctypes.data, flags.ctypes.data, state.ctypes.data,
+                                ang_major, awidth, aheight, width, height, chnls, cpi.ctypes.data, cpd.ctypes.data, counts.ctypes.data,
+                                scales.ctypes.data)
+    if rc != 0:
+        raise LfBm5dError("consist_LF failed (message on stdout)")
+    return (flags, state.astype(np.int64)) + tuple(int(v) for v in counts) + (tuple(scales),)

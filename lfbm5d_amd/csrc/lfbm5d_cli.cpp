@@ -48,6 +48,18 @@
  *                     LFBM5D_SIGMA=poisson, and in LFBM3Ddenoising (which has no 5-D parameters), only the synthesis runs, and the
  *                     command says so.  Prints `View synthesis: <n> of <A> SAIs missing, <m> left; disparities <dmin>..<dmax>, <K>
  *                     refinement steps`.  Combining it with LFBM5D_DEFECTS is an error.  Unset, the output is unchanged;
+ *   LFBM5D_DETECT=auto | <k>   consistency check (consist_LF, run_bm5d.h) of the noisy light field once it exists, loaded or synthesised,
+ *                     ahead of LFBM5D_IMPULSE and LFBM5D_SIGMA: every SAI is predicted from its angular neighbours; values that the other
+ *                     views contradict and SAIs whose residual stands out are found (auto = the library's threshold factor, <k> = that
+ *                     factor, finite, >= 0).  Prints `Consistency check: <b> of <A> SAIs bad [<s>_<t> ...], <n> of <N> values flagged
+ *                     (<pct> %), <u> SAIs untested; scales <s0> <s1> <s2>; <rounds> sweeps`.  The bad SAIs then go through the view
+ *                     synthesis exactly as if LFBM5D_MISSING named them (their files were read, their values are not used), the
+ *                     flagged values through the defect inpainting exactly as if LFBM5D_DEFECTS gave the map: the synthesis first, the
+ *                     fill second, each with its own loop (LFBM5D_MISSING_ITER, LFBM5D_DEFECTS_ITER) and report line.
+ *                     LFBM5D_DETECT_SAVE=<dir> writes the maps as PNGs in LFBM5D_DEFECTS' format and the bad SAIs as one line in
+ *                     LFBM5D_MISSING's format into <dir>/missing.txt (empty when none is bad), so that a camera's fixed map can be
+ *                     reused.  Together with LFBM5D_DEFECTS or LFBM5D_MISSING it is an error (there is no combined loop).  The files
+ *                     hold 8-bit values, so nothing here is non-finite.  Unset, the output is unchanged;
  *   LFBM5D_REPORT_SSIM=1  the average SSIM next to every average PSNR on stdout and an SSIM block behind every PSNR block of the
  *                     results file, computed on the GPU on the images as the files hold them (cli_quality.h); any other value is an
  *                     error; unset, the output is unchanged.
@@ -491,6 +503,79 @@ bool synthesise_missing_LF(vector<vector<float> >& LF_noisy, const vector<unsign
     return true;
 }
 
+/* LFBM5D_DETECT / LFBM5D_DETECT_SAVE: on = false when unset; k < 0 = the library's factor; false (message printed) on a malformed value,
+ * LFBM5D_DETECT_SAVE without LFBM5D_DETECT, or together with LFBM5D_DEFECTS / LFBM5D_MISSING */
+bool detect_mode(bool& on, double& k, const char*& save) {
+    on = false; k = -1.0;
+    save = env("LFBM5D_DETECT_SAVE");
+    const char* e = env("LFBM5D_DETECT");
+    if (!e) {
+        if (save) { cout << "LFBM5D_DETECT_SAVE needs LFBM5D_DETECT" << endl; return false; }
+        return true;
+    }
+    if (strcmp(e, "auto")) {
+        char* q = nullptr;
+        const double v = strtod(e, &q);
+        if (q == e || *q || isspace((unsigned char)*e) || !std::isfinite(v) || v < 0.0) {
+            cout << "LFBM5D_DETECT must be \"auto\" (consistency check with the library's threshold factor) or a factor k >= 0, or unset; got \""
+                 << e << "\"" << endl;
+            return false;
+        }
+        k = v;
+    }
+    if (save && !*save) { cout << "LFBM5D_DETECT_SAVE must name a directory for the detected maps, or be unset" << endl; return false; }
+    if (env("LFBM5D_DEFECTS")) { cout << "LFBM5D_DETECT cannot be combined with LFBM5D_DEFECTS (there is no combined loop of a given and a detected map): run them one after the other" << endl; return false; }
+    if (env("LFBM5D_MISSING")) { cout << "LFBM5D_DETECT cannot be combined with LFBM5D_MISSING (there is no combined loop of given and detected SAIs): run them one after the other" << endl; return false; }
+    on = true;
+    return true;
+}
+
+/* LFBM5D_DETECT: the check; `missing` receives the bad SAIs (left empty when there is none), `defects` the flag planes (left empty when
+ * nothing is flagged); LFBM5D_DETECT_SAVE: the maps and the list */
+bool detect_LF(const vector<vector<float> >& LF_noisy, const vector<unsigned>& mask, double k, const char* save, const char* name, const char* sep,
+               unsigned ang_major, unsigned aw, unsigned ah, unsigned s0, unsigned t0, unsigned W, unsigned H, unsigned C, vector<unsigned>& missing,
+               vector<vector<unsigned char> >& defects) {
+    vector<unsigned> state;
+    vector<vector<unsigned char> > flags;
+    unsigned long long flagged = 0, nonfinite = 0, all = 0; unsigned bad = 0, untested = 0, rounds = 0, sais = 0;
+    double sc[3] = {0.0, 0.0, 0.0};
+    if (consist_LF(LF_noisy, mask, vector<unsigned>(), ang_major, aw, ah, W, H, C, -1, -1, -1, -1, -1, k, -1.0, -1.0, flags, state, flagged, nonfinite, bad,
+                   untested, rounds, sc) != EXIT_SUCCESS) return false;
+    ostringstream list, line;
+    for (unsigned s = 0; s < ah; s++)
+        for (unsigned t = 0; t < aw; t++) {
+            const unsigned st = ang_major == LFBM5D_ROWMAJOR ? s * aw + t : s + t * ah;
+            if (!mask[st]) continue;
+            sais++; all += (unsigned long long)W * H * C;
+            if (state[st] != 2u) continue;
+            list << (list.tellp() > 0 ? " " : "") << s + s0 << "_" << t + t0;
+            line << (line.tellp() > 0 ? "," : "") << s + s0 << "_" << t + t0;
+        }
+    const unsigned long long n = flagged + nonfinite;
+    cout << endl << "Consistency check: " << bad << " of " << sais << " SAIs bad [" << list.str() << "], " << n << " of " << all << " values flagged ("
+         << 100.0 * (double)n / (double)all << " %), " << untested << " SAIs untested; scales " << sc[0] << " " << sc[1] << " " << sc[2] << "; " << rounds
+         << " sweeps" << endl;
+    if (save) {
+        const size_t plane = (size_t)W * H;
+        vector<float> img(plane * C);
+        for (unsigned s = 0; s < ah; s++)
+            for (unsigned t = 0; t < aw; t++) {
+                const unsigned st = ang_major == LFBM5D_ROWMAJOR ? s * aw + t : s + t * ah;
+                if (!mask[st]) continue;
+                for (size_t i = 0; i < plane * C; i++) img[i] = flags[st][i] ? 255.0f : 0.0f;
+                const string p = sai_path(save, name, sep, s + s0, t + t0);
+                if (!png_write_planar_f32(p, img.data(), W, H, C)) { cout << "error :: cannot write the detected map " << p << endl; return false; }
+            }
+        ofstream f(string(save) + "/missing.txt");
+        f << line.str() << endl;
+        if (!f) { cout << "error :: cannot write " << save << "/missing.txt" << endl; return false; }
+    }
+    missing.clear(); defects.clear();
+    if (bad) { missing.assign(mask.size(), 0u); for (size_t st = 0; st < mask.size(); st++) missing[st] = state[st] == 2u; }
+    if (n) defects.swap(flags);
+    return true;
+}
+
 /* LFBM5D_SIGMA=poisson: the model of the noisy light field */
 [[maybe_unused]] bool estimate_pg_LF(const vector<vector<float> >& LF_noisy, const vector<unsigned>& mask, unsigned W, unsigned H, unsigned C, double* pg) {
     return pg_estimate_LF(LF_noisy, mask, W, H, C, pg[0], pg[1]) == EXIT_SUCCESS;
@@ -577,6 +662,8 @@ int main(int argc, char** argv) {
     if (!defects_mode(def_dir, def_iter)) return EXIT_FAILURE;
     vector<unsigned> missing; int miss_iter = -1;
     if (!missing_mode(missing, miss_iter, ang_major, aw, ah, s0, t0)) return EXIT_FAILURE;
+    bool detect = false; double det_k = -1.0; const char* det_save = nullptr;
+    if (!detect_mode(detect, det_k, det_save)) return EXIT_FAILURE;
 
     vector<vector<float> > LF, LF_noisy, LF_basic, LF_den, LF_diff;
     vector<unsigned> mask;
@@ -600,6 +687,8 @@ int main(int argc, char** argv) {
         if (load_LF(d_noisy, name, sep, LF_noisy, mask, ang_major, aw, ah, s0, t0, W, H, C, missing.empty() ? nullptr : &missing) != EXIT_SUCCESS)
             return EXIT_FAILURE;
     }
+    vector<vector<unsigned char> > detected;
+    if (detect && !detect_LF(LF_noisy, mask, det_k, det_save, name, sep, ang_major, aw, ah, s0, t0, W, H, C, missing, detected)) return EXIT_FAILURE;
     vector<unsigned> est_mask = mask;   /* the sigma estimate does not look at reconstructed SAIs */
     if (!missing.empty()) {   /* the synthesis alone, for the same reason as the fill alone below */
         const unsigned hard[9] = {8, 8, 3, 8, 3, 0, LFBM5D_DCT, LFBM5D_SADCT, LFBM5D_HAAR};
@@ -607,10 +696,11 @@ int main(int argc, char** argv) {
         cout << "View synthesis: the synthesis alone (the refinement steps run in LFBM5Ddenoising)" << endl;
         for (size_t st = 0; st < missing.size(); st++) if (missing[st]) est_mask[st] = 0;
     }
-    if (def_dir) {   /* the fill alone: the refinement loop needs the 5-D step's parameters, which this command does not have */
+    if (def_dir || !detected.empty()) {   /* the fill alone: the refinement loop needs the 5-D step's parameters, which this command does not have */
         vector<vector<unsigned char> > defects;
         const unsigned hard[9] = {8, 8, 3, 8, 3, 0, LFBM5D_DCT, LFBM5D_SADCT, LFBM5D_HAAR};
-        if (!load_defects(def_dir, name, sep, defects, mask, ang_major, aw, ah, s0, t0, W, H, C)) return EXIT_FAILURE;
+        if (!def_dir) defects.swap(detected);
+        else if (!load_defects(def_dir, name, sep, defects, mask, ang_major, aw, ah, s0, t0, W, H, C)) return EXIT_FAILURE;
         if (!inpaint_defects_LF(LF_noisy, defects, mask, ang_major, aw, ah, 1, W, H, C, 0, 0, 0.0f, lambda, hard, (unsigned)cs, true)) return EXIT_FAILURE;
         cout << "Defect inpainting: the fill alone (the refinement steps run in LFBM5Ddenoising)" << endl;
     }
@@ -720,6 +810,8 @@ int main(int argc, char** argv) {
     if (!defects_mode(def_dir, def_iter)) return EXIT_FAILURE;
     vector<unsigned> missing; int miss_iter = -1;
     if (!missing_mode(missing, miss_iter, ang_major, aw, ah, s0, t0)) return EXIT_FAILURE;
+    bool detect = false; double det_k = -1.0; const char* det_save = nullptr;
+    if (!detect_mode(detect, det_k, det_save)) return EXIT_FAILURE;
 
     vector<vector<float> > LF, LF_noisy, LF_basic, LF_den, LF_diff;
     vector<unsigned> mask;
@@ -748,6 +840,8 @@ int main(int argc, char** argv) {
     unsigned def_steps = 0;
     vector<unsigned> est_mask = mask;   /* the sigma estimate does not look at reconstructed SAIs */
     unsigned view_steps = 0;
+    if (detect && !detect_LF(LF_noisy, mask, det_k, det_save, name, sep, ang_major, aw, ah, s0, t0, W, H, C, missing, defects)) return EXIT_FAILURE;
+    const bool have_defects = def_dir || !defects.empty();
     if (!missing.empty()) {
         lfbm5d_view_params vp;
         lfbm5d_view_defaults(&vp);
@@ -757,11 +851,11 @@ int main(int argc, char** argv) {
         if (smode >= 2) cout << "View synthesis: the synthesis alone (LFBM5D_SIGMA=poisson: the refinement steps assume one sigma)" << endl;
         for (size_t st = 0; st < missing.size(); st++) if (missing[st]) est_mask[st] = 0;
     }
-    if (def_dir) {
+    if (have_defects) {
         lfbm5d_inpaint_params ip;
         lfbm5d_inpaint_defaults(&ip);
         def_steps = smode >= 2 ? 0u : def_iter >= 0 ? (unsigned)def_iter : ip.iterations;
-        if (!load_defects(def_dir, name, sep, defects, mask, ang_major, aw, ah, s0, t0, W, H, C)) return EXIT_FAILURE;
+        if (def_dir && !load_defects(def_dir, name, sep, defects, mask, ang_major, aw, ah, s0, t0, W, H, C)) return EXIT_FAILURE;
         if (!inpaint_defects_LF(LF_noisy, defects, mask, ang_major, aw, ah, anH, W, H, C, 0, def_steps, 0.0f, lambda, def_hard, (unsigned)cs, true))
             return EXIT_FAILURE;
         if (smode >= 2) cout << "Defect inpainting: the fill alone (LFBM5D_SIGMA=poisson: the refinement steps assume one sigma)" << endl;

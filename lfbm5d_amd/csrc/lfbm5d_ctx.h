@@ -162,6 +162,9 @@ struct lfbm5d_ctx {
     /* view synthesis (lfbm5d_view.hip): the source lists, the disparity histogram, the loop's scratch input of the step, the host form's
      * disparity planes */
     struct ViewBufs { DevBuf table, stats, tmp, disp; } view;
+    /* consistency check (lfbm5d_consist.hip): the leave-one-out source lists, histograms and counters, the prediction light field, the
+     * sweep's disparity planes, the host form's flag and disparity planes */
+    struct ConsistBufs { DevBuf table, stats, pred, disp, flags; } consist;
     /* window lanes (run_graph; the per-SAI BM3D steps): extra contexts on the same device, each with its own stream, window
      * buffers and per-pass work buffers; owned by this context */
     std::vector<lfbm5d_ctx*> lanes;
@@ -227,6 +230,12 @@ int run_step(lfbm5d_ctx* c, int step, const lfbm5d_params* P, float* d_noisy, co
 int run_denoise(lfbm5d_ctx* c, const lfbm5d_params* P1, const lfbm5d_params* P2, float* d_noisy, const unsigned* h_mask, float* d_basic,
                 float* d_out, unsigned ang_major, unsigned awidth, unsigned aheight, unsigned an1, unsigned an2, unsigned W, unsigned H,
                 unsigned C, const HostIO* io = nullptr);
+
+/* lfbm5d_view.hip: k_view_sweep on the context's stream with a caller-built table (d_table: kViewTabStride ints per SAI to synthesise:
+ * its index, n, n x (source index, ds, dt); n_sai rows); d_cnt [17] is accumulated into.  Enqueues only. */
+constexpr int kViewTabStride = 2 + 3 * 24;
+int view_sweep_launch(lfbm5d_ctx* c, const int* d_table, unsigned n_sai, const float* d_in, float* d_out, signed char* d_disp, unsigned W,
+                      unsigned H, unsigned C, int D, int r, unsigned long long* d_cnt);
 
 } /* namespace lfbm5d_host */
 #endif

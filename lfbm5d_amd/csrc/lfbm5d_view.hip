@@ -294,6 +294,17 @@ int view(lfbm5d_ctx* c, const std::string& who, const lfbm5d_view_params* vp, co
 
 } /* namespace */
 
+/* lfbm5d_ctx.h: the sweep for another stage's table (the consistency check's leave-one-out lists) */
+int lfbm5d_host::view_sweep_launch(lfbm5d_ctx* c, const int* d_table, unsigned n_sai, const float* d_in, float* d_out, signed char* d_disp,
+                                   unsigned W, unsigned H, unsigned C, int D, int r, unsigned long long* d_cnt) {
+    static_assert(kViewTabStride == kTabStride, "lfbm5d_ctx.h");
+    const unsigned tx_n = (W + kTW - 1) / kTW, ty_n = (H + kTH - 1) / kTH;
+    hipLaunchKernelGGL(k_view_sweep, dim3(tx_n * ty_n, n_sai), dim3(kThreads), 0, c->stream, d_in, d_out, d_disp, d_table, (int)C, (int)W, (int)H,
+                       tx_n, D, r, d_cnt);
+    HIPCK(c, hipGetLastError());
+    return 0;
+}
+
 extern "C" {
 
 void lfbm5d_view_defaults(lfbm5d_view_params* out) {

@@ -587,6 +587,83 @@ extern "C" int lfbm5d_view_synth_probe(const float* in_flat, const unsigned* mas
     return 0;
 }
 
+/* consistency check on the caller's vectors (one pointer per SAI; the library stages in and out) */
+int consist_LF(const std::vector<std::vector<float> >& LF, const std::vector<unsigned>& LF_SAI_mask, const std::vector<unsigned>& exclude,
+               const unsigned ang_major, const unsigned awidth, const unsigned aheight, const unsigned width, const unsigned height,
+               const unsigned chnls, const int maxDisparity, const int boxRadius, const int angRadius, const int minSources, const int maxRounds,
+               const double k, const double spread, const double saiFactor, std::vector<std::vector<unsigned char> >& flags,
+               std::vector<unsigned>& state, unsigned long long& flagged, unsigned long long& nonfinite, unsigned& bad, unsigned& untested,
+               unsigned& rounds, double scales[3]) {
+    const unsigned asize = awidth * aheight;
+    lfbm5d_consist_result result;
+    std::memset(&result, 0, sizeof(result));
+    flagged = nonfinite = 0; bad = untested = rounds = 0;
+    scales[0] = scales[1] = scales[2] = 0.0;
+    if (LF.size() != asize || LF_SAI_mask.size() != asize || (!exclude.empty() && exclude.size() != asize)) {
+        std::cout << "consist_LF: light field, mask and exclude must hold awidth*aheight SAIs" << std::endl;
+        return EXIT_FAILURE;
+    }
+    lfbm5d_consist_params cp;
+    lfbm5d_consist_defaults(&cp);
+    if (maxDisparity >= 0) cp.max_disparity = (unsigned)maxDisparity;
+    if (boxRadius >= 0) cp.box_radius = (unsigned)boxRadius;
+    if (angRadius >= 0) cp.ang_radius = (unsigned)angRadius;
+    if (minSources >= 0) cp.min_sources = (unsigned)minSources;
+    if (maxRounds >= 0) cp.max_rounds = (unsigned)maxRounds;
+    if (k >= 0.0) cp.k = k;
+    if (spread >= 0.0) cp.spread = spread;
+    if (saiFactor >= 0.0) cp.sai_factor = saiFactor;
+    lfbm5d_ctx* ctx = context();
+    if (!ctx) return EXIT_FAILURE;
+    const size_t img = (size_t)width * height * chnls;
+    std::vector<const float*> p(asize, nullptr);
+    std::vector<unsigned char*> f(asize, nullptr);
+    flags.assign(asize, std::vector<unsigned char>());
+    state.assign(asize, 0u);
+    for (size_t st = 0; st < asize; st++)
+        if (LF_SAI_mask[st]) {
+            if (LF[st].size() != img) {
+                std::cout << "consist_LF: a non-empty SAI does not hold width*height*chnls values" << std::endl;
+                return EXIT_FAILURE;
+            }
+            flags[st].assign(img, 0);
+            p[st] = LF[st].data(); f[st] = flags[st].data();
+        }
+    if (lfbm5d_consist_host_sai(ctx, &cp, p.data(), LF_SAI_mask.data(), exclude.empty() ? nullptr : exclude.data(), f.data(), state.data(), nullptr,
+                                nullptr, nullptr, ang_major, awidth, aheight, width, height, chnls, &result) != 0) {
+        std::cout << "LFBM5D GPU backend: " << lfbm5d_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+    }
+    for (unsigned c = 0; c < 3; c++) { flagged += result.flagged[c][0]; nonfinite += result.flagged[c][1]; scales[c] = result.scale_channel[c]; }
+    bad = result.bad; untested = result.untested; rounds = result.rounds;
+    return EXIT_SUCCESS;
+}
+
+/* Test hook: consist_LF on a vector<vector<float>> light field built from a flat copy [asize][chnls*height*width]; the flags go to
+ * flags_flat (planes of empty SAIs untouched), the states to state_out.  cpi = {maxDisparity, boxRadius, angRadius, minSources, maxRounds},
+ * cpd = {k, spread, saiFactor}; exclude may be NULL;
+ * counts = {flagged, nonfinite, bad, untested, rounds}, scales [3]. */
+extern "C" int lfbm5d_consist_probe(const float* in_flat, const unsigned* mask, const unsigned* exclude, unsigned char* flags_flat,
+                                    unsigned* state_out, unsigned ang_major, unsigned awidth, unsigned aheight, unsigned width, unsigned height,
+                                    unsigned chnls, const int* cpi, const double* cpd, unsigned long long* counts, double* scales) {
+    const size_t asize = (size_t)awidth * aheight, img = (size_t)width * height * chnls;
+    std::vector<unsigned> m(mask, mask + asize), ex, state;
+    if (exclude) ex.assign(exclude, exclude + asize);
+    std::vector<std::vector<float> > LF(asize);
+    for (size_t st = 0; st < asize; st++) if (m[st]) LF[st].assign(in_flat + st * img, in_flat + (st + 1) * img);
+    std::vector<std::vector<unsigned char> > fl;
+    unsigned long long flagged = 0, nonfinite = 0; unsigned bad = 0, untested = 0, rounds = 0; double sc[3];
+    if (consist_LF(LF, m, ex, ang_major, awidth, aheight, width, height, chnls, cpi[0], cpi[1], cpi[2], cpi[3], cpi[4], cpd[0], cpd[1], cpd[2], fl,
+                   state, flagged, nonfinite, bad, untested, rounds, sc) != EXIT_SUCCESS) return 1;
+    for (size_t st = 0; st < asize; st++) {
+        state_out[st] = state[st];
+        if (m[st]) std::memcpy(flags_flat + st * img, fl[st].data(), img);
+    }
+    if (counts) { counts[0] = flagged; counts[1] = nonfinite; counts[2] = bad; counts[3] = untested; counts[4] = rounds; }
+    if (scales) { scales[0] = sc[0]; scales[1] = sc[1]; scales[2] = sc[2]; }
+    return 0;
+}
+
 /* run_bm3d_LF (src/bm3d_LF.h:10-35, bm3d_LF.cpp:75-125): BM3D on every SAI of the mask */
 #include "run_bm3d_lf.h"
 int run_bm3d_LF(const float sigma, std::vector<std::vector<float> >& LF_noisy, std::vector<unsigned>& LF_SAI_mask,

@@ -297,6 +297,44 @@ int view_synth_LF(
 ,   int &dmax
 );
 
+//! Consistency check -- not in the reference: every usable SAI is predicted on the GPU from its angular neighbours by the view synthesis'
+//! plane sweep with the SAI itself left out; a value is flagged (1) when its residual exceeds k times the light field's median residual
+//! and `spread` times the sources' own disagreement, or (2) when it is not finite; an SAI is bad when its median residual stands out
+//! among its neighbours' (lfbm5d_consist_host_sai, include/lfbm5d.h).  LF is only read.  `exclude` (empty, or one entry per SAI,
+//! non-zero = known bad) is neither tested nor used.  maxDisparity, boxRadius, angRadius, minSources, maxRounds < 0 and k, spread,
+//! saiFactor < 0: the library's defaults (lfbm5d_consist_defaults); saiFactor = 0: no bad-SAI decision.  `flags` is resized to one
+//! plane of width*height*chnls codes per non-empty SAI (the map of inpaint_LF), `state` to one entry per SAI (0 empty, 1 tested, 2 bad,
+//! 3 untested, 4 excluded; the bad ones are the `missing` of view_synth_LF); `flagged` and `nonfinite` count the values with code 1 and
+//! code 2 over all channels, `scales` receives the median residual of the three stored channels, `rounds` the sweeps.  Returns
+//! EXIT_SUCCESS, or EXIT_FAILURE with the message on stdout.
+int consist_LF(
+    const std::vector<std::vector<float> > &LF
+,   const std::vector<unsigned> &LF_SAI_mask
+,   const std::vector<unsigned> &exclude
+,   const unsigned ang_major
+,   const unsigned awidth
+,   const unsigned aheight
+,   const unsigned width
+,   const unsigned height
+,   const unsigned chnls
+,   const int      maxDisparity
+,   const int      boxRadius
+,   const int      angRadius
+,   const int      minSources
+,   const int      maxRounds
+,   const double   k
+,   const double   spread
+,   const double   saiFactor
+,   std::vector<std::vector<unsigned char> > &flags
+,   std::vector<unsigned> &state
+,   unsigned long long &flagged
+,   unsigned long long &nonfinite
+,   unsigned &bad
+,   unsigned &untested
+,   unsigned &rounds
+,   double scales[3]
+);
+
 //! Super-resolution -- not in the reference's master branch: the scheme of SR-LFBM5D (iterative back-projection regularised by the
 //! hard-thresholding step above) with the operators of include/lfbm5d.h, on the GPU (lfbm5d_superres_host_sai).  LF_low holds
 //! width x height SAIs and is only read; LF_high is (re)sized to scale*width x scale*height SAIs and filled.  kernel: 0 = bicubic,

@@ -168,3 +168,22 @@ def add_defects(shape, seed=1):
         ci, cj = rng.integers(8, n - 8, 2)
         fl[st, 0][(yy - ci) ** 2 + (xx - cj) ** 2 <= 16] = True
     return np.ascontiguousarray(np.broadcast_to(fl, (A, C, n, n)))
+
+
+def degrade_sai(lf, st, kind, seed=1):
+    """A copy of the light field `lf` ([A][...], nominally 0..255) with the sub-aperture image `st` made bad, from numpy's
+    default_rng(seed): "dim": every value times 0.5 (a vignetted or under-exposed view); "noise": every value replaced by a uniform value
+    of [0, 255) (a corrupt file, a failed camera); "shift": the view rolled by 7 rows and 5 columns in its last two axes (a view filed
+    under the wrong angular position).  lf is [A][C][H][W]; "dim" and "noise" also take [A][C*H*W].  Returns float32."""
+    out = np.array(lf, dtype=np.float32, copy=True)
+    if kind == "dim":
+        out[st] = out[st] * np.float32(0.5)
+    elif kind == "noise":
+        out[st] = (np.random.default_rng(seed).random(out[st].shape) * 255.0).astype(np.float32)
+    elif kind == "shift":
+        if out[st].ndim < 2:
+            raise ValueError('degrade_sai: "shift" needs the light field as [A][C][H][W]')
+        out[st] = np.roll(out[st], (7, 5), axis=(-2, -1))
+    else:
+        raise ValueError('degrade_sai: kind must be "dim", "noise" or "shift"')
+    return out
