@@ -703,68 +703,37 @@ def _u32(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.uint32))
 
 
-def _dev_ptr(t):
-    """Raw device pointer of a CUDA tensor.  The library launches on the context's own stream and knows nothing
-    about torch's: work torch has queued on the tensor's device (a zero-fill, a copy) must have finished before the
-    library reads the buffer, so the current torch stream is drained here (include/lfbm5d.h: "buffers are ready on
-    entry, results complete on return")."""
+# what a plane's element type is called in the two messages below: float32 values, uint8 flags, int8 disparities
+_PLANES = {np.float32: ("device entry points need contiguous float32 CUDA tensors",
+                        "per-SAI host buffers must be contiguous float32 numpy arrays"),
+           np.uint8: ("flag planes on the device must be contiguous uint8 CUDA tensors",
+                      "per-SAI host flag planes must be contiguous uint8 numpy arrays"),
+           np.int8: ("disparity planes on the device must be contiguous int8 CUDA tensors",
+                     "per-SAI host disparity planes must be contiguous int8 numpy arrays")}
+
+
+def _dev_ptr(t, dtype=np.float32):
+    """Raw device pointer of a contiguous CUDA tensor of `dtype` (np.float32: values, np.uint8: flag planes, np.int8: disparity
+    planes).  The library launches on the context's own stream and knows nothing about torch's: work torch has queued on the tensor's
+    device (a zero-fill, a copy) must have finished before the library reads the buffer, so the current torch stream is drained here
+    (include/lfbm5d.h: "buffers are ready on entry, results complete on return")."""
     import torch
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-        raise LfBm5dError("device entry points need contiguous float32 CUDA tensors")
+    dtype = np.dtype(dtype).type
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == getattr(torch, np.dtype(dtype).name) and t.is_contiguous()):
+        raise LfBm5dError(_PLANES[dtype][0])
     torch.cuda.current_stream(t.device).synchronize()
     return C.c_void_p(t.data_ptr())
 
 
-def _dev_ptr_u8(t):
-    """Raw device pointer of a contiguous uint8 CUDA tensor (flag planes); see _dev_ptr."""
-    import torch
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
-        raise LfBm5dError("flag planes on the device must be contiguous uint8 CUDA tensors")
-    torch.cuda.current_stream(t.device).synchronize()
-    return C.c_void_p(t.data_ptr())
-
-
-def _dev_ptr_i8(t):
-    """Raw device pointer of a contiguous int8 CUDA tensor (disparity planes); see _dev_ptr."""
-    import torch
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int8 and t.is_contiguous()):
-        raise LfBm5dError("disparity planes on the device must be contiguous int8 CUDA tensors")
-    torch.cuda.current_stream(t.device).synchronize()
-    return C.c_void_p(t.data_ptr())
-
-
-def _sai_ptrs_i8(arrays, mask):
-    """signed char*[asize] over a list of per-SAI int8 arrays."""
+def _sai_ptrs(arrays, mask, dtype=np.float32):
+    """dtype*[asize] over a list of per-SAI arrays of `dtype` (entries of empty SAIs may be None)."""
+    dtype = np.dtype(dtype).type
     out = (C.c_void_p * len(arrays))()
     for i, a in enumerate(arrays):
         if a is None or not mask[i]:
             continue
-        if not (isinstance(a, np.ndarray) and a.dtype == np.int8 and a.flags.c_contiguous):
-            raise LfBm5dError("per-SAI host disparity planes must be contiguous int8 numpy arrays")
-        out[i] = a.ctypes.data
-    return out
-
-
-def _sai_ptrs_u8(arrays, mask):
-    """unsigned char*[asize] over a list of per-SAI uint8 arrays."""
-    out = (C.c_void_p * len(arrays))()
-    for i, a in enumerate(arrays):
-        if a is None or not mask[i]:
-            continue
-        if not (isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.flags.c_contiguous):
-            raise LfBm5dError("per-SAI host flag planes must be contiguous uint8 numpy arrays")
-        out[i] = a.ctypes.data
-    return out
-
-
-def _sai_ptrs(arrays, mask):
-    """float*[asize] over a list of per-SAI float32 arrays (entries of empty SAIs may be None)."""
-    out = (C.c_void_p * len(arrays))()
-    for i, a in enumerate(arrays):
-        if a is None or not mask[i]:
-            continue
-        if not (isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.c_contiguous):
-            raise LfBm5dError("per-SAI host buffers must be contiguous float32 numpy arrays")
+        if not (isinstance(a, np.ndarray) and a.dtype == dtype and a.flags.c_contiguous):
+            raise LfBm5dError(_PLANES[dtype][1])
         out[i] = a.ctypes.data
     return out
 
@@ -1008,6 +977,47 @@ class Context:
             raise LfBm5dError("host light fields must be float32")
         return list(LF) if isinstance(LF, (list, tuple)) else [np.ascontiguousarray(a) for a in LF]
 
+    # ---- what impulse_repair, inpaint, view_synth and consist share: results to write into, host form or device form ----
+    def _host_out(self, arrays, out, m=None, img=0):
+        """(out, its per-SAI list): a missing `out` is a copy of the input (img: zeros of that size for a non-empty SAI without one)."""
+        if out is None:
+            out = [(np.zeros(img, np.float32) if img and m[i] else None) if a is None else np.array(a, np.float32, copy=True)
+                   for i, a in enumerate(arrays)]
+        return out, self._host_sais(out)
+
+    @staticmethod
+    def _host_planes(arrays, given, wanted, dtype, n=None):
+        """Optional per-SAI output planes of the host form (flags, disparities): `given`, fresh zeros when only `wanted`, else None.
+        n: values per plane (default: shaped like the SAI's array, None where there is none)."""
+        if given is not None:
+            return list(given)
+        if not wanted:
+            return None
+        return [np.zeros(n, dtype) if n is not None else None if a is None else np.zeros(np.shape(a), dtype) for a in arrays]
+
+    @staticmethod
+    def _stacked(noisy, x, like_input=True):
+        """A per-SAI list back in the form of a numpy input: one array (like_input: of the input's shape); anything else as it is."""
+        if not isinstance(noisy, np.ndarray) or x is None or isinstance(x, np.ndarray):
+            return x
+        return np.stack(x).reshape(noisy.shape) if like_input else np.stack(x)
+
+    @staticmethod
+    def _dev_out(noisy, out, m=None):
+        """A missing `out` of the device form: a copy of the input (m: uninitialised when no SAI is empty, every plane is written)."""
+        import torch
+        if out is not None:
+            return out
+        return torch.empty_like(noisy) if m is not None and m.all() else noisy.clone()
+
+    @staticmethod
+    def _dev_planes(noisy, given, wanted, shape, dtype):
+        """Optional output planes of the device form (uint8 flags, int8 disparities): `given`, fresh zeros when only `wanted`, else None."""
+        import torch
+        if given is None and wanted:
+            return torch.zeros(shape, dtype=dtype, device=noisy.device)
+        return given
+
     def pg_histogram(self, LF, LF_SAI_mask, width, height, chnls):
         """The block statistics of lfbm5d_pg_histogram_device on a CUDA float32 tensor [asize][C*H*W]: (hist uint64 [C][64][322],
         sum_m uint64 [C][64], blocks, skipped)."""
@@ -1103,32 +1113,23 @@ class Context:
         tail = (asize, int(width), int(height), C_, C.byref(res), cs.ctypes.data_as(C.POINTER(C.c_ulonglong)))
         if isinstance(noisy, (list, tuple, np.ndarray)):
             arrays = self._host_sais(noisy)
-            if out is None:
-                out = [None if a is None else np.array(a, np.float32, copy=True) for a in arrays]
-            outs = self._host_sais(out)
+            out, outs = self._host_out(arrays, out)
             fin = None
             if flags is not None:
                 fin = [None if a is None else np.ascontiguousarray(a, np.uint8) for a in flags]
-            fo = None
-            if return_flags or flags_out is not None:
-                fo = [None if a is None else np.zeros(a.shape, np.uint8) for a in arrays] if flags_out is None else list(flags_out)
-            self._ck(self._L.lfbm5d_impulse_repair_host_sai(self._h, C.byref(P), _sai_ptrs(arrays, m), None if fin is None else _sai_ptrs_u8(fin, m),
-                                                            mp, _sai_ptrs(outs, m), None if fo is None else _sai_ptrs_u8(fo, m), *tail))
-            if isinstance(noisy, np.ndarray):
-                out = out if isinstance(out, np.ndarray) else np.stack(outs).reshape(noisy.shape)
-                fo = fo if fo is None or isinstance(fo, np.ndarray) else np.stack(fo).reshape(noisy.shape)
+            fo = self._host_planes(arrays, flags_out, return_flags, np.uint8)
+            self._ck(self._L.lfbm5d_impulse_repair_host_sai(self._h, C.byref(P), _sai_ptrs(arrays, m), None if fin is None else _sai_ptrs(fin, m, np.uint8),
+                                                            mp, _sai_ptrs(outs, m), None if fo is None else _sai_ptrs(fo, m, np.uint8), *tail))
+            out, fo = self._stacked(noisy, out), self._stacked(noisy, fo)
         else:
             import torch
-            if out is None:
-                out = noisy.clone() if not m.all() else torch.empty_like(noisy)
-            fo = flags_out
-            if fo is None and return_flags:
-                fo = torch.zeros(noisy.shape, dtype=torch.uint8, device=noisy.device)
-            fop = None if fo is None else _dev_ptr_u8(fo)
+            out = self._dev_out(noisy, out, m)
+            fo = self._dev_planes(noisy, flags_out, return_flags, noisy.shape, torch.uint8)
+            fop = None if fo is None else _dev_ptr(fo, np.uint8)
             if flags is None:
                 self._ck(self._L.lfbm5d_impulse_repair_device(self._h, C.byref(P), _dev_ptr(noisy), mp, _dev_ptr(out), fop, *tail))
             else:
-                self._ck(self._L.lfbm5d_impulse_repair_flags_device(self._h, _dev_ptr(noisy), _dev_ptr_u8(flags), mp, _dev_ptr(out), fop, *tail))
+                self._ck(self._L.lfbm5d_impulse_repair_flags_device(self._h, _dev_ptr(noisy), _dev_ptr(flags, np.uint8), mp, _dev_ptr(out), fop, *tail))
         return ImpulseRepair(out, fo, res.scale, tuple(res.scale_channel[:C_]), tuple(res.threshold[:C_]), tuple(res.flagged[:C_]),
                              tuple(res.repaired[:C_]), tuple(res.left[:C_]), int(res.pixels), int(res.skipped),
                              cs[:asize, :C_].astype(np.int64))
@@ -1147,20 +1148,17 @@ class Context:
         m = _u32(mask)
         C_ = int(chnls)
         res = InpaintResultStruct()
-        if out is None:
-            out = noisy.clone() if not m.all() else torch.empty_like(noisy)
-        fo = flags_out
-        if fo is None and return_flags:
-            fo = torch.zeros(noisy.shape, dtype=torch.uint8, device=noisy.device)
-        self._ck(self._L.lfbm5d_inpaint_fill_device(self._h, _dev_ptr(noisy), _dev_ptr_u8(flags), m.ctypes.data_as(C.POINTER(C.c_uint)),
-                                                    _dev_ptr(out), None if fo is None else _dev_ptr_u8(fo), m.size, int(width), int(height),
+        out = self._dev_out(noisy, out, m)
+        fo = self._dev_planes(noisy, flags_out, return_flags, noisy.shape, torch.uint8)
+        self._ck(self._L.lfbm5d_inpaint_fill_device(self._h, _dev_ptr(noisy), _dev_ptr(flags, np.uint8), m.ctypes.data_as(C.POINTER(C.c_uint)),
+                                                    _dev_ptr(out), None if fo is None else _dev_ptr(fo, np.uint8), m.size, int(width), int(height),
                                                     C_, C.byref(res)))
         return self._inpaint_result(out, fo, res, C_)
 
     def inpaint_project(self, flags, x, y, mask, out, width, height, chnls):
         """out = flags ? x : y on the non-empty SAIs (lfbm5d_inpaint_project_device); CUDA tensors, out may be x or y."""
         m = _u32(mask)
-        self._ck(self._L.lfbm5d_inpaint_project_device(self._h, _dev_ptr_u8(flags), _dev_ptr(x), _dev_ptr(y),
+        self._ck(self._L.lfbm5d_inpaint_project_device(self._h, _dev_ptr(flags, np.uint8), _dev_ptr(x), _dev_ptr(y),
                                                        m.ctypes.data_as(C.POINTER(C.c_uint)), _dev_ptr(out), m.size, int(width), int(height),
                                                        int(chnls)))
 
@@ -1180,40 +1178,24 @@ class Context:
         tail = (ang_major, awidth, aheight, an, int(width), int(height), C_, C.byref(res))
         if isinstance(noisy, (list, tuple, np.ndarray)):
             arrays = self._host_sais(noisy)
-            if out is None:
-                out = [None if a is None else np.array(a, np.float32, copy=True) for a in arrays]
-            outs = self._host_sais(out)
+            out, outs = self._host_out(arrays, out)
             fin = [None if a is None else np.ascontiguousarray(a, np.uint8) for a in flags]
-            fo = None
-            if return_flags or flags_out is not None:
-                fo = [None if a is None else np.zeros(a.shape, np.uint8) for a in arrays] if flags_out is None else list(flags_out)
-            self._ck(self._L.lfbm5d_inpaint_host_sai(self._h, C.byref(ip), C.byref(P), _sai_ptrs(arrays, m), _sai_ptrs_u8(fin, m), mp,
-                                                     _sai_ptrs(outs, m), None if fo is None else _sai_ptrs_u8(fo, m), *tail))
-            if isinstance(noisy, np.ndarray):
-                out = out if isinstance(out, np.ndarray) else np.stack(outs).reshape(noisy.shape)
-                fo = fo if fo is None or isinstance(fo, np.ndarray) else np.stack(fo).reshape(noisy.shape)
+            fo = self._host_planes(arrays, flags_out, return_flags, np.uint8)
+            self._ck(self._L.lfbm5d_inpaint_host_sai(self._h, C.byref(ip), C.byref(P), _sai_ptrs(arrays, m), _sai_ptrs(fin, m, np.uint8), mp,
+                                                     _sai_ptrs(outs, m), None if fo is None else _sai_ptrs(fo, m, np.uint8), *tail))
+            out, fo = self._stacked(noisy, out), self._stacked(noisy, fo)
         else:
             import torch
-            if out is None:
-                out = noisy.clone() if not m.all() else torch.empty_like(noisy)
-            fo = flags_out
-            if fo is None and return_flags:
-                fo = torch.zeros(noisy.shape, dtype=torch.uint8, device=noisy.device)
-            self._ck(self._L.lfbm5d_inpaint_device(self._h, C.byref(ip), C.byref(P), _dev_ptr(noisy), _dev_ptr_u8(flags), mp, _dev_ptr(out),
-                                                   None if fo is None else _dev_ptr_u8(fo), *tail))
+            out = self._dev_out(noisy, out, m)
+            fo = self._dev_planes(noisy, flags_out, return_flags, noisy.shape, torch.uint8)
+            self._ck(self._L.lfbm5d_inpaint_device(self._h, C.byref(ip), C.byref(P), _dev_ptr(noisy), _dev_ptr(flags, np.uint8), mp, _dev_ptr(out),
+                                                   None if fo is None else _dev_ptr(fo, np.uint8), *tail))
         return self._inpaint_result(out, fo, res, C_)
 
     # ---- view synthesis ----
     @staticmethod
     def _view_result(out, disp, res):
         return ViewSynth(out, disp, int(res.missing), int(res.synthesised), int(res.left), int(res.pixels), tuple(res.disparity_hist))
-
-    @staticmethod
-    def _view_disp(noisy, asize, width, height, disparity_out, return_disparity):
-        import torch
-        if disparity_out is None and return_disparity:
-            return torch.zeros((asize, int(width) * int(height)), dtype=torch.int8, device=noisy.device)
-        return disparity_out
 
     def view_fill(self, noisy, mask, missing, ang_major, awidth, aheight, width, height, chnls, max_disparity=None, box_radius=None,
                   ang_radius=None, return_disparity=False, out=None, disparity_out=None):
@@ -1224,12 +1206,12 @@ class Context:
         m, ms = _u32(mask), _u32(missing)
         vp = view_params(max_disparity, box_radius, ang_radius)
         res = ViewResultStruct()
-        if out is None:
-            out = noisy.clone()
-        dp = self._view_disp(noisy, m.size, width, height, disparity_out, return_disparity)
+        import torch
+        out = self._dev_out(noisy, out)
+        dp = self._dev_planes(noisy, disparity_out, return_disparity, (m.size, int(width) * int(height)), torch.int8)
         up = C.POINTER(C.c_uint)
         self._ck(self._L.lfbm5d_view_fill_device(self._h, C.byref(vp), _dev_ptr(noisy), m.ctypes.data_as(up), ms.ctypes.data_as(up),
-                                                 _dev_ptr(out), None if dp is None else _dev_ptr_i8(dp), ang_major, awidth, aheight,
+                                                 _dev_ptr(out), None if dp is None else _dev_ptr(dp, np.int8), ang_major, awidth, aheight,
                                                  int(width), int(height), int(chnls), C.byref(res)))
         return self._view_result(out, dp, res)
 
@@ -1252,25 +1234,17 @@ class Context:
         tail = (ang_major, awidth, aheight, an, int(width), int(height), int(chnls), C.byref(res))
         if isinstance(noisy, (list, tuple, np.ndarray)):
             arrays = self._host_sais(noisy)
-            img = int(chnls) * int(width) * int(height)
-            if out is None:
-                out = [(np.zeros(img, np.float32) if m[i] else None) if a is None else np.array(a, np.float32, copy=True)
-                       for i, a in enumerate(arrays)]
-            outs = self._host_sais(out)
-            dp = None
-            if return_disparity or disparity_out is not None:
-                dp = [np.zeros(int(width) * int(height), np.int8) for _ in arrays] if disparity_out is None else list(disparity_out)
+            out, outs = self._host_out(arrays, out, m, int(chnls) * int(width) * int(height))
+            dp = self._host_planes(arrays, disparity_out, return_disparity, np.int8, int(width) * int(height))
             self._ck(self._L.lfbm5d_view_host_sai(self._h, C.byref(vp), C.byref(P), _sai_ptrs(arrays, m), mp, msp, _sai_ptrs(outs, m),
-                                                  None if dp is None else _sai_ptrs_i8(dp, m), *tail))
-            if isinstance(noisy, np.ndarray):
-                out = out if isinstance(out, np.ndarray) else np.stack(outs).reshape(noisy.shape)
-                dp = dp if dp is None or isinstance(dp, np.ndarray) else np.stack(dp)
+                                                  None if dp is None else _sai_ptrs(dp, m, np.int8), *tail))
+            out, dp = self._stacked(noisy, out), self._stacked(noisy, dp, False)
         else:
-            if out is None:
-                out = noisy.clone()
-            dp = self._view_disp(noisy, asize, width, height, disparity_out, return_disparity)
+            import torch
+            out = self._dev_out(noisy, out)
+            dp = self._dev_planes(noisy, disparity_out, return_disparity, (asize, int(width) * int(height)), torch.int8)
             self._ck(self._L.lfbm5d_view_device(self._h, C.byref(vp), C.byref(P), _dev_ptr(noisy), mp, msp, _dev_ptr(out),
-                                                None if dp is None else _dev_ptr_i8(dp), *tail))
+                                                None if dp is None else _dev_ptr(dp, np.int8), *tail))
         return self._view_result(out, dp, res)
 
     # ---- consistency check ----
@@ -1311,17 +1285,13 @@ class Context:
                 d = torch.from_numpy(full).cuda()
                 filled = self.inpaint_fill(d, torch.zeros(d.shape, dtype=torch.uint8, device=d.device), m, W_, H_, C_).out.cpu().numpy()
                 arrays = [np.ascontiguousarray(filled[i].reshape(np.shape(arrays[i]))) if i in holes else arrays[i] for i in range(asize)]
-            fo = [None if a is None else np.zeros(np.shape(a), np.uint8) for a in arrays] if flags_out is None else list(flags_out)
-            dp = None
-            if return_disparity or disparity_out is not None:
-                dp = [np.zeros(W_ * H_, np.int8) for _ in arrays] if disparity_out is None else list(disparity_out)
-            self._ck(self._L.lfbm5d_consist_host_sai(*head, _sai_ptrs(arrays, m), *mid, _sai_ptrs_u8(fo, m), state.ctypes.data_as(up),
-                                                     None if dp is None else _sai_ptrs_i8(dp, m), *tail))
+            fo = self._host_planes(arrays, flags_out, True, np.uint8)
+            dp = self._host_planes(arrays, disparity_out, return_disparity, np.int8, W_ * H_)
+            self._ck(self._L.lfbm5d_consist_host_sai(*head, _sai_ptrs(arrays, m), *mid, _sai_ptrs(fo, m, np.uint8), state.ctypes.data_as(up),
+                                                     None if dp is None else _sai_ptrs(dp, m, np.int8), *tail))
             for i, h in holes.items():
                 fo[i][h] = 2
-            if isinstance(noisy, np.ndarray):
-                fo = fo if isinstance(fo, np.ndarray) else np.stack(fo).reshape(noisy.shape)
-                dp = dp if dp is None or isinstance(dp, np.ndarray) else np.stack(dp)
+            fo, dp = self._stacked(noisy, fo), self._stacked(noisy, dp, False)
         else:
             import torch
             src, hole = noisy, None
@@ -1330,10 +1300,10 @@ class Context:
                 hole = ~torch.isfinite(noisy)
                 hole[~live] = False
                 src = self.inpaint_fill(noisy, torch.zeros(noisy.shape, dtype=torch.uint8, device=noisy.device), m, W_, H_, C_).out
-            fo = flags_out if flags_out is not None else torch.zeros(noisy.shape, dtype=torch.uint8, device=noisy.device)
-            dp = self._view_disp(noisy, asize, W_, H_, disparity_out, return_disparity)
-            self._ck(self._L.lfbm5d_consist_device(*head, _dev_ptr(src), *mid, _dev_ptr_u8(fo), state.ctypes.data_as(up),
-                                                   None if dp is None else _dev_ptr_i8(dp), *tail))
+            fo = self._dev_planes(noisy, flags_out, True, noisy.shape, torch.uint8)
+            dp = self._dev_planes(noisy, disparity_out, return_disparity, (asize, W_ * H_), torch.int8)
+            self._ck(self._L.lfbm5d_consist_device(*head, _dev_ptr(src), *mid, _dev_ptr(fo, np.uint8), state.ctypes.data_as(up),
+                                                   None if dp is None else _dev_ptr(dp, np.int8), *tail))
             if hole is not None:
                 fo[hole] = 2
         st = state.astype(np.int64)

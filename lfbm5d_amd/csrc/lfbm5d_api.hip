@@ -73,13 +73,14 @@ void lfbm5d_destroy(lfbm5d_ctx* c) {
                       &c->t_noisy, &c->t_basic, &c->t_tnum, &c->t_tden, &c->und_num, &c->und_den, &c->sub_flags, &c->sub_cnt, &c->shape, &c->filt, &c->wgt, &c->aggpos, &c->gpos, &c->gofs, &c->gok, &c->sa_list, &c->gshape, &c->band_noisy, &c->band_basic, &c->band_out, &c->band_src, &c->band_pack, &c->band_gather, &c->counters, &c->small, &c->t_num, &c->t_den, &c->d_mask, &c->g_num, &c->g_den, &c->w_noisy,
                       &c->w_basic, &c->w_num, &c->w_den, &c->h2d_noisy, &c->h2d_basic, &c->h2d_out, &c->d_own, &c->gscratch, &c->scan_lcol};
     for (DevBuf* b : bufs) b->release();
-    c->noise.sai.release(); c->noise.part.release(); c->noise.cells.release(); c->noise.m.release(); c->noise.pool.release();
-    c->sr.sai.release(); c->sr.tab.release(); c->sr.hi.release(); c->sr.lo.release();
-    c->quality.sai.release(); c->quality.part.release(); c->quality.out.release();
-    c->pg.sai.release(); c->pg.stats.release(); c->pg.lf.release();
-    c->imp.sai.release(); c->imp.stats.release(); c->imp.flags.release();
-    c->inp.sai.release(); c->inp.stats.release(); c->inp.state[0].release(); c->inp.state[1].release(); c->inp.tmp.release(); c->inp.flags.release();
-    c->view.table.release(); c->view.stats.release(); c->view.tmp.release(); c->view.disp.release();
+    c->side.sai.release(); c->side.lf.release();
+    c->noise.part.release(); c->noise.cells.release(); c->noise.m.release(); c->noise.pool.release();
+    c->sr.tab.release(); c->sr.lo.release();
+    c->quality.part.release(); c->quality.out.release();
+    c->pg.stats.release();
+    c->imp.stats.release(); c->imp.flags.release();
+    c->inp.stats.release(); c->inp.state[0].release(); c->inp.state[1].release(); c->inp.flags.release();
+    c->view.table.release(); c->view.stats.release(); c->view.disp.release();
     c->consist.table.release(); c->consist.stats.release(); c->consist.pred.release(); c->consist.disp.release(); c->consist.flags.release();
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     if (c->h_small) (void)hipHostFree(c->h_small);

@@ -13,10 +13,8 @@
  *                     (d* varies per pixel: cached gathers), the two tests, the code byte; counts per (SAI, channel, code) through LDS.
  * Integer atomics only; the quantiles and the bad-SAI decision run on the host in double on the integer histograms.
  */
-#include "lfbm5d_ctx.h"
+#include "lfbm5d_side.h"
 #include "lfbm5d_consist_device.h"
-
-#include <cstdint>
 
 using namespace lfbm5d_host;
 using namespace lfbm5d_consist;
@@ -66,32 +64,17 @@ __global__ __launch_bounds__(kThreads) void k_consist_flag(const float* __restri
     if (tid < 6 && cnt[tid]) atomicAdd(&counts[(size_t)tab[0] * 6 + tid], (unsigned long long)cnt[tid]);
 }
 
-void coords(unsigned st, unsigned ang_major, unsigned aw, unsigned ah, int& s, int& t) {
-    if (ang_major == LFBM5D_ROWMAJOR) { s = (int)(st / aw); t = (int)(st % aw); }
-    else { s = (int)(st % ah); t = (int)(st / ah); }
-}
-
 struct Geometry { unsigned ang_major, aw, ah, asize, W, H, C, tx_n, ty_n; };
 
 /* the leave-one-out tables under the exclude set: one row per tested SAI; SAIs with fewer than min_sources sources are untested */
 void plan(const Geometry& G, const lfbm5d_consist_params* P, const unsigned* h_mask, const std::vector<unsigned char>& excl,
           std::vector<int>& table, std::vector<unsigned>& tested, std::vector<unsigned>& untested) {
     table.clear(); tested.clear(); untested.clear();
-    const int R = (int)P->ang_radius;
     for (unsigned m = 0; m < G.asize; m++) {
         if (!h_mask[m] || excl[m]) continue;
-        int sm, tm;
-        coords(m, G.ang_major, G.aw, G.ah, sm, tm);
-        int row[kTabStride] = {(int)m, 0};
-        for (unsigned q = 0; q < G.asize; q++) {
-            if (q == m || !h_mask[q] || excl[q]) continue;
-            int s, t;
-            coords(q, G.ang_major, G.aw, G.ah, s, t);
-            if (std::abs(s - sm) > R || std::abs(t - tm) > R) continue;
-            int* at = row + 2 + 3 * row[1]++;
-            at[0] = (int)q; at[1] = s - sm; at[2] = t - tm;
-        }
-        if ((unsigned)row[1] < P->min_sources) { untested.push_back(m); continue; }
+        int row[kTabStride];
+        const int n = source_row(m, G.ang_major, G.aw, G.ah, (int)P->ang_radius, [&](unsigned q) { return q != m && h_mask[q] && !excl[q]; }, row);
+        if ((unsigned)n < P->min_sources) { untested.push_back(m); continue; }
         tested.push_back(m);
         table.insert(table.end(), row, row + kTabStride);
     }
@@ -136,12 +119,12 @@ void decide(const Geometry& G, const lfbm5d_consist_params* P, const std::vector
         if (!has[m]) { bad.push_back(m); continue; }
         if (!exceeds[m]) continue;
         int sm, tm;
-        coords(m, G.ang_major, G.aw, G.ah, sm, tm);
+        sai_coords(m, G.ang_major, G.aw, G.ah, sm, tm);
         bool beaten = false;
         for (unsigned q : tested) {
             if (q == m || !exceeds[q]) continue;
             int sq, tq;
-            coords(q, G.ang_major, G.aw, G.ah, sq, tq);
+            sai_coords(q, G.ang_major, G.aw, G.ah, sq, tq);
             if (std::abs(sq - sm) > R || std::abs(tq - tm) > R) continue;
             if (s[q] > s[m] || (s[q] == s[m] && q < m)) beaten = true;
         }
@@ -169,15 +152,12 @@ int consist(lfbm5d_ctx* c, const std::string& who, const lfbm5d_consist_params* 
             unsigned long long* h_hist, unsigned ang_major, unsigned aw, unsigned ah, unsigned W, unsigned H, unsigned C,
             lfbm5d_consist_result* res) {
     if (!P || !d_in || !h_mask || !d_flags || !h_state) return fail(c, who + "NULL pointer for a required buffer");
-    if (C != 1 && C != 3) return fail(c, who + "chnls must be 1 or 3");
-    if (W < 2 || H < 2) return fail(c, who + "width and height must be at least 2");
-    if (ang_major != LFBM5D_ROWMAJOR && ang_major != LFBM5D_COLMAJOR) return fail(c, who + "ang_major must be LFBM5D_ROWMAJOR or LFBM5D_COLMAJOR");
-    if (!aw || !ah) return fail(c, who + "awidth and aheight must be at least 1");
+    if (check_chnls(c, who, C) || check_size(c, who, W, H, 2, "be at least 2") || check_angular(c, who, ang_major, aw, ah)) return 1;
     if (const char* msg = check_params(P)) return fail(c, who + msg);
-    if (c->world > 1 || c->comm || c->ipc) return fail(c, who + "the consistency check runs on one GPU (this context has a communicator or a shard)");
-    Geometry G = {ang_major, aw, ah, aw * ah, W, H, C, (W + kTW - 1) / kTW, (H + kTH - 1) / kTH};
-    if ((unsigned long long)W * H > 0x3fffffffull || (unsigned long long)G.tx_n * G.ty_n > 0x7fffffffull || G.asize > 65535)
-        return fail(c, who + "light field too large");
+    if (check_one_gpu(c, who, "the consistency check runs on one GPU (this context has a communicator or a shard)")) return 1;
+    TileGrid tiles;
+    if (check_tiles(c, who, W, H, aw * ah, 0x3fffffffull, tiles)) return 1;
+    const Geometry G = {ang_major, aw, ah, aw * ah, W, H, C, tiles.tx_n, tiles.ty_n};
     std::vector<unsigned char> excl(G.asize, 0), found(G.asize, 0);
     unsigned nne = 0;
     for (unsigned st = 0; st < G.asize; st++) {
@@ -266,9 +246,7 @@ int consist(lfbm5d_ctx* c, const std::string& who, const lfbm5d_consist_params* 
                            d_flags, d_table, (int)C, (int)W, (int)H, G.tx_n, thr, g, d_cnt);
         HIPCK(c, hipGetLastError());
         HIPCK(c, hipMemcpyAsync(cnt.data(), d_cnt, n_cnt * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        if (d_disp)
-            for (unsigned m : tested)
-                HIPCK(c, hipMemcpyAsync(d_disp + (size_t)m * plane, d_dstar + (size_t)m * plane, plane, hipMemcpyDeviceToDevice, c->stream));
+        if (d_disp && copy_sais(c, G.asize, d_disp, d_dstar, plane, 1, [&](unsigned st) { return h_state[st] == 1u; })) return 1;
     }
     HIPCK(c, hipStreamSynchronize(c->stream));
     for (unsigned m : tested)
@@ -316,26 +294,22 @@ int lfbm5d_consist_host_sai(lfbm5d_ctx* c, const lfbm5d_consist_params* P, const
     if (!c) return 1;
     const std::string who = "lfbm5d_consist_host_sai: ";
     if (!P || !h_in || !h_mask || !h_flags || !h_state) return fail(c, who + "NULL pointer for a required buffer");
-    if (C != 1 && C != 3) return fail(c, who + "chnls must be 1 or 3");
+    if (check_chnls(c, who, C)) return 1;
     const unsigned asize = awidth * aheight;
     const size_t plane = (size_t)W * H, img = plane * C, all = std::max<size_t>(1, (size_t)asize * img);
-    for (unsigned st = 0; st < asize; st++)
-        if (h_mask[st] && (!h_in[st] || !h_flags[st] || (h_disp && !h_disp[st]))) return fail(c, who + "NULL pointer for a non-empty SAI");
+    const auto nonempty = [&](unsigned st) { return h_mask[st] != 0; };
+    if (check_planes(c, who, h_flags, asize, nonempty) || (h_disp && check_planes(c, who, h_disp, asize, nonempty))) return 1;
     (void)hipSetDevice(c->device);
     HIPCK(c, c->h2d_noisy.reserve(all * sizeof(float)));
     HIPCK(c, c->consist.flags.reserve(all + std::max<size_t>(1, (size_t)asize * plane)));
     float* const din = c->h2d_noisy.as<float>();
     unsigned char* const dfl = c->consist.flags.as<unsigned char>();
     signed char* const ddisp = h_disp ? reinterpret_cast<signed char*>(dfl + all) : nullptr;
-    for (unsigned st = 0; st < asize; st++)
-        if (h_mask[st]) HIPCK(c, hipMemcpyAsync(din + (size_t)st * img, h_in[st], img * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (upload_planes(c, who, h_in, din, asize, img, nonempty)) return 1;
     HIPCK(c, hipStreamSynchronize(c->stream));
     if (consist(c, who, P, din, h_mask, h_exclude, dfl, h_state, ddisp, h_scale_sai, h_hist, ang_major, awidth, aheight, W, H, C, out)) return 1;
-    for (unsigned st = 0; st < asize; st++) {
-        if (!h_mask[st]) continue;
-        HIPCK(c, hipMemcpyAsync(h_flags[st], dfl + (size_t)st * img, img, hipMemcpyDeviceToHost, c->stream));
-        if (ddisp && h_state[st] == 1u) HIPCK(c, hipMemcpyAsync(h_disp[st], ddisp + (size_t)st * plane, plane, hipMemcpyDeviceToHost, c->stream));
-    }
+    if (download_planes(c, h_flags, dfl, asize, img, nonempty)) return 1;
+    if (ddisp && download_planes(c, h_disp, ddisp, asize, plane, [&](unsigned st) { return h_state[st] == 1u; })) return 1;
     HIPCK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

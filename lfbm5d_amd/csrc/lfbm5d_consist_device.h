@@ -9,44 +9,25 @@
 #ifndef LFBM5D_CONSIST_DEVICE_H
 #define LFBM5D_CONSIST_DEVICE_H
 
-#include <cstddef>
-
-#ifdef __HIPCC__
-#define LFBM5D_HD __host__ __device__ __forceinline__
-#else
-#define LFBM5D_HD inline
-#endif
+#include "lfbm5d_side_values.h"
 
 #pragma clang fp contract(off)
 
 namespace lfbm5d_consist {
 
-constexpr int kTW = 64, kTH = 32, kThreads = 256;
+using namespace lfbm5d_side;                                      /* the tile, the key layout, the thresholds, mirror, the bit tests */
+
 constexpr int kPer = kTW * kTH / kThreads;                        /* 8 positions per thread */
 constexpr int kRowStep = kThreads / kTW;                          /* 4 */
-constexpr int kKeys = 386, kKeyBase = (-12 + 127) << 4;           /* the impulse stage's histogram layout (LFBM5D_IMPULSE_KEYS) */
 constexpr int kSrcMax = 24, kTabStride = 2 + 3 * kSrcMax;         /* k_view_sweep's table: SAI, n, n x (source, ds, dt) */
 static_assert(kTW * kTH % kThreads == 0 && kThreads % kTW == 0, "a thread owns one column");
 
-struct Thresholds { float t[3]; };
-
-LFBM5D_HD unsigned bits_of(float x) { return __builtin_bit_cast(unsigned, x); }
-LFBM5D_HD bool finite_bits(float x) { return (bits_of(x) & 0x7f800000u) != 0x7f800000u; }
 LFBM5D_HD float abs_bits(float x) { return __builtin_bit_cast(float, bits_of(x) & 0x7fffffffu); }
 
 /* key of a >= 0 (or a NaN, whose bits land in the last key): clamp((bits >> 19) - base + 1, 0, 385) */
 LFBM5D_HD int key_of(float a) {
     const int k = (int)(bits_of(a) >> 19) - kKeyBase + 1;
     return k < 0 ? 0 : k > kKeys - 1 ? kKeys - 1 : k;
-}
-
-/* coordinate g of the mirrored plane (period 2 (n - 1), no edge repeated) -> 0..n-1; n >= 2; any g */
-LFBM5D_HD int mirror(int g, int n) {
-    if ((unsigned)g < (unsigned)n) return g;
-    const int P = 2 * (n - 1);
-    g %= P;
-    if (g < 0) g += P;
-    return g < n ? g : P - g;
 }
 
 /* The statistics of one thread's values: the key of a = |I_m - mu| goes into hist [C][386] (the workgroup's counters), a non-finite I_m

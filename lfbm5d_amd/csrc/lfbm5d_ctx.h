@@ -7,6 +7,10 @@
  *                      streamed host seam
  *   lfbm5d_steps.hip   run_bm5d_1st_step / run_bm5d_2nd_step / both as one job on device buffers: schedule forms, tile mode
  *   lfbm5d_api.hip     the C-ABI of include/lfbm5d.h: context, options, communicators, host entry points, BM3D, inspection
+ *   lfbm5d_side.h      the host frame of the side stages (lfbm5d_noise / quality / resample / pg / impulse / inpaint / view / consist.hip):
+ *                      SAI list, argument checks, staging of per-SAI host planes, the refinement loop, the sweep's source rows
+ *   lfbm5d_side_values.h   what those stages share per value, host-and-device and free of HIP headers: tile, mirror, bit tests, key
+ *                      layout, thresholds, the loop's sigma schedule
  * Internal: nothing here is part of the ABI.
  */
 #ifndef LFBM5D_CTX_H
@@ -141,27 +145,29 @@ struct lfbm5d_ctx {
     Options opt_store; Options* opt = &opt_store;
     hipStream_t io_in = nullptr, io_out = nullptr;
     unsigned* h_small = nullptr; /* pinned, 64 uints */
-    /* noise-level estimate (lfbm5d_noise.hip): non-empty SAI list, bulk partial sums, lag cells, centred scatters, pooled covariances */
-    struct NoiseBufs { DevBuf sai, part, cells, m, pool; } noise;
-    /* quality metrics (lfbm5d_quality.hip): non-empty SAI list, the workgroups' partial sums, the two sums of every SAI */
-    struct QualityBufs { DevBuf sai, part, out; } quality;
-    /* super-resolution (lfbm5d_resample.hip): non-empty SAI list, the tap tables of U and D for the geometry in `key` (host copy, word
-     * offsets of first / w of Ux, Uy, Dx, Dy, their tap counts), the loop's scratch: one high- and one low-resolution light field */
+    /* what the side stages share (lfbm5d_side.h): the non-empty SAIs of the last mask on the device and on the host (sai_list), the
+     * scratch light field a step or a job is handed as its input (scratch_lf: the refinement loop, the inpainting fill's second value plane,
+     * the Poisson-Gaussian job's stabilised light field) */
+    struct SideBufs { DevBuf sai, lf; std::vector<unsigned> sai_host; } side;
+    /* noise-level estimate (lfbm5d_noise.hip): bulk partial sums, lag cells, centred scatters, pooled covariances */
+    struct NoiseBufs { DevBuf part, cells, m, pool; } noise;
+    /* quality metrics (lfbm5d_quality.hip): the workgroups' partial sums, the two sums of every SAI */
+    struct QualityBufs { DevBuf part, out; } quality;
+    /* super-resolution (lfbm5d_resample.hip): the tap tables of U and D for the geometry in `key` (host copy, word offsets of first / w of
+     * Ux, Uy, Dx, Dy, their tap counts), the back-projection's low-resolution residual */
     struct SrBufs {
-        DevBuf sai, tab, hi, lo;
-        std::vector<unsigned> sai_host, host;
+        DevBuf tab, lo;
+        std::vector<unsigned> host;
         unsigned key[5] = {0, 0, 0, 0, 0}; size_t off[8] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned T[4] = {0, 0, 0, 0};
     } sr;
-    /* Poisson-Gaussian noise (lfbm5d_pg.hip): non-empty SAI list, the statistics kernel's counters, the job's stabilised light field */
-    struct PgBufs { DevBuf sai, stats, lf; } pg;
-    /* impulse repair (lfbm5d_impulse.hip): non-empty SAI list, the kernels' counters, the host form's flag planes (in, out) */
-    struct ImpulseBufs { DevBuf sai, stats, flags; } imp;
-    /* defect inpainting (lfbm5d_inpaint.hip): non-empty SAI list, the fill's counters, its state planes and second value plane (also the
-     * loop's scratch input of the step), the host form's flag planes (in, out) */
-    struct InpaintBufs { DevBuf sai, stats, state[2], tmp, flags; } inp;
-    /* view synthesis (lfbm5d_view.hip): the source lists, the disparity histogram, the loop's scratch input of the step, the host form's
-     * disparity planes */
-    struct ViewBufs { DevBuf table, stats, tmp, disp; } view;
+    /* Poisson-Gaussian noise (lfbm5d_pg.hip): the statistics kernel's counters */
+    struct PgBufs { DevBuf stats; } pg;
+    /* impulse repair (lfbm5d_impulse.hip): the kernels' counters, the host form's flag planes (in, out) */
+    struct ImpulseBufs { DevBuf stats, flags; } imp;
+    /* defect inpainting (lfbm5d_inpaint.hip): the fill's counters, its state planes, the host form's flag planes (in, out) */
+    struct InpaintBufs { DevBuf stats, state[2], flags; } inp;
+    /* view synthesis (lfbm5d_view.hip): the source lists, the disparity histogram, the host form's disparity planes */
+    struct ViewBufs { DevBuf table, stats, disp; } view;
     /* consistency check (lfbm5d_consist.hip): the leave-one-out source lists, histograms and counters, the prediction light field, the
      * sweep's disparity planes, the host form's flag and disparity planes */
     struct ConsistBufs { DevBuf table, stats, pred, disp, flags; } consist;

@@ -17,34 +17,16 @@
  * Non-finite values are decided by explicit tests on the bits before any min / max: the hardware's min / max drop a NaN operand.
  * The quantile of a histogram runs on the host in double.
  */
-#include "lfbm5d_ctx.h"
-
-#include <cstdint>
+#include "lfbm5d_side.h"
 
 using namespace lfbm5d_host;
+using namespace lfbm5d_side;
 
 namespace {
 
-constexpr int kEMin = -12, kEMax = 12;
-constexpr int kKeys = (kEMax - kEMin) * 16 + 2;      /* 386 */
-constexpr int kKeyBase = (kEMin + 127) << 4;         /* bits >> 19 of 2^E_MIN */
-constexpr int kTW = 64, kTH = 32, kThreads = 256;
 constexpr int kS1 = kTW + 2, kR1 = kTH + 2;          /* tile with one ring */
 constexpr int kS2 = kTW + 4, kR2 = kTH + 4;          /* tile with two rings */
 static_assert(kKeys == LFBM5D_IMPULSE_KEYS, "include/lfbm5d.h");
-
-struct Thresholds { float t[3]; };
-
-__device__ __forceinline__ bool finite_bits(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-
-/* coordinate g of the mirrored plane (period 2 (n - 1), no edge repeated) -> 0..n-1; n >= 2 */
-__device__ __forceinline__ int mirror(int g, int n) {
-    if ((unsigned)g < (unsigned)n) return g;   /* inside the plane: every lane of an interior tile */
-    const int P = 2 * (n - 1);
-    g %= P;
-    if (g < 0) g += P;
-    return g < n ? g : P - g;
-}
 
 #define CSWAP_F(a, b) { const float lo_ = fminf(a, b), hi_ = fmaxf(a, b); a = lo_; b = hi_; }
 #define CSWAP_I(a, b) { const int lo_ = min(a, b), hi_ = max(a, b); a = lo_; b = hi_; }
@@ -222,29 +204,11 @@ int scale_of(const unsigned long long* h, double* s) {
     return 0;
 }
 
-struct Shape { unsigned nne, tx_n, ty_n; };
+/* prepare_tiled's stage arguments */
+constexpr const char* kOneGpu = "the impulse routines run on one GPU (this context has a communicator or a shard)";
+constexpr unsigned long long kMaxPlane = 0x7fffffffull;
 
-/* the checks every device entry shares, the non-empty SAIs on the device (c->imp.sai) and the tiling; 1 with a message */
-int prepare(lfbm5d_ctx* c, const std::string& who, const unsigned* h_mask, unsigned asize, unsigned W, unsigned H, unsigned C, Shape& s) {
-    if (!h_mask) return fail(c, who + "NULL pointer for a required buffer");
-    if (C != 1 && C != 3) return fail(c, who + "chnls must be 1 or 3");
-    if (W < 2 || H < 2) return fail(c, who + "width and height must be at least 2");
-    if (c->world > 1 || c->comm || c->ipc) return fail(c, who + "the impulse routines run on one GPU (this context has a communicator or a shard)");
-    std::vector<unsigned> sai;
-    for (unsigned st = 0; st < asize; st++) if (h_mask[st]) sai.push_back(st);
-    if (sai.empty()) return fail(c, who + "the mask has no non-empty SAI");
-    s.nne = (unsigned)sai.size();
-    s.tx_n = (W + kTW - 1) / kTW; s.ty_n = (H + kTH - 1) / kTH;
-    if ((unsigned long long)W * H > 0x7fffffffull || (unsigned long long)s.tx_n * s.ty_n > 0x7fffffffull || (unsigned long long)s.nne * C > 65535)
-        return fail(c, who + "light field too large");
-    (void)hipSetDevice(c->device);
-    HIPCK(c, c->imp.sai.reserve(sai.size() * sizeof(unsigned)));
-    HIPCK(c, hipMemcpyAsync(c->imp.sai.p, sai.data(), sai.size() * sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));   /* the list leaves a stack object */
-    return 0;
-}
-
-/* hist [C][386] (host) of the light field in HBM; after prepare() */
+/* hist [C][386] (host) of the light field in HBM; after prepare_tiled() */
 int histogram(lfbm5d_ctx* c, const Shape& s, const float* d_lf, unsigned W, unsigned H, unsigned C, unsigned long long* h_hist,
               unsigned long long* skipped) {
     const size_t nh = (size_t)C * kKeys, words = nh + 1;
@@ -255,7 +219,7 @@ int histogram(lfbm5d_ctx* c, const Shape& s, const float* d_lf, unsigned W, unsi
     HIPCK(c, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
     const unsigned long long total = (unsigned long long)s.tx_n * s.ty_n * s.nne;
     const unsigned wgs = (unsigned)std::min<unsigned long long>(total, std::max(1u, (unsigned)std::max(1, n_cu) * 8u / C));
-    hipLaunchKernelGGL(k_impulse_stats, dim3(wgs, C), dim3(kThreads), 0, c->stream, d_lf, c->imp.sai.as<unsigned>(), s.nne, C, W, H, s.tx_n, s.ty_n,
+    hipLaunchKernelGGL(k_impulse_stats, dim3(wgs, C), dim3(kThreads), 0, c->stream, d_lf, c->side.sai.as<unsigned>(), s.nne, C, W, H, s.tx_n, s.ty_n,
                        d, d + nh);
     HIPCK(c, hipGetLastError());
     std::vector<unsigned long long> host(words);
@@ -266,17 +230,12 @@ int histogram(lfbm5d_ctx* c, const Shape& s, const float* d_lf, unsigned W, unsi
     return 0;
 }
 
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + nb && y < x + na;
-}
-
 /* detection + repair (d_flags_in NULL) or repair under given flags; include/lfbm5d.h */
 int repair(lfbm5d_ctx* c, const std::string& who, const lfbm5d_impulse_params* P, const float* d_in, const unsigned char* d_flags_in,
            const unsigned* h_mask, float* d_out, unsigned char* d_flags_out, unsigned asize, unsigned W, unsigned H, unsigned C,
            lfbm5d_impulse_result* res, unsigned long long* h_counts_sai, bool given) {
     if (!d_in || !d_out || !h_mask || (given ? !d_flags_in : !P)) return fail(c, who + "NULL pointer for a required buffer");
-    if (C != 1 && C != 3) return fail(c, who + "chnls must be 1 or 3");
+    if (check_chnls(c, who, C)) return 1;
     const size_t values = (size_t)asize * C * W * H;
     if (overlap(d_in, values * sizeof(float), d_out, values * sizeof(float)))
         return fail(c, who + "d_out must not alias d_in (neighbours are read across tile edges)");
@@ -289,7 +248,7 @@ int repair(lfbm5d_ctx* c, const std::string& who, const lfbm5d_impulse_params* P
             if (std::isnan(P->threshold[ch]) || std::isinf(P->threshold[ch])) return fail(c, who + "threshold must be finite (<= 0: take k x scale)");
     }
     Shape s;
-    if (prepare(c, who, h_mask, asize, W, H, C, s)) return 1;
+    if (prepare_tiled(c, who, kOneGpu, h_mask, asize, W, H, C, kMaxPlane, s)) return 1;
     lfbm5d_impulse_result r;
     std::memset(&r, 0, sizeof(r));
     r.pixels = (unsigned long long)s.nne * C * W * H;
@@ -318,9 +277,9 @@ int repair(lfbm5d_ctx* c, const std::string& who, const lfbm5d_impulse_params* P
     HIPCK(c, hipMemsetAsync(d_cnt, 0, nc * sizeof(unsigned long long), c->stream));
     const dim3 grid(s.tx_n * s.ty_n, s.nne * C);
     if (given) hipLaunchKernelGGL((k_impulse_repair<true>), grid, dim3(kThreads), 0, c->stream, d_in, d_flags_in, d_out, d_flags_out,
-                                  c->imp.sai.as<unsigned>(), C, W, H, s.tx_n, thr, d_cnt);
+                                  c->side.sai.as<unsigned>(), C, W, H, s.tx_n, thr, d_cnt);
     else hipLaunchKernelGGL((k_impulse_repair<false>), grid, dim3(kThreads), 0, c->stream, d_in, d_flags_in, d_out, d_flags_out,
-                            c->imp.sai.as<unsigned>(), C, W, H, s.tx_n, thr, d_cnt);
+                            c->side.sai.as<unsigned>(), C, W, H, s.tx_n, thr, d_cnt);
     HIPCK(c, hipGetLastError());
     std::vector<unsigned long long> cnt(nc);
     HIPCK(c, hipMemcpyAsync(cnt.data(), d_cnt, nc * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
@@ -360,7 +319,7 @@ int lfbm5d_impulse_histogram_device(lfbm5d_ctx* c, const float* d_lf, const unsi
     const std::string who = "lfbm5d_impulse_histogram_device: ";
     if (!d_lf || !h_mask || !h_hist) return fail(c, who + "NULL pointer for a required buffer");
     Shape s;
-    if (prepare(c, who, h_mask, asize, W, H, C, s)) return 1;
+    if (prepare_tiled(c, who, kOneGpu, h_mask, asize, W, H, C, kMaxPlane, s)) return 1;
     unsigned long long skip = 0;
     if (histogram(c, s, d_lf, W, H, C, h_hist, &skip)) return 1;
     if (pixels) *pixels = (unsigned long long)s.nne * C * W * H;
@@ -389,30 +348,21 @@ int lfbm5d_impulse_repair_host_sai(lfbm5d_ctx* c, const lfbm5d_impulse_params* P
     if (!c) return 1;
     const std::string who = "lfbm5d_impulse_repair_host_sai: ";
     if (!h_in || !h_out || !h_mask) return fail(c, who + "NULL pointer for a required buffer");
-    if (C != 1 && C != 3) return fail(c, who + "chnls must be 1 or 3");
+    if (check_chnls(c, who, C)) return 1;
     const size_t img = (size_t)C * W * H, all = std::max<size_t>(1, (size_t)asize * img);
-    for (unsigned st = 0; st < asize; st++)
-        if (h_mask[st] && (!h_in[st] || !h_out[st] || (h_flags_in && !h_flags_in[st]) || (h_flags && !h_flags[st])))
-            return fail(c, who + "NULL pointer for a non-empty SAI");
+    const auto nonempty = [&](unsigned st) { return h_mask[st] != 0; };
+    if (check_planes(c, who, h_out, asize, nonempty) || (h_flags && check_planes(c, who, h_flags, asize, nonempty))) return 1;
     (void)hipSetDevice(c->device);
     HIPCK(c, c->h2d_noisy.reserve(all * sizeof(float)));
     HIPCK(c, c->h2d_out.reserve(all * sizeof(float)));
     HIPCK(c, c->imp.flags.reserve(2 * all));
     float* const din = c->h2d_noisy.as<float>(); float* const dout = c->h2d_out.as<float>();
     unsigned char* const dfi = c->imp.flags.as<unsigned char>(); unsigned char* const dfo = dfi + all;
-    for (unsigned st = 0; st < asize; st++) {
-        if (!h_mask[st]) continue;
-        HIPCK(c, hipMemcpyAsync(din + (size_t)st * img, h_in[st], img * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        if (h_flags_in) HIPCK(c, hipMemcpyAsync(dfi + (size_t)st * img, h_flags_in[st], img, hipMemcpyHostToDevice, c->stream));
-    }
+    if (upload_planes(c, who, h_in, din, asize, img, nonempty) || (h_flags_in && upload_planes(c, who, h_flags_in, dfi, asize, img, nonempty))) return 1;
     HIPCK(c, hipStreamSynchronize(c->stream));
     if (repair(c, who, P, din, h_flags_in ? dfi : nullptr, h_mask, dout, h_flags ? dfo : nullptr, asize, W, H, C, out, h_counts_sai,
                h_flags_in != nullptr)) return 1;
-    for (unsigned st = 0; st < asize; st++) {
-        if (!h_mask[st]) continue;
-        HIPCK(c, hipMemcpyAsync(h_out[st], dout + (size_t)st * img, img * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        if (h_flags) HIPCK(c, hipMemcpyAsync(h_flags[st], dfo + (size_t)st * img, img, hipMemcpyDeviceToHost, c->stream));
-    }
+    if (download_planes(c, h_out, dout, asize, img, nonempty) || (h_flags && download_planes(c, h_flags, dfo, asize, img, nonempty))) return 1;
     HIPCK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -18,16 +18,14 @@
  * Sums in a fixed order, one product with a table entry, integer atomics for the counts: the GPU equals tests/inpaint_model.py bit for
  * bit, however the passes fall into launches.
  */
-#include "lfbm5d_ctx.h"
-
-#include <cstdint>
+#include "lfbm5d_side.h"
 
 using namespace lfbm5d_host;
+using namespace lfbm5d_side;
 
 namespace {
 
 constexpr int kR = LFBM5D_INPAINT_PASSES_PER_LAUNCH;
-constexpr int kTW = 64, kTH = 32, kThreads = 256;
 constexpr int kWW = kTW + 2 * kR, kWH = kTH + 2 * kR;       /* the window: tile + halo, 80 x 48 */
 constexpr int kCells = kWW * kWH, kPer = kCells / kThreads;   /* 3840 cells, 15 per thread */
 constexpr unsigned kNone = 0xffffu;
@@ -40,17 +38,6 @@ constexpr unsigned char kSound = 0, kFilled = 1, kOpen = 2;
 
 /* r[n] = (float)(1.0 / n) */
 __constant__ float kRecip[9] = {0.0f, 1.0f, 0.5f, (float)(1.0 / 3.0), 0.25f, (float)(1.0 / 5.0), (float)(1.0 / 6.0), (float)(1.0 / 7.0), 0.125f};
-
-__device__ __forceinline__ bool finite_bits(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-
-/* coordinate g of the mirrored plane (period 2 (n - 1), no edge repeated) -> 0..n-1; n >= 2; any g (the halo is wider than a narrow plane) */
-__device__ __forceinline__ int mirror(int g, int n) {
-    if ((unsigned)g < (unsigned)n) return g;
-    const int P = 2 * (n - 1);
-    g %= P;
-    if (g < 0) g += P;
-    return g < n ? g : P - g;
-}
 
 /* grid (tx_n * ty_n, nne * C), 256 threads.  FIRST: st_in is the caller's defect map (non-zero = defective) and a non-finite value is
  * flagged too; otherwise st_in holds the states the previous launch wrote.  pass_base = the passes run by earlier launches. */
@@ -193,34 +180,11 @@ __global__ __launch_bounds__(kThreads) void k_inpaint_project(const unsigned cha
     }
 }
 
-struct Shape { unsigned nne, tx_n, ty_n; };
+/* prepare_tiled's stage arguments */
+constexpr const char* kOneGpu = "the inpainting routines run on one GPU (this context has a communicator or a shard)";
+constexpr unsigned long long kMaxPlane = 0x3fffffffull;
 
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + nb && y < x + na;
-}
-
-/* the checks every device entry shares, the non-empty SAIs on the device (c->inp.sai) and the tiling; 1 with a message */
-int prepare(lfbm5d_ctx* c, const std::string& who, const unsigned* h_mask, unsigned asize, unsigned W, unsigned H, unsigned C, Shape& s) {
-    if (!h_mask) return fail(c, who + "NULL pointer for a required buffer");
-    if (C != 1 && C != 3) return fail(c, who + "chnls must be 1 or 3");
-    if (W < 2 || H < 2) return fail(c, who + "width and height must be at least 2");
-    if (c->world > 1 || c->comm || c->ipc) return fail(c, who + "the inpainting routines run on one GPU (this context has a communicator or a shard)");
-    std::vector<unsigned> sai;
-    for (unsigned st = 0; st < asize; st++) if (h_mask[st]) sai.push_back(st);
-    if (sai.empty()) return fail(c, who + "the mask has no non-empty SAI");
-    s.nne = (unsigned)sai.size();
-    s.tx_n = (W + kTW - 1) / kTW; s.ty_n = (H + kTH - 1) / kTH;
-    if ((unsigned long long)W * H > 0x3fffffffull || (unsigned long long)s.tx_n * s.ty_n > 0x7fffffffull || (unsigned long long)s.nne * C > 65535)
-        return fail(c, who + "light field too large");
-    (void)hipSetDevice(c->device);
-    HIPCK(c, c->inp.sai.reserve(sai.size() * sizeof(unsigned)));
-    HIPCK(c, hipMemcpyAsync(c->inp.sai.p, sai.data(), sai.size() * sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));   /* the list leaves a stack object */
-    return 0;
-}
-
-/* out = flag ? x : y on the non-empty SAIs; after prepare(); asynchronous on the context's stream */
+/* out = flag ? x : y on the non-empty SAIs; after prepare_tiled(); asynchronous on the context's stream */
 int project(lfbm5d_ctx* c, const Shape& s, const unsigned char* d_flags, const float* d_x, const float* d_y, float* d_out, unsigned W,
             unsigned H, unsigned C) {
     const size_t n = (size_t)C * W * H;
@@ -228,22 +192,13 @@ int project(lfbm5d_ctx* c, const Shape& s, const unsigned char* d_flags, const f
     const bool vec = n % 4 == 0 && bits % 16 == 0 && reinterpret_cast<uintptr_t>(d_flags) % 4 == 0;
     const size_t items = vec ? n / 4 : n;
     const dim3 grid((unsigned)std::min<size_t>((items + kThreads - 1) / kThreads, 4096), s.nne);
-    if (vec) hipLaunchKernelGGL((k_inpaint_project<true>), grid, dim3(kThreads), 0, c->stream, d_flags, d_x, d_y, d_out, c->inp.sai.as<unsigned>(), n);
-    else hipLaunchKernelGGL((k_inpaint_project<false>), grid, dim3(kThreads), 0, c->stream, d_flags, d_x, d_y, d_out, c->inp.sai.as<unsigned>(), n);
+    if (vec) hipLaunchKernelGGL((k_inpaint_project<true>), grid, dim3(kThreads), 0, c->stream, d_flags, d_x, d_y, d_out, c->side.sai.as<unsigned>(), n);
+    else hipLaunchKernelGGL((k_inpaint_project<false>), grid, dim3(kThreads), 0, c->stream, d_flags, d_x, d_y, d_out, c->side.sai.as<unsigned>(), n);
     HIPCK(c, hipGetLastError());
     return 0;
 }
 
-/* the non-empty SAIs' planes of src -> dst (device to device), el bytes per value */
-int copy_sais(lfbm5d_ctx* c, const unsigned* h_mask, unsigned asize, void* dst, const void* src, size_t img, size_t el) {
-    for (unsigned st = 0; st < asize; st++)
-        if (h_mask[st])
-            HIPCK(c, hipMemcpyAsync(static_cast<char*>(dst) + (size_t)st * img * el, static_cast<const char*>(src) + (size_t)st * img * el, img * el,
-                                    hipMemcpyDeviceToDevice, c->stream));
-    return 0;
-}
-
-/* the onion-peel fill; after prepare().  On return the stream is idle, d_out holds the result and *d_codes points at the code plane
+/* the onion-peel fill; after prepare_tiled().  On return the stream is idle, d_out holds the result and *d_codes points at the code plane
  * (d_flags_out when given, else the context's scratch). */
 int fill(lfbm5d_ctx* c, const Shape& s, const float* d_in, const unsigned char* d_flags_in, const unsigned* h_mask, float* d_out,
          unsigned char* d_flags_out, unsigned asize, unsigned W, unsigned H, unsigned C, lfbm5d_inpaint_result& r,
@@ -256,17 +211,17 @@ int fill(lfbm5d_ctx* c, const Shape& s, const float* d_in, const unsigned char* 
     unsigned long long* d_cnt = c->inp.stats.as<unsigned long long>();
     HIPCK(c, hipMemsetAsync(d_cnt, 0, kCntWords * sizeof(unsigned long long), c->stream));
     const dim3 grid(s.tx_n * s.ty_n, s.nne * C);
-    const unsigned* d_sai = c->inp.sai.as<unsigned>();
+    const unsigned* d_sai = c->side.sai.as<unsigned>();
     const float* src = d_in;
     const unsigned char* st_src = d_flags_in;
     unsigned long long cnt[kCntWords], filled_before = 0;
     for (unsigned l = 0;; l++) {
         float* dst = d_out;
         unsigned char* st_dst = d_flags_out ? d_flags_out : c->inp.state[0].as<unsigned char>();
-        if (l & 1) {   /* a launch reads what the one before it wrote: odd launches write the context's second pair of planes */
-            HIPCK(c, c->inp.tmp.reserve(values * sizeof(float)));
+        if (l & 1) {   /* a launch reads what the one before it wrote: odd launches write the scratch light field and the second states */
+            HIPCK(c, c->side.lf.reserve(values * sizeof(float)));
             HIPCK(c, c->inp.state[1].reserve(values));
-            dst = c->inp.tmp.as<float>();
+            dst = c->side.lf.as<float>();
             st_dst = c->inp.state[1].as<unsigned char>();
         }
         if (l) HIPCK(c, hipMemsetAsync(d_cnt + kCntRemain, 0, 3 * sizeof(unsigned long long), c->stream));
@@ -284,8 +239,9 @@ int fill(lfbm5d_ctx* c, const Shape& s, const float* d_in, const unsigned char* 
         filled_before = filled;
     }
     if (src != d_out) {
-        if (copy_sais(c, h_mask, asize, d_out, src, img, sizeof(float))) return 1;
-        if (d_flags_out && copy_sais(c, h_mask, asize, d_flags_out, st_src, img, 1)) return 1;
+        const auto nonempty = [&](unsigned st) { return h_mask[st] != 0; };
+        if (copy_sais(c, asize, d_out, src, img, sizeof(float), nonempty)) return 1;
+        if (d_flags_out && copy_sais(c, asize, d_flags_out, st_src, img, 1, nonempty)) return 1;
         HIPCK(c, hipStreamSynchronize(c->stream));
         if (d_flags_out) st_src = d_flags_out;
     }
@@ -300,22 +256,13 @@ int fill(lfbm5d_ctx* c, const Shape& s, const float* d_in, const unsigned char* 
 int check_buffers(lfbm5d_ctx* c, const std::string& who, const float* d_in, const unsigned char* d_flags_in, const unsigned* h_mask,
                   float* d_out, unsigned char* d_flags_out, unsigned asize, unsigned W, unsigned H, unsigned C) {
     if (!d_in || !d_flags_in || !h_mask || !d_out) return fail(c, who + "NULL pointer for a required buffer");
-    if (C != 1 && C != 3) return fail(c, who + "chnls must be 1 or 3");
+    if (check_chnls(c, who, C)) return 1;
     const size_t values = (size_t)asize * C * W * H;
     if (overlap(d_in, values * sizeof(float), d_out, values * sizeof(float)))
         return fail(c, who + "d_out must not overlap d_in (neighbours are read across tile edges)");
     if (d_flags_out && overlap(d_flags_in, values, d_flags_out, values))
         return fail(c, who + "d_flags must not overlap d_flags_in (neighbours are read across tile edges)");
     return 0;
-}
-
-const char* check_loop(const lfbm5d_inpaint_params* ip) {
-    if (!ip->iterations) return nullptr;
-    if (ip->iterations > 1000) return "iterations must be at most 1000";
-    if (!(ip->sigma_start > 0.0f) || !(ip->sigma_end > 0.0f) || !std::isfinite(ip->sigma_start)) return "sigma_start and sigma_end must be positive";
-    if (ip->sigma_end > ip->sigma_start) return "sigma_end must not exceed sigma_start";
-    if (!(ip->sigma_noise >= 0.0f) || !std::isfinite(ip->sigma_noise)) return "sigma_noise must be finite and not negative";
-    return nullptr;
 }
 
 /* include/lfbm5d.h, lfbm5d_inpaint_device */
@@ -325,30 +272,21 @@ int inpaint(lfbm5d_ctx* c, const std::string& who, const lfbm5d_inpaint_params* 
     if (!ip || !P) return fail(c, who + "NULL pointer for a required buffer");
     const unsigned asize = awidth * aheight;
     if (check_buffers(c, who, d_in, d_flags_in, h_mask, d_out, d_flags_out, asize, W, H, C)) return 1;
-    if (const char* m = check_loop(ip)) return fail(c, who + m);
+    const LoopSchedule sched = {ip->iterations, ip->sigma_start, ip->sigma_end, ip->sigma_noise};
+    if (const char* m = check_schedule(sched)) return fail(c, who + m);
     Shape s;
-    if (prepare(c, who, h_mask, asize, W, H, C, s)) return 1;
+    if (prepare_tiled(c, who, kOneGpu, h_mask, asize, W, H, C, kMaxPlane, s)) return 1;
     lfbm5d_inpaint_result r;
     const unsigned char* d_codes = nullptr;
     if (fill(c, s, d_in, d_flags_in, h_mask, d_out, d_flags_out, asize, W, H, C, r, &d_codes)) return 1;
     if (res) *res = r;
-    const unsigned K = ip->iterations;
-    if (!K) return 0;
+    if (!sched.iterations) return 0;
     if (r.left[0] + r.left[1] + r.left[2])
         return fail(c, who + "a channel plane without one sound value cannot be refined (mask its SAI as empty, or run the fill alone)");
-    const size_t bytes = (size_t)asize * C * W * H * sizeof(float);
-    HIPCK(c, c->inp.tmp.reserve(bytes));
-    float* z = c->inp.tmp.as<float>();
-    if (s.nne < asize) HIPCK(c, hipMemsetAsync(z, 0, bytes, c->stream));   /* the step is handed defined values in empty SAIs too */
-    const double s0 = (double)ip->sigma_start, s1 = (double)ip->sigma_end;
-    for (unsigned k = 1; k <= K; k++) {
-        if (project(c, s, d_codes, d_out, d_in, z, W, H, C)) return 1;       /* x_{k-1}, into the scratch the step may mutate */
-        HIPCK(c, hipStreamSynchronize(c->stream));                          /* the step's contract: its buffers are ready on entry */
-        lfbm5d_params Pk = *P;
-        const double tau = K == 1 ? s0 : s0 * std::pow(s1 / s0, (double)(k - 1) / (double)(K - 1));
-        Pk.sigma = (float)std::max(tau, (double)ip->sigma_noise);
-        if (run_step(c, 1, &Pk, z, h_mask, nullptr, d_out, ang_major, awidth, aheight, an, W, H, C)) return 1;   /* b_k */
-    }
+    /* the step's input is x_{k-1} = flag ? b_{k-1} : y; its output b_k goes over d_out (the fill's result is in d_out by now, so the
+     * scratch the fill's odd launches wrote is free) */
+    if (refine_loop(c, sched, P, h_mask, s.nne, d_out, ang_major, awidth, aheight, an, W, H, C,
+                    [&](unsigned, float* z) { return project(c, s, d_codes, d_out, d_in, z, W, H, C); }, [](unsigned) { return 0; })) return 1;
     if (project(c, s, d_codes, d_out, d_in, d_out, W, H, C)) return 1;       /* x_K */
     HIPCK(c, hipStreamSynchronize(c->stream));
     return 0;
@@ -372,7 +310,7 @@ int lfbm5d_inpaint_fill_device(lfbm5d_ctx* c, const float* d_in, const unsigned 
     const std::string who = "lfbm5d_inpaint_fill_device: ";
     if (check_buffers(c, who, d_in, d_flags_in, h_mask, d_out, d_flags, asize, W, H, C)) return 1;
     Shape s;
-    if (prepare(c, who, h_mask, asize, W, H, C, s)) return 1;
+    if (prepare_tiled(c, who, kOneGpu, h_mask, asize, W, H, C, kMaxPlane, s)) return 1;
     lfbm5d_inpaint_result r;
     const unsigned char* d_codes = nullptr;
     if (fill(c, s, d_in, d_flags_in, h_mask, d_out, d_flags, asize, W, H, C, r, &d_codes)) return 1;
@@ -386,7 +324,7 @@ int lfbm5d_inpaint_project_device(lfbm5d_ctx* c, const unsigned char* d_flags, c
     const std::string who = "lfbm5d_inpaint_project_device: ";
     if (!d_flags || !d_x || !d_y || !d_out) return fail(c, who + "NULL pointer for a required buffer");
     Shape s;
-    if (prepare(c, who, h_mask, asize, W, H, C, s)) return 1;
+    if (prepare_tiled(c, who, kOneGpu, h_mask, asize, W, H, C, kMaxPlane, s)) return 1;
     if (project(c, s, d_flags, d_x, d_y, d_out, W, H, C)) return 1;
     HIPCK(c, hipStreamSynchronize(c->stream));
     return 0;
@@ -406,30 +344,21 @@ int lfbm5d_inpaint_host_sai(lfbm5d_ctx* c, const lfbm5d_inpaint_params* ip, cons
     if (!c) return 1;
     const std::string who = "lfbm5d_inpaint_host_sai: ";
     if (!ip || !P || !h_in || !h_flags_in || !h_out || !h_mask) return fail(c, who + "NULL pointer for a required buffer");
-    if (C != 1 && C != 3) return fail(c, who + "chnls must be 1 or 3");
+    if (check_chnls(c, who, C)) return 1;
     const unsigned asize = awidth * aheight;
     const size_t img = (size_t)C * W * H, all = std::max<size_t>(1, (size_t)asize * img);
-    for (unsigned st = 0; st < asize; st++)
-        if (h_mask[st] && (!h_in[st] || !h_flags_in[st] || !h_out[st] || (h_flags && !h_flags[st])))
-            return fail(c, who + "NULL pointer for a non-empty SAI");
+    const auto nonempty = [&](unsigned st) { return h_mask[st] != 0; };
+    if (check_planes(c, who, h_out, asize, nonempty) || (h_flags && check_planes(c, who, h_flags, asize, nonempty))) return 1;
     (void)hipSetDevice(c->device);
     HIPCK(c, c->h2d_noisy.reserve(all * sizeof(float)));
     HIPCK(c, c->h2d_out.reserve(all * sizeof(float)));
     HIPCK(c, c->inp.flags.reserve(2 * all));
     float* const din = c->h2d_noisy.as<float>(); float* const dout = c->h2d_out.as<float>();
     unsigned char* const dfi = c->inp.flags.as<unsigned char>(); unsigned char* const dfo = dfi + all;
-    for (unsigned st = 0; st < asize; st++) {
-        if (!h_mask[st]) continue;
-        HIPCK(c, hipMemcpyAsync(din + (size_t)st * img, h_in[st], img * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        HIPCK(c, hipMemcpyAsync(dfi + (size_t)st * img, h_flags_in[st], img, hipMemcpyHostToDevice, c->stream));
-    }
+    if (upload_planes(c, who, h_in, din, asize, img, nonempty) || upload_planes(c, who, h_flags_in, dfi, asize, img, nonempty)) return 1;
     HIPCK(c, hipStreamSynchronize(c->stream));
     if (inpaint(c, who, ip, P, din, dfi, h_mask, dout, h_flags ? dfo : nullptr, ang_major, awidth, aheight, an, W, H, C, out)) return 1;
-    for (unsigned st = 0; st < asize; st++) {
-        if (!h_mask[st]) continue;
-        HIPCK(c, hipMemcpyAsync(h_out[st], dout + (size_t)st * img, img * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        if (h_flags) HIPCK(c, hipMemcpyAsync(h_flags[st], dfo + (size_t)st * img, img, hipMemcpyDeviceToHost, c->stream));
-    }
+    if (download_planes(c, h_out, dout, asize, img, nonempty) || (h_flags && download_planes(c, h_flags, dfo, asize, img, nonempty))) return 1;
     HIPCK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -22,7 +22,7 @@
  * cancels about 14 bits) leaves ~1e-12 relative.  Determinism: every sum runs in a fixed order (no atomics): two calls, and the
  * device and host forms, give the same bits.  The input is only read.
  */
-#include "lfbm5d_ctx.h"
+#include "lfbm5d_side.h"
 
 using namespace lfbm5d_host;
 
@@ -290,23 +290,18 @@ void split_statistic(unsigned d, const double* lam, double* sigma, unsigned* com
 
 int noise_level(lfbm5d_ctx* c, const float* d_lf, const float* const* h_lf, const unsigned* h_mask, unsigned asize, unsigned W, unsigned H,
                 unsigned C, unsigned patch, lfbm5d_noise_level* out, double* h_sigma_sai, double* h_eigen) {
-    const char* who = h_lf ? "lfbm5d_noise_level_host_sai: " : "lfbm5d_noise_level_device: ";
-    if (!h_mask || !out || (!d_lf && !h_lf)) return fail(c, std::string(who) + "NULL pointer for a required buffer");
+    const std::string who = h_lf ? "lfbm5d_noise_level_host_sai: " : "lfbm5d_noise_level_device: ";
+    if (!h_mask || !out || (!d_lf && !h_lf)) return fail(c, who + "NULL pointer for a required buffer");
     const unsigned R = patch ? patch : 8;
-    if (C != 1 && C != 3) return fail(c, std::string(who) + "chnls must be 1 or 3");
-    if (R < 4 || R > 8) return fail(c, std::string(who) + "patch must be 4..8 (0 = 8)");
-    if (W < 2 * R || H < 2 * R) return fail(c, std::string(who) + "width and height must be at least twice the patch");
-    std::vector<unsigned> sai;
-    for (unsigned st = 0; st < asize; st++) if (h_mask[st]) sai.push_back(st);
-    if (sai.empty()) return fail(c, std::string(who) + "the mask has no non-empty SAI");
-    if (h_lf)
-        for (unsigned st : sai) if (!h_lf[st]) return fail(c, std::string(who) + "NULL pointer for a non-empty SAI");
-    (void)hipSetDevice(c->device);
+    if (check_chnls(c, who, C)) return 1;
+    if (R < 4 || R > 8) return fail(c, who + "patch must be 4..8 (0 = 8)");
+    if (check_size(c, who, W, H, 2 * R, "be at least twice the patch")) return 1;
+    if (sai_list(c, who, h_mask, asize)) return 1;
+    const std::vector<unsigned>& sai = c->side.sai_host;
     const unsigned nne = (unsigned)sai.size(), nac = nne * C, D = R * R, DD = D * D, NL = (unsigned)n_lags((int)R), K = 2 * R - 1;
     const unsigned nstrips = (W + kStrip - 1) / kStrip, nmat = 1 + C + (h_sigma_sai ? nne : 0);
     const size_t img = (size_t)C * W * H;
     lfbm5d_ctx::NoiseBufs& B = c->noise;
-    HIPCK(c, B.sai.reserve(nne * sizeof(unsigned)));
     HIPCK(c, B.part.reserve((size_t)nac * nstrips * NL * sizeof(double)));
     HIPCK(c, B.cells.reserve((size_t)nac * NL * K * K * sizeof(double)));
     HIPCK(c, B.m.reserve((size_t)nac * DD * sizeof(double)));
@@ -314,12 +309,10 @@ int noise_level(lfbm5d_ctx* c, const float* d_lf, const float* const* h_lf, cons
     const float* lf = d_lf;
     if (h_lf) {   /* stage the non-empty SAIs through HBM, at their places in [asize][C*H*W] */
         HIPCK(c, c->h2d_noisy.reserve((size_t)asize * img * sizeof(float)));
-        for (unsigned st : sai)
-            HIPCK(c, hipMemcpyAsync(c->h2d_noisy.as<float>() + (size_t)st * img, h_lf[st], img * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        if (upload_planes(c, who, h_lf, c->h2d_noisy.as<float>(), asize, img, [&](unsigned st) { return h_mask[st] != 0; })) return 1;
         lf = c->h2d_noisy.as<float>();
     }
-    HIPCK(c, hipMemcpyAsync(B.sai.p, sai.data(), nne * sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
-    const unsigned* ds = B.sai.as<unsigned>();
+    const unsigned* ds = c->side.sai.as<unsigned>();
     double *part = B.part.as<double>(), *cells = B.cells.as<double>(), *M = B.m.as<double>();
     switch (R) {
         case 4: launch<4>(c->stream, lf, ds, nac, C, W, H, nstrips, part, cells, M); break;
@@ -350,7 +343,7 @@ int noise_level(lfbm5d_ctx* c, const float* d_lf, const float* const* h_lf, cons
         for (unsigned i = 0; i < nmat; i += nt) solve(i);
         for (auto& x : th) x.join();
     }
-    for (unsigned i = 0; i < nmat; i++) if (!ok[i]) return fail(c, std::string(who) + "eigenvalue iteration did not converge");
+    for (unsigned i = 0; i < nmat; i++) if (!ok[i]) return fail(c, who + "eigenvalue iteration did not converge");
     std::memset(out, 0, sizeof(*out));
     out->sigma = sig[0];
     for (unsigned ch = 0; ch < C; ch++) out->sigma_channel[ch] = sig[1 + ch];

@@ -17,9 +17,7 @@
  *                  SAI x channel); planes of empty SAIs are not touched; in place is fine (pointwise).
  * The fit of (a, b) to a histogram (quantile of |d| per level -> variance per level -> weighted line) runs on the host in double.
  */
-#include "lfbm5d_ctx.h"
-
-#include <cstdint>
+#include "lfbm5d_side.h"
 
 using namespace lfbm5d_host;
 
@@ -185,33 +183,15 @@ bool coefficients(const lfbm5d_pg_model* m, unsigned C, PgCoef& k) {
     return std::isfinite(k.s) && k.s > 0.0;
 }
 
-int one_gpu(lfbm5d_ctx* c, const std::string& who) {
-    if (c->world > 1 || c->comm || c->ipc) return fail(c, who + "the Poisson-Gaussian routines run on one GPU (this context has a communicator or a shard)");
-    return 0;
-}
-
-/* the non-empty SAIs of the mask, on the host and (B.sai) on the device; 1 with a message when there is none */
-int sai_list(lfbm5d_ctx* c, const std::string& who, const unsigned* h_mask, unsigned asize, std::vector<unsigned>& sai) {
-    sai.clear();
-    for (unsigned st = 0; st < asize; st++) if (h_mask[st]) sai.push_back(st);
-    if (sai.empty()) return fail(c, who + "the mask has no non-empty SAI");
-    (void)hipSetDevice(c->device);
-    HIPCK(c, c->pg.sai.reserve(sai.size() * sizeof(unsigned)));
-    HIPCK(c, hipMemcpyAsync(c->pg.sai.p, sai.data(), sai.size() * sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));   /* the list leaves a stack object */
-    return 0;
-}
+constexpr const char* kOneGpu = "the Poisson-Gaussian routines run on one GPU (this context has a communicator or a shard)";
 
 /* hist [C][64][322], sum [C][64] (host, unsigned 64-bit) of the light field in HBM */
 int histogram(lfbm5d_ctx* c, const std::string& who, const float* d_lf, const unsigned* h_mask, unsigned asize, unsigned W, unsigned H, unsigned C,
               unsigned long long* h_hist, unsigned long long* h_sum, unsigned long long* blocks, unsigned long long* skipped) {
     if (!d_lf || !h_mask || !h_hist || !h_sum) return fail(c, who + "NULL pointer for a required buffer");
-    if (C != 1 && C != 3) return fail(c, who + "chnls must be 1 or 3");
-    if (W < 2 || H < 2) return fail(c, who + "width and height must be at least 2");
-    if (one_gpu(c, who)) return 1;
-    std::vector<unsigned> sai;
-    if (sai_list(c, who, h_mask, asize, sai)) return 1;
-    const unsigned nne = (unsigned)sai.size();
+    if (check_chnls(c, who, C) || check_size(c, who, W, H, 2, "be at least 2") || check_one_gpu(c, who, kOneGpu)) return 1;
+    if (sai_list(c, who, h_mask, asize)) return 1;
+    const unsigned nne = (unsigned)c->side.sai_host.size();
     const size_t nh = (size_t)C * kLevels * kKeys, ns = (size_t)C * kLevels, words = nh + ns + 1;
     HIPCK(c, c->pg.stats.reserve(words * sizeof(unsigned long long)));
     unsigned long long* d = c->pg.stats.as<unsigned long long>();
@@ -224,8 +204,8 @@ int histogram(lfbm5d_ctx* c, const std::string& who, const float* d_lf, const un
     const bool vec = W % 2 == 0 && reinterpret_cast<uintptr_t>(d_lf) % 8 == 0;
     const void* fn = vec ? reinterpret_cast<const void*>(&k_pg_stats<true>) : reinterpret_cast<const void*>(&k_pg_stats<false>);
     HIPCK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPgLds));   /* per device: cheap, so every call */
-    if (vec) hipLaunchKernelGGL((k_pg_stats<true>), dim3(wgs, C), dim3(kPgThreads), kPgLds, c->stream, d_lf, c->pg.sai.as<unsigned>(), nne, C, W, H, d, d + nh, d + nh + ns);
-    else hipLaunchKernelGGL((k_pg_stats<false>), dim3(wgs, C), dim3(kPgThreads), kPgLds, c->stream, d_lf, c->pg.sai.as<unsigned>(), nne, C, W, H, d, d + nh, d + nh + ns);
+    if (vec) hipLaunchKernelGGL((k_pg_stats<true>), dim3(wgs, C), dim3(kPgThreads), kPgLds, c->stream, d_lf, c->side.sai.as<unsigned>(), nne, C, W, H, d, d + nh, d + nh + ns);
+    else hipLaunchKernelGGL((k_pg_stats<false>), dim3(wgs, C), dim3(kPgThreads), kPgLds, c->stream, d_lf, c->side.sai.as<unsigned>(), nne, C, W, H, d, d + nh, d + nh + ns);
     HIPCK(c, hipGetLastError());
     std::vector<unsigned long long> host(words);
     HIPCK(c, hipMemcpyAsync(host.data(), d, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
@@ -240,7 +220,7 @@ int histogram(lfbm5d_ctx* c, const std::string& who, const float* d_lf, const un
 int estimate(lfbm5d_ctx* c, const std::string& who, const float* d_lf, const unsigned* h_mask, unsigned asize, unsigned W, unsigned H, unsigned C,
              lfbm5d_pg_estimate* out, unsigned long long* h_hist, unsigned long long* h_sum) {
     if (!out) return fail(c, who + "NULL pointer for a required buffer");
-    if (C != 1 && C != 3) return fail(c, who + "chnls must be 1 or 3");
+    if (check_chnls(c, who, C)) return 1;
     std::vector<unsigned long long> hist((size_t)C * kLevels * kKeys), sum((size_t)C * kLevels);
     unsigned long long blocks = 0, skipped = 0;
     if (histogram(c, who, d_lf, h_mask, asize, W, H, C, hist.data(), sum.data(), &blocks, &skipped)) return 1;
@@ -265,11 +245,10 @@ int estimate(lfbm5d_ctx* c, const std::string& who, const float* d_lf, const uns
 /* the non-empty SAIs at their places in [asize][C*H*W] of the context's staging buffer */
 int stage(lfbm5d_ctx* c, const std::string& who, const float* const* h_lf, const unsigned* h_mask, unsigned asize, size_t img, DevBuf& buf) {
     if (!h_lf || !h_mask) return fail(c, who + "NULL pointer for a required buffer");
-    for (unsigned st = 0; st < asize; st++) if (h_mask[st] && !h_lf[st]) return fail(c, who + "NULL pointer for a non-empty SAI");
+    const auto nonempty = [&](unsigned st) { return h_mask[st] != 0; };
     (void)hipSetDevice(c->device);
     HIPCK(c, buf.reserve(std::max<size_t>(1, (size_t)asize * img) * sizeof(float)));
-    for (unsigned st = 0; st < asize; st++)
-        if (h_mask[st]) HIPCK(c, hipMemcpyAsync(buf.as<float>() + (size_t)st * img, h_lf[st], img * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (upload_planes(c, who, h_lf, buf.as<float>(), asize, img, nonempty)) return 1;
     HIPCK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -281,7 +260,7 @@ int transform(lfbm5d_ctx* c, const std::string& who, const PgCoef& k, const floa
     if (!plane || plane > 0xffffffffull - 256 || (plane + 255) / 256 > 0x7fffffffull || (unsigned long long)nne * C > 65535)
         return fail(c, who + "light field too large (or empty)");
     hipLaunchKernelGGL((k_pg_transform<INVERSE>), dim3((unsigned)((plane + 255) / 256), nne * C), dim3(256), 0, c->stream, d_in, d_out,
-                       c->pg.sai.as<unsigned>(), C, (unsigned)plane, k);
+                       c->side.sai.as<unsigned>(), C, (unsigned)plane, k);
     HIPCK(c, hipGetLastError());
     return 0;
 }
@@ -291,13 +270,11 @@ int transform_entry(lfbm5d_ctx* c, const char* name, const lfbm5d_pg_model* mode
                     unsigned asize, unsigned W, unsigned H, unsigned C) {
     const std::string who = std::string(name) + ": ";
     if (!model || !d_in || !h_mask || !d_out) return fail(c, who + "NULL pointer for a required buffer");
-    if (C != 1 && C != 3) return fail(c, who + "chnls must be 1 or 3");
+    if (check_chnls(c, who, C)) return 1;
     PgCoef k;
     if (!coefficients(model, C, k)) return fail(c, who + "bad model: every channel needs a >= 0 and 3/8 a^2 + b > 0, finite");
-    if (one_gpu(c, who)) return 1;
-    std::vector<unsigned> sai;
-    if (sai_list(c, who, h_mask, asize, sai)) return 1;
-    if (transform<INVERSE>(c, who, k, d_in, d_out, (unsigned)sai.size(), W, H, C)) return 1;
+    if (check_one_gpu(c, who, kOneGpu) || sai_list(c, who, h_mask, asize)) return 1;
+    if (transform<INVERSE>(c, who, k, d_in, d_out, (unsigned)c->side.sai_host.size(), W, H, C)) return 1;
     HIPCK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -306,9 +283,7 @@ int denoise_pg(lfbm5d_ctx* c, const std::string& who, const lfbm5d_pg_model* mod
                const lfbm5d_params* P2, const float* d_noisy, const unsigned* h_mask, float* d_basic, float* d_denoised, unsigned ang_major,
                unsigned awidth, unsigned aheight, unsigned an1, unsigned an2, unsigned W, unsigned H, unsigned C) {
     if (!P1 || !P2 || !d_noisy || !h_mask || !d_basic || !d_denoised) return fail(c, who + "NULL pointer for a required buffer");
-    if (C != 1 && C != 3) return fail(c, who + "chnls must be 1 or 3");
-    if (W < 2 || H < 2) return fail(c, who + "width and height must be at least 2");
-    if (one_gpu(c, who)) return 1;
+    if (check_chnls(c, who, C) || check_size(c, who, W, H, 2, "be at least 2") || check_one_gpu(c, who, kOneGpu)) return 1;
     const unsigned asize = awidth * aheight;
     lfbm5d_pg_model m;
     if (model) m = *model;
@@ -320,13 +295,10 @@ int denoise_pg(lfbm5d_ctx* c, const std::string& who, const lfbm5d_pg_model* mod
     PgCoef k;
     if (!coefficients(&m, C, k)) return fail(c, who + "bad model: every channel needs a >= 0 and 3/8 a^2 + b > 0, finite");
     if (used) *used = m;
-    std::vector<unsigned> sai;
-    if (sai_list(c, who, h_mask, asize, sai)) return 1;
-    const unsigned nne = (unsigned)sai.size();
-    const size_t bytes = (size_t)asize * C * W * H * sizeof(float);
-    HIPCK(c, c->pg.lf.reserve(bytes));
-    float* t = c->pg.lf.as<float>();
-    if (nne < asize) HIPCK(c, hipMemsetAsync(t, 0, bytes, c->stream));   /* the job is handed defined values in empty SAIs too */
+    if (sai_list(c, who, h_mask, asize)) return 1;
+    const unsigned nne = (unsigned)c->side.sai_host.size();
+    float* t = nullptr;                                                   /* the stabilised light field: the job's input */
+    if (scratch_lf(c, asize, nne, (size_t)C * W * H, t)) return 1;
     if (transform<false>(c, who, k, d_noisy, t, nne, W, H, C)) return 1;
     HIPCK(c, hipStreamSynchronize(c->stream));                            /* the job's contract: its buffers are ready on entry */
     lfbm5d_params Q1 = *P1, Q2 = *P2;
@@ -370,7 +342,7 @@ int lfbm5d_pg_estimate_host_sai(lfbm5d_ctx* c, const float* const* h_lf, const u
                                 lfbm5d_pg_estimate* out, unsigned long long* h_hist, unsigned long long* h_sum) {
     if (!c) return 1;
     const std::string who = "lfbm5d_pg_estimate_host_sai: ";
-    if (C != 1 && C != 3) return fail(c, who + "chnls must be 1 or 3");
+    if (check_chnls(c, who, C)) return 1;
     if (stage(c, who, h_lf, h_mask, asize, (size_t)C * W * H, c->h2d_noisy)) return 1;
     return estimate(c, who, c->h2d_noisy.as<float>(), h_mask, asize, W, H, C, out, h_hist, h_sum);
 }
@@ -401,22 +373,17 @@ int lfbm5d_denoise_pg_host_sai(lfbm5d_ctx* c, const lfbm5d_pg_model* model, lfbm
     if (!c) return 1;
     const std::string who = "lfbm5d_denoise_pg_host_sai: ";
     if (!h_basic || !h_denoised) return fail(c, who + "NULL pointer for a required buffer");
-    if (C != 1 && C != 3) return fail(c, who + "chnls must be 1 or 3");
+    if (check_chnls(c, who, C)) return 1;
     const unsigned asize = awidth * aheight;
     const size_t img = (size_t)C * W * H;
-    if (h_mask)
-        for (unsigned st = 0; st < asize; st++)
-            if (h_mask[st] && (!h_basic[st] || !h_denoised[st])) return fail(c, who + "NULL pointer for a non-empty SAI");
+    const auto nonempty = [&](unsigned st) { return h_mask[st] != 0; };
+    if (h_mask && (check_planes(c, who, h_basic, asize, nonempty) || check_planes(c, who, h_denoised, asize, nonempty))) return 1;
     if (stage(c, who, h_noisy, h_mask, asize, img, c->h2d_noisy)) return 1;
     HIPCK(c, c->h2d_basic.reserve(std::max<size_t>(1, (size_t)asize * img) * sizeof(float)));
     HIPCK(c, c->h2d_out.reserve(std::max<size_t>(1, (size_t)asize * img) * sizeof(float)));
     float* const db = c->h2d_basic.as<float>(); float* const dd = c->h2d_out.as<float>();
     if (denoise_pg(c, who, model, used, P1, P2, c->h2d_noisy.as<float>(), h_mask, db, dd, ang_major, awidth, aheight, an1, an2, W, H, C)) return 1;
-    for (unsigned st = 0; st < asize; st++) {
-        if (!h_mask[st]) continue;
-        HIPCK(c, hipMemcpyAsync(h_basic[st], db + (size_t)st * img, img * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIPCK(c, hipMemcpyAsync(h_denoised[st], dd + (size_t)st * img, img * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    }
+    if (download_planes(c, h_basic, db, asize, img, nonempty) || download_planes(c, h_denoised, dd, asize, img, nonempty)) return 1;
     HIPCK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -20,7 +20,7 @@
  * fixed order -- two calls, the device and host forms, and SSIM on / off (for the squared error) give the same bits.  The inputs
  * are only read; planes of empty SAIs are not touched.
  */
-#include "lfbm5d_ctx.h"
+#include "lfbm5d_side.h"
 
 using namespace lfbm5d_host;
 
@@ -173,36 +173,30 @@ int quality(lfbm5d_ctx* c, const float* d_ref, const float* d_test, const float*
     const bool host = h_ref || h_test;
     const std::string who = host ? "lfbm5d_quality_host_sai: " : "lfbm5d_quality_device: ";
     if (!h_mask || !out || (host ? (!h_ref || !h_test) : (!d_ref || !d_test))) return fail(c, who + "NULL pointer for a required buffer");
-    if (C != 1 && C != 3) return fail(c, who + "chnls must be 1 or 3");
+    if (check_chnls(c, who, C)) return 1;
     if (!(peak >= 0.0) || !std::isfinite(peak)) return fail(c, who + "peak must be finite and not negative (0 = 255)");
-    if (!W || !H) return fail(c, who + "width and height must not be 0");
-    if (want_ssim && (W < (unsigned)kWin || H < (unsigned)kWin)) return fail(c, who + "width and height must be at least 11 for SSIM");
-    std::vector<unsigned> sai;
-    for (unsigned st = 0; st < asize; st++) if (h_mask[st]) sai.push_back(st);
-    if (sai.empty()) return fail(c, who + "the mask has no non-empty SAI");
-    if (host)
-        for (unsigned st : sai) if (!h_ref[st] || !h_test[st]) return fail(c, who + "NULL pointer for a non-empty SAI");
-    (void)hipSetDevice(c->device);
+    if (check_size(c, who, W, H, 1, "not be 0")) return 1;
+    if (want_ssim && check_size(c, who, W, H, kWin, "be at least 11 for SSIM")) return 1;
+    if (sai_list(c, who, h_mask, asize)) return 1;
+    const std::vector<unsigned>& sai = c->side.sai_host;
+    const auto nonempty = [&](unsigned st) { return h_mask[st] != 0; };
     const unsigned nne = (unsigned)sai.size(), nac = nne * C;
     const unsigned xtiles = W >= (unsigned)kWin ? (W - kWin + 1 + kCols - 1) / kCols : 1, ytiles = H >= (unsigned)kWin ? (H - kWin + 1 + kRows - 1) / kRows : 1;
     if (ytiles > 65535 || xtiles > 65535) return fail(c, who + "width or height too large");
     const size_t img = (size_t)C * W * H;
     lfbm5d_ctx::QualityBufs& Q = c->quality;
-    HIPCK(c, Q.sai.reserve(nne * sizeof(unsigned)));
     HIPCK(c, Q.part.reserve((size_t)nac * xtiles * ytiles * 2 * sizeof(double)));
     HIPCK(c, Q.out.reserve((size_t)nne * 2 * sizeof(double)));
     const float *ref = d_ref, *test = d_test;
     if (host) {   /* stage the non-empty SAIs through HBM, at their places in [asize][C*H*W] */
         HIPCK(c, c->h2d_noisy.reserve((size_t)asize * img * sizeof(float)));
         HIPCK(c, c->h2d_basic.reserve((size_t)asize * img * sizeof(float)));
-        for (unsigned st : sai) {
-            HIPCK(c, hipMemcpyAsync(c->h2d_noisy.as<float>() + (size_t)st * img, h_ref[st], img * sizeof(float), hipMemcpyHostToDevice, c->stream));
-            HIPCK(c, hipMemcpyAsync(c->h2d_basic.as<float>() + (size_t)st * img, h_test[st], img * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        }
+        if (upload_planes(c, who, h_ref, c->h2d_noisy.as<float>(), asize, img, nonempty)) return 1;
+        if (upload_planes(c, who, h_test, c->h2d_basic.as<float>(), asize, img, nonempty)) return 1;
         ref = c->h2d_noisy.as<float>();
         test = c->h2d_basic.as<float>();
     }
-    HIPCK(c, hipMemcpyAsync(Q.sai.p, sai.data(), nne * sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
+    const unsigned* d_sai = c->side.sai.as<unsigned>();
     const double pk = peak == 0.0 ? 255.0 : peak;
     Taps taps;
     double gs = 0.0;
@@ -211,9 +205,9 @@ int quality(lfbm5d_ctx* c, const float* d_ref, const float* d_test, const float*
     const double c1 = (0.01 * pk) * (0.01 * pk), c2 = (0.03 * pk) * (0.03 * pk);
     const dim3 grid(nac, xtiles, ytiles);
     if (want_ssim)
-        hipLaunchKernelGGL((k_quality<true>), grid, dim3(256), 0, c->stream, ref, test, Q.sai.as<unsigned>(), C, W, H, xtiles, ytiles, taps, c1, c2, Q.part.as<double>());
+        hipLaunchKernelGGL((k_quality<true>), grid, dim3(256), 0, c->stream, ref, test, d_sai, C, W, H, xtiles, ytiles, taps, c1, c2, Q.part.as<double>());
     else
-        hipLaunchKernelGGL((k_quality<false>), grid, dim3(256), 0, c->stream, ref, test, Q.sai.as<unsigned>(), C, W, H, xtiles, ytiles, taps, c1, c2, Q.part.as<double>());
+        hipLaunchKernelGGL((k_quality<false>), grid, dim3(256), 0, c->stream, ref, test, d_sai, C, W, H, xtiles, ytiles, taps, c1, c2, Q.part.as<double>());
     hipLaunchKernelGGL(k_quality_reduce, dim3((nne + 63) / 64), dim3(64), 0, c->stream, Q.part.as<double>(), nne, C, xtiles * ytiles, Q.out.as<double>());
     HIPCK(c, hipGetLastError());
     std::vector<double> sums((size_t)nne * 2);

@@ -19,7 +19,7 @@
  *   kUpdate    z = x + beta * U r   (aux = x, high resolution; z may be x itself: an output element reads aux at its own index only)
  * No atomics, every sum in a fixed order: repeated calls return the same bits.  Planes of empty SAIs are neither read nor written.
  */
-#include "lfbm5d_ctx.h"
+#include "lfbm5d_side.h"
 
 using namespace lfbm5d_host;
 
@@ -165,21 +165,12 @@ int ensure(lfbm5d_ctx* c, const char* who, const lfbm5d_sr_params* sr, const uns
            unsigned C, SrOp& up, SrOp& down, unsigned& nne) {
     if (!h_mask) return fail(c, std::string(who) + "NULL pointer for a required buffer");
     if (const char* m = check_operator(sr)) return fail(c, std::string(who) + m);
-    if (C != 1 && C != 3) return fail(c, std::string(who) + "chnls must be 1 or 3");
+    if (check_chnls(c, who, C)) return 1;
     if (w == 0 || h == 0 || asize == 0) return fail(c, std::string(who) + "empty light field");
     lfbm5d_ctx::SrBufs& B = c->sr;
-    std::vector<unsigned> sai;
-    for (unsigned st = 0; st < asize; st++) if (h_mask[st]) sai.push_back(st);
-    if (sai.empty()) return fail(c, std::string(who) + "the mask has no non-empty SAI");
-    if ((size_t)sai.size() * C > 65535) return fail(c, std::string(who) + "more than 65535 planes");
-    (void)hipSetDevice(c->device);
-    if (sai != B.sai_host) {
-        HIPCK(c, B.sai.reserve(sai.size() * sizeof(unsigned)));
-        B.sai_host = sai;
-        HIPCK(c, hipMemcpyAsync(B.sai.p, B.sai_host.data(), sai.size() * sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
-        HIPCK(c, hipStreamSynchronize(c->stream));
-    }
-    nne = (unsigned)sai.size();
+    if (sai_list(c, who, h_mask, asize)) return 1;
+    nne = (unsigned)c->side.sai_host.size();
+    if ((size_t)nne * C > 65535) return fail(c, std::string(who) + "more than 65535 planes");
     unsigned bits; std::memcpy(&bits, &sr->blur_sigma, sizeof(bits));
     const unsigned key[5] = {sr->scale, sr->kernel, sr->kernel == LFBM5D_SR_GAUSSIAN ? bits : 0u, w, h};
     const unsigned s = sr->scale, W = w * s, H = h * s;
@@ -225,8 +216,8 @@ void launch(lfbm5d_ctx* c, const SrOp& op, const float* in, float* out, const fl
     const bool is_up = op.wout > op.win;
     const unsigned th = is_up ? kUpH : kDownH;
     const dim3 grid((op.wout + kTileW - 1) / kTileW, (op.hout + th - 1) / th, nne * C);
-    if (is_up) hipLaunchKernelGGL((k_resample<MODE, kUpH, kUpRows, kMaxT>), grid, dim3(256), 0, c->stream, op, in, out, aux, beta, c->sr.sai.as<unsigned>(), C);
-    else hipLaunchKernelGGL((k_resample<MODE, kDownH, kDownRows, kMaxT>), grid, dim3(256), 0, c->stream, op, in, out, aux, beta, c->sr.sai.as<unsigned>(), C);
+    if (is_up) hipLaunchKernelGGL((k_resample<MODE, kUpH, kUpRows, kMaxT>), grid, dim3(256), 0, c->stream, op, in, out, aux, beta, c->side.sai.as<unsigned>(), C);
+    else hipLaunchKernelGGL((k_resample<MODE, kDownH, kDownRows, kMaxT>), grid, dim3(256), 0, c->stream, op, in, out, aux, beta, c->side.sai.as<unsigned>(), C);
 }
 
 /* z = x + beta U (y - D x): two launches; r goes through the context's low-resolution scratch */
@@ -245,25 +236,16 @@ int superres(lfbm5d_ctx* c, const char* who, const lfbm5d_sr_params* sr, const l
     if (!sr || !P || !d_low || !h_mask || !d_high) return fail(c, std::string(who) + "NULL pointer for a required buffer");
     if (const char* m = check_operator(sr)) return fail(c, std::string(who) + m);
     if (const char* m = check_loop(sr)) return fail(c, std::string(who) + m);
-    if (c->world > 1 || c->comm || c->ipc) return fail(c, std::string(who) + "super-resolution runs on one GPU (this context has a communicator)");
+    if (check_one_gpu(c, who, "super-resolution runs on one GPU (this context has a communicator)")) return 1;
     const unsigned asize = awidth * aheight, s = sr->scale, W = w * s, H = h * s;
     SrOp up, down; unsigned nne = 0;
     if (ensure(c, who, sr, h_mask, asize, w, h, C, up, down, nne)) return 1;
-    const size_t hi_bytes = (size_t)asize * C * W * H * sizeof(float);
-    HIPCK(c, c->sr.hi.reserve(hi_bytes));
-    float* z = c->sr.hi.as<float>();
-    if (nne < asize) HIPCK(c, hipMemsetAsync(z, 0, hi_bytes, c->stream));   /* the step is handed defined values in empty SAIs too */
     launch<kPlain>(c, up, d_low, d_high, nullptr, 0.0f, nne, C);            /* x_0 = U y */
     HIPCK(c, hipGetLastError());
-    const unsigned K = sr->iterations;
-    const double s0 = (double)sr->sigma_start, s1 = (double)sr->sigma_end;
-    for (unsigned k = 1; k <= K; k++) {
-        if (backproject(c, up, down, d_low, d_high, z, sr->beta, asize, nne, C)) return 1;
-        HIPCK(c, hipStreamSynchronize(c->stream));                          /* the step's contract: its buffers are ready on entry */
-        lfbm5d_params Pk = *P;
-        Pk.sigma = (float)(K == 1 ? s0 : s0 * std::pow(s1 / s0, (double)(k - 1) / (double)(K - 1)));
-        if (run_step(c, 1, &Pk, z, h_mask, nullptr, d_high, ang_major, awidth, aheight, an, W, H, C)) return 1;   /* x_k */
-    }
+    /* x_k = step(x_{k-1} + beta U (y - D x_{k-1})); no noise floor: the schedule ends at sigma_end */
+    if (refine_loop(c, LoopSchedule{sr->iterations, sr->sigma_start, sr->sigma_end, 0.0f}, P, h_mask, nne, d_high, ang_major, awidth, aheight, an, W,
+                    H, C, [&](unsigned, float* z) { return backproject(c, up, down, d_low, d_high, z, sr->beta, asize, nne, C); },
+                    [](unsigned) { return 0; })) return 1;
     if (sr->close_projection && backproject(c, up, down, d_low, d_high, d_high, sr->beta, asize, nne, C)) return 1;
     HIPCK(c, hipStreamSynchronize(c->stream));
     return 0;
@@ -353,19 +335,17 @@ int lfbm5d_superres_host_sai(lfbm5d_ctx* c, const lfbm5d_sr_params* sr, const lf
     if (!sr || !P || !h_low || !h_mask || !h_high) return fail(c, std::string(who) + "NULL pointer for a required buffer");
     if (const char* m = check_operator(sr)) return fail(c, std::string(who) + m);
     const unsigned asize = awidth * aheight;
-    for (unsigned st = 0; st < asize; st++)
-        if (h_mask[st] && (!h_low[st] || !h_high[st])) return fail(c, std::string(who) + "NULL pointer for a non-empty SAI");
+    const auto nonempty = [&](unsigned st) { return h_mask[st] != 0; };
+    if (check_planes(c, who, h_low, asize, nonempty) || check_planes(c, who, h_high, asize, nonempty)) return 1;   /* before anything is reserved */
     (void)hipSetDevice(c->device);
     const size_t lo = (size_t)C * w * h, hi = lo * sr->scale * sr->scale;
     HIPCK(c, c->h2d_noisy.reserve((size_t)asize * lo * sizeof(float)));
     HIPCK(c, c->h2d_out.reserve((size_t)asize * hi * sizeof(float)));
     float* const d_low = c->h2d_noisy.as<float>(); float* const d_high = c->h2d_out.as<float>();
-    for (unsigned st = 0; st < asize; st++)
-        if (h_mask[st]) HIPCK(c, hipMemcpyAsync(d_low + st * lo, h_low[st], lo * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (upload_planes(c, who, h_low, d_low, asize, lo, nonempty)) return 1;
     HIPCK(c, hipStreamSynchronize(c->stream));
     if (superres(c, who, sr, P, d_low, h_mask, d_high, ang_major, awidth, aheight, an, w, h, C)) return 1;
-    for (unsigned st = 0; st < asize; st++)
-        if (h_mask[st]) HIPCK(c, hipMemcpyAsync(h_high[st], d_high + st * hi, hi * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (download_planes(c, h_high, d_high, asize, hi, nonempty)) return 1;
     HIPCK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

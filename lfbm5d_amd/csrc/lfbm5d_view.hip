@@ -15,17 +15,15 @@
  * Sums in a fixed order from +0, no fused multiply-add, one product with a table entry, integer atomics for the histogram (LDS, then
  * global): the GPU equals tests/view_model.py bit for bit.
  */
-#include "lfbm5d_ctx.h"
-
-#include <cstdint>
+#include "lfbm5d_side.h"
 
 using namespace lfbm5d_host;
+using namespace lfbm5d_side;
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kTW = 64, kTH = 32, kThreads = 256;
 constexpr int kRMax = 7, kDMax = 8, kSrcMax = 24;                /* box radius, disparity, sources at ang_radius 2 */
 constexpr int kEW = kTW + 2 * kRMax, kEH = kTH + 2 * kRMax;      /* the error plane: tile + halo, 78 x 46 */
 constexpr int kPer = kTW * kTH / kThreads;                       /* 8 positions per thread */
@@ -39,15 +37,6 @@ __constant__ float kRecip[kSrcMax + 1] = {
     (float)(1.0 / 10.0), (float)(1.0 / 11.0), (float)(1.0 / 12.0), (float)(1.0 / 13.0), (float)(1.0 / 14.0), (float)(1.0 / 15.0), 0.0625f,
     (float)(1.0 / 17.0), (float)(1.0 / 18.0), (float)(1.0 / 19.0), (float)(1.0 / 20.0), (float)(1.0 / 21.0), (float)(1.0 / 22.0),
     (float)(1.0 / 23.0), (float)(1.0 / 24.0)};
-
-/* coordinate g of the mirrored plane (period 2 (n - 1), no edge repeated) -> 0..n-1; n >= 2; any g (a shift can exceed a narrow plane) */
-__device__ __forceinline__ int mirror(int g, int n) {
-    if ((unsigned)g < (unsigned)n) return g;
-    const int P = 2 * (n - 1);
-    g %= P;
-    if (g < 0) g += P;
-    return g < n ? g : P - g;
-}
 
 /* the sum of the n sources of channel plane c, warped by hypothesis d, at the in-plane position (y, x): ((+0 + w_1) + w_2) + ... */
 __device__ __forceinline__ float warped_sum(const float* __restrict__ in, const int* __restrict__ tab, int n, int d, int c, int C, int y,
@@ -139,21 +128,11 @@ __global__ __launch_bounds__(kThreads) void k_view_sweep(const float* __restrict
     if (tid < kHist && hist[tid]) atomicAdd(&cnt[tid], (unsigned long long)hist[tid]);
 }
 
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + nb && y < x + na;
-}
-
 struct Plan {
     std::vector<int> table;            /* kTabStride ints per synthesised SAI */
     std::vector<unsigned> synth, left; /* indices, increasing */
     unsigned nne = 0;
 };
-
-void coords(unsigned st, unsigned ang_major, unsigned aw, unsigned ah, int& s, int& t) {
-    if (ang_major == LFBM5D_ROWMAJOR) { s = (int)(st / aw); t = (int)(st % aw); }
-    else { s = (int)(st % ah); t = (int)(st / ah); }
-}
 
 const char* check_params(const lfbm5d_view_params* vp) {
     if (vp->max_disparity > (unsigned)kDMax) return "max_disparity must be 0..8";
@@ -162,25 +141,13 @@ const char* check_params(const lfbm5d_view_params* vp) {
     return nullptr;
 }
 
-const char* check_loop(const lfbm5d_view_params* vp) {
-    if (!vp->iterations) return nullptr;
-    if (vp->iterations > 1000) return "iterations must be at most 1000";
-    if (!(vp->sigma_start > 0.0f) || !(vp->sigma_end > 0.0f) || !std::isfinite(vp->sigma_start)) return "sigma_start and sigma_end must be positive";
-    if (vp->sigma_end > vp->sigma_start) return "sigma_end must not exceed sigma_start";
-    if (!(vp->sigma_noise >= 0.0f) || !std::isfinite(vp->sigma_noise)) return "sigma_noise must be finite and not negative";
-    return nullptr;
-}
-
 /* the checks on the host arguments every entry shares, and the source lists; 1 with a message */
 int plan_sources(lfbm5d_ctx* c, const std::string& who, const lfbm5d_view_params* vp, const unsigned* h_mask, const unsigned* h_missing,
          unsigned ang_major, unsigned aw, unsigned ah, unsigned W, unsigned H, unsigned C, Plan& p) {
     if (!vp || !h_mask || !h_missing) return fail(c, who + "NULL pointer for a required buffer");
-    if (C != 1 && C != 3) return fail(c, who + "chnls must be 1 or 3");
-    if (W < 2 || H < 2) return fail(c, who + "width and height must be at least 2");
-    if (ang_major != LFBM5D_ROWMAJOR && ang_major != LFBM5D_COLMAJOR) return fail(c, who + "ang_major must be LFBM5D_ROWMAJOR or LFBM5D_COLMAJOR");
-    if (!aw || !ah) return fail(c, who + "awidth and aheight must be at least 1");
+    if (check_chnls(c, who, C) || check_size(c, who, W, H, 2, "be at least 2") || check_angular(c, who, ang_major, aw, ah)) return 1;
     if (const char* msg = check_params(vp)) return fail(c, who + msg);
-    if (c->world > 1 || c->comm || c->ipc) return fail(c, who + "the view synthesis runs on one GPU (this context has a communicator or a shard)");
+    if (check_one_gpu(c, who, "the view synthesis runs on one GPU (this context has a communicator or a shard)")) return 1;
     const unsigned asize = aw * ah;
     unsigned n_missing = 0;
     for (unsigned st = 0; st < asize; st++) {
@@ -190,23 +157,15 @@ int plan_sources(lfbm5d_ctx* c, const std::string& who, const lfbm5d_view_params
         if (!h_mask[st]) return fail(c, who + "a missing SAI is masked empty (the filter processes a reconstructed SAI: mark it non-empty)");
     }
     if (!n_missing) return fail(c, who + "no SAI is marked missing");
-    if ((unsigned long long)W * H > 0x3fffffffull || (unsigned long long)((W + kTW - 1) / kTW) * ((H + kTH - 1) / kTH) > 0x7fffffffull || asize > 65535)
-        return fail(c, who + "light field too large");
-    const int R = (int)vp->ang_radius;
+    TileGrid g;
+    if (check_tiles(c, who, W, H, asize, 0x3fffffffull, g)) return 1;
     for (unsigned m = 0; m < asize; m++) {
         if (!h_missing[m]) continue;
-        int sm, tm;
-        coords(m, ang_major, aw, ah, sm, tm);
-        int row[kTabStride] = {(int)m, 0};
-        for (unsigned q = 0; q < asize; q++) {
-            if (!h_mask[q] || h_missing[q]) continue;
-            int s, t;
-            coords(q, ang_major, aw, ah, s, t);
-            if (std::abs(s - sm) > R || std::abs(t - tm) > R) continue;
-            int* at = row + 2 + 3 * row[1]++;
-            at[0] = (int)q; at[1] = s - sm; at[2] = t - tm;
+        int row[kTabStride];
+        if (!source_row(m, ang_major, aw, ah, (int)vp->ang_radius, [&](unsigned q) { return h_mask[q] && !h_missing[q]; }, row)) {
+            p.left.push_back(m);
+            continue;
         }
-        if (!row[1]) { p.left.push_back(m); continue; }
         p.synth.push_back(m);
         p.table.insert(p.table.end(), row, row + kTabStride);
     }
@@ -215,7 +174,7 @@ int plan_sources(lfbm5d_ctx* c, const std::string& who, const lfbm5d_view_params
 
 int check_buffers(lfbm5d_ctx* c, const std::string& who, const float* d_in, float* d_out, unsigned asize, unsigned W, unsigned H, unsigned C) {
     if (!d_in || !d_out) return fail(c, who + "NULL pointer for a required buffer");
-    if (C != 1 && C != 3) return fail(c, who + "chnls must be 1 or 3");
+    if (check_chnls(c, who, C)) return 1;
     const size_t bytes = (size_t)asize * C * W * H * sizeof(float);
     if (overlap(d_in, bytes, d_out, bytes)) return fail(c, who + "d_out must not overlap d_in (sources are read across tile edges)");
     return 0;
@@ -245,15 +204,6 @@ int sweep(lfbm5d_ctx* c, const Plan& p, const lfbm5d_view_params* vp, const floa
     return 0;
 }
 
-/* planes of the SAIs with keep(st) of src -> dst (device to device) */
-template <class F>
-int copy_sais(lfbm5d_ctx* c, unsigned asize, float* dst, const float* src, size_t img, F keep) {
-    for (unsigned st = 0; st < asize; st++)
-        if (keep(st))
-            HIPCK(c, hipMemcpyAsync(dst + (size_t)st * img, src + (size_t)st * img, img * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-    return 0;
-}
-
 /* include/lfbm5d.h, lfbm5d_view_device */
 int view(lfbm5d_ctx* c, const std::string& who, const lfbm5d_view_params* vp, const lfbm5d_params* P, const float* d_in, const unsigned* h_mask,
          const unsigned* h_missing, float* d_out, signed char* d_disp, unsigned ang_major, unsigned aw, unsigned ah, unsigned an, unsigned W,
@@ -261,7 +211,8 @@ int view(lfbm5d_ctx* c, const std::string& who, const lfbm5d_view_params* vp, co
     if (!vp || !P) return fail(c, who + "NULL pointer for a required buffer");
     const unsigned asize = aw * ah;
     if (check_buffers(c, who, d_in, d_out, asize, W, H, C)) return 1;
-    if (const char* msg = check_loop(vp)) return fail(c, who + msg);
+    const LoopSchedule sched = {vp->iterations, vp->sigma_start, vp->sigma_end, vp->sigma_noise};
+    if (const char* msg = check_schedule(sched)) return fail(c, who + msg);
     Plan p;
     if (plan_sources(c, who, vp, h_mask, h_missing, ang_major, aw, ah, W, H, C, p)) return 1;
     lfbm5d_view_result r;
@@ -269,27 +220,18 @@ int view(lfbm5d_ctx* c, const std::string& who, const lfbm5d_view_params* vp, co
     if (res) *res = r;
     const size_t img = (size_t)C * W * H;
     const auto sound = [&](unsigned st) { return h_mask[st] && !h_missing[st]; };
-    if (copy_sais(c, asize, d_out, d_in, img, sound)) return 1;             /* x_0: the input with the synthesised SAIs replaced */
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    const unsigned K = vp->iterations;
-    if (!K) return 0;
-    if (r.left) return fail(c, who + "a missing SAI without a source within ang_radius cannot be refined (run the synthesis alone, or widen ang_radius)");
-    const size_t bytes = (size_t)asize * img * sizeof(float);
-    HIPCK(c, c->view.tmp.reserve(bytes));
-    float* z = c->view.tmp.as<float>();
-    if (p.nne < asize) HIPCK(c, hipMemsetAsync(z, 0, bytes, c->stream));   /* the step is handed defined values in empty SAIs too */
-    const double s0 = (double)vp->sigma_start, s1 = (double)vp->sigma_end;
-    for (unsigned k = 1; k <= K; k++) {
-        if (copy_sais(c, asize, z, d_out, img, [&](unsigned st) { return h_mask[st] != 0; })) return 1;   /* x_{k-1}, into the scratch the step may mutate */
-        HIPCK(c, hipStreamSynchronize(c->stream));                          /* the step's contract: its buffers are ready on entry */
-        lfbm5d_params Pk = *P;
-        const double tau = K == 1 ? s0 : s0 * std::pow(s1 / s0, (double)(k - 1) / (double)(K - 1));
-        Pk.sigma = (float)std::max(tau, (double)vp->sigma_noise);
-        if (run_step(c, 1, &Pk, z, h_mask, nullptr, d_out, ang_major, aw, ah, an, W, H, C)) return 1;   /* b_k */
-        if (copy_sais(c, asize, d_out, d_in, img, sound)) return 1;         /* x_k = f ? b_k : y: a selection moves bits, so a copy is one */
+    const auto put_back = [&](unsigned) {                                   /* f ? b : y: a selection moves bits, so a copy is one */
+        if (copy_sais(c, asize, d_out, d_in, img, sizeof(float), sound)) return 1;
         HIPCK(c, hipStreamSynchronize(c->stream));
-    }
-    return 0;
+        return 0;
+    };
+    if (put_back(0)) return 1;                                              /* x_0: the input with the synthesised SAIs replaced */
+    if (!sched.iterations) return 0;
+    if (r.left) return fail(c, who + "a missing SAI without a source within ang_radius cannot be refined (run the synthesis alone, or widen ang_radius)");
+    /* the step's input is x_{k-1}, its output b_k goes over d_out, x_k = f ? b_k : y */
+    return refine_loop(c, sched, P, h_mask, p.nne, d_out, ang_major, aw, ah, an, W, H, C,
+                       [&](unsigned, float* z) { return copy_sais(c, asize, z, d_out, img, sizeof(float), [&](unsigned st) { return h_mask[st] != 0; }); },
+                       put_back);
 }
 
 } /* namespace */
@@ -345,23 +287,20 @@ int lfbm5d_view_host_sai(lfbm5d_ctx* c, const lfbm5d_view_params* vp, const lfbm
     if (!c) return 1;
     const std::string who = "lfbm5d_view_host_sai: ";
     if (!vp || !P || !h_in || !h_out || !h_mask || !h_missing) return fail(c, who + "NULL pointer for a required buffer");
-    if (C != 1 && C != 3) return fail(c, who + "chnls must be 1 or 3");
+    if (check_chnls(c, who, C)) return 1;
     const unsigned asize = awidth * aheight;
     const size_t img = (size_t)C * W * H, plane = (size_t)W * H, all = std::max<size_t>(1, (size_t)asize * img);
-    for (unsigned st = 0; st < asize; st++) {
-        if (!h_mask[st]) continue;
-        if (!h_out[st] || (!h_missing[st] && !h_in[st]) || (h_missing[st] && h_disp && !h_disp[st]))
-            return fail(c, who + "NULL pointer for a non-empty SAI");
-    }
+    const auto nonempty = [&](unsigned st) { return h_mask[st] != 0; };
+    const auto sound = [&](unsigned st) { return h_mask[st] && !h_missing[st]; };
+    const auto missing = [&](unsigned st) { return h_mask[st] && h_missing[st]; };
+    if (check_planes(c, who, h_out, asize, nonempty) || (h_disp && check_planes(c, who, h_disp, asize, missing))) return 1;
     (void)hipSetDevice(c->device);
     HIPCK(c, c->h2d_noisy.reserve(all * sizeof(float)));
     HIPCK(c, c->h2d_out.reserve(all * sizeof(float)));
     if (h_disp) HIPCK(c, c->view.disp.reserve(std::max<size_t>(1, (size_t)asize * plane)));
     float* const din = c->h2d_noisy.as<float>(); float* const dout = c->h2d_out.as<float>();
     signed char* const ddisp = h_disp ? c->view.disp.as<signed char>() : nullptr;
-    for (unsigned st = 0; st < asize; st++)
-        if (h_mask[st] && !h_missing[st])
-            HIPCK(c, hipMemcpyAsync(din + (size_t)st * img, h_in[st], img * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (upload_planes(c, who, h_in, din, asize, img, sound)) return 1;
     HIPCK(c, hipStreamSynchronize(c->stream));
     lfbm5d_view_result r;
     std::memset(&r, 0, sizeof(r));
@@ -371,12 +310,9 @@ int lfbm5d_view_host_sai(lfbm5d_ctx* c, const lfbm5d_view_params* vp, const lfbm
     /* an SAI that was left (K = 0 only) was not written on the device: its host planes stay as they are */
     Plan p;
     if (r.left && plan_sources(c, who, vp, h_mask, h_missing, ang_major, awidth, aheight, W, H, C, p)) return 1;
-    for (unsigned st = 0; st < asize; st++) {
-        if (!h_mask[st]) continue;
-        if (h_missing[st] && r.left && std::find(p.left.begin(), p.left.end(), st) != p.left.end()) continue;
-        HIPCK(c, hipMemcpyAsync(h_out[st], dout + (size_t)st * img, img * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        if (h_disp && h_missing[st]) HIPCK(c, hipMemcpyAsync(h_disp[st], ddisp + (size_t)st * plane, plane, hipMemcpyDeviceToHost, c->stream));
-    }
+    const auto written = [&](unsigned st) { return h_mask[st] && std::find(p.left.begin(), p.left.end(), st) == p.left.end(); };
+    if (download_planes(c, h_out, dout, asize, img, written)) return 1;
+    if (h_disp && download_planes(c, h_disp, ddisp, asize, plane, [&](unsigned st) { return missing(st) && written(st); })) return 1;
     HIPCK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

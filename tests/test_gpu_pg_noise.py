@@ -289,6 +289,34 @@ def test_job_is_the_three_calls_made_by_hand(ctx):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("C_", [1, 3])
+def test_job_host_forms_with_empty_sais(ctx, C_):
+    """3 x 3 SAIs, column-major, SAI 0 and the centre empty, 67 x 35 pixels (one 64 x 32 tile plus a remainder, width no multiple of 4):
+    the host forms (flat array, one array per SAI with None for the empty ones) return the device form's bits and leave the planes of
+    empty SAIs alone.  The model is given: the light field is too small for the estimate, whose host forms
+    test_estimate_forms_determinism_and_read_only_input compares under a holed mask."""
+    import torch
+    H, W = 35, 67
+    noisy, mask = _noisy_lf(3, C_, H, W, masked=[0, 4])
+    tail = (L.COLMAJOR, 3, 3, 1, 1, W, H, C_)
+    live = mask != 0
+    d = _dev(noisy)
+    basic, den = torch.zeros_like(d), torch.zeros_like(d)
+    model = (2.0, 25.0)
+    used = ctx.denoise_pg(model, P1(1.0), P2(1.0), d, mask, basic, den, *tail)
+    assert np.array_equal(_bits(d), noisy.view(np.uint32))
+    hb, hd = np.full_like(noisy, -7.0), np.full_like(noisy, -7.0)
+    hused = ctx.denoise_pg(model, P1(1.0), P2(1.0), noisy.copy(), mask, hb, hd, *tail)
+    assert list(hused.a) == list(used.a) and list(hused.b) == list(used.b)
+    assert np.array_equal(hb.view(np.uint32)[live], _bits(basic)[live]) and np.array_equal(hd.view(np.uint32)[live], _bits(den)[live])
+    assert (hb[~live] == -7.0).all() and (hd[~live] == -7.0).all()
+    lb, ld = ([np.zeros(noisy.shape[1], np.float32) if mask[i] else None for i in range(9)] for _ in range(2))
+    ctx.denoise_pg(model, P1(1.0), P2(1.0), [noisy[i].copy() if mask[i] else None for i in range(9)], mask, lb, ld, *tail)
+    for i in np.nonzero(live)[0]:
+        assert np.array_equal(lb[i].view(np.uint32), _bits(basic)[i]) and np.array_equal(ld[i].view(np.uint32), _bits(den)[i])
+
+
+@pytest.mark.gpu
 def test_job_on_pure_gaussian_noise_is_the_plain_job(ctx):
     clean = _clean_crop()
     noisy = synth.add_noise_mt19937(clean, 20.0, seed=1)
