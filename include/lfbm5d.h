@@ -688,8 +688,9 @@ int lfbm5d_inpaint_host_sai(lfbm5d_ctx* ctx, const lfbm5d_inpaint_params* params
 /* ---- view synthesis: whole missing sub-aperture images from their angular neighbours, refined by the hard-thresholding step ----
  * Not in the reference.  The stages above repair values; an SAI that is lost, corrupt or too dark, a failed member of a camera array, or the
  * views an angular up-sampling asks for (3 x 3 in, 5 x 5 out) have no sound value at all.  A point seen at x in SAI (s, t) is seen at
- * x + d (ds, dt) in SAI (s + ds, t + dt) with one scalar disparity d: a plane sweep over integer d synthesises the view from its sound
- * neighbours, and the loop of the defect inpainting refines it.  Opt-in.
+ * x + d (ds, dt) in SAI (s + ds, t + dt) with one scalar disparity d: a plane sweep over d synthesises the view from its sound
+ * neighbours, and the loop of the defect inpainting refines it.  d is an integer in the forms below and a multiple of 1 / steps in
+ * the *_steps_* forms ("Sub-pixel disparities").  Opt-in.
  * Data.  Light fields are [asize][C*H*W] float32, channels as stored; C = 1 or 3; W, H >= 2.  h_mask marks non-empty SAIs as everywhere;
  * h_missing is unsigned [asize], non-zero = to be reconstructed.  A missing SAI must be non-empty in h_mask (the filter processes it).  The
  * planes of a missing SAI in d_in are never read.  (s, t) of index st: ROWMAJOR st = s awidth + t, COLMAJOR st = s + t aheight; s moves along
@@ -711,7 +712,24 @@ int lfbm5d_inpaint_host_sai(lfbm5d_ctx* ctx, const lfbm5d_inpaint_params* params
  * Loop.  f = every value of the synthesised SAIs; x_0 = the input with those SAIs replaced; for k = 1..K: b = the basic estimate of
  * lfbm5d_step1_device on a scratch copy of x_{k-1} with P.sigma = max(tau_k, sigma_noise), tau_k on the schedule of the defect inpainting;
  * x_k = f ? b : y.  K = 0 is the synthesis alone.  K >= 1 with an SAI left returns 1 with a message, after `out` is filled in.
- * Limits: integer disparities; occlusions are not modelled; one scalar d per pixel; sources only within ang_radius; which SAIs are bad is
+ * Sub-pixel disparities (the *_steps_* forms, include/lfbm5d_steps.h, with steps = Q in {1, 2, 4}; lenslet cameras, dense arrays and an
+ * angular up-sampling move a fraction of a pixel per view).  Everything above stands but the hypotheses and the warp.
+ * Hypotheses: j in the order 0, -1, +1, ..., -DQ, +DQ, d = j / Q; one replaces the best so far only if E_j < E_best (ties keep the
+ * smaller |j|).
+ * Warp of source q with (ds, dt) = (s_q - s_m, t_q - t_m) at (y, x): ny = Q y - j ds, iy = floor(ny / Q) (floor also for negative ny),
+ * py = ny - Q iy (0 <= py < Q); nx, ix, px the same from x and dt.  py and px depend on (j, ds, dt) alone.  wy = (float)py / Q,
+ * wx = (float)px / Q, both exact.  lerp(a, b, p, w) = a when p = 0, else a + w (b - a): a difference, a product and a sum in that
+ * order, each rounded on its own.  With I the source plane: v00 = I(rho_H(iy), rho_W(ix)), v01 = I(rho_H(iy), rho_W(ix + 1)),
+ * v10 = I(rho_H(iy + 1), rho_W(ix)), v11 = I(rho_H(iy + 1), rho_W(ix + 1)); top = lerp(v00, v01, px, wx), bot = lerp(v10, v11, px, wx),
+ * w_{q,j} = lerp(top, bot, py, wy); with py = 0 bot is neither needed nor read.  rho is applied to every index on its own, so any
+ * shift in any plane of W, H >= 2 is defined.
+ * Hence a hypothesis with j a multiple of Q warps exactly as the integer sweep at d = j / Q, in bits, and steps = 1 is the integer
+ * sweep: the forms without steps are the steps = 1 calls of the *_steps_* forms.
+ * Outputs: d_disp holds j* (d* in units of 1 / Q, |j*| <= 32); the histogram has LFBM5D_VIEW_STEPS_HIST = 65 bins, index j* + 32 for
+ * every Q (h_hist_steps); disparity_hist[17] of the result is filled for steps = 1 and all zero otherwise.
+ * The GPU equals the numpy model of tests/subpel_model.py bit for bit, values and j*.
+ * Limits: bilinear interpolation softens the synthesised view; on noisy sources interpolation lowers the noise of a warped source, so
+ * the cost leans towards fractional hypotheses (profiles/view_subpel.txt); Q <= 4; occlusions are not modelled; one scalar d per pixel; sources only within ang_radius; which SAIs are bad is
  * not decided here (the consistency check below does that); one GPU; every step of
  * the loop filters the whole light field; the defaults are the best row of a sweep on one light field (profiles/view_defaults.txt). */
 typedef struct {
@@ -785,7 +803,10 @@ int lfbm5d_view_host_sai(lfbm5d_ctx* ctx, const lfbm5d_view_params* params, cons
  * false) but meaningless; fill such values first (lfbm5d_inpaint_fill_device under an empty map), as the Python wrapper does.
  * Sums in a fixed order, integer atomics, quantiles on integer histograms: the GPU equals the numpy model of tests/consist_model.py bit
  * for bit in every integer and float it returns, and repeated calls return the same bits.
- * Limits: integer disparities and no occlusion reasoning (the view synthesis'); a defect at the same position with zero disparity in
+ * Sub-pixel disparities (the *_steps_* forms, include/lfbm5d_steps.h): the prediction is the view synthesis' sweep with steps
+ * hypotheses per pixel, d_disp holds j*, and the spread v uses the interpolated warp w_{q,j*} of that section; residual, histograms,
+ * decisions and everything else are unchanged given the prediction.  The GPU equals tests/subpel_model.py bit for bit.
+ * Limits: the view synthesis' (interpolation, Q <= 4, no occlusion reasoning); a defect at the same position with zero disparity in
  * every view is consistent, hence invisible; one noise level for the whole field (no per-SAI noise model); one GPU; the defaults are
  * one row of a sweep on one light field (profiles/consist_defaults.txt). */
 typedef struct {
@@ -873,6 +894,9 @@ int lfbm5d_free(void* dptr);
 int lfbm5d_memcpy_h2d(void* dst, const void* src, size_t bytes);
 int lfbm5d_memcpy_d2h(void* dst, const void* src, size_t bytes);
 int lfbm5d_device_count(void);
+
+/* ---- the sub-pixel forms of the view synthesis and the consistency check (lfbm5d_*_steps_*) ---- */
+#include "lfbm5d_steps.h"
 
 #ifdef __cplusplus
 }

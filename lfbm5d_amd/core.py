@@ -99,6 +99,7 @@ class ImpulseResultStruct(C.Structure):
 
 
 IMPULSE_KEYS = 386
+VIEW_STEPS_HIST = 65    # LFBM5D_VIEW_STEPS_HIST: positions per j*, index j* + 32
 
 
 class InpaintParamsStruct(C.Structure):
@@ -176,7 +177,8 @@ class ViewSynth(NamedTuple):
     """Result of Context.view_fill / Context.view_synth / view_synth: the light field with the missing SAIs reconstructed (a tensor or
     an array like the input), the disparity planes (int8 [asize][H*W], written for the synthesised SAIs; None unless asked for), the
     SAIs marked missing, synthesised and left (no source within ang_radius), the positions of the synthesised SAIs and the positions
-    per disparity (index d + 8)."""
+    per disparity (index d + 8).  With disparity_steps > 1 the disparity planes hold j* = d* in units of 1 / disparity_steps,
+    disparity_hist is all zero and steps_hist holds the positions per j* (65 bins, index j* + 32); steps_hist is None otherwise."""
     out: object
     disparity: object
     missing: int
@@ -184,6 +186,7 @@ class ViewSynth(NamedTuple):
     left: int
     pixels: int
     disparity_hist: tuple
+    steps_hist: tuple = None
 
 
 class Inpaint(NamedTuple):
@@ -404,6 +407,15 @@ def lib():
         L.lfbm5d_view_fill_device.argtypes = [vp, wp, fp, up, up, fp, vp] + [C.c_uint] * 6 + [wr]
         L.lfbm5d_view_device.argtypes = [vp, wp, pp, fp, up, up, fp, vp] + [C.c_uint] * 7 + [wr]
         L.lfbm5d_view_host_sai.argtypes = [vp, wp, pp, vp, up, up, vp, vp] + [C.c_uint] * 7 + [wr]
+    if hasattr(L, "lfbm5d_view_steps_device"):   # the sub-pixel forms: `steps` behind the parameters, the 65-bin histogram at the end
+        wp, wr, pp = C.POINTER(ViewParamsStruct), C.POINTER(ViewResultStruct), C.POINTER(Params)
+        cp, cr = C.POINTER(ConsistParamsStruct), C.POINTER(ConsistResultStruct)
+        ullp, dp = C.POINTER(C.c_ulonglong), C.POINTER(C.c_double)
+        L.lfbm5d_view_fill_steps_device.argtypes = [vp, wp, C.c_uint, fp, up, up, fp, vp] + [C.c_uint] * 6 + [wr, ullp]
+        L.lfbm5d_view_steps_device.argtypes = [vp, wp, C.c_uint, pp, fp, up, up, fp, vp] + [C.c_uint] * 7 + [wr, ullp]
+        L.lfbm5d_view_steps_host_sai.argtypes = [vp, wp, C.c_uint, pp, vp, up, up, vp, vp] + [C.c_uint] * 7 + [wr, ullp]
+        L.lfbm5d_consist_steps_device.argtypes = [vp, cp, C.c_uint, fp, up, up, vp, up, vp, dp, ullp] + [C.c_uint] * 6 + [cr]
+        L.lfbm5d_consist_steps_host_sai.argtypes = [vp, cp, C.c_uint, vp, up, up, vp, up, vp, dp, ullp] + [C.c_uint] * 6 + [cr]
     if hasattr(L, "lfbm5d_consist_device"):   # (absent from older builds loaded through LFBM5D_HIP_LIB for A/B runs)
         cp, cr = C.POINTER(ConsistParamsStruct), C.POINTER(ConsistResultStruct)
         dp, ullp = C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)
@@ -1194,15 +1206,27 @@ class Context:
 
     # ---- view synthesis ----
     @staticmethod
-    def _view_result(out, disp, res):
-        return ViewSynth(out, disp, int(res.missing), int(res.synthesised), int(res.left), int(res.pixels), tuple(res.disparity_hist))
+    def _view_result(out, disp, res, steps_hist=None):
+        return ViewSynth(out, disp, int(res.missing), int(res.synthesised), int(res.left), int(res.pixels), tuple(res.disparity_hist),
+                         None if steps_hist is None else tuple(int(v) for v in steps_hist))
+
+    @staticmethod
+    def _steps(disparity_steps):
+        """(steps, the 65-bin histogram to fill or None, its pointer): the integer forms serve disparity_steps = 1."""
+        steps = int(disparity_steps)
+        if steps == 1:
+            return 1, None, None
+        hist = np.zeros(VIEW_STEPS_HIST, np.uint64)
+        return steps, hist, hist.ctypes.data_as(C.POINTER(C.c_ulonglong))
 
     def view_fill(self, noisy, mask, missing, ang_major, awidth, aheight, width, height, chnls, max_disparity=None, box_radius=None,
-                  ang_radius=None, return_disparity=False, out=None, disparity_out=None):
+                  ang_radius=None, return_disparity=False, out=None, disparity_out=None, disparity_steps=1):
         """The plane-sweep synthesis of lfbm5d_view_fill_device on CUDA tensors: noisy float32 [asize][C*H*W] (only read; the planes of
         the SAIs `missing` marks are never read).  out / disparity_out (int8 [asize][H*W]): optional tensors to write into, distinct
-        from the input; only the planes of the synthesised SAIs are written, a fresh `out` is a copy of the input elsewhere.  Returns a
-        ViewSynth."""
+        from the input; only the planes of the synthesised SAIs are written, a fresh `out` is a copy of the input elsewhere.
+        disparity_steps = 1, 2 or 4 hypotheses per pixel (lfbm5d_view_fill_steps_device; sources are interpolated bilinearly): the
+        result's `disparity` is in units of 1 / disparity_steps, and above 1 its steps_hist is the histogram.  Returns a ViewSynth."""
+        steps, sh, shp = self._steps(disparity_steps)
         m, ms = _u32(mask), _u32(missing)
         vp = view_params(max_disparity, box_radius, ang_radius)
         res = ViewResultStruct()
@@ -1210,22 +1234,28 @@ class Context:
         out = self._dev_out(noisy, out)
         dp = self._dev_planes(noisy, disparity_out, return_disparity, (m.size, int(width) * int(height)), torch.int8)
         up = C.POINTER(C.c_uint)
-        self._ck(self._L.lfbm5d_view_fill_device(self._h, C.byref(vp), _dev_ptr(noisy), m.ctypes.data_as(up), ms.ctypes.data_as(up),
-                                                 _dev_ptr(out), None if dp is None else _dev_ptr(dp, np.int8), ang_major, awidth, aheight,
-                                                 int(width), int(height), int(chnls), C.byref(res)))
-        return self._view_result(out, dp, res)
+        args = (_dev_ptr(noisy), m.ctypes.data_as(up), ms.ctypes.data_as(up), _dev_ptr(out), None if dp is None else _dev_ptr(dp, np.int8),
+                ang_major, awidth, aheight, int(width), int(height), int(chnls), C.byref(res))
+        if steps == 1:
+            self._ck(self._L.lfbm5d_view_fill_device(self._h, C.byref(vp), *args))
+        else:
+            self._ck(self._L.lfbm5d_view_fill_steps_device(self._h, C.byref(vp), steps, *args, shp))
+        return self._view_result(out, dp, res, sh)
 
     def view_synth(self, noisy, mask, missing, P, ang_major, awidth, aheight, an, width, height, chnls, max_disparity=None,
                    box_radius=None, ang_radius=None, iterations=None, sigma_start=None, sigma_end=None, sigma_noise=None,
-                   return_disparity=False, out=None, disparity_out=None):
+                   return_disparity=False, out=None, disparity_out=None, disparity_steps=1):
         """View synthesis (lfbm5d_view_*, include/lfbm5d.h): the SAIs `missing` marks (non-zero; they must be non-empty in `mask`) are
         synthesised from their sound angular neighbours by a plane sweep over the integer disparities -max_disparity..max_disparity
         and refined by `iterations` hard-thresholding steps (P, its sigma replaced by the schedule sigma_start -> sigma_end, not below
         sigma_noise) with the sound SAIs put back after every step; iterations = 0 is the synthesis alone, None the library's
         defaults.  noisy: a CUDA float32 tensor [asize][C*H*W] (device form), or a float32 numpy array of that shape or a list of
         per-SAI arrays, None allowed for missing SAIs (host form, staged through HBM; identical results).  The input is only read.
-        return_disparity: the int8 planes [asize][H*W] of d*.  Returns a ViewSynth."""
+        return_disparity: the int8 planes [asize][H*W] of d*.  disparity_steps = 1, 2 or 4 hypotheses per pixel (the *_steps_* forms;
+        sources are interpolated bilinearly): `disparity` is in units of 1 / disparity_steps, and above 1 the result's steps_hist is
+        the histogram.  Returns a ViewSynth."""
         m, ms = _u32(mask), _u32(missing)
+        steps, sh, shp = self._steps(disparity_steps)
         asize = m.size
         vp = view_params(max_disparity, box_radius, ang_radius, iterations, sigma_start, sigma_end, sigma_noise)
         res = ViewResultStruct()
@@ -1236,20 +1266,26 @@ class Context:
             arrays = self._host_sais(noisy)
             out, outs = self._host_out(arrays, out, m, int(chnls) * int(width) * int(height))
             dp = self._host_planes(arrays, disparity_out, return_disparity, np.int8, int(width) * int(height))
-            self._ck(self._L.lfbm5d_view_host_sai(self._h, C.byref(vp), C.byref(P), _sai_ptrs(arrays, m), mp, msp, _sai_ptrs(outs, m),
-                                                  None if dp is None else _sai_ptrs(dp, m, np.int8), *tail))
+            args = (C.byref(P), _sai_ptrs(arrays, m), mp, msp, _sai_ptrs(outs, m), None if dp is None else _sai_ptrs(dp, m, np.int8), *tail)
+            if steps == 1:
+                self._ck(self._L.lfbm5d_view_host_sai(self._h, C.byref(vp), *args))
+            else:
+                self._ck(self._L.lfbm5d_view_steps_host_sai(self._h, C.byref(vp), steps, *args, shp))
             out, dp = self._stacked(noisy, out), self._stacked(noisy, dp, False)
         else:
             import torch
             out = self._dev_out(noisy, out)
             dp = self._dev_planes(noisy, disparity_out, return_disparity, (asize, int(width) * int(height)), torch.int8)
-            self._ck(self._L.lfbm5d_view_device(self._h, C.byref(vp), C.byref(P), _dev_ptr(noisy), mp, msp, _dev_ptr(out),
-                                                None if dp is None else _dev_ptr(dp, np.int8), *tail))
-        return self._view_result(out, dp, res)
+            args = (C.byref(P), _dev_ptr(noisy), mp, msp, _dev_ptr(out), None if dp is None else _dev_ptr(dp, np.int8), *tail)
+            if steps == 1:
+                self._ck(self._L.lfbm5d_view_device(self._h, C.byref(vp), *args))
+            else:
+                self._ck(self._L.lfbm5d_view_steps_device(self._h, C.byref(vp), steps, *args, shp))
+        return self._view_result(out, dp, res, sh)
 
     # ---- consistency check ----
     def consist(self, noisy, mask, ang_major, awidth, aheight, width, height, chnls, exclude=None, return_disparity=False,
-                flags_out=None, disparity_out=None, fill_nonfinite=True, **params):
+                flags_out=None, disparity_out=None, fill_nonfinite=True, disparity_steps=1, **params):
         """Consistency check (lfbm5d_consist_*, include/lfbm5d.h): every usable SAI is predicted from its angular neighbours by the view
         synthesis' plane sweep with the SAI itself left out; a value is flagged when its residual exceeds k x the light field's median
         residual and spread x the sources' own disagreement, an SAI is bad when its median residual stands out among its neighbours'.
@@ -1257,9 +1293,11 @@ class Context:
         (host form, staged through HBM; identical results).  The input is only read.  exclude: SAIs known bad (non-zero), neither
         tested nor used.  params: the fields of consist_params.  fill_nonfinite: when the input holds a value that is not finite, the
         check runs on a copy with those values filled (inpaint_fill under an empty map) and they are reported with code 2 on top of
-        the library's flags (the counts are the library's).  Returns a Consist, whose flags go to inpaint(...) as the map and whose
-        .missing goes to view_synth(...)."""
+        the library's flags (the counts are the library's).  disparity_steps = 1, 2 or 4 hypotheses per pixel in the sweep (the
+        *_steps_* forms): `disparity` is in units of 1 / disparity_steps.  Returns a Consist, whose flags go to inpaint(...) as the map
+        and whose .missing goes to view_synth(...)."""
         m = _u32(mask)
+        steps = int(disparity_steps)
         asize, C_, W_, H_ = m.size, int(chnls), int(width), int(height)
         P = consist_params(**params)
         res = ConsistResultStruct()
@@ -1268,7 +1306,9 @@ class Context:
         state = np.zeros(asize, np.uint32)
         ssai = np.zeros(asize, np.float64)
         hist = np.zeros((asize, max(C_, 1), IMPULSE_KEYS), np.uint64)
-        head = (self._h, C.byref(P))
+        head = (self._h, C.byref(P)) if steps == 1 else (self._h, C.byref(P), steps)
+        host_sai = self._L.lfbm5d_consist_host_sai if steps == 1 else self._L.lfbm5d_consist_steps_host_sai
+        device = self._L.lfbm5d_consist_device if steps == 1 else self._L.lfbm5d_consist_steps_device
         mid = (m.ctypes.data_as(up), None if ex is None else ex.ctypes.data_as(up))
         tail = (ssai.ctypes.data_as(C.POINTER(C.c_double)), hist.ctypes.data_as(C.POINTER(C.c_ulonglong)), ang_major, awidth, aheight,
                 W_, H_, C_, C.byref(res))
@@ -1287,8 +1327,8 @@ class Context:
                 arrays = [np.ascontiguousarray(filled[i].reshape(np.shape(arrays[i]))) if i in holes else arrays[i] for i in range(asize)]
             fo = self._host_planes(arrays, flags_out, True, np.uint8)
             dp = self._host_planes(arrays, disparity_out, return_disparity, np.int8, W_ * H_)
-            self._ck(self._L.lfbm5d_consist_host_sai(*head, _sai_ptrs(arrays, m), *mid, _sai_ptrs(fo, m, np.uint8), state.ctypes.data_as(up),
-                                                     None if dp is None else _sai_ptrs(dp, m, np.int8), *tail))
+            self._ck(host_sai(*head, _sai_ptrs(arrays, m), *mid, _sai_ptrs(fo, m, np.uint8), state.ctypes.data_as(up),
+                              None if dp is None else _sai_ptrs(dp, m, np.int8), *tail))
             for i, h in holes.items():
                 fo[i][h] = 2
             fo, dp = self._stacked(noisy, fo), self._stacked(noisy, dp, False)
@@ -1302,8 +1342,8 @@ class Context:
                 src = self.inpaint_fill(noisy, torch.zeros(noisy.shape, dtype=torch.uint8, device=noisy.device), m, W_, H_, C_).out
             fo = self._dev_planes(noisy, flags_out, True, noisy.shape, torch.uint8)
             dp = self._dev_planes(noisy, disparity_out, return_disparity, (asize, W_ * H_), torch.int8)
-            self._ck(self._L.lfbm5d_consist_device(*head, _dev_ptr(src), *mid, _dev_ptr(fo, np.uint8), state.ctypes.data_as(up),
-                                                   None if dp is None else _dev_ptr(dp, np.int8), *tail))
+            self._ck(device(*head, _dev_ptr(src), *mid, _dev_ptr(fo, np.uint8), state.ctypes.data_as(up),
+                            None if dp is None else _dev_ptr(dp, np.int8), *tail))
             if hole is not None:
                 fo[hole] = 2
         st = state.astype(np.int64)
@@ -1580,9 +1620,10 @@ def inpaint_probe(noisy, flags, mask, awidth, aheight, width, height, chnls, lam
 
 
 def view_synth_probe(noisy, mask, missing, awidth, aheight, width, height, chnls, lambda_, hard, max_disparity=-1, box_radius=-1, ang_radius=-1,
-                     iterations=-1, sigma_start=0.0, sigma_end=0.0, sigma_noise=0.0, color_space="opp", ang_major=ROWMAJOR, an=1):
+                     iterations=-1, sigma_start=0.0, sigma_end=0.0, sigma_noise=0.0, color_space="opp", ang_major=ROWMAJOR, an=1, disparity_steps=1):
     """The C++ drop-in's view_synth_LF (liblfbm5d_dropin.so, run_bm5d.h) on a vector<vector<float>> light field built from `noisy`
     [asize][chnls*height*width] (the vectors of missing SAIs are left empty); hard = (N, nSim, nDisp, k, p, tau_2D, tau_4D, tau_5D[, useSD]).
+    disparity_steps: view_synth_LF's trailing argument (dmin and dmax are then in units of 1 / disparity_steps).
     Returns (the completed light field, synthesised, left, dmin, dmax)."""
     path = os.path.join(os.path.dirname(library_path()), "liblfbm5d_dropin.so")
     if not os.path.exists(path):
@@ -1597,18 +1638,20 @@ def view_synth_probe(noisy, mask, missing, awidth, aheight, width, height, chnls
     vpi = np.array([max_disparity, box_radius, ang_radius, iterations], np.int32)
     vpf = np.array([sigma_start, sigma_end, sigma_noise, lambda_], np.float32)
     counts = np.zeros(4, np.int32)
-    rc = D.lfbm5d_view_synth_probe(noisy.ctypes.data, m.ctypes.data, ms.ctypes.data, out.ctypes.data, ang_major, awidth, aheight, an, width,
-                                   height, chnls, vpi.ctypes.data, vpf.ctypes.data, hv.ctypes.data,
-                                   _CS[color_space] if isinstance(color_space, str) else int(color_space), counts.ctypes.data)
+    D.lfbm5d_view_synth_steps_probe.argtypes = D.lfbm5d_view_synth_probe.argtypes + [C.c_uint]
+    args = (noisy.ctypes.data, m.ctypes.data, ms.ctypes.data, out.ctypes.data, ang_major, awidth, aheight, an, width, height, chnls,
+            vpi.ctypes.data, vpf.ctypes.data, hv.ctypes.data, _CS[color_space] if isinstance(color_space, str) else int(color_space),
+            counts.ctypes.data)
+    rc = D.lfbm5d_view_synth_probe(*args) if int(disparity_steps) == 1 else D.lfbm5d_view_synth_steps_probe(*args, int(disparity_steps))
     if rc != 0:
         raise LfBm5dError("view_synth_LF failed (message on stdout)")
     return out, int(counts[0]), int(counts[1]), int(counts[2]), int(counts[3])
 
 
 def consist_probe(noisy, mask, awidth, aheight, width, height, chnls, exclude=None, max_disparity=-1, box_radius=-1, ang_radius=-1,
-                  min_sources=-1, max_rounds=-1, k=-1.0, spread=-1.0, sai_factor=-1.0, ang_major=ROWMAJOR):
+                  min_sources=-1, max_rounds=-1, k=-1.0, spread=-1.0, sai_factor=-1.0, ang_major=ROWMAJOR, disparity_steps=1):
     """The C++ drop-in's consist_LF (liblfbm5d_dropin.so, run_bm5d.h) on a vector<vector<float>> light field built from `noisy`
-    [asize][chnls*height*width].  Returns (flags uint8 like noisy, state int64 [asize], flagged, nonfinite, bad, untested, rounds,
+    [asize][chnls*height*width]; disparity_steps: its trailing argument.  Returns (flags uint8 like noisy, state int64 [asize], flagged, nonfinite, bad, untested, rounds,
     the three channel scales)."""
     path = os.path.join(os.path.dirname(library_path()), "liblfbm5d_dropin.so")
     if not os.path.exists(path):
@@ -1623,9 +1666,10 @@ def consist_probe(noisy, mask, awidth, aheight, width, height, chnls, exclude=No
     cpi = np.array([max_disparity, box_radius, ang_radius, min_sources, max_rounds], np.int32)
     cpd = np.array([k, spread, sai_factor], np.float64)
     counts, scales = np.zeros(5, np.uint64), np.zeros(3, np.float64)
-    rc = D.lfbm5d_consist_probe(noisy.ctypes.data, m.ctypes.data, None if ex is None else ex.ctypes.data, flags.ctypes.data, state.ctypes.data,
-                                ang_major, awidth, aheight, width, height, chnls, cpi.ctypes.data, cpd.ctypes.data, counts.ctypes.data,
-                                scales.ctypes.data)
+    D.lfbm5d_consist_steps_probe.argtypes = D.lfbm5d_consist_probe.argtypes + [C.c_uint]
+    args = (noisy.ctypes.data, m.ctypes.data, None if ex is None else ex.ctypes.data, flags.ctypes.data, state.ctypes.data, ang_major, awidth,
+            aheight, width, height, chnls, cpi.ctypes.data, cpd.ctypes.data, counts.ctypes.data, scales.ctypes.data)
+    rc = D.lfbm5d_consist_probe(*args) if int(disparity_steps) == 1 else D.lfbm5d_consist_steps_probe(*args, int(disparity_steps))
     if rc != 0:
         raise LfBm5dError("consist_LF failed (message on stdout)")
     return (flags, state.astype(np.int64)) + tuple(int(v) for v in counts) + (tuple(scales),)

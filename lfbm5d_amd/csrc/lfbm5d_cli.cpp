@@ -60,6 +60,11 @@
  *                     LFBM5D_MISSING's format into <dir>/missing.txt (empty when none is bad), so that a camera's fixed map can be
  *                     reused.  Together with LFBM5D_DEFECTS or LFBM5D_MISSING it is an error (there is no combined loop).  The files
  *                     hold 8-bit values, so nothing here is non-finite.  Unset, the output is unchanged;
+ *   LFBM5D_DISPARITY_STEPS=1|2|4   hypotheses per pixel of disparity in the plane sweeps of LFBM5D_MISSING and LFBM5D_DETECT (sources are
+ *                     interpolated bilinearly above 1; for light fields that move a fraction of a pixel per view).  Above 1 the
+ *                     `View synthesis:` line prints the disparity range as decimals and ends `, <Q> steps per pixel`, and the
+ *                     `Consistency check:` line ends the same.  Any other value, and the variable without LFBM5D_MISSING or
+ *                     LFBM5D_DETECT, is an error.  Unset or 1, the output is unchanged;
  *   LFBM5D_REPORT_SSIM=1  the average SSIM next to every average PSNR on stdout and an SSIM block behind every PSNR block of the
  *                     results file, computed on the GPU on the images as the files hold them (cli_quality.h); any other value is an
  *                     error; unset, the output is unchanged.
@@ -492,14 +497,18 @@ bool missing_mode(vector<unsigned>& missing, int& iter, unsigned ang_major, unsi
  * print the line of the header comment, with the steps that are still to come. */
 bool synthesise_missing_LF(vector<vector<float> >& LF_noisy, const vector<unsigned>& mask, const vector<unsigned>& missing, unsigned ang_major,
                            unsigned aw, unsigned ah, unsigned an, unsigned W, unsigned H, unsigned C, unsigned steps, unsigned steps_to_come,
-                           float sigma_noise, float lambda, const unsigned* hard, unsigned cs, bool report) {
+                           float sigma_noise, float lambda, const unsigned* hard, unsigned cs, bool report, unsigned dsteps) {
     unsigned done = 0, left = 0, all = 0, n = 0; int dmin = 0, dmax = 0;
     if (view_synth_LF(LF_noisy, mask, missing, ang_major, aw, ah, an, W, H, C, -1, -1, -1, (int)steps, 0.0f, 0.0f, sigma_noise, lambda, hard[0],
-                      hard[1], hard[2], hard[3], hard[4], hard[5] != 0, hard[6], hard[7], hard[8], cs, done, left, dmin, dmax) != EXIT_SUCCESS) return false;
+                      hard[1], hard[2], hard[3], hard[4], hard[5] != 0, hard[6], hard[7], hard[8], cs, done, left, dmin, dmax, dsteps) != EXIT_SUCCESS)
+        return false;
     for (size_t st = 0; st < mask.size(); st++) { if (mask[st]) all++; if (missing[st]) n++; }
-    if (report)
+    if (report && dsteps == 1)
         cout << endl << "View synthesis: " << n << " of " << all << " SAIs missing, " << left << " left; disparities " << dmin << ".." << dmax << ", "
              << steps_to_come << " refinement steps" << endl;
+    else if (report)                                                            /* the range is in units of 1 / dsteps: printed in pixels */
+        cout << endl << "View synthesis: " << n << " of " << all << " SAIs missing, " << left << " left; disparities " << dmin / (double)dsteps << ".."
+             << dmax / (double)dsteps << ", " << steps_to_come << " refinement steps, " << dsteps << " steps per pixel" << endl;
     return true;
 }
 
@@ -530,17 +539,32 @@ bool detect_mode(bool& on, double& k, const char*& save) {
     return true;
 }
 
+/* LFBM5D_DISPARITY_STEPS: 1 when unset; false (message printed) on anything but 1, 2 or 4, or without a sweep to apply it to.  After
+ * missing_mode() and detect_mode(). */
+bool disparity_steps_mode(unsigned& dsteps, bool sweeps) {
+    dsteps = 1;
+    const char* e = env("LFBM5D_DISPARITY_STEPS");
+    if (!e) return true;
+    if (strcmp(e, "1") && strcmp(e, "2") && strcmp(e, "4")) {
+        cout << "LFBM5D_DISPARITY_STEPS must be 1, 2 or 4, or unset; got \"" << e << "\"" << endl;
+        return false;
+    }
+    if (!sweeps) { cout << "LFBM5D_DISPARITY_STEPS needs LFBM5D_MISSING or LFBM5D_DETECT" << endl; return false; }
+    dsteps = (unsigned)(e[0] - '0');
+    return true;
+}
+
 /* LFBM5D_DETECT: the check; `missing` receives the bad SAIs (left empty when there is none), `defects` the flag planes (left empty when
  * nothing is flagged); LFBM5D_DETECT_SAVE: the maps and the list */
 bool detect_LF(const vector<vector<float> >& LF_noisy, const vector<unsigned>& mask, double k, const char* save, const char* name, const char* sep,
                unsigned ang_major, unsigned aw, unsigned ah, unsigned s0, unsigned t0, unsigned W, unsigned H, unsigned C, vector<unsigned>& missing,
-               vector<vector<unsigned char> >& defects) {
+               vector<vector<unsigned char> >& defects, unsigned dsteps) {
     vector<unsigned> state;
     vector<vector<unsigned char> > flags;
     unsigned long long flagged = 0, nonfinite = 0, all = 0; unsigned bad = 0, untested = 0, rounds = 0, sais = 0;
     double sc[3] = {0.0, 0.0, 0.0};
     if (consist_LF(LF_noisy, mask, vector<unsigned>(), ang_major, aw, ah, W, H, C, -1, -1, -1, -1, -1, k, -1.0, -1.0, flags, state, flagged, nonfinite, bad,
-                   untested, rounds, sc) != EXIT_SUCCESS) return false;
+                   untested, rounds, sc, dsteps) != EXIT_SUCCESS) return false;
     ostringstream list, line;
     for (unsigned s = 0; s < ah; s++)
         for (unsigned t = 0; t < aw; t++) {
@@ -554,7 +578,9 @@ bool detect_LF(const vector<vector<float> >& LF_noisy, const vector<unsigned>& m
     const unsigned long long n = flagged + nonfinite;
     cout << endl << "Consistency check: " << bad << " of " << sais << " SAIs bad [" << list.str() << "], " << n << " of " << all << " values flagged ("
          << 100.0 * (double)n / (double)all << " %), " << untested << " SAIs untested; scales " << sc[0] << " " << sc[1] << " " << sc[2] << "; " << rounds
-         << " sweeps" << endl;
+         << " sweeps";
+    if (dsteps > 1) cout << ", " << dsteps << " steps per pixel";
+    cout << endl;
     if (save) {
         const size_t plane = (size_t)W * H;
         vector<float> img(plane * C);
@@ -664,6 +690,8 @@ int main(int argc, char** argv) {
     if (!missing_mode(missing, miss_iter, ang_major, aw, ah, s0, t0)) return EXIT_FAILURE;
     bool detect = false; double det_k = -1.0; const char* det_save = nullptr;
     if (!detect_mode(detect, det_k, det_save)) return EXIT_FAILURE;
+    unsigned dsteps = 1;
+    if (!disparity_steps_mode(dsteps, detect || !missing.empty())) return EXIT_FAILURE;
 
     vector<vector<float> > LF, LF_noisy, LF_basic, LF_den, LF_diff;
     vector<unsigned> mask;
@@ -688,11 +716,11 @@ int main(int argc, char** argv) {
             return EXIT_FAILURE;
     }
     vector<vector<unsigned char> > detected;
-    if (detect && !detect_LF(LF_noisy, mask, det_k, det_save, name, sep, ang_major, aw, ah, s0, t0, W, H, C, missing, detected)) return EXIT_FAILURE;
+    if (detect && !detect_LF(LF_noisy, mask, det_k, det_save, name, sep, ang_major, aw, ah, s0, t0, W, H, C, missing, detected, dsteps)) return EXIT_FAILURE;
     vector<unsigned> est_mask = mask;   /* the sigma estimate does not look at reconstructed SAIs */
     if (!missing.empty()) {   /* the synthesis alone, for the same reason as the fill alone below */
         const unsigned hard[9] = {8, 8, 3, 8, 3, 0, LFBM5D_DCT, LFBM5D_SADCT, LFBM5D_HAAR};
-        if (!synthesise_missing_LF(LF_noisy, mask, missing, ang_major, aw, ah, 1, W, H, C, 0, 0, 0.0f, lambda, hard, (unsigned)cs, true)) return EXIT_FAILURE;
+        if (!synthesise_missing_LF(LF_noisy, mask, missing, ang_major, aw, ah, 1, W, H, C, 0, 0, 0.0f, lambda, hard, (unsigned)cs, true, dsteps)) return EXIT_FAILURE;
         cout << "View synthesis: the synthesis alone (the refinement steps run in LFBM5Ddenoising)" << endl;
         for (size_t st = 0; st < missing.size(); st++) if (missing[st]) est_mask[st] = 0;
     }
@@ -812,6 +840,8 @@ int main(int argc, char** argv) {
     if (!missing_mode(missing, miss_iter, ang_major, aw, ah, s0, t0)) return EXIT_FAILURE;
     bool detect = false; double det_k = -1.0; const char* det_save = nullptr;
     if (!detect_mode(detect, det_k, det_save)) return EXIT_FAILURE;
+    unsigned dsteps = 1;
+    if (!disparity_steps_mode(dsteps, detect || !missing.empty())) return EXIT_FAILURE;
 
     vector<vector<float> > LF, LF_noisy, LF_basic, LF_den, LF_diff;
     vector<unsigned> mask;
@@ -840,13 +870,13 @@ int main(int argc, char** argv) {
     unsigned def_steps = 0;
     vector<unsigned> est_mask = mask;   /* the sigma estimate does not look at reconstructed SAIs */
     unsigned view_steps = 0;
-    if (detect && !detect_LF(LF_noisy, mask, det_k, det_save, name, sep, ang_major, aw, ah, s0, t0, W, H, C, missing, defects)) return EXIT_FAILURE;
+    if (detect && !detect_LF(LF_noisy, mask, det_k, det_save, name, sep, ang_major, aw, ah, s0, t0, W, H, C, missing, defects, dsteps)) return EXIT_FAILURE;
     const bool have_defects = def_dir || !defects.empty();
     if (!missing.empty()) {
         lfbm5d_view_params vp;
         lfbm5d_view_defaults(&vp);
         view_steps = smode >= 2 ? 0u : miss_iter >= 0 ? (unsigned)miss_iter : vp.iterations;
-        if (!synthesise_missing_LF(LF_noisy, mask, missing, ang_major, aw, ah, anH, W, H, C, 0, view_steps, 0.0f, lambda, def_hard, (unsigned)cs, true))
+        if (!synthesise_missing_LF(LF_noisy, mask, missing, ang_major, aw, ah, anH, W, H, C, 0, view_steps, 0.0f, lambda, def_hard, (unsigned)cs, true, dsteps))
             return EXIT_FAILURE;
         if (smode >= 2) cout << "View synthesis: the synthesis alone (LFBM5D_SIGMA=poisson: the refinement steps assume one sigma)" << endl;
         for (size_t st = 0; st < missing.size(); st++) if (missing[st]) est_mask[st] = 0;
@@ -863,7 +893,7 @@ int main(int argc, char** argv) {
     if (imp_k >= 0.0 && !repair_impulses_LF(LF_noisy, mask, W, H, C, imp_k)) return EXIT_FAILURE;
     if (smode == 1 && !estimate_sigma_LF(LF_noisy, est_mask, W, H, C, sigma)) return EXIT_FAILURE;
     if (view_steps && !synthesise_missing_LF(LF_noisy, mask, missing, ang_major, aw, ah, anH, W, H, C, view_steps, view_steps, sigma, lambda, def_hard,
-                                             (unsigned)cs, false)) return EXIT_FAILURE;
+                                             (unsigned)cs, false, dsteps)) return EXIT_FAILURE;
     if (def_steps && !inpaint_defects_LF(LF_noisy, defects, mask, ang_major, aw, ah, anH, W, H, C, def_steps, def_steps, sigma, lambda, def_hard,
                                          (unsigned)cs, false)) return EXIT_FAILURE;
     LF_basic.assign(awh, vector<float>((size_t)W * H * C, 0.0f));

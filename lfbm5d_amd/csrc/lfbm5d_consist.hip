@@ -9,7 +9,7 @@
  * lfbm5d_consist_device.h, which also compiles for the host):
  *   k_consist_stats   grid (tiles, tested SAIs): rho = I_m - mu and the key of |rho| per value, counted in C x 386 LDS counters
  *                     (32-bit LDS atomics); the non-zero counters are flushed by 64-bit global atomics into [SAI][C][386].
- *   k_consist_flag    grid (tiles, tested SAIs): per value mu from the prediction plane, v = the sources' squared deviations at d*
+ *   k_consist_flag    (k_consist_flag_subpel behind a sweep with 2 or 4 steps per pixel) grid (tiles, tested SAIs): per value mu from the prediction plane, v = the sources' squared deviations at d*
  *                     (d* varies per pixel: cached gathers), the two tests, the code byte; counts per (SAI, channel, code) through LDS.
  * Integer atomics only; the quantiles and the bad-SAI decision run on the host in double on the integer histograms.
  */
@@ -25,7 +25,7 @@ namespace {
 
 static_assert(kKeys == LFBM5D_IMPULSE_KEYS, "include/lfbm5d.h");
 static_assert(kTabStride == kViewTabStride, "lfbm5d_view.hip's table");
-constexpr int kHistD = 17;
+constexpr int kHistD = lfbm5d_subpel::kHist;   /* the sweep's histogram: 17 bins at steps = 1, 65 otherwise */
 
 struct AtomicInc { __device__ __forceinline__ void operator()(unsigned* p) const { atomicAdd(p, 1u); } };
 
@@ -60,6 +60,22 @@ __global__ __launch_bounds__(kThreads) void k_consist_flag(const float* __restri
     if (tid < 6) cnt[tid] = 0u;
     __syncthreads();
     flag_thread(in, pred, disp, flags, tab, C, W, H, (int)(tx * kTW), (int)(ty * kTH), tid, thr, g, cnt, AtomicInc());
+    __syncthreads();
+    if (tid < 6 && cnt[tid]) atomicAdd(&counts[(size_t)tab[0] * 6 + tid], (unsigned long long)cnt[tid]);
+}
+
+/* the same behind the sweep with Q = 2 or 4 hypotheses per pixel: disp holds j*, the spread comes from the interpolated warp */
+__global__ __launch_bounds__(kThreads) void k_consist_flag_subpel(const float* __restrict__ in, const float* __restrict__ pred,
+                                                                  const signed char* __restrict__ disp, unsigned char* __restrict__ flags,
+                                                                  const int* __restrict__ table, int C, int W, int H, unsigned tx_n,
+                                                                  Thresholds thr, float g, unsigned long long* __restrict__ counts, int Q) {
+    __shared__ unsigned cnt[6];
+    const int tid = (int)threadIdx.x;
+    const int* __restrict__ tab = table + (size_t)blockIdx.y * kTabStride;
+    const unsigned ty = blockIdx.x / tx_n, tx = blockIdx.x - ty * tx_n;
+    if (tid < 6) cnt[tid] = 0u;
+    __syncthreads();
+    flag_thread<true>(in, pred, disp, flags, tab, C, W, H, (int)(tx * kTW), (int)(ty * kTH), tid, thr, g, cnt, AtomicInc(), Q);
     __syncthreads();
     if (tid < 6 && cnt[tid]) atomicAdd(&counts[(size_t)tab[0] * 6 + tid], (unsigned long long)cnt[tid]);
 }
@@ -146,14 +162,15 @@ const char* check_params(const lfbm5d_consist_params* P) {
     return nullptr;
 }
 
-/* include/lfbm5d.h, lfbm5d_consist_device */
-int consist(lfbm5d_ctx* c, const std::string& who, const lfbm5d_consist_params* P, const float* d_in, const unsigned* h_mask,
+/* include/lfbm5d.h, lfbm5d_consist_steps_device */
+int consist(lfbm5d_ctx* c, const std::string& who, const lfbm5d_consist_params* P, unsigned steps, const float* d_in, const unsigned* h_mask,
             const unsigned* h_exclude, unsigned char* d_flags, unsigned* h_state, signed char* d_disp, double* h_scale_sai,
             unsigned long long* h_hist, unsigned ang_major, unsigned aw, unsigned ah, unsigned W, unsigned H, unsigned C,
             lfbm5d_consist_result* res) {
     if (!P || !d_in || !h_mask || !d_flags || !h_state) return fail(c, who + "NULL pointer for a required buffer");
     if (check_chnls(c, who, C) || check_size(c, who, W, H, 2, "be at least 2") || check_angular(c, who, ang_major, aw, ah)) return 1;
     if (const char* msg = check_params(P)) return fail(c, who + msg);
+    if (steps != 1 && steps != 2 && steps != 4) return fail(c, who + "steps must be 1, 2 or 4");
     if (check_one_gpu(c, who, "the consistency check runs on one GPU (this context has a communicator or a shard)")) return 1;
     TileGrid tiles;
     if (check_tiles(c, who, W, H, aw * ah, 0x3fffffffull, tiles)) return 1;
@@ -196,8 +213,10 @@ int consist(lfbm5d_ctx* c, const std::string& who, const lfbm5d_consist_params* 
         HIPCK(c, hipMemsetAsync(d_hist, 0, words * sizeof(unsigned long long), c->stream));
         if (!tested.empty()) {
             HIPCK(c, hipMemcpyAsync(d_table, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+            unsigned most = 0;
+            for (size_t i = 0; i < tested.size(); i++) most = std::max(most, (unsigned)table[i * kTabStride + 1]);
             if (view_sweep_launch(c, d_table, (unsigned)tested.size(), d_in, d_pred, d_dstar, W, H, C, (int)P->max_disparity,
-                                  (int)P->box_radius, d_dh)) return 1;
+                                  (int)P->box_radius, d_dh, steps, most)) return 1;
             hipLaunchKernelGGL(k_consist_stats, dim3(G.tx_n * G.ty_n, (unsigned)tested.size()), dim3(kThreads), 0, c->stream, d_in, d_pred,
                                d_table, (int)C, (int)W, (int)H, G.tx_n, d_hist, d_skip);
             HIPCK(c, hipGetLastError());
@@ -242,8 +261,13 @@ int consist(lfbm5d_ctx* c, const std::string& who, const lfbm5d_consist_params* 
     for (unsigned m : tested) h_state[m] = 1u;
     std::vector<unsigned long long> cnt(n_cnt, 0ull);
     if (!tested.empty()) {
-        hipLaunchKernelGGL(k_consist_flag, dim3(G.tx_n * G.ty_n, (unsigned)tested.size()), dim3(kThreads), 0, c->stream, d_in, d_pred, d_dstar,
-                           d_flags, d_table, (int)C, (int)W, (int)H, G.tx_n, thr, g, d_cnt);
+        const dim3 grid(G.tx_n * G.ty_n, (unsigned)tested.size());
+        if (steps == 1)
+            hipLaunchKernelGGL(k_consist_flag, grid, dim3(kThreads), 0, c->stream, d_in, d_pred, d_dstar, d_flags, d_table, (int)C, (int)W, (int)H,
+                               G.tx_n, thr, g, d_cnt);
+        else
+            hipLaunchKernelGGL(k_consist_flag_subpel, grid, dim3(kThreads), 0, c->stream, d_in, d_pred, d_dstar, d_flags, d_table, (int)C, (int)W,
+                               (int)H, G.tx_n, thr, g, d_cnt, (int)steps);
         HIPCK(c, hipGetLastError());
         HIPCK(c, hipMemcpyAsync(cnt.data(), d_cnt, n_cnt * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
         if (d_disp && copy_sais(c, G.asize, d_disp, d_dstar, plane, 1, [&](unsigned st) { return h_state[st] == 1u; })) return 1;
@@ -257,6 +281,33 @@ int consist(lfbm5d_ctx* c, const std::string& who, const lfbm5d_consist_params* 
     if (h_scale_sai) std::memcpy(h_scale_sai, s_report.data(), G.asize * sizeof(double));
     if (h_hist) std::memcpy(h_hist, host.data(), n_hist * sizeof(unsigned long long));
     if (res) *res = r;
+    return 0;
+}
+
+/* include/lfbm5d.h, lfbm5d_consist_steps_host_sai */
+int host_sai(lfbm5d_ctx* c, const std::string& who, const lfbm5d_consist_params* P, unsigned steps, const float* const* h_in,
+             const unsigned* h_mask, const unsigned* h_exclude, unsigned char* const* h_flags, unsigned* h_state, signed char* const* h_disp,
+             double* h_scale_sai, unsigned long long* h_hist, unsigned ang_major, unsigned awidth, unsigned aheight, unsigned W, unsigned H,
+             unsigned C, lfbm5d_consist_result* out) {
+    if (!P || !h_in || !h_mask || !h_flags || !h_state) return fail(c, who + "NULL pointer for a required buffer");
+    if (check_chnls(c, who, C)) return 1;
+    const unsigned asize = awidth * aheight;
+    const size_t plane = (size_t)W * H, img = plane * C, all = std::max<size_t>(1, (size_t)asize * img);
+    const auto nonempty = [&](unsigned st) { return h_mask[st] != 0; };
+    if (check_planes(c, who, h_flags, asize, nonempty) || (h_disp && check_planes(c, who, h_disp, asize, nonempty))) return 1;
+    (void)hipSetDevice(c->device);
+    HIPCK(c, c->h2d_noisy.reserve(all * sizeof(float)));
+    HIPCK(c, c->consist.flags.reserve(all + std::max<size_t>(1, (size_t)asize * plane)));
+    float* const din = c->h2d_noisy.as<float>();
+    unsigned char* const dfl = c->consist.flags.as<unsigned char>();
+    signed char* const ddisp = h_disp ? reinterpret_cast<signed char*>(dfl + all) : nullptr;
+    if (upload_planes(c, who, h_in, din, asize, img, nonempty)) return 1;
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    if (consist(c, who, P, steps, din, h_mask, h_exclude, dfl, h_state, ddisp, h_scale_sai, h_hist, ang_major, awidth, aheight, W, H, C, out))
+        return 1;
+    if (download_planes(c, h_flags, dfl, asize, img, nonempty)) return 1;
+    if (ddisp && download_planes(c, h_disp, ddisp, asize, plane, [&](unsigned st) { return h_state[st] == 1u; })) return 1;
+    HIPCK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 
@@ -278,13 +329,31 @@ void lfbm5d_consist_defaults(lfbm5d_consist_params* out) {
     out->min_scale = 0.5;                   /* half a grey level of 8-bit data: below the quantisation step a ratio of scales means nothing */
 }
 
+int lfbm5d_consist_steps_device(lfbm5d_ctx* c, const lfbm5d_consist_params* P, unsigned steps, const float* d_in, const unsigned* h_mask,
+                                const unsigned* h_exclude, unsigned char* d_flags, unsigned* h_state, signed char* d_disp, double* h_scale_sai,
+                                unsigned long long* h_hist, unsigned ang_major, unsigned awidth, unsigned aheight, unsigned W, unsigned H,
+                                unsigned C, lfbm5d_consist_result* out) {
+    if (!c) return 1;
+    return consist(c, "lfbm5d_consist_steps_device: ", P, steps, d_in, h_mask, h_exclude, d_flags, h_state, d_disp, h_scale_sai, h_hist, ang_major,
+                   awidth, aheight, W, H, C, out);
+}
+
 int lfbm5d_consist_device(lfbm5d_ctx* c, const lfbm5d_consist_params* P, const float* d_in, const unsigned* h_mask, const unsigned* h_exclude,
                           unsigned char* d_flags, unsigned* h_state, signed char* d_disp, double* h_scale_sai, unsigned long long* h_hist,
                           unsigned ang_major, unsigned awidth, unsigned aheight, unsigned W, unsigned H, unsigned C,
                           lfbm5d_consist_result* out) {
     if (!c) return 1;
-    return consist(c, "lfbm5d_consist_device: ", P, d_in, h_mask, h_exclude, d_flags, h_state, d_disp, h_scale_sai, h_hist, ang_major, awidth,
+    return consist(c, "lfbm5d_consist_device: ", P, 1, d_in, h_mask, h_exclude, d_flags, h_state, d_disp, h_scale_sai, h_hist, ang_major, awidth,
                    aheight, W, H, C, out);
+}
+
+int lfbm5d_consist_steps_host_sai(lfbm5d_ctx* c, const lfbm5d_consist_params* P, unsigned steps, const float* const* h_in,
+                                  const unsigned* h_mask, const unsigned* h_exclude, unsigned char* const* h_flags, unsigned* h_state,
+                                  signed char* const* h_disp, double* h_scale_sai, unsigned long long* h_hist, unsigned ang_major,
+                                  unsigned awidth, unsigned aheight, unsigned W, unsigned H, unsigned C, lfbm5d_consist_result* out) {
+    if (!c) return 1;
+    return host_sai(c, "lfbm5d_consist_steps_host_sai: ", P, steps, h_in, h_mask, h_exclude, h_flags, h_state, h_disp, h_scale_sai, h_hist,
+                    ang_major, awidth, aheight, W, H, C, out);
 }
 
 int lfbm5d_consist_host_sai(lfbm5d_ctx* c, const lfbm5d_consist_params* P, const float* const* h_in, const unsigned* h_mask,
@@ -292,26 +361,8 @@ int lfbm5d_consist_host_sai(lfbm5d_ctx* c, const lfbm5d_consist_params* P, const
                             double* h_scale_sai, unsigned long long* h_hist, unsigned ang_major, unsigned awidth, unsigned aheight, unsigned W,
                             unsigned H, unsigned C, lfbm5d_consist_result* out) {
     if (!c) return 1;
-    const std::string who = "lfbm5d_consist_host_sai: ";
-    if (!P || !h_in || !h_mask || !h_flags || !h_state) return fail(c, who + "NULL pointer for a required buffer");
-    if (check_chnls(c, who, C)) return 1;
-    const unsigned asize = awidth * aheight;
-    const size_t plane = (size_t)W * H, img = plane * C, all = std::max<size_t>(1, (size_t)asize * img);
-    const auto nonempty = [&](unsigned st) { return h_mask[st] != 0; };
-    if (check_planes(c, who, h_flags, asize, nonempty) || (h_disp && check_planes(c, who, h_disp, asize, nonempty))) return 1;
-    (void)hipSetDevice(c->device);
-    HIPCK(c, c->h2d_noisy.reserve(all * sizeof(float)));
-    HIPCK(c, c->consist.flags.reserve(all + std::max<size_t>(1, (size_t)asize * plane)));
-    float* const din = c->h2d_noisy.as<float>();
-    unsigned char* const dfl = c->consist.flags.as<unsigned char>();
-    signed char* const ddisp = h_disp ? reinterpret_cast<signed char*>(dfl + all) : nullptr;
-    if (upload_planes(c, who, h_in, din, asize, img, nonempty)) return 1;
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    if (consist(c, who, P, din, h_mask, h_exclude, dfl, h_state, ddisp, h_scale_sai, h_hist, ang_major, awidth, aheight, W, H, C, out)) return 1;
-    if (download_planes(c, h_flags, dfl, asize, img, nonempty)) return 1;
-    if (ddisp && download_planes(c, h_disp, ddisp, asize, plane, [&](unsigned st) { return h_state[st] == 1u; })) return 1;
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return host_sai(c, "lfbm5d_consist_host_sai: ", P, 1, h_in, h_mask, h_exclude, h_flags, h_state, h_disp, h_scale_sai, h_hist, ang_major,
+                    awidth, aheight, W, H, C, out);
 }
 
 } /* extern "C" */

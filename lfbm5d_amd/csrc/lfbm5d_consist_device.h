@@ -10,6 +10,7 @@
 #define LFBM5D_CONSIST_DEVICE_H
 
 #include "lfbm5d_side_values.h"
+#include "lfbm5d_subpel_device.h"
 
 #pragma clang fp contract(off)
 
@@ -53,11 +54,12 @@ LFBM5D_HD void stats_thread(const float* __restrict__ in, const float* __restric
 
 /* The decision of one thread's values.  tab: the SAI's row of the sweep's table; disp: d* [asize][H][W]; flags: [asize][C][H][W];
  * g = (float)(spread^2); cnt [3][2]: the workgroup's counters of code 1 and code 2 per channel.
- * code 2: I_m is not finite.  code 1: a > T_c and (rho rho) (float)(n - 1) > g v, v = sum_q (w_{q,d*} - mu)^2 from +0 in source order. */
-template <class Add>
+ * code 2: I_m is not finite.  code 1: a > T_c and (rho rho) (float)(n - 1) > g v, v = sum_q (w_{q,d*} - mu)^2 from +0 in source order.
+ * SUBPEL: disp holds j* in units of 1 / Q and w is the sweep's interpolated warp (lfbm5d_subpel_device.h); otherwise Q is not looked at. */
+template <bool SUBPEL = false, class Add>
 LFBM5D_HD void flag_thread(const float* __restrict__ in, const float* __restrict__ pred, const signed char* __restrict__ disp,
                            unsigned char* __restrict__ flags, const int* __restrict__ tab, int C, int W, int H, int x0, int y0, int tid,
-                           Thresholds thr, float g, unsigned* cnt, Add add) {
+                           Thresholds thr, float g, unsigned* cnt, Add add, int Q = 1) {
     const size_t plane = (size_t)W * H;
     const int m = tab[0], n = tab[1];
     const float n1 = (float)(n - 1);
@@ -76,8 +78,15 @@ LFBM5D_HD void flag_thread(const float* __restrict__ in, const float* __restrict
             else {
                 float v = 0.0f;
                 for (int q = 0; q < n; q++) {
-                    const int sy = mirror(gy - d * tab[3 + 3 * q], H), sx = mirror(gx - d * tab[4 + 3 * q], W);
-                    const float diff = in[((size_t)tab[2 + 3 * q] * C + c) * plane + (size_t)sy * W + sx] - mu;
+                    float w;
+                    if (SUBPEL) {
+                        const lfbm5d_subpel::Tap t = lfbm5d_subpel::make_tap(tab, q, d, Q);
+                        w = lfbm5d_subpel::warp(in + ((size_t)t.src * C + c) * plane, t, gy, gx, W, H);
+                    } else {
+                        const int sy = mirror(gy - d * tab[3 + 3 * q], H), sx = mirror(gx - d * tab[4 + 3 * q], W);
+                        w = in[((size_t)tab[2 + 3 * q] * C + c) * plane + (size_t)sy * W + sx];
+                    }
+                    const float diff = w - mu;
                     const float sq = diff * diff;
                     v = v + sq;
                 }

@@ -237,11 +237,13 @@ int run_denoise(lfbm5d_ctx* c, const lfbm5d_params* P1, const lfbm5d_params* P2,
                 float* d_out, unsigned ang_major, unsigned awidth, unsigned aheight, unsigned an1, unsigned an2, unsigned W, unsigned H,
                 unsigned C, const HostIO* io = nullptr);
 
-/* lfbm5d_view.hip: k_view_sweep on the context's stream with a caller-built table (d_table: kViewTabStride ints per SAI to synthesise:
- * its index, n, n x (source index, ds, dt); n_sai rows); d_cnt [17] is accumulated into.  Enqueues only. */
+/* lfbm5d_view.hip: the plane sweep on the context's stream with a caller-built table (d_table: kViewTabStride ints per SAI to synthesise:
+ * its index, n, n x (source index, ds, dt); n_sai rows).  steps = 1: k_view_sweep, d_cnt [17] (index d* + 8) is accumulated into;
+ * steps = 2 or 4: k_view_sweep_subpel, d_cnt [65] (index j* + 32), max_sources = the largest n of the table (it picks the instantiation).
+ * Enqueues only. */
 constexpr int kViewTabStride = 2 + 3 * 24;
 int view_sweep_launch(lfbm5d_ctx* c, const int* d_table, unsigned n_sai, const float* d_in, float* d_out, signed char* d_disp, unsigned W,
-                      unsigned H, unsigned C, int D, int r, unsigned long long* d_cnt);
+                      unsigned H, unsigned C, int D, int r, unsigned long long* d_cnt, unsigned steps, unsigned max_sources);
 
 } /* namespace lfbm5d_host */
 #endif

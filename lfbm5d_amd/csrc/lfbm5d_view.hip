@@ -12,10 +12,14 @@
  *                  barrier, vertical box sums into registers and the running (E_best, d*) update.  After the last hypothesis the mean at
  *                  d* is recomputed from the sources and stored with the disparity.  Lanes run along x in every phase: global loads are
  *                  rows shifted by a uniform amount, LDS reads of both box passes are consecutive words (no bank conflict).
+ *   k_view_sweep_subpel   the same sweep with 2 or 4 hypotheses per pixel of disparity and a bilinear warp (the *_steps_* entry points;
+ *                  steps = 1 runs k_view_sweep); its phases are lfbm5d_subpel_device.h, which also compiles for the host, and it equals
+ *                  tests/subpel_model.py bit for bit.
  * Sums in a fixed order from +0, no fused multiply-add, one product with a table entry, integer atomics for the histogram (LDS, then
  * global): the GPU equals tests/view_model.py bit for bit.
  */
 #include "lfbm5d_side.h"
+#include "lfbm5d_subpel_device.h"
 
 using namespace lfbm5d_host;
 using namespace lfbm5d_side;
@@ -128,11 +132,60 @@ __global__ __launch_bounds__(kThreads) void k_view_sweep(const float* __restrict
     if (tid < kHist && hist[tid]) atomicAdd(&cnt[tid], (unsigned long long)hist[tid]);
 }
 
+struct AtomicInc { __device__ __forceinline__ void operator()(unsigned* p) const { atomicAdd(p, 1u); } };
+
+/* The sweep with Q = 2 or 4 hypotheses per pixel, d = j / Q, sources warped by bilinear interpolation (lfbm5d_subpel_device.h holds
+ * the phases; this is their order and the barriers).  The same grid, tile and three phases per hypothesis as k_view_sweep.  What a
+ * hypothesis makes of each source (offsets, fractions, weights) is the same for every cell: n threads write it into taps ahead of the
+ * error phase -- for the next hypothesis between the two barriers, when the error phase that read the table has ended.  HOLD (n <= 8):
+ * a channel's warped values stay in registers between mean and deviations.  cnt[kHist]: positions per j* + 32. */
+template <bool HOLD>
+__global__ __launch_bounds__(kThreads) void k_view_sweep_subpel(const float* __restrict__ in, float* __restrict__ out,
+                                                                signed char* __restrict__ disp, const int* __restrict__ table, int C, int W,
+                                                                int H, unsigned tx_n, int J, int Q, int r, unsigned long long* __restrict__ cnt) {
+    namespace S = lfbm5d_subpel;
+    __shared__ float e[S::kEH * S::kEW];
+    __shared__ float h[S::kEH * kTW];
+    __shared__ S::Tap taps[S::kSrcMax];
+    __shared__ unsigned hist[S::kHist];
+    const int tid = (int)threadIdx.x;
+    const int* __restrict__ tab = table + (size_t)blockIdx.y * kTabStride;
+    const int n = tab[1];
+    const float rn = kRecip[n];
+    const unsigned ty = blockIdx.x / tx_n, tx = blockIdx.x - ty * tx_n;
+    const int x0 = (int)(tx * kTW), y0 = (int)(ty * kTH);
+    if (tid < S::kHist) hist[tid] = 0u;
+    if (tid < n) taps[tid] = S::make_tap(tab, tid, 0, Q);
+    __syncthreads();
+
+    float best[S::kPer];
+    int jstar[S::kPer];
+#pragma unroll
+    for (int k = 0; k < S::kPer; k++) { best[k] = 0.0f; jstar[k] = 0; }
+
+    for (int i = 0; i <= 2 * J; i++) {
+        const int j = S::hypothesis(i);
+        S::error_phase<HOLD>(in, taps, n, rn, C, W, H, x0, y0, r, tid, e);
+        __syncthreads();
+        if (tid < n && i < 2 * J) taps[tid] = S::make_tap(tab, tid, S::hypothesis(i + 1), Q);
+        S::hbox_phase(e, h, r, tid);
+        __syncthreads();
+        S::vbox_phase(h, r, tid, i == 0, j, best, jstar);
+        /* the next hypothesis writes e at once (its readers passed the second barrier) and h only behind its first barrier */
+    }
+
+    S::store_phase(in, out, disp, tab, rn, Q, C, W, H, x0, y0, tid, jstar, hist, AtomicInc());
+    __syncthreads();
+    if (tid < S::kHist && hist[tid]) atomicAdd(&cnt[tid], (unsigned long long)hist[tid]);
+}
+
 struct Plan {
     std::vector<int> table;            /* kTabStride ints per synthesised SAI */
     std::vector<unsigned> synth, left; /* indices, increasing */
     unsigned nne = 0;
 };
+
+const char* check_steps(unsigned steps) { return steps == 1 || steps == 2 || steps == 4 ? nullptr : "steps must be 1, 2 or 4"; }
 
 const char* check_params(const lfbm5d_view_params* vp) {
     if (vp->max_disparity > (unsigned)kDMax) return "max_disparity must be 0..8";
@@ -142,11 +195,12 @@ const char* check_params(const lfbm5d_view_params* vp) {
 }
 
 /* the checks on the host arguments every entry shares, and the source lists; 1 with a message */
-int plan_sources(lfbm5d_ctx* c, const std::string& who, const lfbm5d_view_params* vp, const unsigned* h_mask, const unsigned* h_missing,
-         unsigned ang_major, unsigned aw, unsigned ah, unsigned W, unsigned H, unsigned C, Plan& p) {
+int plan_sources(lfbm5d_ctx* c, const std::string& who, const lfbm5d_view_params* vp, unsigned steps, const unsigned* h_mask,
+                 const unsigned* h_missing, unsigned ang_major, unsigned aw, unsigned ah, unsigned W, unsigned H, unsigned C, Plan& p) {
     if (!vp || !h_mask || !h_missing) return fail(c, who + "NULL pointer for a required buffer");
     if (check_chnls(c, who, C) || check_size(c, who, W, H, 2, "be at least 2") || check_angular(c, who, ang_major, aw, ah)) return 1;
     if (const char* msg = check_params(vp)) return fail(c, who + msg);
+    if (const char* msg = check_steps(steps)) return fail(c, who + msg);
     if (check_one_gpu(c, who, "the view synthesis runs on one GPU (this context has a communicator or a shard)")) return 1;
     const unsigned asize = aw * ah;
     unsigned n_missing = 0;
@@ -180,10 +234,14 @@ int check_buffers(lfbm5d_ctx* c, const std::string& who, const float* d_in, floa
     return 0;
 }
 
-/* the synthesis; after plan_sources().  On return the stream is idle and the planes of the synthesised SAIs of d_out (and d_disp) are written. */
-int sweep(lfbm5d_ctx* c, const Plan& p, const lfbm5d_view_params* vp, const float* d_in, float* d_out, signed char* d_disp, unsigned W,
-          unsigned H, unsigned C, lfbm5d_view_result& r) {
+/* the synthesis; after plan_sources().  On return the stream is idle and the planes of the synthesised SAIs of d_out (and d_disp) are
+ * written.  h_hist_steps ([65] or NULL): positions per j* + 32; r.disparity_hist is filled for steps = 1 alone. */
+int sweep(lfbm5d_ctx* c, const Plan& p, const lfbm5d_view_params* vp, unsigned steps, const float* d_in, float* d_out, signed char* d_disp,
+          unsigned W, unsigned H, unsigned C, lfbm5d_view_result& r, unsigned long long* h_hist_steps) {
+    namespace S = lfbm5d_subpel;
+    static_assert(S::kHist == LFBM5D_VIEW_STEPS_HIST && S::kHist >= kHist, "include/lfbm5d.h");
     std::memset(&r, 0, sizeof(r));
+    if (h_hist_steps) std::memset(h_hist_steps, 0, S::kHist * sizeof(unsigned long long));
     r.missing = (unsigned)(p.synth.size() + p.left.size());
     r.synthesised = (unsigned)p.synth.size();
     r.left = (unsigned)p.left.size();
@@ -191,32 +249,36 @@ int sweep(lfbm5d_ctx* c, const Plan& p, const lfbm5d_view_params* vp, const floa
     if (p.synth.empty()) return 0;
     (void)hipSetDevice(c->device);
     HIPCK(c, c->view.table.reserve(p.table.size() * sizeof(int)));
-    HIPCK(c, c->view.stats.reserve(kHist * sizeof(unsigned long long)));
+    HIPCK(c, c->view.stats.reserve(S::kHist * sizeof(unsigned long long)));
     unsigned long long* d_cnt = c->view.stats.as<unsigned long long>();
     HIPCK(c, hipMemcpyAsync(c->view.table.p, p.table.data(), p.table.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemsetAsync(d_cnt, 0, kHist * sizeof(unsigned long long), c->stream));
-    const unsigned tx_n = (W + kTW - 1) / kTW, ty_n = (H + kTH - 1) / kTH;
-    hipLaunchKernelGGL(k_view_sweep, dim3(tx_n * ty_n, (unsigned)p.synth.size()), dim3(kThreads), 0, c->stream, d_in, d_out, d_disp,
-                       c->view.table.as<int>(), (int)C, (int)W, (int)H, tx_n, (int)vp->max_disparity, (int)vp->box_radius, d_cnt);
-    HIPCK(c, hipGetLastError());
-    HIPCK(c, hipMemcpyAsync(r.disparity_hist, d_cnt, kHist * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipMemsetAsync(d_cnt, 0, S::kHist * sizeof(unsigned long long), c->stream));
+    unsigned most = 0;
+    for (size_t i = 0; i < p.synth.size(); i++) most = std::max(most, (unsigned)p.table[i * kTabStride + 1]);
+    if (view_sweep_launch(c, c->view.table.as<int>(), (unsigned)p.synth.size(), d_in, d_out, d_disp, W, H, C, (int)vp->max_disparity,
+                          (int)vp->box_radius, d_cnt, steps, most)) return 1;
+    unsigned long long got[S::kHist];
+    const int bins = steps == 1 ? kHist : S::kHist;
+    HIPCK(c, hipMemcpyAsync(got, d_cnt, bins * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));   /* the table leaves a caller's object; the histogram is read */
+    if (steps == 1) std::memcpy(r.disparity_hist, got, kHist * sizeof(unsigned long long));
+    if (h_hist_steps) std::memcpy(h_hist_steps + (steps == 1 ? S::kJMax - kDMax : 0), got, bins * sizeof(unsigned long long));
     return 0;
 }
 
-/* include/lfbm5d.h, lfbm5d_view_device */
-int view(lfbm5d_ctx* c, const std::string& who, const lfbm5d_view_params* vp, const lfbm5d_params* P, const float* d_in, const unsigned* h_mask,
-         const unsigned* h_missing, float* d_out, signed char* d_disp, unsigned ang_major, unsigned aw, unsigned ah, unsigned an, unsigned W,
-         unsigned H, unsigned C, lfbm5d_view_result* res) {
+/* include/lfbm5d.h, lfbm5d_view_steps_device */
+int view(lfbm5d_ctx* c, const std::string& who, const lfbm5d_view_params* vp, unsigned steps, const lfbm5d_params* P, const float* d_in,
+         const unsigned* h_mask, const unsigned* h_missing, float* d_out, signed char* d_disp, unsigned ang_major, unsigned aw, unsigned ah,
+         unsigned an, unsigned W, unsigned H, unsigned C, lfbm5d_view_result* res, unsigned long long* h_hist_steps) {
     if (!vp || !P) return fail(c, who + "NULL pointer for a required buffer");
     const unsigned asize = aw * ah;
     if (check_buffers(c, who, d_in, d_out, asize, W, H, C)) return 1;
     const LoopSchedule sched = {vp->iterations, vp->sigma_start, vp->sigma_end, vp->sigma_noise};
     if (const char* msg = check_schedule(sched)) return fail(c, who + msg);
     Plan p;
-    if (plan_sources(c, who, vp, h_mask, h_missing, ang_major, aw, ah, W, H, C, p)) return 1;
+    if (plan_sources(c, who, vp, steps, h_mask, h_missing, ang_major, aw, ah, W, H, C, p)) return 1;
     lfbm5d_view_result r;
-    if (sweep(c, p, vp, d_in, d_out, d_disp, W, H, C, r)) return 1;
+    if (sweep(c, p, vp, steps, d_in, d_out, d_disp, W, H, C, r, h_hist_steps)) return 1;
     if (res) *res = r;
     const size_t img = (size_t)C * W * H;
     const auto sound = [&](unsigned st) { return h_mask[st] && !h_missing[st]; };
@@ -234,58 +296,24 @@ int view(lfbm5d_ctx* c, const std::string& who, const lfbm5d_view_params* vp, co
                        put_back);
 }
 
-} /* namespace */
-
-/* lfbm5d_ctx.h: the sweep for another stage's table (the consistency check's leave-one-out lists) */
-int lfbm5d_host::view_sweep_launch(lfbm5d_ctx* c, const int* d_table, unsigned n_sai, const float* d_in, float* d_out, signed char* d_disp,
-                                   unsigned W, unsigned H, unsigned C, int D, int r, unsigned long long* d_cnt) {
-    static_assert(kViewTabStride == kTabStride, "lfbm5d_ctx.h");
-    const unsigned tx_n = (W + kTW - 1) / kTW, ty_n = (H + kTH - 1) / kTH;
-    hipLaunchKernelGGL(k_view_sweep, dim3(tx_n * ty_n, n_sai), dim3(kThreads), 0, c->stream, d_in, d_out, d_disp, d_table, (int)C, (int)W, (int)H,
-                       tx_n, D, r, d_cnt);
-    HIPCK(c, hipGetLastError());
-    return 0;
-}
-
-extern "C" {
-
-void lfbm5d_view_defaults(lfbm5d_view_params* out) {
-    if (!out) return;
-    out->max_disparity = 4;                  /* the best row of the sweep in profiles/view_defaults.txt */
-    out->box_radius = 3;
-    out->ang_radius = 1;
-    out->iterations = 4;
-    out->sigma_start = 30.0f;
-    out->sigma_end = 5.0f;
-    out->sigma_noise = 0.0f;
-}
-
-int lfbm5d_view_fill_device(lfbm5d_ctx* c, const lfbm5d_view_params* vp, const float* d_in, const unsigned* h_mask, const unsigned* h_missing,
-                            float* d_out, signed char* d_disp, unsigned ang_major, unsigned awidth, unsigned aheight, unsigned W, unsigned H,
-                            unsigned C, lfbm5d_view_result* out) {
-    if (!c) return 1;
-    const std::string who = "lfbm5d_view_fill_device: ";
+/* include/lfbm5d.h, lfbm5d_view_fill_steps_device */
+int fill(lfbm5d_ctx* c, const std::string& who, const lfbm5d_view_params* vp, unsigned steps, const float* d_in, const unsigned* h_mask,
+         const unsigned* h_missing, float* d_out, signed char* d_disp, unsigned ang_major, unsigned awidth, unsigned aheight, unsigned W,
+         unsigned H, unsigned C, lfbm5d_view_result* out, unsigned long long* h_hist_steps) {
     if (check_buffers(c, who, d_in, d_out, awidth * aheight, W, H, C)) return 1;
     Plan p;
-    if (plan_sources(c, who, vp, h_mask, h_missing, ang_major, awidth, aheight, W, H, C, p)) return 1;
+    if (plan_sources(c, who, vp, steps, h_mask, h_missing, ang_major, awidth, aheight, W, H, C, p)) return 1;
     lfbm5d_view_result r;
-    if (sweep(c, p, vp, d_in, d_out, d_disp, W, H, C, r)) return 1;
+    if (sweep(c, p, vp, steps, d_in, d_out, d_disp, W, H, C, r, h_hist_steps)) return 1;
     if (out) *out = r;
     return 0;
 }
 
-int lfbm5d_view_device(lfbm5d_ctx* c, const lfbm5d_view_params* vp, const lfbm5d_params* P, const float* d_in, const unsigned* h_mask,
-                       const unsigned* h_missing, float* d_out, signed char* d_disp, unsigned ang_major, unsigned awidth, unsigned aheight,
-                       unsigned an, unsigned W, unsigned H, unsigned C, lfbm5d_view_result* out) {
-    if (!c) return 1;
-    return view(c, "lfbm5d_view_device: ", vp, P, d_in, h_mask, h_missing, d_out, d_disp, ang_major, awidth, aheight, an, W, H, C, out);
-}
-
-int lfbm5d_view_host_sai(lfbm5d_ctx* c, const lfbm5d_view_params* vp, const lfbm5d_params* P, const float* const* h_in, const unsigned* h_mask,
-                         const unsigned* h_missing, float* const* h_out, signed char* const* h_disp, unsigned ang_major, unsigned awidth,
-                         unsigned aheight, unsigned an, unsigned W, unsigned H, unsigned C, lfbm5d_view_result* out) {
-    if (!c) return 1;
-    const std::string who = "lfbm5d_view_host_sai: ";
+/* include/lfbm5d.h, lfbm5d_view_steps_host_sai */
+int host_sai(lfbm5d_ctx* c, const std::string& who, const lfbm5d_view_params* vp, unsigned steps, const lfbm5d_params* P,
+             const float* const* h_in, const unsigned* h_mask, const unsigned* h_missing, float* const* h_out, signed char* const* h_disp,
+             unsigned ang_major, unsigned awidth, unsigned aheight, unsigned an, unsigned W, unsigned H, unsigned C, lfbm5d_view_result* out,
+             unsigned long long* h_hist_steps) {
     if (!vp || !P || !h_in || !h_out || !h_mask || !h_missing) return fail(c, who + "NULL pointer for a required buffer");
     if (check_chnls(c, who, C)) return 1;
     const unsigned asize = awidth * aheight;
@@ -304,17 +332,101 @@ int lfbm5d_view_host_sai(lfbm5d_ctx* c, const lfbm5d_view_params* vp, const lfbm
     HIPCK(c, hipStreamSynchronize(c->stream));
     lfbm5d_view_result r;
     std::memset(&r, 0, sizeof(r));
-    const int rc = view(c, who, vp, P, din, h_mask, h_missing, dout, ddisp, ang_major, awidth, aheight, an, W, H, C, &r);
+    const int rc = view(c, who, vp, steps, P, din, h_mask, h_missing, dout, ddisp, ang_major, awidth, aheight, an, W, H, C, &r, h_hist_steps);
     if (out) *out = r;
     if (rc) return 1;
     /* an SAI that was left (K = 0 only) was not written on the device: its host planes stay as they are */
     Plan p;
-    if (r.left && plan_sources(c, who, vp, h_mask, h_missing, ang_major, awidth, aheight, W, H, C, p)) return 1;
+    if (r.left && plan_sources(c, who, vp, steps, h_mask, h_missing, ang_major, awidth, aheight, W, H, C, p)) return 1;
     const auto written = [&](unsigned st) { return h_mask[st] && std::find(p.left.begin(), p.left.end(), st) == p.left.end(); };
     if (download_planes(c, h_out, dout, asize, img, written)) return 1;
     if (h_disp && download_planes(c, h_disp, ddisp, asize, plane, [&](unsigned st) { return missing(st) && written(st); })) return 1;
     HIPCK(c, hipStreamSynchronize(c->stream));
     return 0;
+}
+
+} /* namespace */
+
+/* lfbm5d_ctx.h: the sweep for another stage's table (the consistency check's leave-one-out lists) */
+int lfbm5d_host::view_sweep_launch(lfbm5d_ctx* c, const int* d_table, unsigned n_sai, const float* d_in, float* d_out, signed char* d_disp,
+                                   unsigned W, unsigned H, unsigned C, int D, int r, unsigned long long* d_cnt, unsigned steps,
+                                   unsigned max_sources) {
+    static_assert(kViewTabStride == kTabStride && lfbm5d_subpel::kTabStride == kTabStride, "lfbm5d_ctx.h");
+    const unsigned tx_n = (W + kTW - 1) / kTW, ty_n = (H + kTH - 1) / kTH;
+    const dim3 grid(tx_n * ty_n, n_sai);
+    if (steps == 1) {
+        hipLaunchKernelGGL(k_view_sweep, grid, dim3(kThreads), 0, c->stream, d_in, d_out, d_disp, d_table, (int)C, (int)W, (int)H, tx_n, D, r, d_cnt);
+    } else {
+        /* one launch serves every row of the table: the values stay in registers only if no row has more than 8 sources */
+        const bool hold = max_sources <= lfbm5d_subpel::kHold;
+        const auto k = hold ? k_view_sweep_subpel<true> : k_view_sweep_subpel<false>;
+        hipLaunchKernelGGL(k, grid, dim3(kThreads), 0, c->stream, d_in, d_out, d_disp, d_table, (int)C, (int)W, (int)H, tx_n, D * (int)steps,
+                           (int)steps, r, d_cnt);
+    }
+    HIPCK(c, hipGetLastError());
+    return 0;
+}
+
+extern "C" {
+
+void lfbm5d_view_defaults(lfbm5d_view_params* out) {
+    if (!out) return;
+    out->max_disparity = 4;                  /* the best row of the sweep in profiles/view_defaults.txt */
+    out->box_radius = 3;
+    out->ang_radius = 1;
+    out->iterations = 4;
+    out->sigma_start = 30.0f;
+    out->sigma_end = 5.0f;
+    out->sigma_noise = 0.0f;
+}
+
+int lfbm5d_view_fill_steps_device(lfbm5d_ctx* c, const lfbm5d_view_params* vp, unsigned steps, const float* d_in, const unsigned* h_mask,
+                                  const unsigned* h_missing, float* d_out, signed char* d_disp, unsigned ang_major, unsigned awidth,
+                                  unsigned aheight, unsigned W, unsigned H, unsigned C, lfbm5d_view_result* out,
+                                  unsigned long long* h_hist_steps) {
+    if (!c) return 1;
+    return fill(c, "lfbm5d_view_fill_steps_device: ", vp, steps, d_in, h_mask, h_missing, d_out, d_disp, ang_major, awidth, aheight, W, H, C, out,
+                h_hist_steps);
+}
+
+int lfbm5d_view_fill_device(lfbm5d_ctx* c, const lfbm5d_view_params* vp, const float* d_in, const unsigned* h_mask, const unsigned* h_missing,
+                            float* d_out, signed char* d_disp, unsigned ang_major, unsigned awidth, unsigned aheight, unsigned W, unsigned H,
+                            unsigned C, lfbm5d_view_result* out) {
+    if (!c) return 1;
+    return fill(c, "lfbm5d_view_fill_device: ", vp, 1, d_in, h_mask, h_missing, d_out, d_disp, ang_major, awidth, aheight, W, H, C, out, nullptr);
+}
+
+int lfbm5d_view_steps_device(lfbm5d_ctx* c, const lfbm5d_view_params* vp, unsigned steps, const lfbm5d_params* P, const float* d_in,
+                             const unsigned* h_mask, const unsigned* h_missing, float* d_out, signed char* d_disp, unsigned ang_major,
+                             unsigned awidth, unsigned aheight, unsigned an, unsigned W, unsigned H, unsigned C, lfbm5d_view_result* out,
+                             unsigned long long* h_hist_steps) {
+    if (!c) return 1;
+    return view(c, "lfbm5d_view_steps_device: ", vp, steps, P, d_in, h_mask, h_missing, d_out, d_disp, ang_major, awidth, aheight, an, W, H, C, out,
+                h_hist_steps);
+}
+
+int lfbm5d_view_device(lfbm5d_ctx* c, const lfbm5d_view_params* vp, const lfbm5d_params* P, const float* d_in, const unsigned* h_mask,
+                       const unsigned* h_missing, float* d_out, signed char* d_disp, unsigned ang_major, unsigned awidth, unsigned aheight,
+                       unsigned an, unsigned W, unsigned H, unsigned C, lfbm5d_view_result* out) {
+    if (!c) return 1;
+    return view(c, "lfbm5d_view_device: ", vp, 1, P, d_in, h_mask, h_missing, d_out, d_disp, ang_major, awidth, aheight, an, W, H, C, out, nullptr);
+}
+
+int lfbm5d_view_steps_host_sai(lfbm5d_ctx* c, const lfbm5d_view_params* vp, unsigned steps, const lfbm5d_params* P, const float* const* h_in,
+                               const unsigned* h_mask, const unsigned* h_missing, float* const* h_out, signed char* const* h_disp,
+                               unsigned ang_major, unsigned awidth, unsigned aheight, unsigned an, unsigned W, unsigned H, unsigned C,
+                               lfbm5d_view_result* out, unsigned long long* h_hist_steps) {
+    if (!c) return 1;
+    return host_sai(c, "lfbm5d_view_steps_host_sai: ", vp, steps, P, h_in, h_mask, h_missing, h_out, h_disp, ang_major, awidth, aheight, an, W, H,
+                    C, out, h_hist_steps);
+}
+
+int lfbm5d_view_host_sai(lfbm5d_ctx* c, const lfbm5d_view_params* vp, const lfbm5d_params* P, const float* const* h_in, const unsigned* h_mask,
+                         const unsigned* h_missing, float* const* h_out, signed char* const* h_disp, unsigned ang_major, unsigned awidth,
+                         unsigned aheight, unsigned an, unsigned W, unsigned H, unsigned C, lfbm5d_view_result* out) {
+    if (!c) return 1;
+    return host_sai(c, "lfbm5d_view_host_sai: ", vp, 1, P, h_in, h_mask, h_missing, h_out, h_disp, ang_major, awidth, aheight, an, W, H, C, out,
+                    nullptr);
 }
 
 } /* extern "C" */

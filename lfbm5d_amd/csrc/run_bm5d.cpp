@@ -520,7 +520,7 @@ int view_synth_LF(std::vector<std::vector<float> >& LF, const std::vector<unsign
                   const int iterations, const float sigmaStart, const float sigmaEnd, const float sigmaNoise, const float lambdaHard5D,
                   const unsigned NHard, const unsigned nSim, const unsigned nDisp, const unsigned kHard, const unsigned pHard, const bool useSD,
                   const unsigned tau_2D, unsigned tau_4D, const unsigned tau_5D, const unsigned color_space, unsigned& synthesised,
-                  unsigned& left, int& dmin, int& dmax) {
+                  unsigned& left, int& dmin, int& dmax, const unsigned disparity_steps) {
     const unsigned asize = awidth * aheight;
     synthesised = left = 0; dmin = dmax = 0;
     if (LF.size() != asize || LF_SAI_mask.size() != asize || missing.size() != asize) {
@@ -552,12 +552,19 @@ int view_synth_LF(std::vector<std::vector<float> >& LF, const std::vector<unsign
     const lfbm5d_params P = make(0.0f, lambdaHard5D, NHard, nSim, nDisp, kHard, pHard, useSD, tau_2D, tau_4D, tau_5D, color_space);
     lfbm5d_view_result r;
     std::memset(&r, 0, sizeof(r));
-    const int rc = lfbm5d_view_host_sai(ctx, &vp, &P, p.data(), LF_SAI_mask.data(), missing.data(), p.data(), nullptr, ang_major, awidth,
-                                        aheight, anHard, width, height, chnls, &r);
+    unsigned long long hist[LFBM5D_VIEW_STEPS_HIST] = {0};
+    int rc;
+    if (disparity_steps == 1) {                                                 /* the integer form: its name in the messages */
+        rc = lfbm5d_view_host_sai(ctx, &vp, &P, p.data(), LF_SAI_mask.data(), missing.data(), p.data(), nullptr, ang_major, awidth, aheight,
+                                  anHard, width, height, chnls, &r);
+        for (int d = -8; d <= 8; d++) hist[d + 32] = r.disparity_hist[d + 8];
+    } else
+        rc = lfbm5d_view_steps_host_sai(ctx, &vp, disparity_steps, &P, p.data(), LF_SAI_mask.data(), missing.data(), p.data(), nullptr,
+                                        ang_major, awidth, aheight, anHard, width, height, chnls, &r, hist);
     synthesised = r.synthesised; left = r.left;
     bool any = false;
-    for (int d = -8; d <= 8; d++)
-        if (r.disparity_hist[d + 8]) { if (!any) dmin = d; dmax = d; any = true; }
+    for (int j = -32; j <= 32; j++)
+        if (hist[j + 32]) { if (!any) dmin = j; dmax = j; any = true; }
     if (rc != 0) {
         std::cout << "LFBM5D GPU backend: " << lfbm5d_last_error(ctx) << std::endl;
         return EXIT_FAILURE;
@@ -569,9 +576,9 @@ int view_synth_LF(std::vector<std::vector<float> >& LF, const std::vector<unsign
  * missing SAIs stay empty); the result goes to out_flat.  vpi = {maxDisparity, boxRadius, angRadius, iterations},
  * vpf = {sigmaStart, sigmaEnd, sigmaNoise, lambda}, hard = {N, nSim, nDisp, k, p, useSD, tau_2D, tau_4D, tau_5D},
  * counts = {synthesised, left, dmin, dmax}. */
-extern "C" int lfbm5d_view_synth_probe(const float* in_flat, const unsigned* mask, const unsigned* missing, float* out_flat, unsigned ang_major,
-                                       unsigned awidth, unsigned aheight, unsigned an, unsigned width, unsigned height, unsigned chnls,
-                                       const int* vpi, const float* vpf, const unsigned* hard, unsigned color_space, int* counts) {
+static int view_synth_probe(const float* in_flat, const unsigned* mask, const unsigned* missing, float* out_flat, unsigned ang_major,
+                            unsigned awidth, unsigned aheight, unsigned an, unsigned width, unsigned height, unsigned chnls, const int* vpi,
+                            const float* vpf, const unsigned* hard, unsigned color_space, int* counts, unsigned disparity_steps) {
     const size_t asize = (size_t)awidth * aheight, img = (size_t)width * height * chnls;
     std::vector<unsigned> m(mask, mask + asize), ms(missing, missing + asize);
     std::vector<std::vector<float> > LF(asize);
@@ -580,11 +587,27 @@ extern "C" int lfbm5d_view_synth_probe(const float* in_flat, const unsigned* mas
     unsigned synthesised = 0, left = 0; int dmin = 0, dmax = 0;
     const int rc = view_synth_LF(LF, m, ms, ang_major, awidth, aheight, an, width, height, chnls, vpi[0], vpi[1], vpi[2], vpi[3], vpf[0], vpf[1],
                                  vpf[2], vpf[3], hard[0], hard[1], hard[2], hard[3], hard[4], hard[5] != 0, hard[6], hard[7], hard[8], color_space,
-                                 synthesised, left, dmin, dmax);
+                                 synthesised, left, dmin, dmax, disparity_steps);
     if (counts) { counts[0] = (int)synthesised; counts[1] = (int)left; counts[2] = dmin; counts[3] = dmax; }
     if (rc != EXIT_SUCCESS) return 1;
     for (size_t st = 0; st < asize; st++) if (m[st] && LF[st].size() == img) std::memcpy(out_flat + st * img, LF[st].data(), img * sizeof(float));
     return 0;
+}
+
+extern "C" int lfbm5d_view_synth_probe(const float* in_flat, const unsigned* mask, const unsigned* missing, float* out_flat, unsigned ang_major,
+                                       unsigned awidth, unsigned aheight, unsigned an, unsigned width, unsigned height, unsigned chnls,
+                                       const int* vpi, const float* vpf, const unsigned* hard, unsigned color_space, int* counts) {
+    return view_synth_probe(in_flat, mask, missing, out_flat, ang_major, awidth, aheight, an, width, height, chnls, vpi, vpf, hard, color_space,
+                            counts, 1);
+}
+
+/* The same with view_synth_LF's disparity_steps; dmin and dmax are then in units of 1 / disparity_steps. */
+extern "C" int lfbm5d_view_synth_steps_probe(const float* in_flat, const unsigned* mask, const unsigned* missing, float* out_flat,
+                                             unsigned ang_major, unsigned awidth, unsigned aheight, unsigned an, unsigned width, unsigned height,
+                                             unsigned chnls, const int* vpi, const float* vpf, const unsigned* hard, unsigned color_space,
+                                             int* counts, unsigned disparity_steps) {
+    return view_synth_probe(in_flat, mask, missing, out_flat, ang_major, awidth, aheight, an, width, height, chnls, vpi, vpf, hard, color_space,
+                            counts, disparity_steps);
 }
 
 /* consistency check on the caller's vectors (one pointer per SAI; the library stages in and out) */
@@ -593,7 +616,7 @@ int consist_LF(const std::vector<std::vector<float> >& LF, const std::vector<uns
                const unsigned chnls, const int maxDisparity, const int boxRadius, const int angRadius, const int minSources, const int maxRounds,
                const double k, const double spread, const double saiFactor, std::vector<std::vector<unsigned char> >& flags,
                std::vector<unsigned>& state, unsigned long long& flagged, unsigned long long& nonfinite, unsigned& bad, unsigned& untested,
-               unsigned& rounds, double scales[3]) {
+               unsigned& rounds, double scales[3], const unsigned disparity_steps) {
     const unsigned asize = awidth * aheight;
     lfbm5d_consist_result result;
     std::memset(&result, 0, sizeof(result));
@@ -629,8 +652,13 @@ int consist_LF(const std::vector<std::vector<float> >& LF, const std::vector<uns
             flags[st].assign(img, 0);
             p[st] = LF[st].data(); f[st] = flags[st].data();
         }
-    if (lfbm5d_consist_host_sai(ctx, &cp, p.data(), LF_SAI_mask.data(), exclude.empty() ? nullptr : exclude.data(), f.data(), state.data(), nullptr,
-                                nullptr, nullptr, ang_major, awidth, aheight, width, height, chnls, &result) != 0) {
+    const unsigned* ex = exclude.empty() ? nullptr : exclude.data();
+    const int rc = disparity_steps == 1                                         /* the integer form: its name in the messages */
+        ? lfbm5d_consist_host_sai(ctx, &cp, p.data(), LF_SAI_mask.data(), ex, f.data(), state.data(), nullptr, nullptr, nullptr, ang_major, awidth,
+                                  aheight, width, height, chnls, &result)
+        : lfbm5d_consist_steps_host_sai(ctx, &cp, disparity_steps, p.data(), LF_SAI_mask.data(), ex, f.data(), state.data(), nullptr, nullptr,
+                                        nullptr, ang_major, awidth, aheight, width, height, chnls, &result);
+    if (rc != 0) {
         std::cout << "LFBM5D GPU backend: " << lfbm5d_last_error(ctx) << std::endl;
         return EXIT_FAILURE;
     }
@@ -643,9 +671,9 @@ int consist_LF(const std::vector<std::vector<float> >& LF, const std::vector<uns
  * flags_flat (planes of empty SAIs untouched), the states to state_out.  cpi = {maxDisparity, boxRadius, angRadius, minSources, maxRounds},
  * cpd = {k, spread, saiFactor}; exclude may be NULL;
  * counts = {flagged, nonfinite, bad, untested, rounds}, scales [3]. */
-extern "C" int lfbm5d_consist_probe(const float* in_flat, const unsigned* mask, const unsigned* exclude, unsigned char* flags_flat,
-                                    unsigned* state_out, unsigned ang_major, unsigned awidth, unsigned aheight, unsigned width, unsigned height,
-                                    unsigned chnls, const int* cpi, const double* cpd, unsigned long long* counts, double* scales) {
+static int consist_probe(const float* in_flat, const unsigned* mask, const unsigned* exclude, unsigned char* flags_flat, unsigned* state_out,
+                         unsigned ang_major, unsigned awidth, unsigned aheight, unsigned width, unsigned height, unsigned chnls, const int* cpi,
+                         const double* cpd, unsigned long long* counts, double* scales, unsigned disparity_steps) {
     const size_t asize = (size_t)awidth * aheight, img = (size_t)width * height * chnls;
     std::vector<unsigned> m(mask, mask + asize), ex, state;
     if (exclude) ex.assign(exclude, exclude + asize);
@@ -654,7 +682,7 @@ extern "C" int lfbm5d_consist_probe(const float* in_flat, const unsigned* mask, 
     std::vector<std::vector<unsigned char> > fl;
     unsigned long long flagged = 0, nonfinite = 0; unsigned bad = 0, untested = 0, rounds = 0; double sc[3];
     if (consist_LF(LF, m, ex, ang_major, awidth, aheight, width, height, chnls, cpi[0], cpi[1], cpi[2], cpi[3], cpi[4], cpd[0], cpd[1], cpd[2], fl,
-                   state, flagged, nonfinite, bad, untested, rounds, sc) != EXIT_SUCCESS) return 1;
+                   state, flagged, nonfinite, bad, untested, rounds, sc, disparity_steps) != EXIT_SUCCESS) return 1;
     for (size_t st = 0; st < asize; st++) {
         state_out[st] = state[st];
         if (m[st]) std::memcpy(flags_flat + st * img, fl[st].data(), img);
@@ -662,6 +690,21 @@ extern "C" int lfbm5d_consist_probe(const float* in_flat, const unsigned* mask, 
     if (counts) { counts[0] = flagged; counts[1] = nonfinite; counts[2] = bad; counts[3] = untested; counts[4] = rounds; }
     if (scales) { scales[0] = sc[0]; scales[1] = sc[1]; scales[2] = sc[2]; }
     return 0;
+}
+
+extern "C" int lfbm5d_consist_probe(const float* in_flat, const unsigned* mask, const unsigned* exclude, unsigned char* flags_flat,
+                                    unsigned* state_out, unsigned ang_major, unsigned awidth, unsigned aheight, unsigned width, unsigned height,
+                                    unsigned chnls, const int* cpi, const double* cpd, unsigned long long* counts, double* scales) {
+    return consist_probe(in_flat, mask, exclude, flags_flat, state_out, ang_major, awidth, aheight, width, height, chnls, cpi, cpd, counts, scales, 1);
+}
+
+/* The same with consist_LF's disparity_steps. */
+extern "C" int lfbm5d_consist_steps_probe(const float* in_flat, const unsigned* mask, const unsigned* exclude, unsigned char* flags_flat,
+                                          unsigned* state_out, unsigned ang_major, unsigned awidth, unsigned aheight, unsigned width,
+                                          unsigned height, unsigned chnls, const int* cpi, const double* cpd, unsigned long long* counts,
+                                          double* scales, unsigned disparity_steps) {
+    return consist_probe(in_flat, mask, exclude, flags_flat, state_out, ang_major, awidth, aheight, width, height, chnls, cpi, cpd, counts, scales,
+                         disparity_steps);
 }
 
 /* run_bm3d_LF (src/bm3d_LF.h:10-35, bm3d_LF.cpp:75-125): BM3D on every SAI of the mask */

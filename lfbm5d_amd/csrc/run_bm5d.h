@@ -261,7 +261,8 @@ int inpaint_LF(
 //! every step (lfbm5d_view_host_sai, include/lfbm5d.h).  LF is completed in place.  maxDisparity, boxRadius, angRadius, iterations < 0,
 //! sigmaStart = 0, sigmaEnd = 0: the library's defaults (lfbm5d_view_defaults); iterations = 0: the synthesis alone.  `left` counts the
 //! missing SAIs without a source (unchanged); dmin..dmax is the range of the disparities chosen (0..0 when nothing was synthesised).
-//! Returns EXIT_SUCCESS, or EXIT_FAILURE with the message on stdout.
+//! disparity_steps = 1, 2 or 4 hypotheses per pixel (lfbm5d_view_steps_host_sai; above 1 the sources are interpolated bilinearly and
+//! dmin..dmax is in units of 1 / disparity_steps).  Returns EXIT_SUCCESS, or EXIT_FAILURE with the message on stdout.
 int view_synth_LF(
     std::vector<std::vector<float> > &LF
 ,   const std::vector<unsigned> &LF_SAI_mask
@@ -295,6 +296,7 @@ int view_synth_LF(
 ,   unsigned &left
 ,   int &dmin
 ,   int &dmax
+,   const unsigned disparity_steps = 1
 );
 
 //! Consistency check -- not in the reference: every usable SAI is predicted on the GPU from its angular neighbours by the view synthesis'
@@ -305,8 +307,9 @@ int view_synth_LF(
 //! saiFactor < 0: the library's defaults (lfbm5d_consist_defaults); saiFactor = 0: no bad-SAI decision.  `flags` is resized to one
 //! plane of width*height*chnls codes per non-empty SAI (the map of inpaint_LF), `state` to one entry per SAI (0 empty, 1 tested, 2 bad,
 //! 3 untested, 4 excluded; the bad ones are the `missing` of view_synth_LF); `flagged` and `nonfinite` count the values with code 1 and
-//! code 2 over all channels, `scales` receives the median residual of the three stored channels, `rounds` the sweeps.  Returns
-//! EXIT_SUCCESS, or EXIT_FAILURE with the message on stdout.
+//! code 2 over all channels, `scales` receives the median residual of the three stored channels, `rounds` the sweeps.
+//! disparity_steps = 1, 2 or 4 hypotheses per pixel in the sweep (lfbm5d_consist_steps_host_sai).  Returns EXIT_SUCCESS, or
+//! EXIT_FAILURE with the message on stdout.
 int consist_LF(
     const std::vector<std::vector<float> > &LF
 ,   const std::vector<unsigned> &LF_SAI_mask
@@ -333,6 +336,7 @@ int consist_LF(
 ,   unsigned &untested
 ,   unsigned &rounds
 ,   double scales[3]
+,   const unsigned disparity_steps = 1
 );
 
 //! Super-resolution -- not in the reference's master branch: the scheme of SR-LFBM5D (iterative back-projection regularised by the

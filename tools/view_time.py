@@ -11,8 +11,11 @@ its own under its own time limit; the first step that fails ends the run.
 The ratios are added by the parent.  The timed light field is 17x17x512x512x3, device-resident: the golden light field tiled 2 x 2 and
 repeated over the SAIs.  HIP events around a batch of whole calls, warm-up first; median / min / max / std over `reps` windows of the
 per-call time.  No counter run is made here: what bounds the kernel is not measured by this tool.
-usage: python tools/view_time.py [reps] [output file, default profiles/view.txt] [batch]
-       python tools/view_time.py --step <name> reps batch     (what the parent starts)"""
+--steps Q (1, 2 or 4): only fill_one and fill_odd, with Q hypotheses per pixel of disparity (lfbm5d_view_fill_steps_device; Q = 1 calls
+lfbm5d_view_fill_device, so that the tool also times a library from before the sub-pixel sweep, loaded through LFBM5D_HIP_LIB); the
+records carry the number of hypotheses (2 D Q + 1) and the time per hypothesis; the file defaults to profiles/view_steps<Q>.txt.
+usage: python tools/view_time.py [--steps Q] [reps] [output file, default profiles/view.txt] [batch]
+       python tools/view_time.py --step <name> reps batch [Q]     (what the parent starts)"""
 import json
 import os
 import subprocess
@@ -71,7 +74,7 @@ def timed(fns, stream, reps, batch):
     return [stats(v) for v in ms]
 
 
-def step(name, reps, batch):
+def step(name, reps, batch, q=1):
     import torch
     import lfbm5d_amd as L
     from lfbm5d_amd import core
@@ -89,13 +92,18 @@ def step(name, reps, batch):
     elif name.startswith("fill"):
         missing = missing_of(name)
         vp = L.view_params()
-        r = ctx.view_fill(y, mask, missing, L.ROWMAJOR, AW, AH, W, H, 3, out=out)
+        kw = dict(disparity_steps=q) if q != 1 else {}
+        r = ctx.view_fill(y, mask, missing, L.ROWMAJOR, AW, AH, W, H, 3, out=out, **kw)
         disp = torch.zeros((AH * AW, W * H), dtype=torch.int8, device="cuda")
-        t = timed([lambda: ctx.view_fill(y, mask, missing, L.ROWMAJOR, AW, AH, W, H, 3, out=out),
-                   lambda: ctx.view_fill(y, mask, missing, L.ROWMAJOR, AW, AH, W, H, 3, out=out, disparity_out=disp)], st, reps, batch)
+        t = timed([lambda: ctx.view_fill(y, mask, missing, L.ROWMAJOR, AW, AH, W, H, 3, out=out, **kw),
+                   lambda: ctx.view_fill(y, mask, missing, L.ROWMAJOR, AW, AH, W, H, 3, out=out, disparity_out=disp, **kw)], st, reps, batch)
         rec.update(fill_ms=t[0], fill_with_disparity_planes_ms=t[1], missing=r.missing, synthesised=r.synthesised, left=r.left,
                    max_disparity=vp.max_disparity, box_radius=vp.box_radius, ang_radius=vp.ang_radius,
                    fill_ms_per_synthesised_sai=round(t[0]["median"] / max(1, r.synthesised), 4))
+        if "--steps" in sys.argv or q != 1:
+            hyp = 2 * vp.max_disparity * q + 1
+            rec.update(disparity_steps=q, hypotheses=hyp, fill_ms_per_hypothesis=round(t[0]["median"] / hyp, 4),
+                       library=os.environ.get("LFBM5D_HIP_LIB") or "the tree's")
     else:
         missing = missing_of(name)
         P = core.make_params(0.0, 2.7, *HT)
@@ -113,9 +121,34 @@ def step(name, reps, batch):
     print("RESULT " + json.dumps(rec), flush=True)
 
 
+def sweep_steps(q, rest):
+    """--steps Q: fill_one and fill_odd at Q hypotheses per pixel, each in a child of its own; the first that fails ends the run."""
+    if q not in (1, 2, 4):
+        sys.exit("--steps takes 1, 2 or 4")
+    reps = int(rest[0]) if rest else 5
+    path = rest[1] if len(rest) > 1 else os.path.join(ROOT, "profiles", f"view_steps{q}.txt")
+    batch = int(rest[2]) if len(rest) > 2 else 3
+    lines = []
+    for name, limit in STEPS[:2]:
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", name, str(reps), str(batch), str(q), "--steps"],
+                           capture_output=True, text=True, timeout=limit)
+        line = [x for x in r.stdout.splitlines() if x.startswith("RESULT ")]
+        if r.returncode != 0 or not line:
+            sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
+            sys.exit(f"step {name} failed with exit status {r.returncode}: nothing further is started")
+        lines.append(line[-1][7:])
+        print(lines[-1], flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        f.write("# tools/view_time.py --steps %d %d <file> %d  (MI355X; times in ms; see the tool's docstring)\n" % (q, reps, batch))
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--step":
-        return step(sys.argv[2], int(sys.argv[3]), int(sys.argv[4]))
+        return step(sys.argv[2], int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5]) if len(sys.argv) > 5 else 1)
+    if len(sys.argv) > 1 and sys.argv[1] == "--steps":
+        return sweep_steps(int(sys.argv[2]), sys.argv[3:])
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
     path = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "view.txt")
     batch = int(sys.argv[3]) if len(sys.argv) > 3 else 10
