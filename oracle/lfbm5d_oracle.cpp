@@ -30,6 +30,8 @@ int g_threads = 0; /* 0 = OpenMP default */
 std::vector<unsigned> g_last_windows; /* run API: processed SAI of every window of the last step, in order */
 int g_tiles = 1; /* run API: 1 = untiled (nb_threads == 1 semantics), > 1 = the reference's OpenMP tile mode with that many tiles */
 double g_time_limit = 0.0; /* run API: stop after the window that exceeds it (0 = none) */
+int g_tie_order = 0; /* block matching, tie census only: 0 = scan order (the project's definition), 1 = whatever std::partial_sort /
+                        std::sort with a first-only comparator leave, as the reference calls them (orc_set_tie_order) */
 
 double now_s() {
     using namespace std::chrono;
@@ -639,8 +641,11 @@ int bm_self(const float* img, unsigned W, unsigned H, unsigned k, unsigned N, un
             }
             const unsigned nSx = N > cand.size() ? pow2_floor((unsigned)cand.size()) : N;
             if (nSx == 1 && cand.empty()) cand.push_back({0.0f, k_r, 0});
-            /* std::partial_sort in the reference; tie order unspecified there -> scan order here */
-            std::stable_sort(cand.begin(), cand.end(), [](const Cand& a, const Cand& b) { return a.d < b.d; });
+            /* std::partial_sort in the reference; tie order unspecified there -> scan order here.  The census switch runs the
+             * library's partial_sort on the same scan-ordered vector, to count how often that differs. */
+            const auto first_only = [](const Cand& a, const Cand& b) { return a.d < b.d; };
+            if (g_tie_order) std::partial_sort(cand.begin(), cand.begin() + nSx, cand.end(), first_only);
+            else std::stable_sort(cand.begin(), cand.end(), first_only);
             unsigned cnt = 0;
             for (unsigned n = 0; n < nSx; n++) out_idx[(size_t)r * N + cnt++] = cand[n].idx;
             if (nSx == 1) out_idx[(size_t)r * N + cnt++] = cand[0].idx; /* duplicate rule core:3443-3444 */
@@ -659,6 +664,31 @@ int bm_stereo(const float* img1, const float* img2, unsigned W, unsigned H, unsi
     std::vector<float> diff(WH + (size_t)k * W + k, 0.0f), sum(WH, 0.0f), bestd(WH, 0.0f);
     std::vector<unsigned> bestorder(WH, 0xffffffffu);
     const unsigned lo = nDisp, hi_r = H - nDisp - k + 1, hi_c = W - nDisp - k + 1;
+    if (g_tie_order) {
+        /* census switch: every table kept, then per position the candidates in scan order, std::sort with a first-only
+         * comparator, entry [0] -- the library call the reference makes at core:3600 */
+        std::vector<float> all;
+        try { all.assign((size_t)Ns * Ns * WH, 0.0f); } catch (...) { return 1; }
+        for (unsigned di = 0; di < Ns; di++)
+            for (unsigned dj = 0; dj < Ns; dj++) {
+                const int dk = (int)(di * W + dj) - (int)(nDisp * (1 + W));
+                integral_table(img1, img2, dk, W, H, k, nDisp, k - 1, diff.data(), all.data() + (size_t)(dj * Ns + di) * WH);
+            }
+        std::vector<std::pair<float, unsigned> > cand(Ns * Ns);
+        for (unsigned i = lo; i < hi_r; i++)
+            for (unsigned j = lo; j < hi_c; j++) {
+                const size_t q = (size_t)i * W + j;
+                for (unsigned dj = 0, o = 0; dj < Ns; dj++)
+                    for (unsigned di = 0; di < Ns; di++, o++)
+                        cand[o] = std::make_pair(all[(size_t)o * WH + q],
+                                                 (unsigned)((int)q + ((int)di - (int)nDisp) * (int)W + ((int)dj - (int)nDisp)));
+                std::sort(cand.begin(), cand.end(),
+                          [](const std::pair<float, unsigned>& a, const std::pair<float, unsigned>& b) { return a.first < b.first; });
+                best[q] = cand[0].second;
+                shape[q] = cand[0].first < threshold ? 1 : 0;
+            }
+        return 0;
+    }
     for (unsigned di = 0; di < Ns; di++)
         for (unsigned dj = 0; dj < Ns; dj++) {
             const int dk = (int)(di * W + dj) - (int)(nDisp * (1 + W));
@@ -1625,6 +1655,7 @@ int orc_last_windows(unsigned* out, unsigned cap) {
     return (int)g_last_windows.size();
 }
 void orc_set_time_limit(double seconds) { g_time_limit = seconds; }
+void orc_set_tie_order(int mode) { g_tie_order = mode ? 1 : 0; }
 void orc_set_tiles(int n) {   /* floored to a power of two like main.cpp:101-102 does with nb_threads */
     int t = 1;
     while (t * 2 <= n) t *= 2;

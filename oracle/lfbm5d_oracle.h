@@ -183,6 +183,10 @@ void orc_set_time_limit(double seconds);
 /* run API: n > 1 selects the reference's OpenMP tile mode (bm5d.cpp:411-708; n = its nb_threads, a power of two): every SAI is cut
  * into n sub-images with a halo, tiles run independently, halo output is discarded.  1 = untiled (the parity mode). */
 void orc_set_tiles(int n);
+/* block matching, test infrastructure for the tie census only: 0 (default) = exact ties keep candidate scan order; 1 = orc_bm_self
+ * orders its candidates with std::partial_sort and orc_bm_stereo sorts each position's candidates with std::sort, both with a
+ * comparator that looks at the distance alone -- the library calls of core:3435 / :3600, whose tie order is unspecified. */
+void orc_set_tie_order(int mode);
 int  orc_get_threads(void);
 
 #ifdef __cplusplus

@@ -109,9 +109,8 @@ def _check_pass(ctx, case, strict):
     _check_window(ctx, name, step, sigma, pk, useSD, win, Wb, Hb, Cc, strict)
 
 
-def _check_window(ctx, name, step, sigma, pk, useSD, win, Wb, Hb, Cc, strict):
-    basic = None
-    if step == 2:  # a plausible pilot: the oracle's own HT estimate of this window
+def _check_window(ctx, name, step, sigma, pk, useSD, win, Wb, Hb, Cc, strict, basic=None):
+    if step == 2 and basic is None:  # a plausible pilot: the oracle's own HT estimate of this window
         n1, d1, _ = Hh.oracle_pass(1, sigma, (pk[0] // 2 or 1,) + pk[1:5] + ("id", "sadct", "haar"), win, None, Wb, Hb, Cc)
         basic = np.ascontiguousarray(Hh.estimate(n1, d1, win).astype(np.float32))
     num_o, den_o, st = Hh.oracle_pass(step, sigma, pk, win, basic, Wb, Hb, Cc, useSD=useSD)
