@@ -644,6 +644,13 @@ int lfbm5d_last_group_list(lfbm5d_ctx* c, unsigned* n, unsigned* out, unsigned c
 size_t lfbm5d_last_scores(lfbm5d_ctx* c, float* h_scores, size_t n_floats) {
     if (!c) return 0;
     (void)hipSetDevice(c->device);
+    /* a pass that skipped the fill of `scores` (pass_impl) left stale values where the table kernel does not write: patched here, at
+     * the read-out, rather than by filling whenever a read-out might follow */
+    if (c->unfilled.pending) {
+        const lfbm5d_ctx::UnfilledScores& u = c->unfilled;
+        if (launch_scores_patch(c->stream, c->scores.as<float>(), u.n_rows, u.n_cols, u.W, u.nSim, u.nHW, u.p, u.last_r, u.last_c, u.fill) != hipSuccess) return 0;
+        c->unfilled.pending = false;
+    }
     if (hipStreamSynchronize(c->stream) != hipSuccess) return 0;
     const size_t have = c->scores.cap / sizeof(float);
     if (!h_scores) return have;

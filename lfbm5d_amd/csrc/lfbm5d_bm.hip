@@ -714,6 +714,29 @@ __device__ __forceinline__ unsigned f2ord(float f) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+/* minimum of a 64-bit key over the wavefront by DPP row shifts / row broadcasts (a `__shfl_xor` butterfly is six dependent
+ * pairs of ds_bpermute: with 2 nSx of these reductions per reference patch that was half the kernel) */
+__device__ __forceinline__ unsigned long long wave_min(unsigned long long v) {
+    auto step = [&](auto ctrl, auto rmask, auto bmask, unsigned long long src) {
+        constexpr int C = decltype(ctrl)::value, R = decltype(rmask)::value, B = decltype(bmask)::value;
+        const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)v, (int)(unsigned)src, C, R, B, false);
+        const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)(v >> 32), (int)(unsigned)(src >> 32), C, R, B, false);
+        const unsigned long long oth = ((unsigned long long)hi << 32) | lo;   /* lanes the pattern does not write keep their own key */
+        v = oth < v ? oth : v;
+    };
+    using std::integral_constant;
+    const unsigned long long v0 = v;
+    step(integral_constant<int, 0x111>{}, integral_constant<int, 0xf>{}, integral_constant<int, 0xf>{}, v0);   /* row_shr:1 */
+    step(integral_constant<int, 0x112>{}, integral_constant<int, 0xf>{}, integral_constant<int, 0xf>{}, v0);   /* row_shr:2 */
+    step(integral_constant<int, 0x113>{}, integral_constant<int, 0xf>{}, integral_constant<int, 0xf>{}, v0);   /* row_shr:3 */
+    step(integral_constant<int, 0x114>{}, integral_constant<int, 0xf>{}, integral_constant<int, 0xe>{}, v);    /* row_shr:4 */
+    step(integral_constant<int, 0x118>{}, integral_constant<int, 0xf>{}, integral_constant<int, 0xc>{}, v);    /* row_shr:8 */
+    step(integral_constant<int, 0x142>{}, integral_constant<int, 0xa>{}, integral_constant<int, 0xf>{}, v);    /* row_bcast:15 */
+    step(integral_constant<int, 0x143>{}, integral_constant<int, 0xc>{}, integral_constant<int, 0xf>{}, v);    /* row_bcast:31 */
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
 /* Candidate selection of precompute_BM (core:3397-3445), one wave per reference patch. */
 __global__ __launch_bounds__(64) void k_self_select(const float* __restrict__ scores,
                                                      const unsigned* __restrict__ refs, unsigned n_refs,
@@ -779,28 +802,6 @@ __global__ __launch_bounds__(64) void k_self_select(const float* __restrict__ sc
         if (lane == 0) { out[0] = k_r; out[1] = k_r; self_cnt[ref] = 2; }
         return;
     }
-    /* minimum of a 64-bit key over the wavefront by DPP row shifts / row broadcasts (a `__shfl_xor` butterfly is six dependent
-     * pairs of ds_bpermute: with 2 nSx of these reductions per reference patch that was half the kernel) */
-    auto wave_min = [](unsigned long long v) {
-        auto step = [&](auto ctrl, auto rmask, auto bmask, unsigned long long src) {
-            constexpr int C = decltype(ctrl)::value, R = decltype(rmask)::value, B = decltype(bmask)::value;
-            const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)v, (int)(unsigned)src, C, R, B, false);
-            const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)(v >> 32), (int)(unsigned)(src >> 32), C, R, B, false);
-            const unsigned long long oth = ((unsigned long long)hi << 32) | lo;   /* lanes the pattern does not write keep their own key */
-            v = oth < v ? oth : v;
-        };
-        using std::integral_constant;
-        const unsigned long long v0 = v;
-        step(integral_constant<int, 0x111>{}, integral_constant<int, 0xf>{}, integral_constant<int, 0xf>{}, v0);   /* row_shr:1 */
-        step(integral_constant<int, 0x112>{}, integral_constant<int, 0xf>{}, integral_constant<int, 0xf>{}, v0);   /* row_shr:2 */
-        step(integral_constant<int, 0x113>{}, integral_constant<int, 0xf>{}, integral_constant<int, 0xf>{}, v0);   /* row_shr:3 */
-        step(integral_constant<int, 0x114>{}, integral_constant<int, 0xf>{}, integral_constant<int, 0xe>{}, v);    /* row_shr:4 */
-        step(integral_constant<int, 0x118>{}, integral_constant<int, 0xf>{}, integral_constant<int, 0xc>{}, v);    /* row_shr:8 */
-        step(integral_constant<int, 0x142>{}, integral_constant<int, 0xa>{}, integral_constant<int, 0xf>{}, v);    /* row_bcast:15 */
-        step(integral_constant<int, 0x143>{}, integral_constant<int, 0xc>{}, integral_constant<int, 0xf>{}, v);    /* row_bcast:31 */
-        const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
-        return ((unsigned long long)hi << 32) | lo;
-    };
     /* number of lanes whose key is smaller than this lane's (equal keys -- only the sentinels -- by lane number): 64
      * broadcast-compare steps, no dependent chain (nSx rounds of a wave minimum are nSx x 7 dependent DPP steps) */
     auto wave_rank = [&](unsigned long long v) {
@@ -870,6 +871,207 @@ __global__ __launch_bounds__(64) void k_self_select(const float* __restrict__ sc
         }
     }
     if (lane == 0) self_cnt[ref] = nSx == 1 ? 2 : nSx;
+}
+
+/* Which entries of a regular-grid reference patch's score row the ring-sharing table kernel writes (lfbm5d_scan2.hip, self search:
+ * emit0, the row-0 stores and the chunk loop's pattern / look-up stores).  Table (di, dj) holds at position (ty, tx), ty in
+ * [nHW, H - nHW), tx in [nHW, W - nHW), the distance between the patches at (ty, tx) and (ty + di, tx + dj - nSim), and stores it
+ *   forward:  row of the reference (ty, tx), entry (dip, djp) = (di, dj - nSim)              -- when (ty, tx) is a grid position;
+ *   backward: row of the reference (ty + di, tx + dj - nSim), entry (dip, djp) = (-di, nSim - dj), di > 0
+ *                                                                                            -- when that is a grid position.
+ * Every store path applies exactly these conditions: column 0 (emit0: all nrows rows, rslot / s2_grid_index of the two references),
+ * row 0 (col_ok lanes, s2_grid_index of row nHW and row nHW + di), the other rows (general form: act, rs[y], rs[y + di]; pattern form:
+ * the same rows through boundF / boundB), the forced last grid row / column being grid positions like the stepped ones.  A reference
+ * (y, x) of the grid always lies inside the table, so all its forward entries are written; its backward entry (dip < 0, djp) comes
+ * from table position (y + dip, x + djp) and is written exactly when that position is inside the table.  (y + dip < H - nHW always.) */
+__device__ __forceinline__ bool scan2_writes_backward(int y, int x, int dip, int djp, int W, int nHW) {
+    return y + dip >= nHW && (unsigned)(x + djp - nHW) < (unsigned)(W - 2 * nHW);
+}
+
+constexpr int kSelWaves = 4;      /* reference patches (wavefronts) of a workgroup of k_self_select_regs */
+constexpr int kSelMaxRows = 32;   /* largest instantiation: search windows of up to 64 * 32 candidates */
+
+struct SelectArgs {
+    const float* scores; const unsigned* refs; unsigned n_refs;
+    int W, nSim, N; float thr;
+    unsigned* self_idx; unsigned* self_cnt;
+    int grid_cols, nHW, p, last_r, last_c;
+    int unfilled;   /* `scores` was not filled before the table kernel ran: an entry that kernel does not write counts as `fill` */
+    float fill;     /* 2 thr */
+};
+
+/* The same selection with a reference patch's score row in registers (search windows of up to 64 ROWS candidates on the regular
+ * grid), one wavefront per reference patch, kSelWaves independent ones per workgroup.  The kernel is bound by its vector
+ * instructions (a wavefront's instruction takes four cycles of its SIMD), so the point is their number:
+ *   - ROWS coalesced loads issued together; the row is staged in LDS once, and the backward half's test value -- the same row's
+ *     forward entry at the mirrored displacement (core:3415-3419) -- is the staged entry ncand - e: with e = q Ns + r the mirrored
+ *     index (2 nSim - q) Ns + (Ns - r) is just that;
+ *   - keys stay in registers as their upper halves (the lower half of entry u of a lane is its scan index u * 64 + lane); a
+ *     candidate that fails the threshold holds the upper half 0xffffffff.  (A PASSING score with that upper half -- the bit pattern
+ *     0x7fffffff, a NaN payload no arithmetic produces -- would count as failing here; k_self_select sorts it last.)
+ *   - the pruning bound of k_self_select -- the nSx-th smallest of the 64 per-lane minima -- by a radix select over the lanes: one
+ *     compare and a scalar population count per key bit (32 + 11 steps) instead of a rank (64 broadcast-compare steps);
+ *   - only the keys at or below the bound go to LDS, compacted in scan order, and one rank over them, read back as LDS broadcasts,
+ *     is the selection.  More than 64 survivors (exact ties at the bound, or nothing to prune): nSx rounds of a wave minimum over
+ *     the registers;
+ *   - a reference patch at least nSim inside the table has no unwritten entry: the test per entry is skipped for the wavefront.
+ * Same keys, same order, same quirks as k_self_select -- self_idx / self_cnt are bit-identical.
+ * SURE: rows u < SURE lie inside every search window the instantiation is launched for. */
+template <int ROWS, int SURE>
+__global__ __launch_bounds__(kSelWaves * 64) void k_self_select_regs(SelectArgs a) {
+    static_assert(ROWS <= kSelMaxRows && ROWS * 64 <= 2048, "scan indices are 11 bits in the radix select");
+    __shared__ float stage[kSelWaves][ROWS * 64];
+    __shared__ __attribute__((aligned(16))) unsigned long long skeys[kSelWaves][64];
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const unsigned ref = blockIdx.x * kSelWaves + wv;
+    if (ref >= a.n_refs) return;   /* (no workgroup barrier below: the wavefronts are independent) */
+    const int W = a.W, nSim = a.nSim, N = a.N, nHW = a.nHW;
+    const int Ns = 2 * nSim + 1, ncand = Ns * Ns;
+    const float thr = a.thr;
+    /* e / Ns by a 24-bit multiplication: exact for e < 2^18 / Ns, i.e. for every index below 2048 (Ns <= 45) */
+    const unsigned div_m = ((1u << 18) + (unsigned)Ns - 1) / (unsigned)Ns;
+    const int k_r = __builtin_amdgcn_readfirstlane((int)a.refs[ref]);
+    const int y = k_r / W, x = k_r - y * W;
+    size_t row = ref;
+    if (a.grid_cols) {
+        const int gi = y == a.last_r ? (a.last_r - nHW + a.p - 1) / a.p : (y - nHW) / a.p;
+        const int gj = x == a.last_c ? (a.last_c - nHW + a.p - 1) / a.p : (x - nHW) / a.p;
+        row = (size_t)gi * a.grid_cols + gj;
+    }
+    const float* sc = a.scores + row * ncand;
+    float v[ROWS];
+#pragma unroll
+    for (int u = 0; u < ROWS; u++) {
+        const int e = u * 64 + lane;
+        v[u] = (u < SURE || e < ncand) ? sc[e] : 0.0f;
+    }
+    float* st = stage[wv];
+#pragma unroll
+    for (int u = 0; u < ROWS; u++) {
+        const int e = u * 64 + lane;
+        if (u < SURE || e < ncand) st[e] = v[u];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    unsigned hk[ROWS];       /* upper key halves, 0xffffffff: not a candidate */
+    int cnt = 0;
+    unsigned mhi = 0xffffffffu, mlo = 0xffffffffu;   /* this lane's smallest key */
+    auto scan_rows = [&](auto edge_tag) {
+        constexpr bool EDGE = decltype(edge_tag)::value;
+#pragma unroll
+        for (int u = 0; u < ROWS; u++) {
+            const int e = u * 64 + lane;
+            const bool in = u < SURE || e < ncand;
+            const int q = (int)(__umul24((unsigned)e, div_m) >> 18);
+            const int r = e - (int)__umul24((unsigned)q, (unsigned)Ns);
+            const bool fwd = r <= nSim;
+            const float t = st[max(ncand - e, 0)];   /* (used by the backward half, whose mirrored entry exists) */
+            float score = v[u];
+            if (EDGE) score = (fwd || scan2_writes_backward(y, x, r - Ns, q - nSim, W, nHW)) ? score : a.fill;
+            const bool pass = in && (fwd ? v[u] : t) < thr;
+            hk[u] = pass ? f2ord(score) : 0xffffffffu;
+            cnt += __popcll(__ballot(hk[u] != 0xffffffffu));
+            if (hk[u] < mhi) { mhi = hk[u]; mlo = (unsigned)e; }
+        }
+    };
+    /* wave-uniform: some backward entry (dip in [-nSim, -1], djp in [-nSim, nSim]) of this reference is not written */
+    if (a.unfilled && !(y - nSim >= nHW && x - nSim >= nHW && x + nSim < W - nHW)) scan_rows(std::true_type{});
+    else scan_rows(std::false_type{});
+    unsigned nSx;
+    if (N > cnt) { nSx = 1; while (nSx * 2 <= (unsigned)cnt) nSx *= 2; } else nSx = N;
+    unsigned* out = a.self_idx + (size_t)ref * N;
+    if (cnt == 0) { /* core:3429-3432 */
+        if (lane == 0) { out[0] = k_r; out[1] = k_r; a.self_cnt[ref] = 2; }
+        return;
+    }
+    auto place = [&](unsigned long long kk, unsigned n) {   /* the n-th patch of the group */
+        const int e = (int)(kk & 0xffffffffu);
+        const int djp = e / Ns - nSim, r = e % Ns;
+        const int dip = (r <= nSim) ? r : r - 2 * nSim - 1;
+        out[n] = (unsigned)(k_r + dip * W + djp);
+        if (nSx == 1) out[1] = out[0]; /* duplicate rule core:3443-3444 */
+    };
+    /* The pruning bound of k_self_select: the nSx-th smallest of the per-lane minima (there are nSx distinct keys at or below it).
+     * Bit by bit from the top: the bit is set when fewer than nSx minima lie below the value tried.  Fewer than nSx lanes with a
+     * key: the upper half comes out as 0xffffffff and nothing is pruned, as with 64 candidates or fewer. */
+    unsigned bhi = 0xffffffffu; int blo = -1;   /* candidates: hk < bhi, or hk == bhi and scan index <= blo */
+    if (cnt > 64) {
+        unsigned ahi = 0;
+        for (int b = 31; b >= 0; b--) {
+            const unsigned trial = ahi | (1u << b);
+            if ((unsigned)__popcll(__ballot(mhi < trial)) < nSx) ahi = trial;
+        }
+        if (ahi != 0xffffffffu) {
+            const unsigned need = nSx - (unsigned)__popcll(__ballot(mhi < ahi));   /* among the minima with this upper half */
+            unsigned alo = 0;
+            for (int b = 10; b >= 0; b--) {
+                const unsigned trial = alo | (1u << b);
+                if ((unsigned)__popcll(__ballot(mhi == ahi && mlo < trial)) < need) alo = trial;
+            }
+            bhi = ahi; blo = (int)alo;
+        }
+    }
+    auto kept = [&](int u) { return hk[u] < bhi || (hk[u] == bhi && u * 64 + lane <= blo); };
+    auto key_of = [&](int u) { return ((unsigned long long)hk[u] << 32) | (unsigned)(u * 64 + lane); };
+    unsigned long long* keys = skeys[wv];
+    int c2 = 0;
+#pragma unroll
+    for (int u = 0; u < ROWS; u++) {
+        const bool keep = kept(u);
+        const unsigned long long bal = __ballot(keep);
+        if (bal) {
+            const int pos = c2 + __popcll(bal & ((1ull << lane) - 1ull));
+            if (keep && pos < 64) keys[pos] = key_of(u);
+            c2 += __popcll(bal);
+        }
+    }
+    if (c2 <= 64) {
+        /* one key per lane: its rank is its place in the selection (core:3437-3441: partial_sort by distance, ties in scan order).
+         * The rank: the number of smaller keys, every lane reading the keys one after the other (LDS broadcasts) */
+        if (lane >= c2) keys[lane] = ~0ull;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const unsigned long long kk = keys[lane];
+        unsigned rk = 0;
+        for (int j = 0; j < c2; j += 8) {
+#pragma unroll
+            for (int i = 0; i < 8; i++) rk += keys[j + i] < kk ? 1u : 0u;
+        }
+        if (lane < c2 && rk < nSx) place(kk, rk);
+        if (lane == 0) a.self_cnt[ref] = nSx == 1 ? 2 : nSx;
+        return;
+    }
+    unsigned long long last = 0;
+    for (unsigned n = 0; n < nSx; n++) { /* n-th smallest (distance, scan order) key */
+        unsigned long long best = ~0ull;
+#pragma unroll
+        for (int u = 0; u < ROWS; u++) {
+            const unsigned long long kk = key_of(u);
+            if (kept(u) && (n == 0 || kk > last) && kk < best) best = kk;
+        }
+        best = wave_min(best);
+        last = best;
+        if (lane == 0) place(best, n);
+    }
+    if (lane == 0) a.self_cnt[ref] = nSx == 1 ? 2 : nSx;
+}
+
+/* lfbm5d_last_scores after a pass whose score table was not filled: the entries the table kernel does not write get the fill
+ * value, so that the read-out is what a filled table would hold.  One thread per entry of the regular grid's table. */
+__global__ __launch_bounds__(256) void k_scores_patch(float* __restrict__ scores, unsigned n_rows, unsigned n_cols, int W, int nSim, int nHW,
+                                                       int p, int last_r, int last_c, float fill) {
+    const int Ns = 2 * nSim + 1, ncand = Ns * Ns;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)n_rows * n_cols * ncand) return;
+    const unsigned ref = (unsigned)(i / ncand);
+    const int e = (int)(i - (size_t)ref * ncand);
+    const unsigned gi = ref / n_cols, gj = ref - gi * n_cols;
+    const int y = gi == n_rows - 1 ? last_r : nHW + (int)gi * p, x = gj == n_cols - 1 ? last_c : nHW + (int)gj * p;
+    const int q = e / Ns, r = e - q * Ns;
+    if (r <= nSim) return;
+    if (!scan2_writes_backward(y, x, r - Ns, q - nSim, W, nHW)) scores[i] = fill;
 }
 
 __global__ void k_self_trivial(const unsigned* __restrict__ refs, unsigned n_refs,
@@ -1026,6 +1228,37 @@ hipError_t launch_self_select(hipStream_t s, const float* scores, const unsigned
     hipLaunchKernelGGL(k_self_select, dim3(n_refs), dim3(64), (size_t)Ns * Ns * sizeof(unsigned long long), s,
                        scores, refs, n_refs, (int)W, (int)nSim, (int)N, thr, self_idx, self_cnt,
                        (int)grid_cols, (int)nHW, (int)p, (int)last_r, (int)last_c);
+    return hipGetLastError();
+}
+
+bool self_select_regs_covers(unsigned nSim) { return (2 * nSim + 1) * (2 * nSim + 1) <= 64u * kSelMaxRows; }
+
+hipError_t launch_self_select_regs(hipStream_t s, const float* scores, const unsigned* refs, unsigned n_refs,
+                                   unsigned W, unsigned nSim, unsigned N, float thr, unsigned* self_idx, unsigned* self_cnt,
+                                   unsigned grid_cols, unsigned nHW, unsigned p, unsigned last_r, unsigned last_c, bool unfilled) {
+    if (!self_select_regs_covers(nSim)) return hipErrorInvalidValue;
+    SelectArgs a;
+    a.scores = scores; a.refs = refs; a.n_refs = n_refs; a.W = (int)W; a.nSim = (int)nSim; a.N = (int)N; a.thr = thr;
+    a.self_idx = self_idx; a.self_cnt = self_cnt;
+    a.grid_cols = (int)grid_cols; a.nHW = (int)nHW; a.p = (int)p; a.last_r = (int)last_r; a.last_c = (int)last_c;
+    a.unfilled = unfilled ? 1 : 0; a.fill = 2 * thr;
+    const unsigned rows = ((2 * nSim + 1) * (2 * nSim + 1) + 63) / 64;
+    const dim3 grid((n_refs + kSelWaves - 1) / kSelWaves), block(kSelWaves * 64);
+#define LFBM5D_SELECT(R_, SURE_) hipLaunchKernelGGL((k_self_select_regs<R_, SURE_>), grid, block, 0, s, a)
+    /* rows per lane (the headline's 22, nSim = 18, has an instantiation of its own), and the rows every window that gets here fills */
+    if (rows <= 1) LFBM5D_SELECT(1, 0); else if (rows <= 2) LFBM5D_SELECT(2, 1); else if (rows <= 4) LFBM5D_SELECT(4, 2);
+    else if (rows <= 8) LFBM5D_SELECT(8, 4); else if (rows <= 16) LFBM5D_SELECT(16, 8); else if (rows <= 22) LFBM5D_SELECT(22, 16);
+    else LFBM5D_SELECT(32, 22);
+#undef LFBM5D_SELECT
+    return hipGetLastError();
+}
+
+hipError_t launch_scores_patch(hipStream_t s, float* scores, unsigned n_rows, unsigned n_cols, unsigned W, unsigned nSim, unsigned nHW,
+                               unsigned p, unsigned last_r, unsigned last_c, float fill) {
+    const size_t n = (size_t)n_rows * n_cols * (2 * nSim + 1) * (2 * nSim + 1);
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_scores_patch, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, scores, n_rows, n_cols, (int)W, (int)nSim, (int)nHW,
+                       (int)p, (int)last_r, (int)last_c, fill);
     return hipGetLastError();
 }
 

@@ -179,6 +179,9 @@ struct lfbm5d_ctx {
     std::vector<PassEvents> pending;
     /* last pass (inspection) */
     unsigned last_n_refs = 0, last_N = 0, last_A = 0; size_t last_plane = 0; int last_gslot = 0;   /* geometry slot of that pass */
+    /* ... whose score table was not filled in front of the table kernel (pass_impl): lfbm5d_last_scores writes `fill` into the
+     * entries that kernel left out before it copies the table (launch_scores_patch), once */
+    struct UnfilledScores { bool pending = false; unsigned n_rows = 0, n_cols = 0, W = 0, nSim = 0, nHW = 0, p = 0, last_r = 0, last_c = 0; float fill = 0; } unfilled;
 };
 
 namespace lfbm5d_host {

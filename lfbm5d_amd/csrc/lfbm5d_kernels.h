@@ -363,6 +363,18 @@ hipError_t launch_self_select(hipStream_t s, const float* scores, const unsigned
                                * the last one forced to last_r / last_c) and `refs` lists some of them: a reference's scores are
                                * taken from its place in that grid */
                               unsigned grid_cols = 0, unsigned nHW = 0, unsigned p = 1, unsigned last_r = 0, unsigned last_c = 0);
+/* The same selection, register-resident (k_self_select_regs): for reference lists on the regular grid and search windows
+ * self_select_regs_covers accepts.  grid_cols as above (0: `refs` is the whole grid in raster order).  unfilled: `scores` was
+ * NOT filled with 2 thr in front of the ring-sharing table kernel (launch_bm_scan2 on the regular grid); the entries that kernel
+ * does not write are recognised from the geometry and count as 2 thr. */
+bool self_select_regs_covers(unsigned nSim);
+hipError_t launch_self_select_regs(hipStream_t s, const float* scores, const unsigned* refs, unsigned n_refs,
+                                   unsigned W, unsigned nSim, unsigned N, float thr, unsigned* self_idx, unsigned* self_cnt,
+                                   unsigned grid_cols, unsigned nHW, unsigned p, unsigned last_r, unsigned last_c, bool unfilled);
+/* the score table of the regular grid (n_rows x n_cols reference patches) after an `unfilled` pass: `fill` into every entry the
+ * table kernel did not write (lfbm5d_last_scores) */
+hipError_t launch_scores_patch(hipStream_t s, float* scores, unsigned n_rows, unsigned n_cols, unsigned W, unsigned nSim, unsigned nHW,
+                               unsigned p, unsigned last_r, unsigned last_c, float fill);
 hipError_t launch_self_trivial(hipStream_t s, const unsigned* refs, unsigned n_refs, unsigned* self_idx,
                                unsigned* self_cnt);
 hipError_t launch_stereo_argmin(hipStream_t s, const float* tables, const unsigned* st_of_slot, unsigned n_slots,

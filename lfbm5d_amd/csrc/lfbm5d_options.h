@@ -36,6 +36,7 @@ enum : unsigned {
     kOptSubsetScanV1 = 1u << 11,    /* subset passes: round 2's table kernel through the position map */
     kOptFiltGroupMajor = 1u << 12,  /* wide windows (11 x 11 SAIs and more): filtered patches group-major like the 3 x 3 windows' (rounds 1-5) instead of SAI-major */
     kOptHtReferenceOrder = 1u << 13,   /* 3x3 hard-thresholding windows: k_group_id_haar (reference-order arithmetic) instead of k_group_id_haar_fast */
+    kOptSelectPrefill = 1u << 14,   /* self search: every pass fills `scores` with 2 thr and selects with k_self_select (rounds 1-8) instead of k_self_select_regs on an unfilled table */
 };
 
 struct Options {
@@ -80,6 +81,7 @@ inline const OptionKey* option_keys(size_t* n) {
         {"subset_list_host", "LFBM5D_SUBSET_LIST_HOST", nullptr, kOptSubsetListHost}, {"subset_scan_v1", "LFBM5D_SUBSET_SCAN_V1", nullptr, kOptSubsetScanV1},
         {"filt_group_major", "LFBM5D_FILT_GROUP_MAJOR", nullptr, kOptFiltGroupMajor},
         {"ht_reference_order", "LFBM5D_HT_REF_ORDER", nullptr, kOptHtReferenceOrder},
+        {"select_prefill", "LFBM5D_SELECT_PREFILL", nullptr, kOptSelectPrefill},
     };
     *n = sizeof(keys) / sizeof(keys[0]);
     return keys;

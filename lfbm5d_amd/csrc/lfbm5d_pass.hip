@@ -384,7 +384,6 @@ int pass_impl(lfbm5d_ctx* c, int step, const lfbm5d_params* P, unsigned aw, unsi
     sa.n_stereo = n_slots * NsD * NsD;
     for (unsigned i = 0; i < n_slots; i++) sa.st_of_slot[i] = slots[i];
     sa.est_planes = A;
-    if (N > 1) HIPCK(c, launch_fill_f32(s, c->scores.as<float>(), 2 * thr, (size_t)R_sc * NsS * NsS));
     /* which generation of the table kernel, and its workgroup list: functions of the search geometry (and of the two
      * environment switches bm_scan_version reads), cached with it */
     sa.opt = c->opt->kernels; sa.lds_cap = (unsigned)std::max(0, c->opt->scan_lds_cap);
@@ -395,6 +394,20 @@ int pass_impl(lfbm5d_ctx* c, int step, const lfbm5d_params* P, unsigned aw, unsi
     if (scan_changed) gc.scan_version = bm_scan_version(sa);
     const int scan_version = gc.scan_version;
     c->last_scan_version = scan_version;
+    /* The selection: register-resident (k_self_select_regs) for reference lists on the regular grid -- a centre pass, or a subset
+     * pass scored on the full grid -- unless the search window is beyond its instantiations or the option select_prefill asks for
+     * rounds 1-8's form.  The entries of `scores` the table kernel does not write have to read as 2 thr: where the ring-sharing
+     * kernel runs on the regular grid that set follows from the geometry alone, the selection works it out (stateless: a lane's
+     * context alternates between windows with other R and thr) and the 88 MB fill of the headline's pass is left out; every other
+     * table kernel (round 2's, the any-patch-size one, position maps, 12 x 12 patches, the per-SAI BM3D flavour) keeps the fill. */
+    const bool select_regs = N > 1 && (centre || full_scan) && self_select_regs_covers(P->nSim) && !(c->opt->kernels & kOptSelectPrefill);
+    const bool unfilled = select_regs && scan_version >= 2 && sa.refmap == nullptr && !bm3d;
+    if (N > 1 && !unfilled) HIPCK(c, launch_fill_f32(s, c->scores.as<float>(), 2 * thr, (size_t)R_sc * NsS * NsS));
+    c->unfilled.pending = unfilled;   /* lfbm5d_last_scores patches those entries when it is asked for the table */
+    if (unfilled) {
+        c->unfilled.n_rows = gc.n_ref_rows; c->unfilled.n_cols = gc.n_ref_cols; c->unfilled.W = Wb; c->unfilled.nSim = P->nSim; c->unfilled.nHW = nHW;
+        c->unfilled.p = P->p; c->unfilled.last_r = Hb - k - nHW; c->unfilled.last_c = Wb - k - nHW; c->unfilled.fill = 2 * thr;
+    }
     if (scan_version == 1) {
         HIPCK(c, c->tables.reserve(std::max<size_t>(1, scan_tables_floats(sa, 1, n_slots, 0)) * sizeof(float)));
         sa.tables = c->tables.as<float>();
@@ -418,7 +431,11 @@ int pass_impl(lfbm5d_ctx* c, int step, const lfbm5d_params* P, unsigned aw, unsi
     } else
         HIPCK(c, launch_bm_scan(s, sa));
     std::memcpy(gc.scan_key, skey, sizeof(skey));
-    if (N > 1)
+    if (select_regs)
+        HIPCK(c, launch_self_select_regs(s, c->scores.as<float>(), gc.refs.as<unsigned>(), R, Wb, P->nSim, N, thr,
+                                         c->self_idx.as<unsigned>(), c->self_cnt.as<unsigned>(),
+                                         full_scan ? gc.n_ref_cols : 0u, nHW, P->p, Hb - k - nHW, Wb - k - nHW, unfilled));
+    else if (N > 1)
         HIPCK(c, launch_self_select(s, c->scores.as<float>(), gc.refs.as<unsigned>(), R, Wb, P->nSim, N, thr,
                                     c->self_idx.as<unsigned>(), c->self_cnt.as<unsigned>(),
                                     full_scan ? gc.n_ref_cols : 0u, nHW, P->p, Hb - k - nHW, Wb - k - nHW));
