@@ -543,6 +543,89 @@ int lfbm5d_denoise_pg_host_sai(lfbm5d_ctx* ctx, const lfbm5d_pg_model* model, lf
                                float* const* h_denoised, unsigned ang_major, unsigned awidth, unsigned aheight, unsigned an1, unsigned an2,
                                unsigned W, unsigned H, unsigned C);
 
+/* ---- data clipped to a known range: the noise level from the blocks the clipping left alone, and the inverse of the clipped mean ----
+ * Not in the reference.  A light field read from 8-bit files has been rounded and clipped to 0..255 (the LFSourceDir = none case).  Near
+ * black and white the clipping removes part of the noise, which biases the blind estimates above low, and it moves the mean: a filter
+ * estimates E[clip(y + sigma n)], not y -- at y = lo that is sigma phi(0) = 0.4 sigma too bright, and as much too dark at hi.  Both have
+ * a pointwise remedy that leaves the filter alone.  Light fields are [asize][C*H*W] float32, channels as stored; planes of empty SAIs are
+ * neither read nor written; C = 1 or 3; W, H >= 2.  One GPU: contexts with a communicator or a shard return 1.
+ * Range: lo < hi, both finite (and still different, with a finite 255 / (hi - lo), as floats); a value p is censored when p <= lo or
+ * p >= hi (compared as floats).
+ * Limits: near the bounds the noise's standard deviation is smaller than sigma and the filter is not told (Foi 2009's variance-stabilised
+ * form is not built); the inverse's slope reaches 2 at the bounds, so it doubles the residual error there; one sigma for all channels
+ * and SAIs; Poisson-Gaussian noise combined with clipping is not covered; one GPU.
+ *
+ * Statistics (GPU, integers: independent of any order, equal to tests/clip_model.py bit for bit).  s = (float)(255 / (hi - lo)); every
+ * pixel becomes p' = (p - (float)lo) * s in float32 (no fused multiply-add; exact at 0..255: p' = p); m, d, the 64 levels and the 322
+ * keys of |d| of every 2 x 2 block, hist[c][lev][key] and sum[c][lev] are those of the Poisson-Gaussian statistics above on p'.
+ * cens[c][lev] counts the (unskipped) blocks with at least one censored pixel, whole[c] those whose four pixels are whole numbers
+ * (p == rint(p)).  At the default range hist and sum equal lfbm5d_pg_histogram_device's.
+ * Fit (host, double) of one histogram h[64][322] with cens[64] and whole.  When whole equals the histogram's total the data are quantised:
+ * every d is a multiple of delta = s / 2, a count stands for the continuous values within delta / 2 of its d, and the keys' edges fall on
+ * multiples of delta -- read as they are, the edges bias the quantile by delta / 2 (0.8 in sigma at 0..255).  So edge e[k], k >= 1, is
+ * replaced by ceil(e[k] / delta) delta - delta / 2; otherwise delta = 0 and the edges stay.  A level's n, T, k*, Qv are those of
+ * lfbm5d_pg_fit on these edges; v = (Qv / 0.31863936396437514)^2 - delta^2 / 3 (the rounding's own variance); the level is populated when
+ * n >= 256, 0 < k* < 321 and v > 0.  A populated level counts under f_max when cens[l] <= f_max n; sigma'^2 = sum w v / sum w over the
+ * levels that count, w = n / v^2, in level order (lfbm5d_pg_fit's a = 0 branch); sigma = sigma' / s.  f_max runs down the ladder 0.05,
+ * 0.1, 0.2, 0.4, 1 until at least 4 levels count; fewer than 4 populated levels: the fit fails.  heavily_clipped = f_max > 0.1.  The
+ * light field's sigma is the fit of the channels' counts added together, a channel's sigma the fit (with its own ladder) of its own.
+ * Map.  For sigma > 0, a = (lo - y) / sigma, b = (hi - y) / sigma:
+ *   E(y) = lo Phi(a) + hi (1 - Phi(b)) + y (Phi(b) - Phi(a)) + sigma (phi(a) - phi(b)),
+ * strictly increasing with slope Phi(b) - Phi(a).  Declipping is out = clamp(E^-1(in), lo, hi): in <= E(lo) gives lo, in >= E(hi) gives
+ * hi, a non-finite value passes through; evaluated by Newton steps on E from the start value in, four in float and then two in double, which
+ * leave |E(out) - in| below 1e-11 (the identity where in is more than 9 sigma from both bounds), rounded once to float.  The result is non-decreasing in `in` and the same bits on every call. */
+#define LFBM5D_CLIP_LEVELS 64
+#define LFBM5D_CLIP_KEYS   322
+typedef struct {
+    double sigma;                /* the light field's noise level: every non-empty SAI and channel pooled               */
+    double sigma_channel[3];     /* per stored channel (NaN for a channel whose own fit fails; grey: [0] only, rest 0)  */
+    double f_max;                /* the rung of the ladder that was used                                                */
+    double censored;             /* blocks with a censored pixel / blocks counted, all levels                           */
+    unsigned levels;             /* levels that counted                                                                 */
+    unsigned heavily_clipped;    /* 1 when f_max > 0.1: the estimate leans on levels the clipping has touched           */
+    unsigned quantised;          /* 1 when every block counted holds whole numbers: the fit used delta = s / 2          */
+    unsigned reserved;
+    unsigned long long blocks;   /* 2 x 2 blocks visited (0 from lfbm5d_clip_fit)                                       */
+    unsigned long long skipped;  /* of those, skipped for a non-finite m or d                                           */
+} lfbm5d_clip_estimate;
+/* d_lf [asize][C*H*W] in HBM, read only; h_hist [C][64][322], h_sum [C][64], h_cens [C][64], h_whole [C] (host) receive the counts;
+ * blocks / skipped may be NULL.  Returns 1 with a message on a rejected input. */
+int lfbm5d_clip_histogram_device(lfbm5d_ctx* ctx, const float* d_lf, const unsigned* h_mask, unsigned asize, unsigned W, unsigned H,
+                                 unsigned C, double lo, double hi, unsigned long long* h_hist, unsigned long long* h_sum,
+                                 unsigned long long* h_cens, unsigned long long* h_whole, unsigned long long* blocks,
+                                 unsigned long long* skipped);
+/* Host only, needs no GPU: the fit above of hist [C][64][322], cens [C][64], whole [C] (sum [C][64], the level means, belongs to the
+ * statistics and is not read: the fit has no slope; it may be NULL).  Returns 1 when fewer than 4 levels are populated (or on a NULL
+ * pointer, C or a bad range; no message: there is no context). */
+int lfbm5d_clip_fit(const unsigned long long* hist, const unsigned long long* sum, const unsigned long long* cens,
+                    const unsigned long long* whole, unsigned C, double lo, double hi, lfbm5d_clip_estimate* out);
+/* Statistics + fit.  Returns 1 with a message when the fit fails. */
+int lfbm5d_noise_level_clipped_device(lfbm5d_ctx* ctx, const float* d_lf, const unsigned* h_mask, unsigned asize, unsigned W, unsigned H,
+                                      unsigned C, double lo, double hi, lfbm5d_clip_estimate* out);
+/* The same on host light fields, one pointer per SAI (NULL allowed for empty SAIs), staged through HBM: identical results. */
+int lfbm5d_noise_level_clipped_host_sai(lfbm5d_ctx* ctx, const float* const* h_lf, const unsigned* h_mask, unsigned asize, unsigned W,
+                                        unsigned H, unsigned C, double lo, double hi, lfbm5d_clip_estimate* out);
+/* d_out = declipped d_in, both [asize][C*H*W] in HBM; d_out may be d_in.  sigma must be finite and positive. */
+int lfbm5d_declip_device(lfbm5d_ctx* ctx, double sigma, double lo, double hi, const float* d_in, const unsigned* h_mask, float* d_out,
+                         unsigned asize, unsigned W, unsigned H, unsigned C);
+int lfbm5d_declip_host_sai(lfbm5d_ctx* ctx, double sigma, double lo, double hi, const float* const* h_in, const unsigned* h_mask,
+                           float* const* h_out, unsigned asize, unsigned W, unsigned H, unsigned C);
+/* The job: sigma <= 0: lfbm5d_noise_level_clipped_device on d_noisy first (`est`, may be NULL, receives it; zeros when sigma was
+ * given); lfbm5d_denoise_device on the clipped data with P1->sigma = P2->sigma = (float)sigma (the sigmas passed are ignored; d_noisy
+ * in/out exactly as that call leaves it; the basic estimate between the steps stays in the clipped domain: it is the Wiener pilot of the
+ * clipped noisy data); lfbm5d_declip_device in place on d_basic and d_denoised.  Bit-identical to those calls made by hand.
+ * `sigma_used` (may be NULL) receives the sigma that was applied.  A sigma that is not finite is rejected. */
+int lfbm5d_denoise_clipped_device(lfbm5d_ctx* ctx, double sigma, double lo, double hi, lfbm5d_clip_estimate* est, double* sigma_used,
+                                  const lfbm5d_params* P1, const lfbm5d_params* P2, float* d_noisy, const unsigned* h_mask, float* d_basic,
+                                  float* d_denoised, unsigned ang_major, unsigned awidth, unsigned aheight, unsigned an1, unsigned an2,
+                                  unsigned W, unsigned H, unsigned C);
+/* The same on host light fields, one pointer per SAI (NULL allowed for empty SAIs), staged through HBM with blocking copies:
+ * bit-identical to the device form.  h_noisy is only read. */
+int lfbm5d_denoise_clipped_host_sai(lfbm5d_ctx* ctx, double sigma, double lo, double hi, lfbm5d_clip_estimate* est, double* sigma_used,
+                                    const lfbm5d_params* P1, const lfbm5d_params* P2, const float* const* h_noisy, const unsigned* h_mask,
+                                    float* const* h_basic, float* const* h_denoised, unsigned ang_major, unsigned awidth,
+                                    unsigned aheight, unsigned an1, unsigned an2, unsigned W, unsigned H, unsigned C);
+
 /* ---- impulse-noise repair: outlier detection and replacement ahead of the denoiser ----
  * Not in the reference (its authors run such a stage in front of it: README [4]).  The estimators above and the filter assume that every
  * pixel carries Gaussian-like noise; hot and dead pixels, salt and pepper and drop-outs written as 0, 255 or NaN count as noise for the

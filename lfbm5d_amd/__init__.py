@@ -14,7 +14,8 @@ from .core import (Context, Params, Bm3dParams, Stats, run_bm5d_1st_step, run_bm
                    denoise_pg, ImpulseParamsStruct, ImpulseResultStruct, ImpulseRepair, impulse_params, impulse_scale, impulse_repair,
                    InpaintParamsStruct, InpaintResultStruct, Inpaint, inpaint_params, inpaint,
                    ViewParamsStruct, ViewResultStruct, ViewSynth, view_params, view_synth,
-                   ConsistParamsStruct, ConsistResultStruct, Consist, consist_params, consist)
+                   ConsistParamsStruct, ConsistResultStruct, Consist, consist_params, consist,
+                   ClipEstimateStruct, ClipNoiseLevel, clip_fit, noise_level_clipped, denoise_clipped)
 
 __all__ = ["Context", "Params", "Bm3dParams", "Stats", "run_bm5d_1st_step", "run_bm5d_2nd_step", "run_bm3d_LF", "shard_rows",
            "YUV", "YCBCR", "OPP", "RGB", "ID", "DCT", "SADCT", "BIOR", "HADAMARD", "HAAR",
@@ -25,4 +26,5 @@ __all__ = ["Context", "Params", "Bm3dParams", "Stats", "run_bm5d_1st_step", "run
            "ImpulseParamsStruct", "ImpulseResultStruct", "ImpulseRepair", "impulse_params", "impulse_scale", "impulse_repair",
            "InpaintParamsStruct", "InpaintResultStruct", "Inpaint", "inpaint_params", "inpaint",
            "ViewParamsStruct", "ViewResultStruct", "ViewSynth", "view_params", "view_synth",
-           "ConsistParamsStruct", "ConsistResultStruct", "Consist", "consist_params", "consist"]
+           "ConsistParamsStruct", "ConsistResultStruct", "Consist", "consist_params", "consist",
+           "ClipEstimateStruct", "ClipNoiseLevel", "clip_fit", "noise_level_clipped", "denoise_clipped"]

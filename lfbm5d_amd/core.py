@@ -86,6 +86,13 @@ class PgEstimateStruct(C.Structure):
 PG_LEVELS, PG_KEYS = 64, 322
 
 
+class ClipEstimateStruct(C.Structure):
+    """lfbm5d_clip_estimate: the clipping-aware noise level of a light field (include/lfbm5d.h)."""
+    _fields_ = [("sigma", C.c_double), ("sigma_channel", C.c_double * 3), ("f_max", C.c_double), ("censored", C.c_double),
+                ("levels", C.c_uint), ("heavily_clipped", C.c_uint), ("quantised", C.c_uint), ("reserved", C.c_uint),
+                ("blocks", C.c_ulonglong), ("skipped", C.c_ulonglong)]
+
+
 class ImpulseParamsStruct(C.Structure):
     """lfbm5d_impulse_params: threshold factor, floor and given thresholds of the impulse repair (include/lfbm5d.h)."""
     _fields_ = [("k", C.c_double), ("min_threshold", C.c_double), ("threshold", C.c_double * 3)]
@@ -235,6 +242,23 @@ class PgEstimate(NamedTuple):
     sum_m: np.ndarray
 
 
+class ClipNoiseLevel(NamedTuple):
+    """Result of Context.noise_level_clipped / noise_level_clipped / clip_fit: sigma of the whole light field (what to pass as
+    `sigma`), per stored channel (NaN where a channel's own fit fails), the levels that counted, the rung f_max of the ladder that was
+    used (a level counts while at most that fraction of its blocks holds a censored pixel), the censored fraction of all blocks,
+    heavily_clipped (f_max > 0.1: the estimate leans on levels the clipping has touched), quantised (every block holds whole numbers:
+    the fit allowed for the rounding) and the 2 x 2 blocks visited and skipped (0 from clip_fit)."""
+    sigma: float
+    sigma_channel: tuple
+    levels: int
+    f_max: float
+    censored: float
+    heavily_clipped: bool
+    quantised: bool
+    blocks: int
+    skipped: int
+
+
 class NoiseLevel(NamedTuple):
     """Result of Context.noise_level / noise_level: sigma of the whole light field (what to pass as `sigma`), per stored channel
     (grey: [0] only), the size m of the noise subspace, the patches pooled, the eigenvalues of the pooled covariance (ascending)
@@ -382,6 +406,17 @@ def lib():
         L.lfbm5d_pg_inverse_device.argtypes = [vp, mp_, fp, up, fp] + [C.c_uint] * 4
         L.lfbm5d_denoise_pg_device.argtypes = [vp, mp_, mp_, pp, pp, fp, up, fp, fp] + [C.c_uint] * 8
         L.lfbm5d_denoise_pg_host_sai.argtypes = [vp, mp_, mp_, pp, pp, fp, up, fp, fp] + [C.c_uint] * 8
+    if hasattr(L, "lfbm5d_denoise_clipped_device"):   # (absent from older builds loaded through LFBM5D_HIP_LIB for A/B runs)
+        ullp, cep, dp, pp = C.POINTER(C.c_ulonglong), C.POINTER(ClipEstimateStruct), C.POINTER(C.c_double), C.POINTER(Params)
+        rng = [C.c_double, C.c_double]
+        L.lfbm5d_clip_histogram_device.argtypes = [vp, fp, up] + [C.c_uint] * 4 + rng + [ullp] * 6
+        L.lfbm5d_clip_fit.argtypes = [ullp, ullp, ullp, ullp, C.c_uint] + rng + [cep]
+        L.lfbm5d_noise_level_clipped_device.argtypes = [vp, fp, up] + [C.c_uint] * 4 + rng + [cep]
+        L.lfbm5d_noise_level_clipped_host_sai.argtypes = [vp, fp, up] + [C.c_uint] * 4 + rng + [cep]
+        L.lfbm5d_declip_device.argtypes = [vp, C.c_double] + rng + [fp, up, fp] + [C.c_uint] * 4
+        L.lfbm5d_declip_host_sai.argtypes = [vp, C.c_double] + rng + [fp, up, fp] + [C.c_uint] * 4
+        L.lfbm5d_denoise_clipped_device.argtypes = [vp, C.c_double] + rng + [cep, dp, pp, pp, fp, up, fp, fp] + [C.c_uint] * 8
+        L.lfbm5d_denoise_clipped_host_sai.argtypes = [vp, C.c_double] + rng + [cep, dp, pp, pp, fp, up, fp, fp] + [C.c_uint] * 8
     if hasattr(L, "lfbm5d_impulse_repair_device"):   # (absent from older builds loaded through LFBM5D_HIP_LIB for A/B runs)
         dp, ullp = C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)
         ip, rp = C.POINTER(ImpulseParamsStruct), C.POINTER(ImpulseResultStruct)
@@ -557,6 +592,31 @@ def pg_fit(hist, sum_m):
     if lib().lfbm5d_pg_fit(h.ctypes.data_as(ullp), sm.ctypes.data_as(ullp), C.byref(a), C.byref(b)) != 0:
         raise LfBm5dError("lfbm5d_pg_fit: no valid level (every level holds fewer than 256 blocks, or its quantile fell into an end bin)")
     return a.value, b.value
+
+
+def _clip_result(res, chnls):
+    return ClipNoiseLevel(res.sigma, tuple(res.sigma_channel[:chnls]), int(res.levels), res.f_max, res.censored, bool(res.heavily_clipped),
+                          bool(res.quantised), int(res.blocks), int(res.skipped))
+
+
+def clip_fit(hist, sum_m, cens, whole, lo=0.0, hi=255.0):
+    """lfbm5d_clip_fit (host only, no GPU): the ClipNoiseLevel of the statistics hist uint64 [C][64][322], cens uint64 [C][64] and whole
+    uint64 [C] of Context.clip_histogram (sum_m [C][64] belongs to them and is not read; it may be None).  Raises when fewer than 4
+    levels are populated (include/lfbm5d.h has the definition)."""
+    h = np.ascontiguousarray(hist, np.uint64)
+    cz = np.ascontiguousarray(cens, np.uint64)
+    wh = np.ascontiguousarray(whole, np.uint64).reshape(-1)
+    sm = None if sum_m is None else np.ascontiguousarray(sum_m, np.uint64)
+    if h.ndim != 3 or h.shape[0] not in (1, 3) or h.shape[1:] != (PG_LEVELS, PG_KEYS) or cz.shape != h.shape[:2] or wh.shape != h.shape[:1] \
+            or (sm is not None and sm.shape != h.shape[:2]):
+        raise LfBm5dError("lfbm5d_clip_fit: hist must be [C][64][322], sum_m and cens [C][64], whole [C], C = 1 or 3")
+    ullp = C.POINTER(C.c_ulonglong)
+    res = ClipEstimateStruct()
+    if lib().lfbm5d_clip_fit(h.ctypes.data_as(ullp), sm.ctypes.data_as(ullp) if sm is not None else None, cz.ctypes.data_as(ullp),
+                             wh.ctypes.data_as(ullp), h.shape[0], float(lo), float(hi), C.byref(res)) != 0:
+        raise LfBm5dError("lfbm5d_clip_fit: fewer than 4 levels are populated (256 blocks, a quantile outside the end bins), or the range "
+                          "is bad (lo < hi, both finite)")
+    return _clip_result(res, h.shape[0])
 
 
 def pg_model(a, b, chnls=3):
@@ -1094,6 +1154,71 @@ class Context:
             self._ck(self._L.lfbm5d_denoise_pg_device(*head, _dev_ptr(noisy), mp, _dev_ptr(basic), _dev_ptr(denoised), *tail))
         return used
 
+    # ---- clipped data ----
+    def clip_histogram(self, LF, LF_SAI_mask, width, height, chnls, lo=0.0, hi=255.0):
+        """The block statistics of lfbm5d_clip_histogram_device on a CUDA float32 tensor [asize][C*H*W]: (hist uint64 [C][64][322],
+        sum_m uint64 [C][64], cens uint64 [C][64], whole uint64 [C], blocks, skipped)."""
+        m = _u32(LF_SAI_mask)
+        C_ = int(chnls)
+        n = max(C_, 1)
+        hist, sm, cens = np.zeros((n, PG_LEVELS, PG_KEYS), np.uint64), np.zeros((n, PG_LEVELS), np.uint64), np.zeros((n, PG_LEVELS), np.uint64)
+        whole = np.zeros(n, np.uint64)
+        blocks, skipped = C.c_ulonglong(), C.c_ulonglong()
+        ullp = C.POINTER(C.c_ulonglong)
+        self._ck(self._L.lfbm5d_clip_histogram_device(self._h, _dev_ptr(LF), m.ctypes.data_as(C.POINTER(C.c_uint)), m.size, int(width),
+                                                      int(height), C_, float(lo), float(hi), hist.ctypes.data_as(ullp),
+                                                      sm.ctypes.data_as(ullp), cens.ctypes.data_as(ullp), whole.ctypes.data_as(ullp),
+                                                      C.byref(blocks), C.byref(skipped)))
+        return hist, sm, cens, whole, blocks.value, skipped.value
+
+    clip_fit = staticmethod(clip_fit)
+
+    def noise_level_clipped(self, LF, LF_SAI_mask, width, height, chnls, lo=0.0, hi=255.0):
+        """The noise sigma of a light field whose values were clipped to lo..hi (8-bit files: 0..255), from the levels the clipping left
+        alone (lfbm5d_noise_level_clipped_*, include/lfbm5d.h).  LF: a CUDA float32 tensor [asize][C*H*W] (device form, read only), a
+        float32 numpy array of that shape or a list of per-SAI float32 arrays (host form, staged through HBM; identical results).
+        Returns a ClipNoiseLevel."""
+        m = _u32(LF_SAI_mask)
+        C_ = int(chnls)
+        res = ClipEstimateStruct()
+        tail = (m.ctypes.data_as(C.POINTER(C.c_uint)), m.size, int(width), int(height), C_, float(lo), float(hi), C.byref(res))
+        if isinstance(LF, (list, tuple, np.ndarray)):
+            self._ck(self._L.lfbm5d_noise_level_clipped_host_sai(self._h, _sai_ptrs(self._host_sais(LF), m), *tail))
+        else:
+            self._ck(self._L.lfbm5d_noise_level_clipped_device(self._h, _dev_ptr(LF), *tail))
+        return _clip_result(res, C_)
+
+    def declip(self, sigma, LF, mask, out, width, height, chnls, lo=0.0, hi=255.0):
+        """out = clamp(E^-1(LF), lo, hi), the inverse of the mean of a value clipped to lo..hi under noise of `sigma`
+        (lfbm5d_declip_*): what takes a denoised clipped light field back to the unclipped signal.  CUDA float32 tensors
+        [asize][C*H*W] (device form), or float32 numpy arrays / lists of per-SAI arrays (host form; bit-identical); out may be LF."""
+        m = _u32(mask)
+        mp = m.ctypes.data_as(C.POINTER(C.c_uint))
+        head = (self._h, float(sigma), float(lo), float(hi))
+        tail = (m.size, int(width), int(height), int(chnls))
+        if isinstance(LF, (list, tuple, np.ndarray)):
+            self._ck(self._L.lfbm5d_declip_host_sai(*head, _sai_ptrs(self._host_sais(LF), m), mp, _sai_ptrs(self._host_sais(out), m), *tail))
+        else:
+            self._ck(self._L.lfbm5d_declip_device(*head, _dev_ptr(LF), mp, _dev_ptr(out), *tail))
+
+    def denoise_clipped(self, sigma, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, Cc, lo=0.0, hi=255.0):
+        """The two-step job on data clipped to lo..hi (lfbm5d_denoise_clipped_*): sigma None (or <= 0): noise_level_clipped() of `noisy`
+        first; denoise() with that sigma (P1.sigma / P2.sigma are ignored); declip() of basic and denoised in place.  CUDA float32
+        tensors (device form: noisy is left as denoise() leaves it), or float32 numpy arrays / lists of per-SAI arrays (host form:
+        noisy is only read; bit-identical).  Returns (the sigma that was applied, the ClipNoiseLevel or None when sigma was given)."""
+        m = _u32(mask)
+        mp = m.ctypes.data_as(C.POINTER(C.c_uint))
+        res, used = ClipEstimateStruct(), C.c_double()
+        sig = 0.0 if sigma is None else float(sigma)
+        head = (self._h, sig, float(lo), float(hi), C.byref(res), C.byref(used), C.byref(P1), C.byref(P2))
+        tail = (ang_major, awidth, aheight, an1, an2, int(W), int(H), int(Cc))
+        if isinstance(noisy, (list, tuple, np.ndarray)):
+            n, b, d = (self._host_sais(x) for x in (noisy, basic, denoised))
+            self._ck(self._L.lfbm5d_denoise_clipped_host_sai(*head, _sai_ptrs(n, m), mp, _sai_ptrs(b, m), _sai_ptrs(d, m), *tail))
+        else:
+            self._ck(self._L.lfbm5d_denoise_clipped_device(*head, _dev_ptr(noisy), mp, _dev_ptr(basic), _dev_ptr(denoised), *tail))
+        return used.value, (_clip_result(res, int(Cc)) if sig <= 0.0 else None)
+
     # ---- impulse repair ----
     def impulse_histogram(self, LF, LF_SAI_mask, width, height, chnls):
         """The ROAD histogram of lfbm5d_impulse_histogram_device on a CUDA float32 tensor [asize][C*H*W]: (hist uint64 [C][386], pixels,
@@ -1529,6 +1654,18 @@ def consist(noisy, mask, ang_major, awidth, aheight, width, height, chnls, ctx=N
 def denoise_pg(model, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls, ctx=None):
     """Context.denoise_pg on the default context (device 0); returns the model that was used."""
     return (ctx or _ctx()).denoise_pg(model, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls)
+
+
+def noise_level_clipped(LF, LF_SAI_mask, width, height, chnls, lo=0.0, hi=255.0, ctx=None):
+    """Context.noise_level_clipped on the default context (device 0): the noise sigma of a light field clipped to lo..hi."""
+    return (ctx or _ctx()).noise_level_clipped(LF, LF_SAI_mask, width, height, chnls, lo, hi)
+
+
+def denoise_clipped(sigma, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls, lo=0.0, hi=255.0,
+                    ctx=None):
+    """Context.denoise_clipped on the default context (device 0); returns (sigma applied, the estimate or None)."""
+    return (ctx or _ctx()).denoise_clipped(sigma, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls,
+                                           lo, hi)
 
 
 def superres(sr, P, low, mask, high, ang_major, awidth, aheight, an, w, h, chnls, ctx=None):

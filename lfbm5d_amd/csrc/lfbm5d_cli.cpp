@@ -65,6 +65,16 @@
  *                     `View synthesis:` line prints the disparity range as decimals and ends `, <Q> steps per pixel`, and the
  *                     `Consistency check:` line ends the same.  Any other value, and the variable without LFBM5D_MISSING or
  *                     LFBM5D_DETECT, is an error.  Unset or 1, the output is unchanged;
+ *   LFBM5D_CLIP=auto | <lo>,<hi>   the noisy light field was clipped to lo..hi (auto: 0..255, what an 8-bit file does to it).  With
+ *                     LFBM5D_SIGMA=auto the clipping-aware estimate (noise_level_clipped_LF, run_bm5d.h) replaces the blind one; the
+ *                     line reads `Estimated noise level: sigma = <v> (clipping-aware: <L> levels, censored blocks <= <pct> %)`.
+ *                     Otherwise the argument's sigma is used.  Both steps run as one job (denoise_clipped_LF; LFBM3Ddenoising:
+ *                     run_bm3d_LF, declip_LF) and the basic and the denoised light field are taken through the inverse of the clipped
+ *                     mean before PSNR, SSIM and saving: `Declipping: range <lo>..<hi>, sigma = <s>`.  It runs after LFBM5D_DETECT /
+ *                     MISSING / DEFECTS / IMPULSE, which stay as they are.  With LFBM5D_SIGMA=poisson it is an error, and so is any
+ *                     other value.  With a ground truth LFBM5D_CLIP_ADD=1 first rounds the synthesised noisy light field to whole
+ *                     numbers and clips it to the range (0..255 without LFBM5D_CLIP: the filter then runs on clipped data as it
+ *                     would on a file's), before LFBM5D_IMPULSE_ADD.  Unset, the output is unchanged;
  *   LFBM5D_REPORT_SSIM=1  the average SSIM next to every average PSNR on stdout and an SSIM block behind every PSNR block of the
  *                     results file, computed on the GPU on the images as the files hold them (cli_quality.h); any other value is an
  *                     error; unset, the output is unchanged.
@@ -360,6 +370,65 @@ bool impulse_mode(double& k, double& add) {
         add = v;
     }
     return true;
+}
+
+/* LFBM5D_CLIP / LFBM5D_CLIP_ADD: on = false when unset (lo..hi = 0..255, for LFBM5D_CLIP_ADD alone); false (message printed) on a
+ * malformed value or together with LFBM5D_SIGMA=poisson (smode >= 2) */
+bool clip_mode(bool& on, double& lo, double& hi, bool& add, int smode) {
+    on = add = false; lo = 0.0; hi = 255.0;
+    if (const char* e = env("LFBM5D_CLIP")) {
+        if (strcmp(e, "auto")) {
+            char* q = nullptr; char* r = nullptr;
+            lo = strtod(e, &q);
+            bool ok = q != e && *q == ',' && !isspace((unsigned char)*e) && !isspace((unsigned char)q[1]);
+            if (ok) { hi = strtod(q + 1, &r); ok = r != q + 1 && !*r; }
+            if (!ok || !std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi)) {
+                cout << "LFBM5D_CLIP must be \"auto\" (the noisy light field was clipped to 0..255) or a range \"<lo>,<hi>\" with lo < hi, or unset; got \""
+                     << e << "\"" << endl;
+                return false;
+            }
+        }
+        if (smode >= 2) {
+            cout << "LFBM5D_CLIP cannot be combined with LFBM5D_SIGMA=poisson (Poisson-Gaussian noise combined with clipping is not covered)" << endl;
+            return false;
+        }
+        on = true;
+    }
+    if (const char* e = env("LFBM5D_CLIP_ADD")) {
+        if (strcmp(e, "1")) { cout << "LFBM5D_CLIP_ADD must be \"1\" (round and clip the synthesised noisy light field to the range of LFBM5D_CLIP, 0..255 without it) or unset; got \"" << e << "\"" << endl; return false; }
+        add = true;
+    }
+    return true;
+}
+
+/* LFBM5D_CLIP_ADD: what storing the synthesised noisy light field in an integer format of range lo..hi does to it */
+void clip_round_LF(vector<vector<float> >& LF_noisy, const vector<unsigned>& mask, double lo, double hi) {
+    unsigned long long hit = 0, all = 0;
+    for (size_t st = 0; st < LF_noisy.size(); st++) {
+        if (!mask[st]) continue;
+        for (float& v : LF_noisy[st]) {
+            const float r = std::nearbyint(v);
+            all++;
+            hit += r <= (float)lo || r >= (float)hi;
+            v = std::min(std::max(r, (float)lo), (float)hi);
+        }
+    }
+    cout << "Round and clip [range " << lo << ".." << hi << "]: " << hit << " of " << all << " values at the bounds" << endl;
+}
+
+/* LFBM5D_CLIP with LFBM5D_SIGMA=auto: replace `sigma` with the clipping-aware estimate on the noisy light field */
+bool estimate_sigma_clipped_LF(const vector<vector<float> >& LF_noisy, const vector<unsigned>& mask, unsigned W, unsigned H, unsigned C, double lo,
+                               double hi, float& sigma) {
+    float est = 0.0f; unsigned levels = 0; double f_max = 0.0;
+    if (noise_level_clipped_LF(LF_noisy, mask, W, H, C, lo, hi, est, levels, f_max) != EXIT_SUCCESS) return false;
+    cout << endl << "Estimated noise level: sigma = " << setprecision(8) << est << setprecision(6) << " (clipping-aware: " << levels
+         << " levels, censored blocks <= " << 100.0 * f_max << " %)" << endl;
+    sigma = est;
+    return true;
+}
+
+void print_declipping(double lo, double hi, float sigma) {
+    cout << endl << "Declipping: range " << lo << ".." << hi << ", sigma = " << setprecision(8) << sigma << setprecision(6) << endl;
 }
 
 /* LFBM5D_IMPULSE_ADD: salt and pepper on the synthesised noisy light field, one <random> stream through the SAIs in order */
@@ -692,6 +761,8 @@ int main(int argc, char** argv) {
     if (!detect_mode(detect, det_k, det_save)) return EXIT_FAILURE;
     unsigned dsteps = 1;
     if (!disparity_steps_mode(dsteps, detect || !missing.empty())) return EXIT_FAILURE;
+    bool clip_on = false, clip_add = false; double clip_lo = 0.0, clip_hi = 255.0;
+    if (!clip_mode(clip_on, clip_lo, clip_hi, clip_add, smode)) return EXIT_FAILURE;
 
     vector<vector<float> > LF, LF_noisy, LF_basic, LF_den, LF_diff;
     vector<unsigned> mask;
@@ -707,6 +778,7 @@ int main(int argc, char** argv) {
         t = now_s();
         add_noise_LF(LF, mask, LF_noisy, sigma, smode == 3 ? pg : nullptr);
         cout << "done in " << now_s() - t << "s." << endl;
+        if (clip_add) clip_round_LF(LF_noisy, mask, clip_lo, clip_hi);
         if (imp_add > 0.0) add_impulses_LF(LF_noisy, mask, imp_add);
         for (size_t st = 0; st < missing.size(); st++) if (missing[st]) LF_noisy[st].assign(LF_noisy[st].size(), 0.0f);   /* dropped */
         cout << endl << "Save noisy light field..." << endl;
@@ -733,7 +805,8 @@ int main(int argc, char** argv) {
         cout << "Defect inpainting: the fill alone (the refinement steps run in LFBM5Ddenoising)" << endl;
     }
     if (imp_k >= 0.0 && !repair_impulses_LF(LF_noisy, mask, W, H, C, imp_k)) return EXIT_FAILURE;
-    if (smode == 1 && !estimate_sigma_LF(LF_noisy, est_mask, W, H, C, sigma)) return EXIT_FAILURE;
+    if (smode == 1 && !(clip_on ? estimate_sigma_clipped_LF(LF_noisy, est_mask, W, H, C, clip_lo, clip_hi, sigma)
+                                : estimate_sigma_LF(LF_noisy, est_mask, W, H, C, sigma))) return EXIT_FAILURE;
     LF_basic.assign(awh, vector<float>((size_t)W * H * C, 0.0f));
     LF_den = LF_basic; LF_diff = LF_basic;
     vector<float> ps, rm; float sp = 0, ar = 0, sr = 0;
@@ -761,6 +834,11 @@ int main(int argc, char** argv) {
     } else
     if (run_bm3d_LF(sigma, LF_noisy, mask, LF_basic, LF_den, W, H, C, n[0], n[1], k[0], k[1], N[0], N[1], p[0], p[1], sd[0] != 0, sd[1] != 0,
                     t2[0], t2[1], lambda, cs, nb_threads, sub) != EXIT_SUCCESS) return EXIT_FAILURE;
+    if (clip_on) {   /* the filter saw the clipped data; its results go through the inverse of the clipped mean */
+        if (declip_LF(sigma, clip_lo, clip_hi, LF_basic, mask, W, H, C) != EXIT_SUCCESS || declip_LF(sigma, clip_lo, clip_hi, LF_den, mask, W, H, C) != EXIT_SUCCESS)
+            return EXIT_FAILURE;
+        print_declipping(clip_lo, clip_hi, sigma);
+    }
     const double secs = now_s() - tb;
     if (gt) {
         psnr_LF(LF, LF_basic, mask, ps, ap_b.psnr, sp, rm, ar, sr);
@@ -842,6 +920,8 @@ int main(int argc, char** argv) {
     if (!detect_mode(detect, det_k, det_save)) return EXIT_FAILURE;
     unsigned dsteps = 1;
     if (!disparity_steps_mode(dsteps, detect || !missing.empty())) return EXIT_FAILURE;
+    bool clip_on = false, clip_add = false; double clip_lo = 0.0, clip_hi = 255.0;
+    if (!clip_mode(clip_on, clip_lo, clip_hi, clip_add, smode)) return EXIT_FAILURE;
 
     vector<vector<float> > LF, LF_noisy, LF_basic, LF_den, LF_diff;
     vector<unsigned> mask;
@@ -857,6 +937,7 @@ int main(int argc, char** argv) {
         t = now_s();
         add_noise_LF(LF, mask, LF_noisy, sigma, smode == 3 ? pg : nullptr);
         cout << "done in " << now_s() - t << "s." << endl;
+        if (clip_add) clip_round_LF(LF_noisy, mask, clip_lo, clip_hi);
         if (imp_add > 0.0) add_impulses_LF(LF_noisy, mask, imp_add);
         for (size_t st = 0; st < missing.size(); st++) if (missing[st]) LF_noisy[st].assign(LF_noisy[st].size(), 0.0f);   /* dropped */
         cout << endl << "Save noisy light field..." << endl;
@@ -891,7 +972,8 @@ int main(int argc, char** argv) {
         if (smode >= 2) cout << "Defect inpainting: the fill alone (LFBM5D_SIGMA=poisson: the refinement steps assume one sigma)" << endl;
     }
     if (imp_k >= 0.0 && !repair_impulses_LF(LF_noisy, mask, W, H, C, imp_k)) return EXIT_FAILURE;
-    if (smode == 1 && !estimate_sigma_LF(LF_noisy, est_mask, W, H, C, sigma)) return EXIT_FAILURE;
+    if (smode == 1 && !(clip_on ? estimate_sigma_clipped_LF(LF_noisy, est_mask, W, H, C, clip_lo, clip_hi, sigma)
+                                : estimate_sigma_LF(LF_noisy, est_mask, W, H, C, sigma))) return EXIT_FAILURE;
     if (view_steps && !synthesise_missing_LF(LF_noisy, mask, missing, ang_major, aw, ah, anH, W, H, C, view_steps, view_steps, sigma, lambda, def_hard,
                                              (unsigned)cs, false, dsteps)) return EXIT_FAILURE;
     if (def_steps && !inpaint_defects_LF(LF_noisy, defects, mask, ang_major, aw, ah, anH, W, H, C, def_steps, def_steps, sigma, lambda, def_hard,
@@ -914,7 +996,7 @@ int main(int argc, char** argv) {
      * inverse(estimate) between the calls: the two differ (0.015 dB on the test light field) because the reference's colour matrices are not
      * inverses of each other */
     const char* one_job_s = env("LFBM5D_ONE_JOB");
-    const bool one_job = smode >= 2 || (one_job_s && *one_job_s && *one_job_s != '0');   /* the Poisson-Gaussian path is one job */
+    const bool one_job = smode >= 2 || clip_on || (one_job_s && *one_job_s && *one_job_s != '0');   /* the Poisson-Gaussian and the clipped path are one job */
     cout << endl << " ---> Running LFBM5D filter <--- " << endl << endl << (one_job ? "Steps 1 and 2 running as one job..." : "Step 1 running...") << endl;
     const double tb = now_s();
     double t1 = now_s();
@@ -925,6 +1007,12 @@ int main(int argc, char** argv) {
                           t4[1], t5[1], cs, nb_threads) != EXIT_SUCCESS) return EXIT_FAILURE;
         job = now_s() - t1;
         print_pg_model(smode == 2, pg, sigma);
+    } else if (clip_on) {
+        if (denoise_clipped_LF(sigma, clip_lo, clip_hi, lambda, LF_noisy, mask, LF_basic, LF_den, ang_major, aw, ah, anH, anW, W, H, C, N[0], nSim[0], nDisp[0],
+                               k[0], p[0], sd[0] != 0, t2[0], t4[0], t5[0], N[1], nSim[1], nDisp[1], k[1], p[1], sd[1] != 0, t2[1], t4[1], t5[1], cs,
+                               nb_threads) != EXIT_SUCCESS) return EXIT_FAILURE;
+        job = now_s() - t1;
+        print_declipping(clip_lo, clip_hi, sigma);
     } else if (one_job) {
         if (run_bm5d(sigma, lambda, LF_noisy, mask, LF_basic, LF_den, ang_major, aw, ah, anH, anW, W, H, C, N[0], nSim[0], nDisp[0], k[0], p[0],
                      sd[0] != 0, t2[0], t4[0], t5[0], N[1], nSim[1], nDisp[1], k[1], p[1], sd[1] != 0, t2[1], t4[1], t5[1], cs, nb_threads) != EXIT_SUCCESS)

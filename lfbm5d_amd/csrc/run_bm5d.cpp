@@ -350,6 +350,86 @@ int denoise_pg_LF(double& a, double& b, const bool estimate, float& sigma, const
     return EXIT_SUCCESS;
 }
 
+/* clipping-aware noise level on the caller's vectors (one pointer per SAI, no flat copy) */
+int noise_level_clipped_LF(const std::vector<std::vector<float> >& LF, const std::vector<unsigned>& LF_SAI_mask, unsigned width, unsigned height,
+                           unsigned chnls, double lo, double hi, float& sigma, unsigned& levels, double& f_max) {
+    if (LF.size() != LF_SAI_mask.size()) {
+        std::cout << "noise_level_clipped_LF: light field and mask must hold the same number of SAIs" << std::endl;
+        return EXIT_FAILURE;
+    }
+    lfbm5d_ctx* ctx = context();
+    if (!ctx) return EXIT_FAILURE;
+    const size_t img = (size_t)width * height * chnls;
+    std::vector<const float*> p(LF.size(), nullptr);
+    for (size_t st = 0; st < LF.size(); st++) if (LF_SAI_mask[st] && LF[st].size() == img) p[st] = LF[st].data();
+    for (size_t st = 0; st < LF.size(); st++)
+        if (LF_SAI_mask[st] && !p[st]) { std::cout << "noise_level_clipped_LF: a non-empty SAI does not hold width*height*chnls values" << std::endl; return EXIT_FAILURE; }
+    lfbm5d_clip_estimate r;
+    if (lfbm5d_noise_level_clipped_host_sai(ctx, p.data(), LF_SAI_mask.data(), (unsigned)LF.size(), width, height, chnls, lo, hi, &r) != 0) {
+        std::cout << "LFBM5D GPU backend: " << lfbm5d_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+    }
+    sigma = (float)r.sigma; levels = r.levels; f_max = r.f_max;
+    return EXIT_SUCCESS;
+}
+
+/* the inverse of the clipped mean on the caller's vectors, in place for the caller (one pointer per SAI; the library stages them) */
+int declip_LF(double sigma, double lo, double hi, std::vector<std::vector<float> >& LF, const std::vector<unsigned>& LF_SAI_mask, unsigned width,
+              unsigned height, unsigned chnls) {
+    if (LF.size() != LF_SAI_mask.size()) {
+        std::cout << "declip_LF: light field and mask must hold the same number of SAIs" << std::endl;
+        return EXIT_FAILURE;
+    }
+    lfbm5d_ctx* ctx = context();
+    if (!ctx) return EXIT_FAILURE;
+    const size_t img = (size_t)width * height * chnls;
+    std::vector<float*> p(LF.size(), nullptr);
+    for (size_t st = 0; st < LF.size(); st++) if (LF_SAI_mask[st] && LF[st].size() == img) p[st] = LF[st].data();
+    for (size_t st = 0; st < LF.size(); st++)
+        if (LF_SAI_mask[st] && !p[st]) { std::cout << "declip_LF: a non-empty SAI does not hold width*height*chnls values" << std::endl; return EXIT_FAILURE; }
+    if (lfbm5d_declip_host_sai(ctx, sigma, lo, hi, p.data(), LF_SAI_mask.data(), p.data(), (unsigned)LF.size(), width, height, chnls) != 0) {
+        std::cout << "LFBM5D GPU backend: " << lfbm5d_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+    }
+    return EXIT_SUCCESS;
+}
+
+int denoise_clipped_LF(float& sigma, double lo, double hi, const float lambdaHard5D, const std::vector<std::vector<float> >& LF_noisy,
+                       std::vector<unsigned>& LF_SAI_mask, std::vector<std::vector<float> >& LF_basic, std::vector<std::vector<float> >& LF_denoised,
+                       const unsigned ang_major, const unsigned awidth, const unsigned aheight, const unsigned anHard, const unsigned anWien,
+                       const unsigned width, const unsigned height, const unsigned chnls, const unsigned NHard, const unsigned nSimHard,
+                       const unsigned nDispHard, const unsigned kHard, const unsigned pHard, const bool useSDHard, const unsigned tau_2D_hard,
+                       unsigned tau_4D_hard, const unsigned tau_5D_hard, const unsigned NWien, const unsigned nSimWien, const unsigned nDispWien,
+                       const unsigned kWien, const unsigned pWien, const bool useSDWien, const unsigned tau_2D_wien, unsigned tau_4D_wien,
+                       const unsigned tau_5D_wien, const unsigned color_space, const unsigned nb_threads) {
+    const unsigned asize = awidth * aheight;
+    if (LF_noisy.size() != asize || LF_SAI_mask.size() != asize) {
+        std::cout << "denoise_clipped_LF: light field and mask must hold awidth*aheight SAIs" << std::endl;
+        return EXIT_FAILURE;
+    }
+    lfbm5d_ctx* ctx = context();
+    if (!ctx) return EXIT_FAILURE;
+    lfbm5d_set_tiles(ctx, tiles_for(nb_threads));
+    if (LF_basic.size() != asize) LF_basic.resize(asize);
+    if (LF_denoised.size() != asize) LF_denoised.resize(asize);
+    const size_t img = (size_t)width * height * chnls;
+    std::vector<const float*> noisy(asize, nullptr);
+    for (size_t st = 0; st < asize; st++) if (LF_SAI_mask[st] && LF_noisy[st].size() == img) noisy[st] = LF_noisy[st].data();
+    for (size_t st = 0; st < asize; st++)
+        if (LF_SAI_mask[st] && !noisy[st]) { std::cout << "denoise_clipped_LF: a non-empty SAI does not hold width*height*chnls values" << std::endl; return EXIT_FAILURE; }
+    const std::vector<float*> basic = sai_ptrs(LF_basic, LF_SAI_mask, img, true), den = sai_ptrs(LF_denoised, LF_SAI_mask, img, true);
+    const lfbm5d_params P1 = make(0.0f, lambdaHard5D, NHard, nSimHard, nDispHard, kHard, pHard, useSDHard, tau_2D_hard, tau_4D_hard, tau_5D_hard, color_space);
+    const lfbm5d_params P2 = make(0.0f, 0.0f, NWien, nSimWien, nDispWien, kWien, pWien, useSDWien, tau_2D_wien, tau_4D_wien, tau_5D_wien, color_space);
+    double used = 0.0;
+    if (lfbm5d_denoise_clipped_host_sai(ctx, (double)sigma, lo, hi, nullptr, &used, &P1, &P2, noisy.data(), LF_SAI_mask.data(), basic.data(),
+                                        den.data(), ang_major, awidth, aheight, anHard, anWien, width, height, chnls) != 0) {
+        std::cout << "LFBM5D GPU backend: " << lfbm5d_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+    }
+    sigma = (float)used;
+    return EXIT_SUCCESS;
+}
+
 int report_ssim_mode() {
     const char* e = std::getenv("LFBM5D_REPORT_SSIM");
     if (!e) return 0;

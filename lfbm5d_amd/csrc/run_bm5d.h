@@ -190,6 +190,63 @@ int denoise_pg_LF(
 ,   const unsigned nb_threads
 );
 
+//! Data clipped to lo..hi (8-bit files: 0..255) -- not in the reference: the noise sigma of such a light field from the intensity levels
+//! the clipping left alone (lfbm5d_noise_level_clipped_host_sai, include/lfbm5d.h).  `levels` and `f_max` receive how many levels
+//! counted and the largest censored fraction admitted (above 0.1: heavily clipped, the estimate leans on touched levels).  LF is only
+//! read.  Returns EXIT_SUCCESS, or EXIT_FAILURE with the message on stdout.
+int noise_level_clipped_LF(
+    const std::vector<std::vector<float> > &LF
+,   const std::vector<unsigned> &LF_SAI_mask
+,   unsigned width
+,   unsigned height
+,   unsigned chnls
+,   double lo
+,   double hi
+,   float &sigma
+,   unsigned &levels
+,   double &f_max
+);
+
+//! The inverse of the clipped mean, in place on the GPU (lfbm5d_declip_host_sai): what takes a light field denoised from data clipped
+//! to lo..hi under noise of `sigma` (any denoiser: run_bm5d_*, run_bm3d_LF) back to the unclipped signal.
+int declip_LF(
+    double sigma
+,   double lo
+,   double hi
+,   std::vector<std::vector<float> > &LF
+,   const std::vector<unsigned> &LF_SAI_mask
+,   unsigned width
+,   unsigned height
+,   unsigned chnls
+);
+
+//! run_bm5d on data clipped to lo..hi (lfbm5d_denoise_clipped_host_sai): sigma <= 0: the clipping-aware estimate of LF_noisy first,
+//! returned in `sigma`; both steps as one job with that sigma; LF_basic and LF_denoised declipped.  LF_noisy is only read.
+int denoise_clipped_LF(
+    float &sigma
+,   double lo
+,   double hi
+,   const float lambdaHard5D
+,   const std::vector<std::vector<float> > &LF_noisy
+,   std::vector<unsigned> &LF_SAI_mask
+,   std::vector<std::vector<float> > &LF_basic
+,   std::vector<std::vector<float> > &LF_denoised
+,   const unsigned ang_major
+,   const unsigned awidth
+,   const unsigned aheight
+,   const unsigned anHard
+,   const unsigned anWien
+,   const unsigned width
+,   const unsigned height
+,   const unsigned chnls
+,   const unsigned NHard, const unsigned nSimHard, const unsigned nDispHard, const unsigned kHard, const unsigned pHard
+,   const bool useSDHard, const unsigned tau_2D_hard, unsigned tau_4D_hard, const unsigned tau_5D_hard
+,   const unsigned NWien, const unsigned nSimWien, const unsigned nDispWien, const unsigned kWien, const unsigned pWien
+,   const bool useSDWien, const unsigned tau_2D_wien, unsigned tau_4D_wien, const unsigned tau_5D_wien
+,   const unsigned color_space
+,   const unsigned nb_threads
+);
+
 //! Quality of LF_2 against LF_1 on the GPU -- compute_psnr_LF (utilities_LF.cpp:639-692) with its argument order, the sizes and the
 //! SSIM triple added: per-SAI PSNR, RMSE and SSIM (0 for empty SAIs) with their mean and population standard deviation over the
 //! non-empty SAIs (lfbm5d_quality_host_sai, include/lfbm5d.h: double sums, peak 255, SSIM with the 11 x 11 Gaussian window over every

@@ -124,6 +124,14 @@ def add_poisson_gaussian(clean, a, b, seed=1):
     return z.astype(np.float32)
 
 
+def clip_round(lf, lo=0.0, hi=255.0):
+    """What storing `lf` (any shape) in an integer format of range lo..hi does to it: round to the nearest whole number (ties to even),
+    then clip to lo..hi (an infinite value goes to its bound; NaN stays).  Returns float32."""
+    if not float(lo) < float(hi):
+        raise ValueError("clip_round: the range needs lo < hi")
+    return np.clip(np.rint(np.asarray(lf, dtype=np.float32)), np.float32(lo), np.float32(hi)).astype(np.float32)
+
+
 def add_impulse(lf, p, seed=1, kind="salt_pepper"):
     """Impulse noise on `lf` (any shape, nominally 0..255) from numpy's default_rng(seed): every value is hit with probability p and
     replaced -- "salt_pepper": by 0 or 255 with equal probability, "random": by a uniform value of [0, 255), "hot": by 255.  The draws
