@@ -812,7 +812,8 @@ int lfbm5d_inpaint_host_sai(lfbm5d_ctx* ctx, const lfbm5d_inpaint_params* params
  * every Q (h_hist_steps); disparity_hist[17] of the result is filled for steps = 1 and all zero otherwise.
  * The GPU equals the numpy model of tests/subpel_model.py bit for bit, values and j*.
  * Limits: bilinear interpolation softens the synthesised view; on noisy sources interpolation lowers the noise of a warped source, so
- * the cost leans towards fractional hypotheses (profiles/view_subpel.txt); Q <= 4; occlusions are not modelled; one scalar d per pixel; sources only within ang_radius; which SAIs are bad is
+ * the cost leans towards fractional hypotheses (profiles/view_subpel.txt); Q <= 4; occlusions are not modelled by these forms (the *_occl_* forms of include/lfbm5d_occl.h choose among
+ * the full set of sources and four half-planes of them, nothing finer); one scalar d per pixel; sources only within ang_radius; which SAIs are bad is
  * not decided here (the consistency check below does that); one GPU; every step of
  * the loop filters the whole light field; the defaults are the best row of a sweep on one light field (profiles/view_defaults.txt). */
 typedef struct {
@@ -889,7 +890,7 @@ int lfbm5d_view_host_sai(lfbm5d_ctx* ctx, const lfbm5d_view_params* params, cons
  * Sub-pixel disparities (the *_steps_* forms, include/lfbm5d_steps.h): the prediction is the view synthesis' sweep with steps
  * hypotheses per pixel, d_disp holds j*, and the spread v uses the interpolated warp w_{q,j*} of that section; residual, histograms,
  * decisions and everything else are unchanged given the prediction.  The GPU equals tests/subpel_model.py bit for bit.
- * Limits: the view synthesis' (interpolation, Q <= 4, no occlusion reasoning); a defect at the same position with zero disparity in
+ * Limits: the view synthesis' (interpolation, Q <= 4, no occlusion reasoning: the check's sweep is the plain one, not lfbm5d_occl.h's); a defect at the same position with zero disparity in
  * every view is consistent, hence invisible; one noise level for the whole field (no per-SAI noise model); one GPU; the defaults are
  * one row of a sweep on one light field (profiles/consist_defaults.txt). */
 typedef struct {
@@ -980,6 +981,8 @@ int lfbm5d_device_count(void);
 
 /* ---- the sub-pixel forms of the view synthesis and the consistency check (lfbm5d_*_steps_*) ---- */
 #include "lfbm5d_steps.h"
+/* ---- the occlusion-aware forms of the view synthesis (lfbm5d_view_*_occl_*) ---- */
+#include "lfbm5d_occl.h"
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,7 @@ from .core import (Context, Params, Bm3dParams, Stats, run_bm5d_1st_step, run_bm
                    SR_BICUBIC, SR_GAUSSIAN, SR_UP, SR_DOWN, PgModelStruct, PgEstimate, pg_model, pg_fit, pg_scale, pg_estimate,
                    denoise_pg, ImpulseParamsStruct, ImpulseResultStruct, ImpulseRepair, impulse_params, impulse_scale, impulse_repair,
                    InpaintParamsStruct, InpaintResultStruct, Inpaint, inpaint_params, inpaint,
-                   ViewParamsStruct, ViewResultStruct, ViewSynth, view_params, view_synth,
+                   ViewParamsStruct, ViewResultStruct, ViewOcclResultStruct, ViewSynth, view_params, view_synth, view_occl_default,
                    ConsistParamsStruct, ConsistResultStruct, Consist, consist_params, consist,
                    ClipEstimateStruct, ClipNoiseLevel, clip_fit, noise_level_clipped, denoise_clipped)
 
@@ -25,6 +25,6 @@ __all__ = ["Context", "Params", "Bm3dParams", "Stats", "run_bm5d_1st_step", "run
            "PgModelStruct", "PgEstimate", "pg_model", "pg_fit", "pg_scale", "pg_estimate", "denoise_pg",
            "ImpulseParamsStruct", "ImpulseResultStruct", "ImpulseRepair", "impulse_params", "impulse_scale", "impulse_repair",
            "InpaintParamsStruct", "InpaintResultStruct", "Inpaint", "inpaint_params", "inpaint",
-           "ViewParamsStruct", "ViewResultStruct", "ViewSynth", "view_params", "view_synth",
+           "ViewParamsStruct", "ViewResultStruct", "ViewOcclResultStruct", "ViewSynth", "view_params", "view_synth", "view_occl_default",
            "ConsistParamsStruct", "ConsistResultStruct", "Consist", "consist_params", "consist",
            "ClipEstimateStruct", "ClipNoiseLevel", "clip_fit", "noise_level_clipped", "denoise_clipped"]

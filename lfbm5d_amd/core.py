@@ -135,6 +135,11 @@ class ViewResultStruct(C.Structure):
                 ("disparity_hist", C.c_ulonglong * 17)]
 
 
+class ViewOcclResultStruct(C.Structure):
+    """lfbm5d_view_occl_result: positions per set chosen by the occlusion-aware synthesis (include/lfbm5d_occl.h)."""
+    _fields_ = [("set_hist", C.c_ulonglong * 5)]
+
+
 class ConsistParamsStruct(C.Structure):
     """lfbm5d_consist_params: the sweep, the two pixel tests and the bad-SAI decision of the consistency check (include/lfbm5d.h)."""
     _fields_ = [("max_disparity", C.c_uint), ("box_radius", C.c_uint), ("ang_radius", C.c_uint), ("min_sources", C.c_uint),
@@ -185,7 +190,10 @@ class ViewSynth(NamedTuple):
     an array like the input), the disparity planes (int8 [asize][H*W], written for the synthesised SAIs; None unless asked for), the
     SAIs marked missing, synthesised and left (no source within ang_radius), the positions of the synthesised SAIs and the positions
     per disparity (index d + 8).  With disparity_steps > 1 the disparity planes hold j* = d* in units of 1 / disparity_steps,
-    disparity_hist is all zero and steps_hist holds the positions per j* (65 bins, index j* + 32); steps_hist is None otherwise."""
+    disparity_hist is all zero and steps_hist holds the positions per j* (65 bins, index j* + 32); steps_hist is None otherwise.
+    With `occlusion` on, steps_hist is filled for every disparity_steps, set_hist holds the positions per set chosen (0 the full set of
+    sources, 1..4 the half-planes dt <= 0, dt >= 0, ds <= 0, ds >= 0) and, with return_sets, sets the uint8 planes [asize][H*W] of it;
+    both are None otherwise."""
     out: object
     disparity: object
     missing: int
@@ -194,6 +202,8 @@ class ViewSynth(NamedTuple):
     pixels: int
     disparity_hist: tuple
     steps_hist: tuple = None
+    set_hist: tuple = None
+    sets: object = None
 
 
 class Inpaint(NamedTuple):
@@ -451,6 +461,14 @@ def lib():
         L.lfbm5d_view_steps_host_sai.argtypes = [vp, wp, C.c_uint, pp, vp, up, up, vp, vp] + [C.c_uint] * 7 + [wr, ullp]
         L.lfbm5d_consist_steps_device.argtypes = [vp, cp, C.c_uint, fp, up, up, vp, up, vp, dp, ullp] + [C.c_uint] * 6 + [cr]
         L.lfbm5d_consist_steps_host_sai.argtypes = [vp, cp, C.c_uint, vp, up, up, vp, up, vp, dp, ullp] + [C.c_uint] * 6 + [cr]
+    if hasattr(L, "lfbm5d_view_occl_device"):   # the occlusion-aware forms: the ratio behind `steps`, the set planes behind the disparities
+        wp, wr, pp = C.POINTER(ViewParamsStruct), C.POINTER(ViewResultStruct), C.POINTER(Params)
+        ullp, orp = C.POINTER(C.c_ulonglong), C.POINTER(ViewOcclResultStruct)
+        L.lfbm5d_view_occl_default.argtypes = []
+        L.lfbm5d_view_occl_default.restype = C.c_float
+        L.lfbm5d_view_fill_occl_device.argtypes = [vp, wp, C.c_uint, C.c_float, fp, up, up, fp, vp, vp] + [C.c_uint] * 6 + [wr, ullp, orp]
+        L.lfbm5d_view_occl_device.argtypes = [vp, wp, C.c_uint, C.c_float, pp, fp, up, up, fp, vp, vp] + [C.c_uint] * 7 + [wr, ullp, orp]
+        L.lfbm5d_view_occl_host_sai.argtypes = [vp, wp, C.c_uint, C.c_float, pp, vp, up, up, vp, vp, vp] + [C.c_uint] * 7 + [wr, ullp, orp]
     if hasattr(L, "lfbm5d_consist_device"):   # (absent from older builds loaded through LFBM5D_HIP_LIB for A/B runs)
         cp, cr = C.POINTER(ConsistParamsStruct), C.POINTER(ConsistResultStruct)
         dp, ullp = C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)
@@ -1331,9 +1349,26 @@ class Context:
 
     # ---- view synthesis ----
     @staticmethod
-    def _view_result(out, disp, res, steps_hist=None):
+    def _view_result(out, disp, res, steps_hist=None, occl=None, sets=None):
         return ViewSynth(out, disp, int(res.missing), int(res.synthesised), int(res.left), int(res.pixels), tuple(res.disparity_hist),
-                         None if steps_hist is None else tuple(int(v) for v in steps_hist))
+                         None if steps_hist is None else tuple(int(v) for v in steps_hist),
+                         None if occl is None else tuple(int(v) for v in occl.set_hist), sets)
+
+    @staticmethod
+    def _occlusion(occlusion, return_sets=False, sets_out=None):
+        """The occl_ratio of `occlusion`: None or False -> 0 (off), True -> the library's default, a number -> itself (the library
+        checks its range).  Set planes without occlusion are an error."""
+        if occlusion is None or occlusion is False:
+            ratio = 0.0
+        elif occlusion is True:
+            ratio = float(lib().lfbm5d_view_occl_default())
+        elif isinstance(occlusion, (int, float, np.integer, np.floating)):
+            ratio = float(occlusion)
+        else:
+            raise LfBm5dError(f"occlusion must be None, True or a ratio, not {type(occlusion).__name__}")
+        if ratio == 0.0 and (return_sets or sets_out is not None):
+            raise LfBm5dError("return_sets and sets_out need occlusion (the plain sweep chooses no set)")
+        return ratio
 
     @staticmethod
     def _steps(disparity_steps):
@@ -1345,12 +1380,16 @@ class Context:
         return steps, hist, hist.ctypes.data_as(C.POINTER(C.c_ulonglong))
 
     def view_fill(self, noisy, mask, missing, ang_major, awidth, aheight, width, height, chnls, max_disparity=None, box_radius=None,
-                  ang_radius=None, return_disparity=False, out=None, disparity_out=None, disparity_steps=1):
+                  ang_radius=None, return_disparity=False, out=None, disparity_out=None, disparity_steps=1, occlusion=None,
+                  return_sets=False, sets_out=None):
         """The plane-sweep synthesis of lfbm5d_view_fill_device on CUDA tensors: noisy float32 [asize][C*H*W] (only read; the planes of
         the SAIs `missing` marks are never read).  out / disparity_out (int8 [asize][H*W]): optional tensors to write into, distinct
         from the input; only the planes of the synthesised SAIs are written, a fresh `out` is a copy of the input elsewhere.
         disparity_steps = 1, 2 or 4 hypotheses per pixel (lfbm5d_view_fill_steps_device; sources are interpolated bilinearly): the
-        result's `disparity` is in units of 1 / disparity_steps, and above 1 its steps_hist is the histogram.  Returns a ViewSynth."""
+        result's `disparity` is in units of 1 / disparity_steps, and above 1 its steps_hist is the histogram.  occlusion: None (off),
+        True (the library's ratio) or a ratio >= 1: the occlusion-aware sweep of lfbm5d_view_fill_occl_device (include/lfbm5d_occl.h);
+        the result gains set_hist and, with return_sets or sets_out (uint8 [asize][H*W]), sets.  Returns a ViewSynth."""
+        ratio = self._occlusion(occlusion, return_sets, sets_out)
         steps, sh, shp = self._steps(disparity_steps)
         m, ms = _u32(mask), _u32(missing)
         vp = view_params(max_disparity, box_radius, ang_radius)
@@ -1361,6 +1400,13 @@ class Context:
         up = C.POINTER(C.c_uint)
         args = (_dev_ptr(noisy), m.ctypes.data_as(up), ms.ctypes.data_as(up), _dev_ptr(out), None if dp is None else _dev_ptr(dp, np.int8),
                 ang_major, awidth, aheight, int(width), int(height), int(chnls), C.byref(res))
+        if ratio != 0.0:
+            sh = np.zeros(VIEW_STEPS_HIST, np.uint64)
+            sp = self._dev_planes(noisy, sets_out, return_sets, (m.size, int(width) * int(height)), torch.uint8)
+            occl = ViewOcclResultStruct()
+            self._ck(self._L.lfbm5d_view_fill_occl_device(self._h, C.byref(vp), steps, ratio, *args[:5], None if sp is None else _dev_ptr(sp, np.uint8),
+                                                          *args[5:], sh.ctypes.data_as(C.POINTER(C.c_ulonglong)), C.byref(occl)))
+            return self._view_result(out, dp, res, sh, occl, sp)
         if steps == 1:
             self._ck(self._L.lfbm5d_view_fill_device(self._h, C.byref(vp), *args))
         else:
@@ -1369,7 +1415,8 @@ class Context:
 
     def view_synth(self, noisy, mask, missing, P, ang_major, awidth, aheight, an, width, height, chnls, max_disparity=None,
                    box_radius=None, ang_radius=None, iterations=None, sigma_start=None, sigma_end=None, sigma_noise=None,
-                   return_disparity=False, out=None, disparity_out=None, disparity_steps=1):
+                   return_disparity=False, out=None, disparity_out=None, disparity_steps=1, occlusion=None, return_sets=False,
+                   sets_out=None):
         """View synthesis (lfbm5d_view_*, include/lfbm5d.h): the SAIs `missing` marks (non-zero; they must be non-empty in `mask`) are
         synthesised from their sound angular neighbours by a plane sweep over the integer disparities -max_disparity..max_disparity
         and refined by `iterations` hard-thresholding steps (P, its sigma replaced by the schedule sigma_start -> sigma_end, not below
@@ -1378,9 +1425,16 @@ class Context:
         per-SAI arrays, None allowed for missing SAIs (host form, staged through HBM; identical results).  The input is only read.
         return_disparity: the int8 planes [asize][H*W] of d*.  disparity_steps = 1, 2 or 4 hypotheses per pixel (the *_steps_* forms;
         sources are interpolated bilinearly): `disparity` is in units of 1 / disparity_steps, and above 1 the result's steps_hist is
-        the histogram.  Returns a ViewSynth."""
+        the histogram.  occlusion: None (off), True (the library's ratio) or a ratio >= 1: the occlusion-aware sweep of the
+        lfbm5d_view_occl_* forms (include/lfbm5d_occl.h); the result gains set_hist and, with return_sets or sets_out (uint8
+        [asize][H*W]; a list of per-SAI planes in the host form), sets.  Returns a ViewSynth."""
+        ratio = self._occlusion(occlusion, return_sets, sets_out)
         m, ms = _u32(mask), _u32(missing)
         steps, sh, shp = self._steps(disparity_steps)
+        occl = sp = None
+        if ratio != 0.0:
+            sh, occl = np.zeros(VIEW_STEPS_HIST, np.uint64), ViewOcclResultStruct()
+            tail_occl = (sh.ctypes.data_as(C.POINTER(C.c_ulonglong)), C.byref(occl))
         asize = m.size
         vp = view_params(max_disparity, box_radius, ang_radius, iterations, sigma_start, sigma_end, sigma_noise)
         res = ViewResultStruct()
@@ -1392,7 +1446,12 @@ class Context:
             out, outs = self._host_out(arrays, out, m, int(chnls) * int(width) * int(height))
             dp = self._host_planes(arrays, disparity_out, return_disparity, np.int8, int(width) * int(height))
             args = (C.byref(P), _sai_ptrs(arrays, m), mp, msp, _sai_ptrs(outs, m), None if dp is None else _sai_ptrs(dp, m, np.int8), *tail)
-            if steps == 1:
+            if ratio != 0.0:
+                sp = self._host_planes(arrays, sets_out, return_sets, np.uint8, int(width) * int(height))
+                self._ck(self._L.lfbm5d_view_occl_host_sai(self._h, C.byref(vp), steps, ratio, *args[:6],
+                                                           None if sp is None else _sai_ptrs(sp, m, np.uint8), *tail, *tail_occl))
+                sp = self._stacked(noisy, sp, False)
+            elif steps == 1:
                 self._ck(self._L.lfbm5d_view_host_sai(self._h, C.byref(vp), *args))
             else:
                 self._ck(self._L.lfbm5d_view_steps_host_sai(self._h, C.byref(vp), steps, *args, shp))
@@ -1402,11 +1461,15 @@ class Context:
             out = self._dev_out(noisy, out)
             dp = self._dev_planes(noisy, disparity_out, return_disparity, (asize, int(width) * int(height)), torch.int8)
             args = (C.byref(P), _dev_ptr(noisy), mp, msp, _dev_ptr(out), None if dp is None else _dev_ptr(dp, np.int8), *tail)
-            if steps == 1:
+            if ratio != 0.0:
+                sp = self._dev_planes(noisy, sets_out, return_sets, (asize, int(width) * int(height)), torch.uint8)
+                self._ck(self._L.lfbm5d_view_occl_device(self._h, C.byref(vp), steps, ratio, *args[:6], None if sp is None else _dev_ptr(sp, np.uint8),
+                                                         *tail, *tail_occl))
+            elif steps == 1:
                 self._ck(self._L.lfbm5d_view_device(self._h, C.byref(vp), *args))
             else:
                 self._ck(self._L.lfbm5d_view_steps_device(self._h, C.byref(vp), steps, *args, shp))
-        return self._view_result(out, dp, res, sh)
+        return self._view_result(out, dp, res, sh, occl, sp)
 
     # ---- consistency check ----
     def consist(self, noisy, mask, ang_major, awidth, aheight, width, height, chnls, exclude=None, return_disparity=False,
@@ -1640,6 +1703,11 @@ def inpaint(noisy, flags, mask, P, ang_major, awidth, aheight, an, width, height
     return (ctx or _ctx()).inpaint(noisy, flags, mask, P, ang_major, awidth, aheight, an, width, height, chnls, **more)
 
 
+def view_occl_default():
+    """The occlusion ratio the library ships (lfbm5d_view_occl_default, host only): what occlusion=True means."""
+    return float(lib().lfbm5d_view_occl_default())
+
+
 def view_synth(noisy, mask, missing, P, ang_major, awidth, aheight, an, width, height, chnls, ctx=None, **more):
     """Context.view_synth on the default context (device 0): missing SAIs synthesised from their angular neighbours, refined by the
     hard-thresholding step."""
@@ -1757,10 +1825,12 @@ def inpaint_probe(noisy, flags, mask, awidth, aheight, width, height, chnls, lam
 
 
 def view_synth_probe(noisy, mask, missing, awidth, aheight, width, height, chnls, lambda_, hard, max_disparity=-1, box_radius=-1, ang_radius=-1,
-                     iterations=-1, sigma_start=0.0, sigma_end=0.0, sigma_noise=0.0, color_space="opp", ang_major=ROWMAJOR, an=1, disparity_steps=1):
+                     iterations=-1, sigma_start=0.0, sigma_end=0.0, sigma_noise=0.0, color_space="opp", ang_major=ROWMAJOR, an=1, disparity_steps=1,
+                     occl_ratio=0.0):
     """The C++ drop-in's view_synth_LF (liblfbm5d_dropin.so, run_bm5d.h) on a vector<vector<float>> light field built from `noisy`
     [asize][chnls*height*width] (the vectors of missing SAIs are left empty); hard = (N, nSim, nDisp, k, p, tau_2D, tau_4D, tau_5D[, useSD]).
-    disparity_steps: view_synth_LF's trailing argument (dmin and dmax are then in units of 1 / disparity_steps).
+    disparity_steps: view_synth_LF's trailing argument (dmin and dmax are then in units of 1 / disparity_steps).  occl_ratio: the one
+    behind it; a sixth value is then returned, the positions per set chosen (5 counters).
     Returns (the completed light field, synthesised, left, dmin, dmax)."""
     path = os.path.join(os.path.dirname(library_path()), "liblfbm5d_dropin.so")
     if not os.path.exists(path):
@@ -1779,10 +1849,16 @@ def view_synth_probe(noisy, mask, missing, awidth, aheight, width, height, chnls
     args = (noisy.ctypes.data, m.ctypes.data, ms.ctypes.data, out.ctypes.data, ang_major, awidth, aheight, an, width, height, chnls,
             vpi.ctypes.data, vpf.ctypes.data, hv.ctypes.data, _CS[color_space] if isinstance(color_space, str) else int(color_space),
             counts.ctypes.data)
-    rc = D.lfbm5d_view_synth_probe(*args) if int(disparity_steps) == 1 else D.lfbm5d_view_synth_steps_probe(*args, int(disparity_steps))
+    sets = np.zeros(5, np.uint64)
+    if float(occl_ratio) != 0.0:
+        D.lfbm5d_view_synth_occl_probe.argtypes = D.lfbm5d_view_synth_steps_probe.argtypes + [C.c_float, C.c_void_p]
+        rc = D.lfbm5d_view_synth_occl_probe(*args, int(disparity_steps), float(occl_ratio), sets.ctypes.data)
+    else:
+        rc = D.lfbm5d_view_synth_probe(*args) if int(disparity_steps) == 1 else D.lfbm5d_view_synth_steps_probe(*args, int(disparity_steps))
     if rc != 0:
         raise LfBm5dError("view_synth_LF failed (message on stdout)")
-    return out, int(counts[0]), int(counts[1]), int(counts[2]), int(counts[3])
+    res = (out, int(counts[0]), int(counts[1]), int(counts[2]), int(counts[3]))
+    return res + (tuple(int(v) for v in sets),) if float(occl_ratio) != 0.0 else res
 
 
 def consist_probe(noisy, mask, awidth, aheight, width, height, chnls, exclude=None, max_disparity=-1, box_radius=-1, ang_radius=-1,

@@ -60,6 +60,11 @@
  *                     LFBM5D_MISSING's format into <dir>/missing.txt (empty when none is bad), so that a camera's fixed map can be
  *                     reused.  Together with LFBM5D_DEFECTS or LFBM5D_MISSING it is an error (there is no combined loop).  The files
  *                     hold 8-bit values, so nothing here is non-finite.  Unset, the output is unchanged;
+ *   LFBM5D_OCCLUSION=auto|<ratio>   the occlusion-aware plane sweep (include/lfbm5d_occl.h) in every view synthesis the command runs
+ *                     (LFBM5D_MISSING, and the bad SAIs LFBM5D_DETECT hands over): `auto` is the library's ratio, <ratio> a finite
+ *                     number >= 1.  The `View synthesis:` line then ends `, occlusion ratio <ratio>: <pct> % of the positions from a
+ *                     half-plane`.  Any other value, and the variable without LFBM5D_MISSING or LFBM5D_DETECT, stop the command
+ *                     with a message before a file is read.  Unset: the plain sweep, the output as without this variable.
  *   LFBM5D_DISPARITY_STEPS=1|2|4   hypotheses per pixel of disparity in the plane sweeps of LFBM5D_MISSING and LFBM5D_DETECT (sources are
  *                     interpolated bilinearly above 1; for light fields that move a fraction of a pixel per view).  Above 1 the
  *                     `View synthesis:` line prints the disparity range as decimals and ends `, <Q> steps per pixel`, and the
@@ -93,6 +98,7 @@
 
 #include <cctype>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -566,18 +572,29 @@ bool missing_mode(vector<unsigned>& missing, int& iter, unsigned ang_major, unsi
  * print the line of the header comment, with the steps that are still to come. */
 bool synthesise_missing_LF(vector<vector<float> >& LF_noisy, const vector<unsigned>& mask, const vector<unsigned>& missing, unsigned ang_major,
                            unsigned aw, unsigned ah, unsigned an, unsigned W, unsigned H, unsigned C, unsigned steps, unsigned steps_to_come,
-                           float sigma_noise, float lambda, const unsigned* hard, unsigned cs, bool report, unsigned dsteps) {
+                           float sigma_noise, float lambda, const unsigned* hard, unsigned cs, bool report, unsigned dsteps,
+                           float occl) {
     unsigned done = 0, left = 0, all = 0, n = 0; int dmin = 0, dmax = 0;
+    unsigned long long sets[5] = {0, 0, 0, 0, 0};
     if (view_synth_LF(LF_noisy, mask, missing, ang_major, aw, ah, an, W, H, C, -1, -1, -1, (int)steps, 0.0f, 0.0f, sigma_noise, lambda, hard[0],
-                      hard[1], hard[2], hard[3], hard[4], hard[5] != 0, hard[6], hard[7], hard[8], cs, done, left, dmin, dmax, dsteps) != EXIT_SUCCESS)
+                      hard[1], hard[2], hard[3], hard[4], hard[5] != 0, hard[6], hard[7], hard[8], cs, done, left, dmin, dmax, dsteps, occl,
+                      sets) != EXIT_SUCCESS)
         return false;
     for (size_t st = 0; st < mask.size(); st++) { if (mask[st]) all++; if (missing[st]) n++; }
     if (report && dsteps == 1)
         cout << endl << "View synthesis: " << n << " of " << all << " SAIs missing, " << left << " left; disparities " << dmin << ".." << dmax << ", "
-             << steps_to_come << " refinement steps" << endl;
+             << steps_to_come << " refinement steps";
     else if (report)                                                            /* the range is in units of 1 / dsteps: printed in pixels */
         cout << endl << "View synthesis: " << n << " of " << all << " SAIs missing, " << left << " left; disparities " << dmin / (double)dsteps << ".."
-             << dmax / (double)dsteps << ", " << steps_to_come << " refinement steps, " << dsteps << " steps per pixel" << endl;
+             << dmax / (double)dsteps << ", " << steps_to_come << " refinement steps, " << dsteps << " steps per pixel";
+    if (report && occl != 0.0f) {
+        const unsigned long long total = sets[0] + sets[1] + sets[2] + sets[3] + sets[4];
+        char txt[96];                                                           /* its own format: cout's flags are the measures' */
+        snprintf(txt, sizeof(txt), ", occlusion ratio %g: %.1f %% of the positions from a half-plane", (double)occl,
+                 total ? 100.0 * (double)(total - sets[0]) / (double)total : 0.0);
+        cout << txt;
+    }
+    if (report) cout << endl;
     return true;
 }
 
@@ -620,6 +637,26 @@ bool disparity_steps_mode(unsigned& dsteps, bool sweeps) {
     }
     if (!sweeps) { cout << "LFBM5D_DISPARITY_STEPS needs LFBM5D_MISSING or LFBM5D_DETECT" << endl; return false; }
     dsteps = (unsigned)(e[0] - '0');
+    return true;
+}
+
+/* LFBM5D_OCCLUSION: 0 (the plain sweep) when unset; false (message printed) on anything but "auto" or a finite ratio >= 1, or without a
+ * synthesis to apply it to.  After missing_mode() and detect_mode(). */
+bool occlusion_mode(float& occl, bool synthesis) {
+    occl = 0.0f;
+    const char* e = env("LFBM5D_OCCLUSION");
+    if (!e) return true;
+    if (!strcmp(e, "auto")) occl = lfbm5d_view_occl_default();
+    else {
+        char* q = nullptr;
+        const float v = strtof(e, &q);
+        if (q == e || *q || !(isdigit((unsigned char)*e) || *e == '.') || strpbrk(e, "xXpP") || !std::isfinite(v) || v < 1.0f) {
+            cout << "LFBM5D_OCCLUSION must be \"auto\" (the library's ratio) or a finite ratio >= 1, or unset; got \"" << e << "\"" << endl;
+            return false;
+        }
+        occl = v;
+    }
+    if (!synthesis) { cout << "LFBM5D_OCCLUSION needs LFBM5D_MISSING or LFBM5D_DETECT" << endl; return false; }
     return true;
 }
 
@@ -761,6 +798,8 @@ int main(int argc, char** argv) {
     if (!detect_mode(detect, det_k, det_save)) return EXIT_FAILURE;
     unsigned dsteps = 1;
     if (!disparity_steps_mode(dsteps, detect || !missing.empty())) return EXIT_FAILURE;
+    float occl = 0.0f;
+    if (!occlusion_mode(occl, detect || !missing.empty())) return EXIT_FAILURE;
     bool clip_on = false, clip_add = false; double clip_lo = 0.0, clip_hi = 255.0;
     if (!clip_mode(clip_on, clip_lo, clip_hi, clip_add, smode)) return EXIT_FAILURE;
 
@@ -792,7 +831,7 @@ int main(int argc, char** argv) {
     vector<unsigned> est_mask = mask;   /* the sigma estimate does not look at reconstructed SAIs */
     if (!missing.empty()) {   /* the synthesis alone, for the same reason as the fill alone below */
         const unsigned hard[9] = {8, 8, 3, 8, 3, 0, LFBM5D_DCT, LFBM5D_SADCT, LFBM5D_HAAR};
-        if (!synthesise_missing_LF(LF_noisy, mask, missing, ang_major, aw, ah, 1, W, H, C, 0, 0, 0.0f, lambda, hard, (unsigned)cs, true, dsteps)) return EXIT_FAILURE;
+        if (!synthesise_missing_LF(LF_noisy, mask, missing, ang_major, aw, ah, 1, W, H, C, 0, 0, 0.0f, lambda, hard, (unsigned)cs, true, dsteps, occl)) return EXIT_FAILURE;
         cout << "View synthesis: the synthesis alone (the refinement steps run in LFBM5Ddenoising)" << endl;
         for (size_t st = 0; st < missing.size(); st++) if (missing[st]) est_mask[st] = 0;
     }
@@ -920,6 +959,8 @@ int main(int argc, char** argv) {
     if (!detect_mode(detect, det_k, det_save)) return EXIT_FAILURE;
     unsigned dsteps = 1;
     if (!disparity_steps_mode(dsteps, detect || !missing.empty())) return EXIT_FAILURE;
+    float occl = 0.0f;
+    if (!occlusion_mode(occl, detect || !missing.empty())) return EXIT_FAILURE;
     bool clip_on = false, clip_add = false; double clip_lo = 0.0, clip_hi = 255.0;
     if (!clip_mode(clip_on, clip_lo, clip_hi, clip_add, smode)) return EXIT_FAILURE;
 
@@ -957,7 +998,7 @@ int main(int argc, char** argv) {
         lfbm5d_view_params vp;
         lfbm5d_view_defaults(&vp);
         view_steps = smode >= 2 ? 0u : miss_iter >= 0 ? (unsigned)miss_iter : vp.iterations;
-        if (!synthesise_missing_LF(LF_noisy, mask, missing, ang_major, aw, ah, anH, W, H, C, 0, view_steps, 0.0f, lambda, def_hard, (unsigned)cs, true, dsteps))
+        if (!synthesise_missing_LF(LF_noisy, mask, missing, ang_major, aw, ah, anH, W, H, C, 0, view_steps, 0.0f, lambda, def_hard, (unsigned)cs, true, dsteps, occl))
             return EXIT_FAILURE;
         if (smode >= 2) cout << "View synthesis: the synthesis alone (LFBM5D_SIGMA=poisson: the refinement steps assume one sigma)" << endl;
         for (size_t st = 0; st < missing.size(); st++) if (missing[st]) est_mask[st] = 0;
@@ -975,7 +1016,7 @@ int main(int argc, char** argv) {
     if (smode == 1 && !(clip_on ? estimate_sigma_clipped_LF(LF_noisy, est_mask, W, H, C, clip_lo, clip_hi, sigma)
                                 : estimate_sigma_LF(LF_noisy, est_mask, W, H, C, sigma))) return EXIT_FAILURE;
     if (view_steps && !synthesise_missing_LF(LF_noisy, mask, missing, ang_major, aw, ah, anH, W, H, C, view_steps, view_steps, sigma, lambda, def_hard,
-                                             (unsigned)cs, false, dsteps)) return EXIT_FAILURE;
+                                             (unsigned)cs, false, dsteps, occl)) return EXIT_FAILURE;
     if (def_steps && !inpaint_defects_LF(LF_noisy, defects, mask, ang_major, aw, ah, anH, W, H, C, def_steps, def_steps, sigma, lambda, def_hard,
                                          (unsigned)cs, false)) return EXIT_FAILURE;
     LF_basic.assign(awh, vector<float>((size_t)W * H * C, 0.0f));

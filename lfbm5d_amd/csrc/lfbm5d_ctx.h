@@ -168,8 +168,8 @@ struct lfbm5d_ctx {
     struct ImpulseBufs { DevBuf stats, flags; } imp;
     /* defect inpainting (lfbm5d_inpaint.hip): the fill's counters, its state planes, the host form's flag planes (in, out) */
     struct InpaintBufs { DevBuf stats, state[2], flags; } inp;
-    /* view synthesis (lfbm5d_view.hip): the source lists, the disparity histogram, the host form's disparity planes */
-    struct ViewBufs { DevBuf table, stats, disp; } view;
+    /* view synthesis (lfbm5d_view.hip): the source lists, the disparity and set histograms, the host form's disparity and set planes */
+    struct ViewBufs { DevBuf table, stats, disp, set; } view;
     /* consistency check (lfbm5d_consist.hip): the leave-one-out source lists, histograms and counters, the prediction light field, the
      * sweep's disparity planes, the host form's flag and disparity planes */
     struct ConsistBufs { DevBuf table, stats, pred, disp, flags; } consist;

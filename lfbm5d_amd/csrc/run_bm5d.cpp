@@ -600,9 +600,10 @@ int view_synth_LF(std::vector<std::vector<float> >& LF, const std::vector<unsign
                   const int iterations, const float sigmaStart, const float sigmaEnd, const float sigmaNoise, const float lambdaHard5D,
                   const unsigned NHard, const unsigned nSim, const unsigned nDisp, const unsigned kHard, const unsigned pHard, const bool useSD,
                   const unsigned tau_2D, unsigned tau_4D, const unsigned tau_5D, const unsigned color_space, unsigned& synthesised,
-                  unsigned& left, int& dmin, int& dmax, const unsigned disparity_steps) {
+                  unsigned& left, int& dmin, int& dmax, const unsigned disparity_steps, const float occl_ratio, unsigned long long* set_hist) {
     const unsigned asize = awidth * aheight;
     synthesised = left = 0; dmin = dmax = 0;
+    if (set_hist) std::memset(set_hist, 0, LFBM5D_VIEW_OCCL_SETS * sizeof(unsigned long long));
     if (LF.size() != asize || LF_SAI_mask.size() != asize || missing.size() != asize) {
         std::cout << "view_synth_LF: light field, mask and missing must hold awidth*aheight SAIs" << std::endl;
         return EXIT_FAILURE;
@@ -634,7 +635,12 @@ int view_synth_LF(std::vector<std::vector<float> >& LF, const std::vector<unsign
     std::memset(&r, 0, sizeof(r));
     unsigned long long hist[LFBM5D_VIEW_STEPS_HIST] = {0};
     int rc;
-    if (disparity_steps == 1) {                                                 /* the integer form: its name in the messages */
+    if (occl_ratio != 0.0f) {                                                   /* (a NaN goes this way too, and is rejected there) */
+        lfbm5d_view_occl_result o = {};
+        rc = lfbm5d_view_occl_host_sai(ctx, &vp, disparity_steps, occl_ratio, &P, p.data(), LF_SAI_mask.data(), missing.data(), p.data(), nullptr,
+                                       nullptr, ang_major, awidth, aheight, anHard, width, height, chnls, &r, hist, &o);
+        if (set_hist) std::memcpy(set_hist, o.set_hist, sizeof(o.set_hist));
+    } else if (disparity_steps == 1) {                                          /* the integer form: its name in the messages */
         rc = lfbm5d_view_host_sai(ctx, &vp, &P, p.data(), LF_SAI_mask.data(), missing.data(), p.data(), nullptr, ang_major, awidth, aheight,
                                   anHard, width, height, chnls, &r);
         for (int d = -8; d <= 8; d++) hist[d + 32] = r.disparity_hist[d + 8];
@@ -658,7 +664,8 @@ int view_synth_LF(std::vector<std::vector<float> >& LF, const std::vector<unsign
  * counts = {synthesised, left, dmin, dmax}. */
 static int view_synth_probe(const float* in_flat, const unsigned* mask, const unsigned* missing, float* out_flat, unsigned ang_major,
                             unsigned awidth, unsigned aheight, unsigned an, unsigned width, unsigned height, unsigned chnls, const int* vpi,
-                            const float* vpf, const unsigned* hard, unsigned color_space, int* counts, unsigned disparity_steps) {
+                            const float* vpf, const unsigned* hard, unsigned color_space, int* counts, unsigned disparity_steps,
+                            float occl_ratio = 0.0f, unsigned long long* set_hist = nullptr) {
     const size_t asize = (size_t)awidth * aheight, img = (size_t)width * height * chnls;
     std::vector<unsigned> m(mask, mask + asize), ms(missing, missing + asize);
     std::vector<std::vector<float> > LF(asize);
@@ -667,7 +674,7 @@ static int view_synth_probe(const float* in_flat, const unsigned* mask, const un
     unsigned synthesised = 0, left = 0; int dmin = 0, dmax = 0;
     const int rc = view_synth_LF(LF, m, ms, ang_major, awidth, aheight, an, width, height, chnls, vpi[0], vpi[1], vpi[2], vpi[3], vpf[0], vpf[1],
                                  vpf[2], vpf[3], hard[0], hard[1], hard[2], hard[3], hard[4], hard[5] != 0, hard[6], hard[7], hard[8], color_space,
-                                 synthesised, left, dmin, dmax, disparity_steps);
+                                 synthesised, left, dmin, dmax, disparity_steps, occl_ratio, set_hist);
     if (counts) { counts[0] = (int)synthesised; counts[1] = (int)left; counts[2] = dmin; counts[3] = dmax; }
     if (rc != EXIT_SUCCESS) return 1;
     for (size_t st = 0; st < asize; st++) if (m[st] && LF[st].size() == img) std::memcpy(out_flat + st * img, LF[st].data(), img * sizeof(float));
@@ -688,6 +695,15 @@ extern "C" int lfbm5d_view_synth_steps_probe(const float* in_flat, const unsigne
                                              int* counts, unsigned disparity_steps) {
     return view_synth_probe(in_flat, mask, missing, out_flat, ang_major, awidth, aheight, an, width, height, chnls, vpi, vpf, hard, color_space,
                             counts, disparity_steps);
+}
+
+/* The same with view_synth_LF's occl_ratio; set_hist [5]: the positions per set chosen. */
+extern "C" int lfbm5d_view_synth_occl_probe(const float* in_flat, const unsigned* mask, const unsigned* missing, float* out_flat,
+                                            unsigned ang_major, unsigned awidth, unsigned aheight, unsigned an, unsigned width, unsigned height,
+                                            unsigned chnls, const int* vpi, const float* vpf, const unsigned* hard, unsigned color_space,
+                                            int* counts, unsigned disparity_steps, float occl_ratio, unsigned long long* set_hist) {
+    return view_synth_probe(in_flat, mask, missing, out_flat, ang_major, awidth, aheight, an, width, height, chnls, vpi, vpf, hard, color_space,
+                            counts, disparity_steps, occl_ratio, set_hist);
 }
 
 /* consistency check on the caller's vectors (one pointer per SAI; the library stages in and out) */

@@ -319,7 +319,10 @@ int inpaint_LF(
 //! sigmaStart = 0, sigmaEnd = 0: the library's defaults (lfbm5d_view_defaults); iterations = 0: the synthesis alone.  `left` counts the
 //! missing SAIs without a source (unchanged); dmin..dmax is the range of the disparities chosen (0..0 when nothing was synthesised).
 //! disparity_steps = 1, 2 or 4 hypotheses per pixel (lfbm5d_view_steps_host_sai; above 1 the sources are interpolated bilinearly and
-//! dmin..dmax is in units of 1 / disparity_steps).  Returns EXIT_SUCCESS, or EXIT_FAILURE with the message on stdout.
+//! dmin..dmax is in units of 1 / disparity_steps).  occl_ratio = 0: the plain sweep; >= 1: the occlusion-aware sweep
+//! (lfbm5d_view_occl_host_sai, include/lfbm5d_occl.h; lfbm5d_view_occl_default() is the ratio the library ships), and set_hist (5
+//! counters, or NULL) receives the positions per set chosen (0 the full set, 1..4 the half-planes; all zero with occl_ratio = 0).
+//! Returns EXIT_SUCCESS, or EXIT_FAILURE with the message on stdout.
 int view_synth_LF(
     std::vector<std::vector<float> > &LF
 ,   const std::vector<unsigned> &LF_SAI_mask
@@ -354,6 +357,8 @@ int view_synth_LF(
 ,   int &dmin
 ,   int &dmax
 ,   const unsigned disparity_steps = 1
+,   const float occl_ratio = 0.0f
+,   unsigned long long *set_hist = nullptr
 );
 
 //! Consistency check -- not in the reference: every usable SAI is predicted on the GPU from its angular neighbours by the view synthesis'
