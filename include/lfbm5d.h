@@ -983,6 +983,8 @@ int lfbm5d_device_count(void);
 #include "lfbm5d_steps.h"
 /* ---- the occlusion-aware forms of the view synthesis (lfbm5d_view_*_occl_*) ---- */
 #include "lfbm5d_occl.h"
+/* ---- photometric equalisation: per-view gains estimated and divided out (lfbm5d_photo_*) ---- */
+#include "lfbm5d_photo.h"
 
 #ifdef __cplusplus
 }

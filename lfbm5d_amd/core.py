@@ -185,6 +185,49 @@ class Consist(NamedTuple):
         return (np.asarray(self.state) == CONSIST_BAD).astype(np.uint32)
 
 
+class PhotoParamsStruct(C.Structure):
+    """lfbm5d_photo_params: the sweep, the admission range, the fit and the rounds of the photometric equalisation
+    (include/lfbm5d_photo.h)."""
+    _fields_ = [("max_disparity", C.c_uint), ("box_radius", C.c_uint), ("ang_radius", C.c_uint), ("steps", C.c_uint),
+                ("min_sources", C.c_uint), ("max_rounds", C.c_uint), ("per_channel", C.c_uint), ("anchor", C.c_uint),
+                ("min_count", C.c_ulonglong), ("tol", C.c_double), ("lo", C.c_double), ("hi", C.c_double)]
+
+
+class PhotoResultStruct(C.Structure):
+    """lfbm5d_photo_result: what one photometric equalisation found (include/lfbm5d_photo.h)."""
+    _fields_ = [("residual", C.c_double), ("gain_min", C.c_double), ("gain_max", C.c_double), ("admitted", C.c_ulonglong),
+                ("skipped_nonfinite", C.c_ulonglong), ("skipped_range", C.c_ulonglong), ("rounds", C.c_uint), ("converged", C.c_uint),
+                ("fitted", C.c_uint), ("untested", C.c_uint), ("unfit", C.c_uint)]
+
+
+PHOTO_KEYS, PHOTO_EDGES, PHOTO_NO_ANCHOR, PHOTO_MAX_SOURCES = 1026, 1025, 0xFFFFFFFF, 24
+PHOTO_EMPTY, PHOTO_FITTED, PHOTO_UNTESTED, PHOTO_UNFIT = 0, 1, 2, 3
+
+
+class Equalise(NamedTuple):
+    """Result of Context.equalise / equalise: the equalised light field (a tensor or an array like the input; planes of empty SAIs are
+    the input's), the gains G that were divided out (float64 [asize][3]; 1 for empty SAIs and channels that are not stored: hand them
+    to apply_gains(..., invert=True) to restore every view's own photometry), the state of every SAI (int64 [asize]: 0 empty,
+    1 fitted, 2 untested, 3 unfit in some channel), the last sweep's histograms (uint64 [asize][C][1026]; None unless asked for), the
+    sweeps, whether the last sweep's ratios were within tol of 1, that sweep's largest |ratio - 1|, the smallest and the largest gain,
+    the numbers of fitted, untested and unfit SAIs, and the values the last sweep counted, found not finite and found out of range."""
+    out: object
+    gain: np.ndarray
+    state: np.ndarray
+    hist: object
+    rounds: int
+    converged: bool
+    residual: float
+    gain_min: float
+    gain_max: float
+    fitted: int
+    untested: int
+    unfit: int
+    admitted: int
+    skipped_nonfinite: int
+    skipped_range: int
+
+
 class ViewSynth(NamedTuple):
     """Result of Context.view_fill / Context.view_synth / view_synth: the light field with the missing SAIs reconstructed (a tensor or
     an array like the input), the disparity planes (int8 [asize][H*W], written for the synthesised SAIs; None unless asked for), the
@@ -476,6 +519,19 @@ def lib():
         L.lfbm5d_consist_defaults.restype = None
         L.lfbm5d_consist_device.argtypes = [vp, cp, fp, up, up, vp, up, vp, dp, ullp] + [C.c_uint] * 6 + [cr]
         L.lfbm5d_consist_host_sai.argtypes = [vp, cp, vp, up, up, vp, up, vp, dp, ullp] + [C.c_uint] * 6 + [cr]
+    if hasattr(L, "lfbm5d_photo_device"):   # (absent from older builds loaded through LFBM5D_HIP_LIB for A/B runs)
+        qp, qr = C.POINTER(PhotoParamsStruct), C.POINTER(PhotoResultStruct)
+        dp, ullp = C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)
+        L.lfbm5d_photo_defaults.argtypes = [qp]
+        L.lfbm5d_photo_defaults.restype = None
+        L.lfbm5d_photo_edges.argtypes = [C.POINTER(C.c_float)]
+        L.lfbm5d_photo_edges.restype = None
+        L.lfbm5d_photo_ratio.argtypes = [ullp, C.c_ulonglong, dp]
+        L.lfbm5d_photo_solve.argtypes = [C.c_uint, dp, up, up, up, C.c_uint, dp]
+        L.lfbm5d_photo_device.argtypes = [vp, qp, fp, up, fp, dp, up, ullp] + [C.c_uint] * 6 + [qr]
+        L.lfbm5d_photo_host_sai.argtypes = [vp, qp, vp, up, vp, dp, up, ullp] + [C.c_uint] * 6 + [qr]
+        L.lfbm5d_photo_apply_device.argtypes = [vp, fp, up, dp, C.c_uint, fp] + [C.c_uint] * 5
+        L.lfbm5d_photo_apply_host_sai.argtypes = [vp, vp, up, dp, C.c_uint, vp] + [C.c_uint] * 5
     L.lfbm5d_malloc.argtypes = [C.POINTER(vp), C.c_size_t]
     L.lfbm5d_free.argtypes = [vp]
     L.lfbm5d_memcpy_h2d.argtypes = [vp, vp, C.c_size_t]
@@ -739,6 +795,63 @@ def consist_params(max_disparity=None, box_radius=None, ang_radius=None, min_sou
         if v is not None:
             setattr(P, name, float(v))
     return P
+
+
+def photo_params(max_disparity=None, box_radius=None, ang_radius=None, steps=None, min_sources=None, max_rounds=None, per_channel=None,
+                 anchor=None, min_count=None, tol=None, lo=None, hi=None):
+    """lfbm5d_photo_params from the defaults of the library (lfbm5d_photo_defaults, host only); None keeps a default (anchor: none)."""
+    P = PhotoParamsStruct()
+    lib().lfbm5d_photo_defaults(C.byref(P))
+    for name, v in (("max_disparity", max_disparity), ("box_radius", box_radius), ("ang_radius", ang_radius), ("steps", steps),
+                    ("min_sources", min_sources), ("max_rounds", max_rounds), ("per_channel", per_channel), ("anchor", anchor),
+                    ("min_count", min_count)):
+        if v is not None:
+            setattr(P, name, int(v))
+    for name, v in (("tol", tol), ("lo", lo), ("hi", hi)):
+        if v is not None:
+            setattr(P, name, float(v))
+    return P
+
+
+def photo_edges():
+    """lfbm5d_photo_edges (host only): the 1025 edges of the ratio keys, float32, 256 per octave over 1/4..4."""
+    e = np.zeros(PHOTO_EDGES, np.float32)
+    lib().lfbm5d_photo_edges(e.ctypes.data_as(C.POINTER(C.c_float)))
+    return e
+
+
+def photo_ratio(hist, min_count=1):
+    """lfbm5d_photo_ratio (host only, no GPU): (r, fitted) of one ratio histogram hist uint64 [1026]: the median ratio interpolated
+    inside its key; (1.0, False) when the histogram holds fewer than min_count values or its median lies in an end key."""
+    h = np.ascontiguousarray(np.asarray(hist, np.uint64).reshape(-1))
+    if h.size != PHOTO_KEYS:
+        raise LfBm5dError("lfbm5d_photo_ratio: hist must be [1026]")
+    r = C.c_double(0.0)
+    rc = lib().lfbm5d_photo_ratio(h.ctypes.data_as(C.POINTER(C.c_ulonglong)), int(min_count), C.byref(r))
+    return r.value, rc == 0
+
+
+def photo_solve(r, neighbours, fitted, anchor=None):
+    """lfbm5d_photo_solve (host only, no GPU): the gains g float64 [asize] from the ratios r [asize], neighbours[m] the source SAIs of
+    m in order (looked at for fitted m only), fitted [asize]; anchor: the SAI whose gain stays 1 (None: the lower median is 1)."""
+    r = np.ascontiguousarray(np.asarray(r, np.float64).reshape(-1))
+    A = r.size
+    fit = _u32(np.asarray(fitted).reshape(-1) != 0)
+    n_src, src = np.zeros(A, np.uint32), np.zeros((A, PHOTO_MAX_SOURCES), np.uint32)
+    for m in range(A):
+        if not fit[m]:
+            continue
+        q = [int(v) for v in neighbours[m]]
+        if not 1 <= len(q) <= PHOTO_MAX_SOURCES:
+            raise LfBm5dError("lfbm5d_photo_solve: a fitted SAI needs 1..24 sources")
+        n_src[m] = len(q)
+        src[m, :len(q)] = q
+    g = np.zeros(A, np.float64)
+    up, dp = C.POINTER(C.c_uint), C.POINTER(C.c_double)
+    if lib().lfbm5d_photo_solve(A, r.ctypes.data_as(dp), n_src.ctypes.data_as(up), src.ctypes.data_as(up), fit.ctypes.data_as(up),
+                                PHOTO_NO_ANCHOR if anchor is None else int(anchor), g.ctypes.data_as(dp)) != 0:
+        raise LfBm5dError("lfbm5d_photo_solve: fitted needs [asize] entries, every source and the anchor an index below asize")
+    return g
 
 
 def sr_defaults(scale, /, **changes):
@@ -1540,6 +1653,60 @@ class Context:
                        tuple(int(i) for i in np.nonzero(st == CONSIST_BAD)[0]), tuple(int(i) for i in np.nonzero(st == CONSIST_UNTESTED)[0]),
                        int(res.rounds), int(res.pixels), int(res.skipped))
 
+    # ---- photometric equalisation ----
+    def equalise(self, noisy, mask, ang_major, awidth, aheight, width, height, chnls, return_hist=False, out=None, **params):
+        """Photometric equalisation (lfbm5d_photo_*, include/lfbm5d_photo.h): every SAI with enough neighbours is predicted from them
+        by the view synthesis' plane sweep with the SAI itself left out, the median ratio of its values to the prediction gives one
+        gain per SAI and stored channel, and the gains are divided out; sweep, fit and correction repeat until the ratios are within
+        tol of 1.  noisy: a CUDA float32 tensor [asize][C*H*W] (device form), or a float32 numpy array of that shape or a list of
+        per-SAI arrays (host form, staged through HBM; identical results).  The input is only read.  params: the fields of
+        photo_params.  Returns an Equalise."""
+        m = _u32(mask)
+        asize, C_, W_, H_ = m.size, int(chnls), int(width), int(height)
+        P = photo_params(**params)
+        res = PhotoResultStruct()
+        up = C.POINTER(C.c_uint)
+        gain, state = np.ones((asize, 3), np.float64), np.zeros(asize, np.uint32)
+        hist = np.zeros((asize, max(C_, 1), PHOTO_KEYS), np.uint64) if return_hist else None
+        tail = (gain.ctypes.data_as(C.POINTER(C.c_double)), state.ctypes.data_as(up),
+                None if hist is None else hist.ctypes.data_as(C.POINTER(C.c_ulonglong)), ang_major, awidth, aheight, W_, H_, C_, C.byref(res))
+        if isinstance(noisy, (list, tuple, np.ndarray)):
+            arrays = self._host_sais(noisy)
+            o, olist = self._host_out(arrays, out)
+            self._ck(self._L.lfbm5d_photo_host_sai(self._h, C.byref(P), _sai_ptrs(arrays, m), m.ctypes.data_as(up), _sai_ptrs(olist, m), *tail))
+            o = self._stacked(noisy, o)
+        else:
+            o = self._dev_out(noisy, out, m)
+            self._ck(self._L.lfbm5d_photo_device(self._h, C.byref(P), _dev_ptr(noisy), m.ctypes.data_as(up), _dev_ptr(o), *tail))
+        return Equalise(o, gain, state.astype(np.int64), hist, int(res.rounds), bool(res.converged), float(res.residual),
+                        float(res.gain_min), float(res.gain_max), int(res.fitted), int(res.untested), int(res.unfit), int(res.admitted),
+                        int(res.skipped_nonfinite), int(res.skipped_range))
+
+    def apply_gains(self, lf, gain, invert=False, *, chnls, mask=None, out=None):
+        """lfbm5d_photo_apply_*: out = lf (float)(invert ? G : 1 / G) per SAI and stored channel, G = gain float64 [asize][3] (an
+        Equalise's .gain).  lf as for equalise, [asize][chnls*H*W].  out: where to write (device form: may be lf itself, the default is
+        a fresh tensor; host form: a list of per-SAI arrays, the default is fresh arrays).  invert=True after denoising gives every
+        view its own photometry back."""
+        g = np.ascontiguousarray(np.asarray(gain, np.float64).reshape(-1, 3))
+        asize, C_ = g.shape[0], int(chnls)
+        m = np.ones(asize, np.uint32) if mask is None else _u32(mask)
+        host = isinstance(lf, (list, tuple, np.ndarray))
+        arrays = self._host_sais(lf) if host else None
+        img = next((int(np.size(a)) for a in arrays if a is not None), 0) if host else int(lf.shape[1])
+        if len(arrays if host else lf) != asize or C_ < 1 or img % C_:
+            raise LfBm5dError("apply_gains: lf must be [asize][chnls*H*W] and gain [asize][3]")
+        up, dp = C.POINTER(C.c_uint), C.POINTER(C.c_double)
+        tail = (asize, 1, img // C_, 1, C_)          # only the products awidth x aheight and W x H matter
+        if host:
+            o, olist = self._host_out(arrays, out)
+            self._ck(self._L.lfbm5d_photo_apply_host_sai(self._h, _sai_ptrs(arrays, m), m.ctypes.data_as(up), g.ctypes.data_as(dp),
+                                                         int(bool(invert)), _sai_ptrs(olist, m), *tail))
+            return self._stacked(lf, o)
+        o = self._dev_out(lf, out)
+        self._ck(self._L.lfbm5d_photo_apply_device(self._h, _dev_ptr(lf), m.ctypes.data_as(up), g.ctypes.data_as(dp), int(bool(invert)),
+                                                   _dev_ptr(o), *tail))
+        return o
+
     # ---- super-resolution ----
     def _sr_tail(self, mask, w, h, Cc):
         m = _u32(mask)
@@ -1719,6 +1886,11 @@ def consist(noisy, mask, ang_major, awidth, aheight, width, height, chnls, ctx=N
     return (ctx or _ctx()).consist(noisy, mask, ang_major, awidth, aheight, width, height, chnls, **more)
 
 
+def equalise(noisy, mask, ang_major, awidth, aheight, width, height, chnls, return_hist=False, ctx=None, **params):
+    """Context.equalise on the default context (device 0): per-view gains estimated from the other views and divided out."""
+    return (ctx or _ctx()).equalise(noisy, mask, ang_major, awidth, aheight, width, height, chnls, return_hist=return_hist, **params)
+
+
 def denoise_pg(model, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls, ctx=None):
     """Context.denoise_pg on the default context (device 0); returns the model that was used."""
     return (ctx or _ctx()).denoise_pg(model, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls)
@@ -1886,3 +2058,24 @@ def consist_probe(noisy, mask, awidth, aheight, width, height, chnls, exclude=No
     if rc != 0:
         raise LfBm5dError("consist_LF failed (message on stdout)")
     return (flags, state.astype(np.int64)) + tuple(int(v) for v in counts) + (tuple(scales),)
+
+
+def equalise_probe(noisy, mask, awidth, aheight, width, height, chnls, max_disparity=-1, box_radius=-1, ang_radius=-1, min_sources=-1,
+                   max_rounds=-1, per_channel=-1, anchor=-1, tol=-1.0, lo=-1.0, hi=-1.0, ang_major=ROWMAJOR, disparity_steps=1, restore=False):
+    """The C++ drop-in's equalise_LF (liblfbm5d_dropin.so, run_bm5d.h) on a vector<vector<float>> light field built from `noisy`
+    [asize][chnls*height*width]; restore: apply_gains_LF(invert) on its output afterwards.  Negative parameters keep the library's
+    defaults.  Returns (out float32 like noisy, planes of empty SAIs zero; gain float64 [asize][3]; state; fitted, untested, unfit,
+    rounds; residual, gain_min, gain_max)."""
+    D = C.CDLL(os.path.join(_HERE, "liblfbm5d_dropin.so"))
+    D.lfbm5d_equalise_probe.argtypes = [C.c_void_p] * 3 + [C.c_uint] * 6 + [C.c_void_p] * 6 + [C.c_int]
+    x = np.ascontiguousarray(noisy, np.float32)
+    m = _u32(mask)
+    out = np.zeros_like(x)
+    gain, state = np.zeros((m.size, 3), np.float64), np.zeros(m.size, np.uint32)
+    ppi = np.array([max_disparity, box_radius, ang_radius, min_sources, max_rounds, per_channel, anchor, disparity_steps], np.int32)
+    ppd = np.array([tol, lo, hi], np.float64)
+    counts, figures = np.zeros(4, np.uint32), np.zeros(3, np.float64)
+    if D.lfbm5d_equalise_probe(x.ctypes.data, m.ctypes.data, out.ctypes.data, ang_major, awidth, aheight, width, height, chnls, ppi.ctypes.data,
+                               ppd.ctypes.data, gain.ctypes.data, state.ctypes.data, counts.ctypes.data, figures.ctypes.data, int(bool(restore))) != 0:
+        raise LfBm5dError("equalise_LF failed (message on stdout)")
+    return (out, gain, state.astype(np.int64), *(int(v) for v in counts), *(float(v) for v in figures))

@@ -83,6 +83,7 @@ void lfbm5d_destroy(lfbm5d_ctx* c) {
     c->inp.stats.release(); c->inp.state[0].release(); c->inp.state[1].release(); c->inp.flags.release();
     c->view.table.release(); c->view.stats.release(); c->view.disp.release(); c->view.set.release();
     c->consist.table.release(); c->consist.stats.release(); c->consist.pred.release(); c->consist.disp.release(); c->consist.flags.release();
+    c->photo.table.release(); c->photo.sweep_table.release(); c->photo.stats.release(); c->photo.pred.release(); c->photo.disp.release(); c->photo.x.release();
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     if (c->h_small) (void)hipHostFree(c->h_small);
     if (c->stream) (void)hipStreamDestroy(c->stream);

@@ -80,6 +80,16 @@
  *                     other value.  With a ground truth LFBM5D_CLIP_ADD=1 first rounds the synthesised noisy light field to whole
  *                     numbers and clips it to the range (0..255 without LFBM5D_CLIP: the filter then runs on clipped data as it
  *                     would on a file's), before LFBM5D_IMPULSE_ADD.  Unset, the output is unchanged;
+ *   LFBM5D_EQUALISE=auto | flat   photometric equalisation (equalise_LF, run_bm5d.h; include/lfbm5d_photo.h) of the noisy light field once
+ *                     it exists, ahead of LFBM5D_DETECT and every later stage: one gain per SAI and stored channel is estimated from
+ *                     what the neighbouring views predict and divided out, so that vignetted or differently exposed views meet the
+ *                     filter's brightness-constancy assumption.  Prints `Photometric equalisation: <f> of <A> SAIs fitted, <u> untested,
+ *                     <n> unfit; gains <min>..<max>; <rounds> sweeps, residual <r>`.  `auto` multiplies the gains back into the basic
+ *                     and the denoised light field before PSNR, SSIM and saving (the files keep every view's own photometry); `flat`
+ *                     leaves them equalised.  LFBM5D_DISPARITY_STEPS applies to its sweep.  With LFBM5D_SIGMA=poisson or LFBM5D_CLIP
+ *                     it is an error (a gain changes the noise model and the clipping range), and so is any other value.  With a
+ *                     ground truth LFBM5D_EQUALISE_ADD=<edge> (0 < edge <= 1) first multiplies the synthesised noisy views by a smooth
+ *                     vignette, 1 at the centre view and <edge> at the corner views.  Unset, the output is unchanged;
  *   LFBM5D_REPORT_SSIM=1  the average SSIM next to every average PSNR on stdout and an SSIM block behind every PSNR block of the
  *                     results file, computed on the GPU on the images as the files hold them (cli_quality.h); any other value is an
  *                     error; unset, the output is unchanged.
@@ -598,6 +608,75 @@ bool synthesise_missing_LF(vector<vector<float> >& LF_noisy, const vector<unsign
     return true;
 }
 
+/* LFBM5D_EQUALISE / LFBM5D_EQUALISE_ADD: mode 0 when unset, 1 = auto, 2 = flat; add = 0 when unset; false (message printed) on a malformed
+ * value, together with LFBM5D_SIGMA=poisson (smode >= 2) or LFBM5D_CLIP, or LFBM5D_EQUALISE_ADD without a ground truth.  Ahead of
+ * disparity_steps_mode(), which counts its sweep. */
+bool equalise_mode(int& mode, double& add, int smode, bool gt) {
+    mode = 0; add = 0.0;
+    if (const char* e = env("LFBM5D_EQUALISE")) {
+        mode = !strcmp(e, "auto") ? 1 : !strcmp(e, "flat") ? 2 : 0;
+        if (!mode) {
+            cout << "LFBM5D_EQUALISE must be \"auto\" (equalise the views, give the results their own photometry back) or \"flat\" (leave the "
+                    "results equalised), or unset; got \"" << e << "\"" << endl;
+            return false;
+        }
+        if (smode >= 2) {
+            cout << "LFBM5D_EQUALISE cannot be combined with LFBM5D_SIGMA=poisson (a gain changes the noise model)" << endl;
+            return false;
+        }
+        if (env("LFBM5D_CLIP")) {
+            cout << "LFBM5D_EQUALISE cannot be combined with LFBM5D_CLIP (a gain changes the clipping range)" << endl;
+            return false;
+        }
+    }
+    if (const char* e = env("LFBM5D_EQUALISE_ADD")) {
+        char* q = nullptr;
+        add = strtod(e, &q);
+        if (q == e || *q || isspace((unsigned char)*e) || !(add > 0.0) || !(add <= 1.0)) {
+            cout << "LFBM5D_EQUALISE_ADD must be the gain of the corner views, 0 < edge <= 1, or unset; got \"" << e << "\"" << endl;
+            return false;
+        }
+        if (!gt) { cout << "LFBM5D_EQUALISE_ADD needs a source light field to synthesise the noisy one from" << endl; return false; }
+    }
+    return true;
+}
+
+/* LFBM5D_EQUALISE_ADD: view (s, t) times 1 - (1 - edge) rho^2, rho its angular distance from the centre, 1 at the corners */
+void add_vignette_LF(vector<vector<float> >& LF_noisy, const vector<unsigned>& mask, unsigned ang_major, unsigned aw, unsigned ah, double edge) {
+    const double cs = (ah - 1) / 2.0, ct = (aw - 1) / 2.0, corner = cs * cs + ct * ct;
+    for (unsigned s = 0; s < ah; s++)
+        for (unsigned t = 0; t < aw; t++) {
+            const unsigned st = ang_major == LFBM5D_ROWMAJOR ? s * aw + t : s + t * ah;
+            if (!mask[st]) continue;
+            const double rho2 = corner > 0.0 ? ((s - cs) * (s - cs) + (t - ct) * (t - ct)) / corner : 0.0;
+            const float g = (float)(1.0 - (1.0 - edge) * rho2);
+            for (float& v : LF_noisy[st]) v = v * g;
+        }
+    cout << "Vignette [corner views x " << edge << "]" << endl;
+}
+
+/* LFBM5D_EQUALISE: the noisy light field equalised in place; `gains` for restore_LF */
+bool equalise_noisy_LF(vector<vector<float> >& LF_noisy, const vector<unsigned>& mask, unsigned ang_major, unsigned aw, unsigned ah, unsigned W,
+                       unsigned H, unsigned C, unsigned dsteps, vector<double>& gains) {
+    vector<unsigned> state;
+    unsigned fitted = 0, untested = 0, unfit = 0, rounds = 0, sais = 0;
+    double residual = 0.0, gmin = 1.0, gmax = 1.0;
+    if (equalise_LF(LF_noisy, mask, LF_noisy, ang_major, aw, ah, W, H, C, -1, -1, -1, -1, -1, -1, -1, -1.0, -1.0, -1.0, gains, state, fitted, untested,
+                    unfit, rounds, residual, gmin, gmax, dsteps) != EXIT_SUCCESS) return false;
+    for (size_t st = 0; st < mask.size(); st++) sais += mask[st] != 0;
+    cout << endl << "Photometric equalisation: " << fitted << " of " << sais << " SAIs fitted, " << untested << " untested, " << unfit << " unfit; gains "
+         << gmin << ".." << gmax << "; " << rounds << " sweeps, residual " << residual;
+    if (dsteps > 1) cout << ", " << dsteps << " steps per pixel";
+    cout << endl;
+    return true;
+}
+
+/* LFBM5D_EQUALISE=auto: a result of the filter gets every view's own photometry back */
+bool restore_LF(vector<vector<float> >& LF_out, const vector<unsigned>& mask, const vector<double>& gains, unsigned aw, unsigned ah, unsigned W,
+                unsigned H, unsigned C) {
+    return apply_gains_LF(LF_out, mask, gains, true, aw, ah, W, H, C) == EXIT_SUCCESS;
+}
+
 /* LFBM5D_DETECT / LFBM5D_DETECT_SAVE: on = false when unset; k < 0 = the library's factor; false (message printed) on a malformed value,
  * LFBM5D_DETECT_SAVE without LFBM5D_DETECT, or together with LFBM5D_DEFECTS / LFBM5D_MISSING */
 bool detect_mode(bool& on, double& k, const char*& save) {
@@ -796,8 +875,11 @@ int main(int argc, char** argv) {
     if (!missing_mode(missing, miss_iter, ang_major, aw, ah, s0, t0)) return EXIT_FAILURE;
     bool detect = false; double det_k = -1.0; const char* det_save = nullptr;
     if (!detect_mode(detect, det_k, det_save)) return EXIT_FAILURE;
+    int eq_mode = 0; double eq_add = 0.0;
+    if (!equalise_mode(eq_mode, eq_add, smode, gt)) return EXIT_FAILURE;
+    vector<double> eq_gains;
     unsigned dsteps = 1;
-    if (!disparity_steps_mode(dsteps, detect || !missing.empty())) return EXIT_FAILURE;
+    if (!disparity_steps_mode(dsteps, detect || !missing.empty() || eq_mode)) return EXIT_FAILURE;
     float occl = 0.0f;
     if (!occlusion_mode(occl, detect || !missing.empty())) return EXIT_FAILURE;
     bool clip_on = false, clip_add = false; double clip_lo = 0.0, clip_hi = 255.0;
@@ -817,6 +899,7 @@ int main(int argc, char** argv) {
         t = now_s();
         add_noise_LF(LF, mask, LF_noisy, sigma, smode == 3 ? pg : nullptr);
         cout << "done in " << now_s() - t << "s." << endl;
+        if (eq_add > 0.0) add_vignette_LF(LF_noisy, mask, ang_major, aw, ah, eq_add);
         if (clip_add) clip_round_LF(LF_noisy, mask, clip_lo, clip_hi);
         if (imp_add > 0.0) add_impulses_LF(LF_noisy, mask, imp_add);
         for (size_t st = 0; st < missing.size(); st++) if (missing[st]) LF_noisy[st].assign(LF_noisy[st].size(), 0.0f);   /* dropped */
@@ -826,6 +909,7 @@ int main(int argc, char** argv) {
         if (load_LF(d_noisy, name, sep, LF_noisy, mask, ang_major, aw, ah, s0, t0, W, H, C, missing.empty() ? nullptr : &missing) != EXIT_SUCCESS)
             return EXIT_FAILURE;
     }
+    if (eq_mode && !equalise_noisy_LF(LF_noisy, mask, ang_major, aw, ah, W, H, C, dsteps, eq_gains)) return EXIT_FAILURE;
     vector<vector<unsigned char> > detected;
     if (detect && !detect_LF(LF_noisy, mask, det_k, det_save, name, sep, ang_major, aw, ah, s0, t0, W, H, C, missing, detected, dsteps)) return EXIT_FAILURE;
     vector<unsigned> est_mask = mask;   /* the sigma estimate does not look at reconstructed SAIs */
@@ -878,6 +962,7 @@ int main(int argc, char** argv) {
             return EXIT_FAILURE;
         print_declipping(clip_lo, clip_hi, sigma);
     }
+    if (eq_mode == 1 && !(restore_LF(LF_basic, mask, eq_gains, aw, ah, W, H, C) && restore_LF(LF_den, mask, eq_gains, aw, ah, W, H, C))) return EXIT_FAILURE;
     const double secs = now_s() - tb;
     if (gt) {
         psnr_LF(LF, LF_basic, mask, ps, ap_b.psnr, sp, rm, ar, sr);
@@ -957,8 +1042,11 @@ int main(int argc, char** argv) {
     if (!missing_mode(missing, miss_iter, ang_major, aw, ah, s0, t0)) return EXIT_FAILURE;
     bool detect = false; double det_k = -1.0; const char* det_save = nullptr;
     if (!detect_mode(detect, det_k, det_save)) return EXIT_FAILURE;
+    int eq_mode = 0; double eq_add = 0.0;
+    if (!equalise_mode(eq_mode, eq_add, smode, gt)) return EXIT_FAILURE;
+    vector<double> eq_gains;
     unsigned dsteps = 1;
-    if (!disparity_steps_mode(dsteps, detect || !missing.empty())) return EXIT_FAILURE;
+    if (!disparity_steps_mode(dsteps, detect || !missing.empty() || eq_mode)) return EXIT_FAILURE;
     float occl = 0.0f;
     if (!occlusion_mode(occl, detect || !missing.empty())) return EXIT_FAILURE;
     bool clip_on = false, clip_add = false; double clip_lo = 0.0, clip_hi = 255.0;
@@ -978,6 +1066,7 @@ int main(int argc, char** argv) {
         t = now_s();
         add_noise_LF(LF, mask, LF_noisy, sigma, smode == 3 ? pg : nullptr);
         cout << "done in " << now_s() - t << "s." << endl;
+        if (eq_add > 0.0) add_vignette_LF(LF_noisy, mask, ang_major, aw, ah, eq_add);
         if (clip_add) clip_round_LF(LF_noisy, mask, clip_lo, clip_hi);
         if (imp_add > 0.0) add_impulses_LF(LF_noisy, mask, imp_add);
         for (size_t st = 0; st < missing.size(); st++) if (missing[st]) LF_noisy[st].assign(LF_noisy[st].size(), 0.0f);   /* dropped */
@@ -987,6 +1076,7 @@ int main(int argc, char** argv) {
         if (load_LF(d_noisy, name, sep, LF_noisy, mask, ang_major, aw, ah, s0, t0, W, H, C, missing.empty() ? nullptr : &missing) != EXIT_SUCCESS)
             return EXIT_FAILURE;
     }
+    if (eq_mode && !equalise_noisy_LF(LF_noisy, mask, ang_major, aw, ah, W, H, C, dsteps, eq_gains)) return EXIT_FAILURE;
     vector<vector<unsigned char> > defects;
     const unsigned def_hard[9] = {N[0], nSim[0], nDisp[0], k[0], p[0], sd[0], (unsigned)t2[0], (unsigned)t4[0], (unsigned)t5[0]};
     unsigned def_steps = 0;
@@ -1065,6 +1155,12 @@ int main(int argc, char** argv) {
     const double step1 = one_job ? job : now_s() - t1;
     if (one_job) cout << endl << "Steps 1 and 2 done in " << job << " secs." << endl << endl;
     else cout << endl << "Step 1 done in " << step1 << " secs." << endl << endl;
+    vector<vector<float> > LF_basic_eq;   /* LFBM5D_EQUALISE=auto: step 2 reads the equalised basic estimate, the file gets the restored one */
+    if (eq_mode == 1) {
+        LF_basic_eq = LF_basic;
+        if (!restore_LF(LF_basic, mask, eq_gains, aw, ah, W, H, C)) return EXIT_FAILURE;
+        if (one_job && !restore_LF(LF_den, mask, eq_gains, aw, ah, W, H, C)) return EXIT_FAILURE;
+    }
     if (gt) {
         psnr_LF(LF, LF_basic, mask, ps, ap_b.psnr, sp, rm, ar, sr);
         if (qmode && !cli_quality::compute(LF, LF_basic, mask, W, H, C, ap_b, qb)) return EXIT_FAILURE;
@@ -1077,10 +1173,12 @@ int main(int argc, char** argv) {
     if (save_LF(d_basic, name, sep, LF_basic, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
     if (!one_job) cout << endl << endl << "Step 2 running..." << endl;
     t1 = now_s();
+    if (eq_mode == 1 && !one_job) LF_basic.swap(LF_basic_eq);
     if (!one_job && run_bm5d_2nd_step(sigma, LF_noisy, mask, LF_basic, LF_den, ang_major, aw, ah, anW, W, H, C, N[1], nSim[1], nDisp[1], k[1], p[1],
                           sd[1] != 0, t2[1], t4[1], t5[1], cs, nb_threads) != EXIT_SUCCESS) return EXIT_FAILURE;
     const double step2 = one_job ? 0.0 : now_s() - t1;
     if (!one_job) cout << endl << "Step 2 done in " << step2 << " secs." << endl << endl;
+    if (eq_mode == 1 && !one_job && !restore_LF(LF_den, mask, eq_gains, aw, ah, W, H, C)) return EXIT_FAILURE;
     if (gt) {
         psnr_LF(LF, LF_den, mask, ps, ap_d.psnr, sp, rm, ar, sr);
         if (qmode && !cli_quality::compute(LF, LF_den, mask, W, H, C, ap_d, qb)) return EXIT_FAILURE;

@@ -7,7 +7,7 @@
  *                      streamed host seam
  *   lfbm5d_steps.hip   run_bm5d_1st_step / run_bm5d_2nd_step / both as one job on device buffers: schedule forms, tile mode
  *   lfbm5d_api.hip     the C-ABI of include/lfbm5d.h: context, options, communicators, host entry points, BM3D, inspection
- *   lfbm5d_side.h      the host frame of the side stages (lfbm5d_noise / quality / resample / pg / impulse / inpaint / view / consist.hip):
+ *   lfbm5d_side.h      the host frame of the side stages (lfbm5d_noise / quality / resample / pg / impulse / inpaint / view / consist / photo.hip):
  *                      SAI list, argument checks, staging of per-SAI host planes, the refinement loop, the sweep's source rows
  *   lfbm5d_side_values.h   what those stages share per value, host-and-device and free of HIP headers: tile, mirror, bit tests, key
  *                      layout, thresholds, the loop's sigma schedule
@@ -173,6 +173,10 @@ struct lfbm5d_ctx {
     /* consistency check (lfbm5d_consist.hip): the leave-one-out source lists, histograms and counters, the prediction light field, the
      * sweep's disparity planes, the host form's flag and disparity planes */
     struct ConsistBufs { DevBuf table, stats, pred, disp, flags; } consist;
+    /* photometric equalisation (lfbm5d_photo.hip): the apply kernel's planes and factors (and the host vectors they are copied from),
+     * the leave-one-out source lists, histograms and counters, the prediction light field, the sweep's disparity planes, the host
+     * form's output light field */
+    struct PhotoBufs { DevBuf table, sweep_table, stats, pred, disp, x; std::vector<unsigned> planes_host; std::vector<float> factors_host; } photo;
     /* window lanes (run_graph; the per-SAI BM3D steps): extra contexts on the same device, each with its own stream, window
      * buffers and per-pass work buffers; owned by this context */
     std::vector<lfbm5d_ctx*> lanes;

@@ -803,6 +803,112 @@ extern "C" int lfbm5d_consist_steps_probe(const float* in_flat, const unsigned* 
                          disparity_steps);
 }
 
+/* photometric equalisation on the caller's vectors (one pointer per SAI; the library stages in and out) */
+int equalise_LF(const std::vector<std::vector<float> >& LF, const std::vector<unsigned>& LF_SAI_mask, std::vector<std::vector<float> >& LF_out,
+                const unsigned ang_major, const unsigned awidth, const unsigned aheight, const unsigned width, const unsigned height,
+                const unsigned chnls, const int maxDisparity, const int boxRadius, const int angRadius, const int minSources, const int maxRounds,
+                const int perChannel, const int anchor, const double tol, const double lo, const double hi, std::vector<double>& gains,
+                std::vector<unsigned>& state, unsigned& fitted, unsigned& untested, unsigned& unfit, unsigned& rounds, double& residual,
+                double& gainMin, double& gainMax, const unsigned disparity_steps) {
+    const unsigned asize = awidth * aheight;
+    lfbm5d_photo_result result;
+    std::memset(&result, 0, sizeof(result));
+    fitted = untested = unfit = rounds = 0;
+    residual = 0.0; gainMin = gainMax = 1.0;
+    if (LF.size() != asize || LF_SAI_mask.size() != asize) {
+        std::cout << "equalise_LF: light field and mask must hold awidth*aheight SAIs" << std::endl;
+        return EXIT_FAILURE;
+    }
+    lfbm5d_photo_params pp;
+    lfbm5d_photo_defaults(&pp);
+    if (maxDisparity >= 0) pp.max_disparity = (unsigned)maxDisparity;
+    if (boxRadius >= 0) pp.box_radius = (unsigned)boxRadius;
+    if (angRadius >= 0) pp.ang_radius = (unsigned)angRadius;
+    if (minSources >= 0) pp.min_sources = (unsigned)minSources;
+    if (maxRounds >= 0) pp.max_rounds = (unsigned)maxRounds;
+    if (perChannel >= 0) pp.per_channel = (unsigned)perChannel;
+    if (anchor >= 0) pp.anchor = (unsigned)anchor;
+    if (tol >= 0.0) pp.tol = tol;
+    if (lo >= 0.0) pp.lo = lo;
+    if (hi >= 0.0) pp.hi = hi;
+    pp.steps = disparity_steps;
+    lfbm5d_ctx* ctx = context();
+    if (!ctx) return EXIT_FAILURE;
+    const size_t img = (size_t)width * height * chnls;
+    for (size_t st = 0; st < asize; st++)
+        if (LF_SAI_mask[st] && LF[st].size() != img) {
+            std::cout << "equalise_LF: a non-empty SAI does not hold width*height*chnls values" << std::endl;
+            return EXIT_FAILURE;
+        }
+    if (&LF_out != &LF) LF_out = LF;
+    std::vector<const float*> p(asize, nullptr);
+    std::vector<float*> o(asize, nullptr);
+    for (size_t st = 0; st < asize; st++)
+        if (LF_SAI_mask[st]) { p[st] = LF[st].data(); o[st] = LF_out[st].data(); }
+    gains.assign((size_t)asize * 3, 1.0);
+    state.assign(asize, 0u);
+    if (lfbm5d_photo_host_sai(ctx, &pp, p.data(), LF_SAI_mask.data(), o.data(), gains.data(), state.data(), nullptr, ang_major, awidth, aheight,
+                              width, height, chnls, &result) != 0) {
+        std::cout << "LFBM5D GPU backend: " << lfbm5d_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+    }
+    fitted = result.fitted; untested = result.untested; unfit = result.unfit; rounds = result.rounds;
+    residual = result.residual; gainMin = result.gain_min; gainMax = result.gain_max;
+    return EXIT_SUCCESS;
+}
+
+int apply_gains_LF(std::vector<std::vector<float> >& LF, const std::vector<unsigned>& LF_SAI_mask, const std::vector<double>& gains,
+                   const bool invert, const unsigned awidth, const unsigned aheight, const unsigned width, const unsigned height,
+                   const unsigned chnls) {
+    const unsigned asize = awidth * aheight;
+    const size_t img = (size_t)width * height * chnls;
+    if (LF.size() != asize || LF_SAI_mask.size() != asize || gains.size() != (size_t)asize * 3) {
+        std::cout << "apply_gains_LF: light field and mask must hold awidth*aheight SAIs, gains 3 values per SAI" << std::endl;
+        return EXIT_FAILURE;
+    }
+    std::vector<float*> p(asize, nullptr);
+    for (size_t st = 0; st < asize; st++)
+        if (LF_SAI_mask[st]) {
+            if (LF[st].size() != img) {
+                std::cout << "apply_gains_LF: a non-empty SAI does not hold width*height*chnls values" << std::endl;
+                return EXIT_FAILURE;
+            }
+            p[st] = LF[st].data();
+        }
+    lfbm5d_ctx* ctx = context();
+    if (!ctx) return EXIT_FAILURE;
+    if (lfbm5d_photo_apply_host_sai(ctx, p.data(), LF_SAI_mask.data(), gains.data(), invert ? 1u : 0u, p.data(), awidth, aheight, width, height,
+                                    chnls) != 0) {
+        std::cout << "LFBM5D GPU backend: " << lfbm5d_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+    }
+    return EXIT_SUCCESS;
+}
+
+/* Test hook: equalise_LF, then (apply = 1) apply_gains_LF with invert on its output, on a vector<vector<float>> light field built from a
+ * flat copy [asize][chnls*height*width]; the result goes to out_flat (planes of empty SAIs untouched).  ppi = {maxDisparity, boxRadius,
+ * angRadius, minSources, maxRounds, perChannel, anchor, disparity_steps}, ppd = {tol, lo, hi}; gains [asize][3], state [asize],
+ * counts = {fitted, untested, unfit, rounds}, figures = {residual, gainMin, gainMax}. */
+extern "C" int lfbm5d_equalise_probe(const float* in_flat, const unsigned* mask, float* out_flat, unsigned ang_major, unsigned awidth,
+                                     unsigned aheight, unsigned width, unsigned height, unsigned chnls, const int* ppi, const double* ppd,
+                                     double* gains_out, unsigned* state_out, unsigned* counts, double* figures, int apply) {
+    const size_t asize = (size_t)awidth * aheight, img = (size_t)width * height * chnls;
+    std::vector<unsigned> m(mask, mask + asize), state;
+    std::vector<std::vector<float> > LF(asize), out;
+    for (size_t st = 0; st < asize; st++) if (m[st]) LF[st].assign(in_flat + st * img, in_flat + (st + 1) * img);
+    std::vector<double> gains;
+    if (equalise_LF(LF, m, out, ang_major, awidth, aheight, width, height, chnls, ppi[0], ppi[1], ppi[2], ppi[3], ppi[4], ppi[5], ppi[6], ppd[0],
+                    ppd[1], ppd[2], gains, state, counts[0], counts[1], counts[2], counts[3], figures[0], figures[1], figures[2],
+                    (unsigned)ppi[7]) != EXIT_SUCCESS) return 1;
+    if (apply && apply_gains_LF(out, m, gains, true, awidth, aheight, width, height, chnls) != EXIT_SUCCESS) return 1;
+    for (size_t st = 0; st < asize; st++) {
+        state_out[st] = state[st];
+        if (m[st]) std::memcpy(out_flat + st * img, out[st].data(), img * sizeof(float));
+    }
+    std::memcpy(gains_out, gains.data(), asize * 3 * sizeof(double));
+    return 0;
+}
+
 /* run_bm3d_LF (src/bm3d_LF.h:10-35, bm3d_LF.cpp:75-125): BM3D on every SAI of the mask */
 #include "run_bm3d_lf.h"
 int run_bm3d_LF(const float sigma, std::vector<std::vector<float> >& LF_noisy, std::vector<unsigned>& LF_SAI_mask,

@@ -401,6 +401,61 @@ int consist_LF(
 ,   const unsigned disparity_steps = 1
 );
 
+//! Photometric equalisation -- not in the reference: every SAI with enough neighbours is predicted on the GPU from them by the view
+//! synthesis' plane sweep with the SAI itself left out, the median ratio of its values to the prediction gives one gain per SAI and
+//! stored channel, and the gains are divided out (lfbm5d_photo_host_sai, include/lfbm5d_photo.h).  LF is only read; LF_out is resized
+//! to the light field's shape and holds the equalised non-empty SAIs (it may be LF itself).  maxDisparity, boxRadius, angRadius,
+//! minSources, maxRounds, perChannel < 0 and tol, lo, hi < 0: the library's defaults (lfbm5d_photo_defaults); anchor < 0: no anchor
+//! (the lower median of the gains is 1).  `gains` is resized to 3 doubles per SAI (1 for empty SAIs and channels that are not stored:
+//! hand them to apply_gains_LF with invert to restore every view's own photometry), `state` to one entry per SAI (0 empty, 1 fitted,
+//! 2 untested, 3 unfit in some channel).  disparity_steps = 1, 2 or 4 hypotheses per pixel in the sweep.  Returns EXIT_SUCCESS, or
+//! EXIT_FAILURE with the message on stdout.
+int equalise_LF(
+    const std::vector<std::vector<float> > &LF
+,   const std::vector<unsigned> &LF_SAI_mask
+,   std::vector<std::vector<float> > &LF_out
+,   const unsigned ang_major
+,   const unsigned awidth
+,   const unsigned aheight
+,   const unsigned width
+,   const unsigned height
+,   const unsigned chnls
+,   const int      maxDisparity
+,   const int      boxRadius
+,   const int      angRadius
+,   const int      minSources
+,   const int      maxRounds
+,   const int      perChannel
+,   const int      anchor
+,   const double   tol
+,   const double   lo
+,   const double   hi
+,   std::vector<double> &gains
+,   std::vector<unsigned> &state
+,   unsigned &fitted
+,   unsigned &untested
+,   unsigned &unfit
+,   unsigned &rounds
+,   double &residual
+,   double &gainMin
+,   double &gainMax
+,   const unsigned disparity_steps = 1
+);
+
+//! LF = LF x (float)(invert ? G : 1 / G) per non-empty SAI and stored channel, in place, on the GPU (lfbm5d_photo_apply_host_sai);
+//! `gains` holds 3 doubles per SAI, as equalise_LF returns them.  Returns EXIT_SUCCESS, or EXIT_FAILURE with the message on stdout.
+int apply_gains_LF(
+    std::vector<std::vector<float> > &LF
+,   const std::vector<unsigned> &LF_SAI_mask
+,   const std::vector<double> &gains
+,   const bool invert
+,   const unsigned awidth
+,   const unsigned aheight
+,   const unsigned width
+,   const unsigned height
+,   const unsigned chnls
+);
+
 //! Super-resolution -- not in the reference's master branch: the scheme of SR-LFBM5D (iterative back-projection regularised by the
 //! hard-thresholding step above) with the operators of include/lfbm5d.h, on the GPU (lfbm5d_superres_host_sai).  LF_low holds
 //! width x height SAIs and is only read; LF_high is (re)sized to scale*width x scale*height SAIs and filled.  kernel: 0 = bicubic,

@@ -195,3 +195,26 @@ def degrade_sai(lf, st, kind, seed=1):
     else:
         raise ValueError('degrade_sai: kind must be "dim", "noise" or "shift"')
     return out
+
+
+def vignette_gains(awidth, aheight, edge):
+    """The gains of a smooth vignette over the views: g(s, t) = 1 - (1 - edge) rho^2, rho the angular distance of view (s, t) from the
+    centre of the aheight x awidth array, normalised to 1 at the corners (so the corner views get `edge`; 3 x 3 at edge 0.6: corners
+    0.6, edge views 0.8, centre 1).  float64 [aheight * awidth], s along the first axis (row-major)."""
+    if not 0.0 < float(edge) <= 1.0:
+        raise ValueError("vignette_gains: edge must be in (0, 1]")
+    cs, ct = (aheight - 1) / 2.0, (awidth - 1) / 2.0
+    s, t = np.mgrid[0:aheight, 0:awidth]
+    corner = cs * cs + ct * ct
+    rho2 = ((s - cs) ** 2 + (t - ct) ** 2) / corner if corner else np.zeros((aheight, awidth))
+    return (1.0 - (1.0 - float(edge)) * rho2).reshape(-1)
+
+
+def apply_gains(lf, gains):
+    """A copy of the light field `lf` ([A][...]) with view m multiplied by gains[m] (gains [A]), or, with lf as [A][C][...] and gains
+    [A][C], channel c of view m by gains[m][c]: one float32 multiplication per value.  Returns float32."""
+    out = np.array(lf, dtype=np.float32, copy=True)
+    g = np.asarray(gains, np.float64).astype(np.float32)
+    if g.shape != out.shape[:g.ndim] or g.ndim not in (1, 2):
+        raise ValueError("apply_gains: gains must be [A] or [A][C] like the light field's first axes")
+    return out * g.reshape(g.shape + (1,) * (out.ndim - g.ndim))
