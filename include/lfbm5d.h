@@ -553,7 +553,7 @@ int lfbm5d_denoise_pg_host_sai(lfbm5d_ctx* ctx, const lfbm5d_pg_model* model, lf
  * p >= hi (compared as floats).
  * Limits: near the bounds the noise's standard deviation is smaller than sigma and the filter is not told (Foi 2009's variance-stabilised
  * form is not built); the inverse's slope reaches 2 at the bounds, so it doubles the residual error there; one sigma for all channels
- * and SAIs; Poisson-Gaussian noise combined with clipping is not covered; one GPU.
+ * and SAIs; Poisson-Gaussian noise combined with clipping is not covered here (lfbm5d_pgclip.h is the stage for it); one GPU.
  *
  * Statistics (GPU, integers: independent of any order, equal to tests/clip_model.py bit for bit).  s = (float)(255 / (hi - lo)); every
  * pixel becomes p' = (p - (float)lo) * s in float32 (no fused multiply-add; exact at 0..255: p' = p); m, d, the 64 levels and the 322
@@ -985,6 +985,8 @@ int lfbm5d_device_count(void);
 #include "lfbm5d_occl.h"
 /* ---- photometric equalisation: per-view gains estimated and divided out (lfbm5d_photo_*) ---- */
 #include "lfbm5d_photo.h"
+/* ---- clipped Poisson-Gaussian noise: censored fit, stabiliser and exact unbiased inverse (lfbm5d_pgclip_*) ---- */
+#include "lfbm5d_pgclip.h"
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,9 @@ from .core import (Context, Params, Bm3dParams, Stats, run_bm5d_1st_step, run_bm
                    ViewParamsStruct, ViewResultStruct, ViewOcclResultStruct, ViewSynth, view_params, view_synth, view_occl_default,
                    ConsistParamsStruct, ConsistResultStruct, Consist, consist_params, consist,
                    PhotoParamsStruct, PhotoResultStruct, Equalise, photo_params, photo_edges, photo_ratio, photo_solve, equalise,
-                   ClipEstimateStruct, ClipNoiseLevel, clip_fit, noise_level_clipped, denoise_clipped)
+                   ClipEstimateStruct, ClipNoiseLevel, clip_fit, noise_level_clipped, denoise_clipped,
+                   PgclipModelStruct, PgclipEstimateStruct, PgclipCurvesStruct, PgclipEstimate, PgclipCurves, pgclip_fit, pgclip_curves,
+                   pgclip_estimate, denoise_pgclip)
 
 __all__ = ["Context", "Params", "Bm3dParams", "Stats", "run_bm5d_1st_step", "run_bm5d_2nd_step", "run_bm3d_LF", "shard_rows",
            "YUV", "YCBCR", "OPP", "RGB", "ID", "DCT", "SADCT", "BIOR", "HADAMARD", "HAAR",
@@ -29,4 +31,6 @@ __all__ = ["Context", "Params", "Bm3dParams", "Stats", "run_bm5d_1st_step", "run
            "ViewParamsStruct", "ViewResultStruct", "ViewOcclResultStruct", "ViewSynth", "view_params", "view_synth", "view_occl_default",
            "ConsistParamsStruct", "ConsistResultStruct", "Consist", "consist_params", "consist",
            "PhotoParamsStruct", "PhotoResultStruct", "Equalise", "photo_params", "photo_edges", "photo_ratio", "photo_solve", "equalise",
-           "ClipEstimateStruct", "ClipNoiseLevel", "clip_fit", "noise_level_clipped", "denoise_clipped"]
+           "ClipEstimateStruct", "ClipNoiseLevel", "clip_fit", "noise_level_clipped", "denoise_clipped",
+           "PgclipModelStruct", "PgclipEstimateStruct", "PgclipCurvesStruct", "PgclipEstimate", "PgclipCurves", "pgclip_fit", "pgclip_curves",
+           "pgclip_estimate", "denoise_pgclip"]

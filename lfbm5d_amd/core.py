@@ -93,6 +93,27 @@ class ClipEstimateStruct(C.Structure):
                 ("blocks", C.c_ulonglong), ("skipped", C.c_ulonglong)]
 
 
+PGCLIP_KNOTS = 4097
+
+
+class PgclipModelStruct(C.Structure):
+    """lfbm5d_pgclip_model: sigma^2(y) = max(a (y - lo) + b, 1/12) on data clipped to lo..hi (include/lfbm5d_pgclip.h)."""
+    _fields_ = [("a", C.c_double), ("b", C.c_double), ("lo", C.c_double), ("hi", C.c_double)]
+
+
+class PgclipEstimateStruct(C.Structure):
+    """lfbm5d_pgclip_estimate: the censored fit of the clipped Poisson-Gaussian model (include/lfbm5d_pgclip.h)."""
+    _fields_ = [("model", PgclipModelStruct), ("a_channel", C.c_double * 3), ("b_channel", C.c_double * 3), ("f_max", C.c_double),
+                ("censored", C.c_double), ("levels", C.c_uint), ("heavily_clipped", C.c_uint), ("quantised", C.c_uint),
+                ("reserved", C.c_uint), ("blocks", C.c_ulonglong), ("skipped", C.c_ulonglong)]
+
+
+class PgclipCurvesStruct(C.Structure):
+    """lfbm5d_pgclip_curves: the stabiliser and its exact unbiased inverse as tables (include/lfbm5d_pgclip.h)."""
+    _fields_ = [("model", PgclipModelStruct), ("s", C.c_double), ("fwd_x0", C.c_double), ("fwd_dx", C.c_double),
+                ("inv_x0", C.c_double), ("inv_dx", C.c_double), ("fwd", C.c_float * PGCLIP_KNOTS), ("inv", C.c_float * PGCLIP_KNOTS)]
+
+
 class ImpulseParamsStruct(C.Structure):
     """lfbm5d_impulse_params: threshold factor, floor and given thresholds of the impulse repair (include/lfbm5d.h)."""
     _fields_ = [("k", C.c_double), ("min_threshold", C.c_double), ("threshold", C.c_double * 3)]
@@ -312,6 +333,42 @@ class ClipNoiseLevel(NamedTuple):
     skipped: int
 
 
+class PgclipEstimate(NamedTuple):
+    """Result of Context.pgclip_estimate / pgclip_estimate / pgclip_fit: the pooled model a, b on the range lo..hi, every stored
+    channel's own fit (NaN where it fails), the levels that counted, the rung f_max of the ladder, the censored fraction of all
+    blocks, heavily_clipped (f_max > 0.1), quantised, and the 2 x 2 blocks visited and skipped (0 from pgclip_fit)."""
+    a: float
+    b: float
+    lo: float
+    hi: float
+    a_channel: tuple
+    b_channel: tuple
+    levels: int
+    f_max: float
+    censored: float
+    heavily_clipped: bool
+    quantised: bool
+    blocks: int
+    skipped: int
+
+
+class PgclipCurves(NamedTuple):
+    """Result of pgclip_curves: the model, s (the filter's sigma on the stabilised data), the tables fwd and inv (float32 [4097]) with
+    the first knot and the spacing of each, and the C struct that Context.pgclip_forward / pgclip_inverse hand to the library."""
+    a: float
+    b: float
+    lo: float
+    hi: float
+    s: float
+    fwd: np.ndarray
+    fwd_x0: float
+    fwd_dx: float
+    inv: np.ndarray
+    inv_x0: float
+    inv_dx: float
+    struct: PgclipCurvesStruct
+
+
 class NoiseLevel(NamedTuple):
     """Result of Context.noise_level / noise_level: sigma of the whole light field (what to pass as `sigma`), per stored channel
     (grey: [0] only), the size m of the noise subspace, the patches pooled, the eigenvalues of the pooled covariance (ascending)
@@ -470,6 +527,20 @@ def lib():
         L.lfbm5d_declip_host_sai.argtypes = [vp, C.c_double] + rng + [fp, up, fp] + [C.c_uint] * 4
         L.lfbm5d_denoise_clipped_device.argtypes = [vp, C.c_double] + rng + [cep, dp, pp, pp, fp, up, fp, fp] + [C.c_uint] * 8
         L.lfbm5d_denoise_clipped_host_sai.argtypes = [vp, C.c_double] + rng + [cep, dp, pp, pp, fp, up, fp, fp] + [C.c_uint] * 8
+    if hasattr(L, "lfbm5d_denoise_pgclip_device"):   # (absent from older builds loaded through LFBM5D_HIP_LIB for A/B runs)
+        ullp, pp = C.POINTER(C.c_ulonglong), C.POINTER(Params)
+        gm, ge, gc = C.POINTER(PgclipModelStruct), C.POINTER(PgclipEstimateStruct), C.POINTER(PgclipCurvesStruct)
+        rng = [C.c_double, C.c_double]
+        L.lfbm5d_pgclip_fit.argtypes = [ullp, ullp, ullp, ullp, C.c_uint] + rng + [ge]
+        L.lfbm5d_pgclip_curves.argtypes = [gm, gc]
+        L.lfbm5d_pgclip_curves_error.argtypes = []
+        L.lfbm5d_pgclip_curves_error.restype = C.c_char_p
+        L.lfbm5d_pgclip_estimate_device.argtypes = [vp, fp, up] + [C.c_uint] * 4 + rng + [ge]
+        L.lfbm5d_pgclip_estimate_host_sai.argtypes = [vp, fp, up] + [C.c_uint] * 4 + rng + [ge]
+        L.lfbm5d_pgclip_forward_device.argtypes = [vp, gc, fp, up, fp] + [C.c_uint] * 4
+        L.lfbm5d_pgclip_inverse_device.argtypes = [vp, gc, fp, up, fp] + [C.c_uint] * 4
+        L.lfbm5d_denoise_pgclip_device.argtypes = [vp, gm] + rng + [gm, C.POINTER(C.c_double), ge, pp, pp, fp, up, fp, fp] + [C.c_uint] * 8
+        L.lfbm5d_denoise_pgclip_host_sai.argtypes = [vp, gm] + rng + [gm, C.POINTER(C.c_double), ge, pp, pp, fp, up, fp, fp] + [C.c_uint] * 8
     if hasattr(L, "lfbm5d_impulse_repair_device"):   # (absent from older builds loaded through LFBM5D_HIP_LIB for A/B runs)
         dp, ullp = C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)
         ip, rp = C.POINTER(ImpulseParamsStruct), C.POINTER(ImpulseResultStruct)
@@ -666,6 +737,41 @@ def pg_fit(hist, sum_m):
     if lib().lfbm5d_pg_fit(h.ctypes.data_as(ullp), sm.ctypes.data_as(ullp), C.byref(a), C.byref(b)) != 0:
         raise LfBm5dError("lfbm5d_pg_fit: no valid level (every level holds fewer than 256 blocks, or its quantile fell into an end bin)")
     return a.value, b.value
+
+
+def _pgclip_result(res, chnls):
+    m = res.model
+    return PgclipEstimate(m.a, m.b, m.lo, m.hi, tuple(res.a_channel[:chnls]), tuple(res.b_channel[:chnls]), int(res.levels), res.f_max,
+                          res.censored, bool(res.heavily_clipped), bool(res.quantised), int(res.blocks), int(res.skipped))
+
+
+def pgclip_fit(hist, sum_m, cens, whole, lo=0.0, hi=255.0):
+    """lfbm5d_pgclip_fit (host only, no GPU): the PgclipEstimate of the statistics hist uint64 [C][64][322], sum_m and cens uint64
+    [C][64] and whole uint64 [C] of Context.clip_histogram.  Raises when fewer than 4 levels are populated or the range is bad."""
+    h, sm = np.ascontiguousarray(hist, np.uint64), np.ascontiguousarray(sum_m, np.uint64)
+    cz, wh = np.ascontiguousarray(cens, np.uint64), np.ascontiguousarray(whole, np.uint64)
+    if h.ndim != 3 or h.shape[0] not in (1, 3) or h.shape[1:] != (PG_LEVELS, PG_KEYS) or sm.shape != h.shape[:2] or cz.shape != h.shape[:2] \
+            or wh.shape != h.shape[:1]:
+        raise LfBm5dError("lfbm5d_pgclip_fit: hist must be [C][64][322], sum_m and cens [C][64], whole [C], C = 1 or 3")
+    ullp = C.POINTER(C.c_ulonglong)
+    res = PgclipEstimateStruct()
+    if lib().lfbm5d_pgclip_fit(h.ctypes.data_as(ullp), sm.ctypes.data_as(ullp), cz.ctypes.data_as(ullp), wh.ctypes.data_as(ullp), h.shape[0],
+                               float(lo), float(hi), C.byref(res)) != 0:
+        raise LfBm5dError("lfbm5d_pgclip_fit: fewer than 4 levels are populated (256 blocks, a quantile outside the end bins), or the "
+                          "range is bad (lo < hi, both finite)")
+    return _pgclip_result(res, h.shape[0])
+
+
+def pgclip_curves(a, b, lo=0.0, hi=255.0):
+    """lfbm5d_pgclip_curves (host only, no GPU): the PgclipCurves of the model sigma^2(y) = max(a (y - lo) + b, 1/12) on lo..hi.  Raises
+    on an invalid model and on one outside the accepted domain (a^2 <= 0.5 b, a <= 5: beyond it denoise_pg is the tool)."""
+    m = PgclipModelStruct(float(a), float(b), float(lo), float(hi))
+    cv = PgclipCurvesStruct()
+    L = lib()
+    if L.lfbm5d_pgclip_curves(C.byref(m), C.byref(cv)) != 0:
+        raise LfBm5dError(L.lfbm5d_pgclip_curves_error().decode())
+    return PgclipCurves(m.a, m.b, m.lo, m.hi, cv.s, np.ctypeslib.as_array(cv.fwd).copy(), cv.fwd_x0, cv.fwd_dx,
+                        np.ctypeslib.as_array(cv.inv).copy(), cv.inv_x0, cv.inv_dx, cv)
 
 
 def _clip_result(res, chnls):
@@ -1350,6 +1456,83 @@ class Context:
             self._ck(self._L.lfbm5d_denoise_clipped_device(*head, _dev_ptr(noisy), mp, _dev_ptr(basic), _dev_ptr(denoised), *tail))
         return used.value, (_clip_result(res, int(Cc)) if sig <= 0.0 else None)
 
+    # ---- clipped Poisson-Gaussian noise ----
+    pgclip_fit = staticmethod(pgclip_fit)
+    pgclip_curves = staticmethod(pgclip_curves)
+
+    def pgclip_estimate(self, LF, LF_SAI_mask, width, height, chnls, lo=0.0, hi=255.0):
+        """The model sigma^2(y) = a (y - lo) + b of a light field whose values were rounded and clipped to lo..hi, from the levels the
+        clipping left alone (lfbm5d_pgclip_estimate_*, include/lfbm5d_pgclip.h).  LF: a CUDA float32 tensor [asize][C*H*W] (device
+        form, read only), a float32 numpy array of that shape or a list of per-SAI float32 arrays (host form, staged through HBM;
+        identical results).  Returns a PgclipEstimate."""
+        m = _u32(LF_SAI_mask)
+        C_ = int(chnls)
+        res = PgclipEstimateStruct()
+        tail = (m.ctypes.data_as(C.POINTER(C.c_uint)), m.size, int(width), int(height), C_, float(lo), float(hi), C.byref(res))
+        if isinstance(LF, (list, tuple, np.ndarray)):
+            self._ck(self._L.lfbm5d_pgclip_estimate_host_sai(self._h, _sai_ptrs(self._host_sais(LF), m), *tail))
+        else:
+            self._ck(self._L.lfbm5d_pgclip_estimate_device(self._h, _dev_ptr(LF), *tail))
+        return _pgclip_result(res, C_)
+
+    def _pgclip_map(self, fn, curves, LF, mask, out, width, height, chnls):
+        m = _u32(mask)
+        cv = curves.struct if isinstance(curves, PgclipCurves) else curves
+        tail = (m.size, int(width), int(height), int(chnls))
+        if isinstance(LF, (list, tuple, np.ndarray)):   # host form: staged through HBM by torch, the result copied back into `out`
+            import torch
+            arrays, outs = self._host_sais(LF), self._host_sais(out)
+            src = np.zeros((m.size, int(chnls) * int(width) * int(height)), np.float32)
+            for st in range(m.size):
+                if m[st]:
+                    src[st] = np.asarray(arrays[st], np.float32).reshape(-1)
+            d = torch.from_numpy(src).to(f"cuda:{self.device}")
+            self._ck(fn(self._h, C.byref(cv), _dev_ptr(d), m.ctypes.data_as(C.POINTER(C.c_uint)), _dev_ptr(d), *tail))
+            res = d.cpu().numpy()
+            for st in range(m.size):
+                if m[st]:
+                    outs[st].reshape(-1)[:] = res[st]
+        else:
+            self._ck(fn(self._h, C.byref(cv), _dev_ptr(LF), m.ctypes.data_as(C.POINTER(C.c_uint)), _dev_ptr(out), *tail))
+
+    def pgclip_forward(self, curves, LF, mask, out, width, height, chnls):
+        """out = the stabiliser F of pgclip_curves() applied to LF by table look-up (lfbm5d_pgclip_forward_device): CUDA float32
+        tensors [asize][C*H*W], or float32 numpy arrays / lists of per-SAI arrays (staged through HBM; bit-identical); out may be LF.
+        Planes of empty SAIs are not touched."""
+        self._pgclip_map(self._L.lfbm5d_pgclip_forward_device, curves, LF, mask, out, width, height, chnls)
+
+    def pgclip_inverse(self, curves, LF, mask, out, width, height, chnls):
+        """out = the exact unbiased inverse G^-1 of pgclip_curves() applied to LF (lfbm5d_pgclip_inverse_device): it undoes the
+        stabiliser and the clipping bias in one step; the output lies in lo..hi.  Arguments as for pgclip_forward."""
+        self._pgclip_map(self._L.lfbm5d_pgclip_inverse_device, curves, LF, mask, out, width, height, chnls)
+
+    def denoise_pgclip(self, model, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, Cc, lo=0.0, hi=255.0):
+        """The two-step job on Poisson-Gaussian data clipped to lo..hi (lfbm5d_denoise_pgclip_*): model None: pgclip_estimate() of
+        `noisy` first, else (a, b) or a PgclipEstimate; pgclip_curves(); pgclip_forward() into a scratch light field; denoise() with
+        sigma = s (P1.sigma / P2.sigma are ignored); pgclip_inverse() of basic and denoised in place.  CUDA float32 tensors (noisy is
+        only read), or float32 numpy arrays / lists of per-SAI arrays (host form; bit-identical).  Returns (the PgclipEstimate of the
+        model that was applied -- the fit's when it was estimated -- , s)."""
+        m = _u32(mask)
+        mp = m.ctypes.data_as(C.POINTER(C.c_uint))
+        used, res, s = PgclipModelStruct(), PgclipEstimateStruct(), C.c_double()
+        given = None
+        if model is not None:
+            a, b = (model.a, model.b) if hasattr(model, "a") else model
+            given = PgclipModelStruct(float(a), float(b), float(lo), float(hi))
+        head = (self._h, C.byref(given) if given is not None else None, float(lo), float(hi), C.byref(used), C.byref(s), C.byref(res), C.byref(P1),
+                C.byref(P2))
+        tail = (ang_major, awidth, aheight, an1, an2, int(W), int(H), int(Cc))
+        if isinstance(noisy, (list, tuple, np.ndarray)):
+            n, b_, d = (self._host_sais(x) for x in (noisy, basic, denoised))
+            self._ck(self._L.lfbm5d_denoise_pgclip_host_sai(*head, _sai_ptrs(n, m), mp, _sai_ptrs(b_, m), _sai_ptrs(d, m), *tail))
+        else:
+            self._ck(self._L.lfbm5d_denoise_pgclip_device(*head, _dev_ptr(noisy), mp, _dev_ptr(basic), _dev_ptr(denoised), *tail))
+        if given is None:
+            est = _pgclip_result(res, int(Cc))
+        else:
+            est = PgclipEstimate(used.a, used.b, used.lo, used.hi, (), (), 0, 0.0, 0.0, False, False, 0, 0)
+        return est, s.value
+
     # ---- impulse repair ----
     def impulse_histogram(self, LF, LF_SAI_mask, width, height, chnls):
         """The ROAD histogram of lfbm5d_impulse_histogram_device on a CUDA float32 tensor [asize][C*H*W]: (hist uint64 [C][386], pixels,
@@ -1899,6 +2082,18 @@ def denoise_pg(model, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, a
 def noise_level_clipped(LF, LF_SAI_mask, width, height, chnls, lo=0.0, hi=255.0, ctx=None):
     """Context.noise_level_clipped on the default context (device 0): the noise sigma of a light field clipped to lo..hi."""
     return (ctx or _ctx()).noise_level_clipped(LF, LF_SAI_mask, width, height, chnls, lo, hi)
+
+
+def pgclip_estimate(LF, LF_SAI_mask, width, height, chnls, lo=0.0, hi=255.0, ctx=None):
+    """Context.pgclip_estimate on the default context (device 0): the clipped Poisson-Gaussian model of a light field."""
+    return (ctx or _ctx()).pgclip_estimate(LF, LF_SAI_mask, width, height, chnls, lo, hi)
+
+
+def denoise_pgclip(model, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls, lo=0.0, hi=255.0,
+                   ctx=None):
+    """Context.denoise_pgclip on the default context (device 0); returns (the model applied as a PgclipEstimate, s)."""
+    return (ctx or _ctx()).denoise_pgclip(model, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls,
+                                          lo, hi)
 
 
 def denoise_clipped(sigma, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls, lo=0.0, hi=255.0,

@@ -79,6 +79,7 @@ void lfbm5d_destroy(lfbm5d_ctx* c) {
     c->quality.part.release(); c->quality.out.release();
     c->pg.stats.release();
     c->clip.stats.release();
+    c->pgclip.tables.release();
     c->imp.stats.release(); c->imp.flags.release();
     c->inp.stats.release(); c->inp.state[0].release(); c->inp.state[1].release(); c->inp.flags.release();
     c->view.table.release(); c->view.stats.release(); c->view.disp.release(); c->view.set.release();

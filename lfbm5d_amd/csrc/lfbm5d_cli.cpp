@@ -23,6 +23,14 @@
  *                     pg_forward_LF, run_bm3d_LF, pg_inverse_LF), with the sigma the transform leaves (also used for the diff images).
  *                     With a ground truth and poisson:<a>,<b> the noise added is Poisson-Gaussian with those parameters (<random>,
  *                     seeded from LFBM5D_SEED; the argument's sigma is unused); any other value is an error;
+ *   LFBM5D_SIGMA=poisson-clipped | poisson-clipped:<a>,<b>   that noise on data rounded and clipped to the range of
+ *                     LFBM5D_CLIP_RANGE=<lo>,<hi> (default 0,255: 8-bit files), sigma^2(y) = a (y - lo) + b: the model is fitted over the
+ *                     intensity levels the clipping left alone (pgclip_estimate_LF, run_bm5d.h; include/lfbm5d_pgclip.h), or given; both
+ *                     steps run as one job between the clipped model's stabiliser and its exact unbiased inverse, which also undoes
+ *                     the clipping bias (denoise_pgclip_LF; LFBM3Ddenoising: pgclip_forward_LF, run_bm3d_LF, pgclip_inverse_LF).  With a
+ *                     ground truth and a given model that Poisson-Gaussian noise is added (LFBM5D_SEED), then rounded and clipped to the
+ *                     range.  A model outside the accepted domain (a^2 <= 0.5 b, a <= 5) is refused: poisson is the mode for it.
+ *                     Towards the other variables it behaves as poisson does (LFBM5D_CLIP and LFBM5D_EQUALISE are refused);
  *   LFBM5D_IMPULSE=auto | <k>   impulse repair (impulse_repair_LF, run_bm5d.h) of the noisy light field once it exists, loaded or
  *                     synthesised, before LFBM5D_SIGMA=auto / poisson look at it and before the filter: hot and dead pixels, salt and
  *                     pepper and values that are not finite are replaced by the lower median of their sound neighbours; auto = the
@@ -343,24 +351,54 @@ void add_noise_LF(const vector<vector<float> >& LF, const vector<unsigned>& mask
 }
 
 /* LFBM5D_SIGMA: unset -> 0 (the argument's sigma), "auto" -> 1 (estimate it), "poisson" -> 2 (Poisson-Gaussian model, estimated),
- * "poisson:<a>,<b>" -> 3 (that model: pg = {a, b}), anything else -> -1 (error, message printed) */
+ * "poisson:<a>,<b>" -> 3 (that model: pg = {a, b}), "poisson-clipped" -> 4 (the clipped Poisson-Gaussian model, estimated),
+ * "poisson-clipped:<a>,<b>" -> 5 (that model; a >= 0, b >= 0, a + b > 0: the library checks the accepted domain), anything else -> -1
+ * (error, message printed) */
 int sigma_mode(double* pg) {
     const char* e = env("LFBM5D_SIGMA");
     if (!e) return 0;
     if (!strcmp(e, "auto")) return 1;
     if (!strcmp(e, "poisson")) return 2;
-    if (!strncmp(e, "poisson:", 8)) {
-        const char* p = e + 8;
+    if (!strcmp(e, "poisson-clipped")) return 4;
+    const bool clipped = !strncmp(e, "poisson-clipped:", 16);
+    if (clipped || !strncmp(e, "poisson:", 8)) {
+        const char* p = e + (clipped ? 16 : 8);
         char *q = nullptr, *r = nullptr;
         const double a = strtod(p, &q);
-        if (q != p && *q == ',' && q[1] && !isspace((unsigned char)q[1])) {
+        if (q != p && !(clipped && isspace((unsigned char)*p)) && *q == ',' && q[1] && !isspace((unsigned char)q[1])) {
             const double b = strtod(q + 1, &r);
-            if (r != q + 1 && !*r && std::isfinite(a) && std::isfinite(b) && a >= 0.0 && 0.375 * a * a + b > 0.0) { pg[0] = a; pg[1] = b; return 3; }
+            const bool ok = r != q + 1 && !*r && std::isfinite(a) && std::isfinite(b) && a >= 0.0;
+            if (ok && (clipped ? b >= 0.0 && a + b > 0.0 : 0.375 * a * a + b > 0.0)) { pg[0] = a; pg[1] = b; return clipped ? 5 : 3; }
         }
     }
     cout << "LFBM5D_SIGMA must be \"auto\" (estimate sigma from the noisy light field), \"poisson\" (estimate a Poisson-Gaussian noise model "
-            "var = a y + b) or \"poisson:<a>,<b>\" (that model; a >= 0, 3/8 a^2 + b > 0), or unset; got \"" << e << "\"" << endl;
+            "var = a y + b), \"poisson:<a>,<b>\" (that model; a >= 0, 3/8 a^2 + b > 0), \"poisson-clipped\" (estimate that model on data "
+            "rounded and clipped to the range of LFBM5D_CLIP_RANGE) or \"poisson-clipped:<a>,<b>\" (that model; a >= 0, b >= 0, a + b > 0), "
+            "or unset; got \"" << e << "\"" << endl;
     return -1;
+}
+
+/* LFBM5D_CLIP_RANGE: the range of LFBM5D_SIGMA=poisson-clipped, 0..255 when unset; false (message printed) on a malformed value */
+bool clip_range_mode(double& lo, double& hi) {
+    lo = 0.0; hi = 255.0;
+    const char* e = env("LFBM5D_CLIP_RANGE");
+    if (!e) return true;
+    char* q = nullptr; char* r = nullptr;
+    lo = strtod(e, &q);
+    bool ok = q != e && *q == ',' && !isspace((unsigned char)*e) && q[1] && !isspace((unsigned char)q[1]);
+    if (ok) { hi = strtod(q + 1, &r); ok = r != q + 1 && !*r; }
+    if (ok && std::isfinite(lo) && std::isfinite(hi) && lo < hi) return true;
+    cout << "LFBM5D_CLIP_RANGE must be the range \"<lo>,<hi>\" with lo < hi that LFBM5D_SIGMA=poisson-clipped assumes the noisy light field was "
+            "rounded and clipped to, or unset (0,255); got \"" << e << "\"" << endl;
+    return false;
+}
+
+/* LFBM5D_SIGMA=poisson-clipped: the line that reports the model and the sigma the filter ran with */
+void print_pgclip_model(bool estimated, const double* pg, double lo, double hi, unsigned levels, double f_max, float s) {
+    cout << endl << (estimated ? "Estimated" : "Given") << " clipped noise model: a = " << setprecision(8) << pg[0] << ", b = " << pg[1]
+         << ", range " << lo << ".." << hi << " (";
+    if (estimated) cout << levels << " levels, censored blocks <= " << 100.0 * f_max << " %; ";
+    cout << "sigma after stabilisation = " << s << ")" << setprecision(6) << endl;
 }
 
 /* LFBM5D_IMPULSE / LFBM5D_IMPULSE_ADD: k < 0 = no repair, add = 0 = no impulses added; false (message printed) on anything else */
@@ -884,6 +922,8 @@ int main(int argc, char** argv) {
     if (!occlusion_mode(occl, detect || !missing.empty())) return EXIT_FAILURE;
     bool clip_on = false, clip_add = false; double clip_lo = 0.0, clip_hi = 255.0;
     if (!clip_mode(clip_on, clip_lo, clip_hi, clip_add, smode)) return EXIT_FAILURE;
+    double pc_lo = 0.0, pc_hi = 255.0; unsigned pc_levels = 0; double pc_fmax = 0.0;   /* LFBM5D_SIGMA=poisson-clipped: its range, its fit */
+    if (!clip_range_mode(pc_lo, pc_hi)) return EXIT_FAILURE;
 
     vector<vector<float> > LF, LF_noisy, LF_basic, LF_den, LF_diff;
     vector<unsigned> mask;
@@ -894,13 +934,14 @@ int main(int argc, char** argv) {
         if (load_LF(src, name, sep, LF, mask, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
         cout << "Loading LF elapsed time = " << now_s() - t << "s." << endl;
         LF_noisy.assign(awh, vector<float>((size_t)W * H * C, 0.0f));
-        if (smode == 3) cout << endl << "Add noise [Poisson-Gaussian, a = " << pg[0] << ", b = " << pg[1] << "] ... " << flush;
+        if (smode == 3 || smode == 5) cout << endl << "Add noise [Poisson-Gaussian, a = " << pg[0] << ", b = " << pg[1] << "] ... " << flush;
         else cout << endl << "Add noise [sigma = " << sigma << "] ... " << flush;
         t = now_s();
-        add_noise_LF(LF, mask, LF_noisy, sigma, smode == 3 ? pg : nullptr);
+        add_noise_LF(LF, mask, LF_noisy, sigma, smode == 3 || smode == 5 ? pg : nullptr);
         cout << "done in " << now_s() - t << "s." << endl;
         if (eq_add > 0.0) add_vignette_LF(LF_noisy, mask, ang_major, aw, ah, eq_add);
         if (clip_add) clip_round_LF(LF_noisy, mask, clip_lo, clip_hi);
+        if (smode == 5) clip_round_LF(LF_noisy, mask, pc_lo, pc_hi);   /* the given clipped model: the data are what it describes */
         if (imp_add > 0.0) add_impulses_LF(LF_noisy, mask, imp_add);
         for (size_t st = 0; st < missing.size(); st++) if (missing[st]) LF_noisy[st].assign(LF_noisy[st].size(), 0.0f);   /* dropped */
         cout << endl << "Save noisy light field..." << endl;
@@ -945,6 +986,16 @@ int main(int argc, char** argv) {
     cout << endl << " ---> Running LFBM3D filter <--- " << endl << endl;
     const double tb = now_s();
     char sub[] = "SAI";
+    if (smode >= 4) {   /* clipped Poisson-Gaussian noise: the same between the clipped model's stabiliser and its exact unbiased inverse */
+        if (smode == 4 && pgclip_estimate_LF(LF_noisy, mask, W, H, C, pc_lo, pc_hi, pg[0], pg[1], pc_levels, pc_fmax) != EXIT_SUCCESS) return EXIT_FAILURE;
+        vector<vector<float> > LF_t = LF_noisy;
+        if (pgclip_forward_LF(pg[0], pg[1], pc_lo, pc_hi, LF_t, mask, W, H, C, sigma) != EXIT_SUCCESS) return EXIT_FAILURE;
+        print_pgclip_model(smode == 4, pg, pc_lo, pc_hi, pc_levels, pc_fmax, sigma);
+        if (run_bm3d_LF(sigma, LF_t, mask, LF_basic, LF_den, W, H, C, n[0], n[1], k[0], k[1], N[0], N[1], p[0], p[1], sd[0] != 0, sd[1] != 0,
+                        t2[0], t2[1], lambda, cs, nb_threads, sub) != EXIT_SUCCESS) return EXIT_FAILURE;
+        if (pgclip_inverse_LF(pg[0], pg[1], pc_lo, pc_hi, LF_basic, mask, W, H, C) != EXIT_SUCCESS ||
+            pgclip_inverse_LF(pg[0], pg[1], pc_lo, pc_hi, LF_den, mask, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
+    } else
     if (smode >= 2) {   /* Poisson-Gaussian noise: stabilise a copy, filter it with the sigma that leaves, invert the results */
         if (smode == 2 && !estimate_pg_LF(LF_noisy, mask, W, H, C, pg)) return EXIT_FAILURE;
         vector<vector<float> > LF_t = LF_noisy;
@@ -1051,6 +1102,8 @@ int main(int argc, char** argv) {
     if (!occlusion_mode(occl, detect || !missing.empty())) return EXIT_FAILURE;
     bool clip_on = false, clip_add = false; double clip_lo = 0.0, clip_hi = 255.0;
     if (!clip_mode(clip_on, clip_lo, clip_hi, clip_add, smode)) return EXIT_FAILURE;
+    double pc_lo = 0.0, pc_hi = 255.0; unsigned pc_levels = 0; double pc_fmax = 0.0;   /* LFBM5D_SIGMA=poisson-clipped: its range, its fit */
+    if (!clip_range_mode(pc_lo, pc_hi)) return EXIT_FAILURE;
 
     vector<vector<float> > LF, LF_noisy, LF_basic, LF_den, LF_diff;
     vector<unsigned> mask;
@@ -1061,13 +1114,14 @@ int main(int argc, char** argv) {
         if (load_LF(src, name, sep, LF, mask, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
         cout << "Loading LF elapsed time = " << now_s() - t << "s." << endl;
         LF_noisy.assign(awh, vector<float>((size_t)W * H * C, 0.0f));
-        if (smode == 3) cout << endl << "Add noise [Poisson-Gaussian, a = " << pg[0] << ", b = " << pg[1] << "] ... " << flush;
+        if (smode == 3 || smode == 5) cout << endl << "Add noise [Poisson-Gaussian, a = " << pg[0] << ", b = " << pg[1] << "] ... " << flush;
         else cout << endl << "Add noise [sigma = " << sigma << "] ... " << flush;
         t = now_s();
-        add_noise_LF(LF, mask, LF_noisy, sigma, smode == 3 ? pg : nullptr);
+        add_noise_LF(LF, mask, LF_noisy, sigma, smode == 3 || smode == 5 ? pg : nullptr);
         cout << "done in " << now_s() - t << "s." << endl;
         if (eq_add > 0.0) add_vignette_LF(LF_noisy, mask, ang_major, aw, ah, eq_add);
         if (clip_add) clip_round_LF(LF_noisy, mask, clip_lo, clip_hi);
+        if (smode == 5) clip_round_LF(LF_noisy, mask, pc_lo, pc_hi);   /* the given clipped model: the data are what it describes */
         if (imp_add > 0.0) add_impulses_LF(LF_noisy, mask, imp_add);
         for (size_t st = 0; st < missing.size(); st++) if (missing[st]) LF_noisy[st].assign(LF_noisy[st].size(), 0.0f);   /* dropped */
         cout << endl << "Save noisy light field..." << endl;
@@ -1132,7 +1186,13 @@ int main(int argc, char** argv) {
     const double tb = now_s();
     double t1 = now_s();
     double job = 0.0;
-    if (smode >= 2) {
+    if (smode >= 4) {
+        if (denoise_pgclip_LF(pg[0], pg[1], pc_lo, pc_hi, smode == 4, sigma, pc_levels, pc_fmax, lambda, LF_noisy, mask, LF_basic, LF_den, ang_major, aw,
+                              ah, anH, anW, W, H, C, N[0], nSim[0], nDisp[0], k[0], p[0], sd[0] != 0, t2[0], t4[0], t5[0], N[1], nSim[1], nDisp[1], k[1],
+                              p[1], sd[1] != 0, t2[1], t4[1], t5[1], cs, nb_threads) != EXIT_SUCCESS) return EXIT_FAILURE;
+        job = now_s() - t1;
+        print_pgclip_model(smode == 4, pg, pc_lo, pc_hi, pc_levels, pc_fmax, sigma);
+    } else if (smode >= 2) {
         if (denoise_pg_LF(pg[0], pg[1], smode == 2, sigma, lambda, LF_noisy, mask, LF_basic, LF_den, ang_major, aw, ah, anH, anW, W, H, C, N[0],
                           nSim[0], nDisp[0], k[0], p[0], sd[0] != 0, t2[0], t4[0], t5[0], N[1], nSim[1], nDisp[1], k[1], p[1], sd[1] != 0, t2[1],
                           t4[1], t5[1], cs, nb_threads) != EXIT_SUCCESS) return EXIT_FAILURE;

@@ -164,6 +164,8 @@ struct lfbm5d_ctx {
     struct PgBufs { DevBuf stats; } pg;
     /* clipping-aware estimate (lfbm5d_clip.hip): the statistics kernel's counters */
     struct ClipBufs { DevBuf stats; } clip;
+    /* clipped Poisson-Gaussian stage (lfbm5d_pgclip.hip): the forward and the inverse table */
+    struct PgclipBufs { DevBuf tables; } pgclip;
     /* impulse repair (lfbm5d_impulse.hip): the kernels' counters, the host form's flag planes (in, out) */
     struct ImpulseBufs { DevBuf stats, flags; } imp;
     /* defect inpainting (lfbm5d_inpaint.hip): the fill's counters, its state planes, the host form's flag planes (in, out) */

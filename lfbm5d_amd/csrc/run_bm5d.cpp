@@ -430,6 +430,115 @@ int denoise_clipped_LF(float& sigma, double lo, double hi, const float lambdaHar
     return EXIT_SUCCESS;
 }
 
+/* clipped Poisson-Gaussian model on the caller's vectors (one pointer per SAI, no flat copy) */
+int pgclip_estimate_LF(const std::vector<std::vector<float> >& LF, const std::vector<unsigned>& LF_SAI_mask, unsigned width, unsigned height,
+                       unsigned chnls, double lo, double hi, double& a, double& b, unsigned& levels, double& f_max) {
+    if (LF.size() != LF_SAI_mask.size()) {
+        std::cout << "pgclip_estimate_LF: light field and mask must hold the same number of SAIs" << std::endl;
+        return EXIT_FAILURE;
+    }
+    lfbm5d_ctx* ctx = context();
+    if (!ctx) return EXIT_FAILURE;
+    const size_t img = (size_t)width * height * chnls;
+    std::vector<const float*> p(LF.size(), nullptr);
+    for (size_t st = 0; st < LF.size(); st++) if (LF_SAI_mask[st] && LF[st].size() == img) p[st] = LF[st].data();
+    for (size_t st = 0; st < LF.size(); st++)
+        if (LF_SAI_mask[st] && !p[st]) { std::cout << "pgclip_estimate_LF: a non-empty SAI does not hold width*height*chnls values" << std::endl; return EXIT_FAILURE; }
+    lfbm5d_pgclip_estimate r;
+    if (lfbm5d_pgclip_estimate_host_sai(ctx, p.data(), LF_SAI_mask.data(), (unsigned)LF.size(), width, height, chnls, lo, hi, &r) != 0) {
+        std::cout << "LFBM5D GPU backend: " << lfbm5d_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+    }
+    a = r.model.a; b = r.model.b; levels = r.levels; f_max = r.f_max;
+    return EXIT_SUCCESS;
+}
+
+namespace {
+
+/* the maps have device forms only: the light field goes through a device buffer of this call */
+int pgclip_map_LF(const char* who, bool inverse, double a, double b, double lo, double hi, std::vector<std::vector<float> >& LF,
+                  const std::vector<unsigned>& mask, unsigned width, unsigned height, unsigned chnls, float* sigma) {
+    if (LF.size() != mask.size()) { std::cout << who << ": light field and mask must hold the same number of SAIs" << std::endl; return EXIT_FAILURE; }
+    const lfbm5d_pgclip_model m = {a, b, lo, hi};
+    std::vector<struct lfbm5d_pgclip_curves> cv(1);
+    if (lfbm5d_pgclip_curves(&m, cv.data()) != 0) { std::cout << who << ": " << lfbm5d_pgclip_curves_error() << std::endl; return EXIT_FAILURE; }
+    lfbm5d_ctx* ctx = context();
+    if (!ctx) return EXIT_FAILURE;
+    const size_t img = (size_t)width * height * chnls, asize = LF.size();
+    for (size_t st = 0; st < asize; st++)
+        if (mask[st] && LF[st].size() != img) { std::cout << who << ": a non-empty SAI does not hold width*height*chnls values" << std::endl; return EXIT_FAILURE; }
+    Flat flat;
+    flatten(LF, mask, img, flat);
+    void* d = nullptr;
+    const size_t bytes = std::max<size_t>(1, asize * img) * sizeof(float);
+    if (lfbm5d_malloc(&d, bytes) != 0) { std::cout << who << ": out of device memory" << std::endl; return EXIT_FAILURE; }
+    int rc = lfbm5d_memcpy_h2d(d, flat.get(), asize * img * sizeof(float));
+    if (!rc) {
+        rc = inverse ? lfbm5d_pgclip_inverse_device(ctx, cv.data(), (const float*)d, mask.data(), (float*)d, (unsigned)asize, width, height, chnls)
+                     : lfbm5d_pgclip_forward_device(ctx, cv.data(), (const float*)d, mask.data(), (float*)d, (unsigned)asize, width, height, chnls);
+        if (rc) std::cout << "LFBM5D GPU backend: " << lfbm5d_last_error(ctx) << std::endl;
+    }
+    if (!rc) rc = lfbm5d_memcpy_d2h(flat.get(), d, asize * img * sizeof(float));
+    lfbm5d_free(d);
+    if (rc) return EXIT_FAILURE;
+    unflatten(LF, mask, img, flat);
+    if (sigma) *sigma = (float)cv[0].s;
+    return EXIT_SUCCESS;
+}
+
+} // namespace
+
+int pgclip_forward_LF(double a, double b, double lo, double hi, std::vector<std::vector<float> >& LF, const std::vector<unsigned>& LF_SAI_mask,
+                      unsigned width, unsigned height, unsigned chnls, float& sigma) {
+    return pgclip_map_LF("pgclip_forward_LF", false, a, b, lo, hi, LF, LF_SAI_mask, width, height, chnls, &sigma);
+}
+
+int pgclip_inverse_LF(double a, double b, double lo, double hi, std::vector<std::vector<float> >& LF, const std::vector<unsigned>& LF_SAI_mask,
+                      unsigned width, unsigned height, unsigned chnls) {
+    return pgclip_map_LF("pgclip_inverse_LF", true, a, b, lo, hi, LF, LF_SAI_mask, width, height, chnls, nullptr);
+}
+
+int denoise_pgclip_LF(double& a, double& b, double lo, double hi, const bool estimate, float& sigma, unsigned& levels, double& f_max,
+                      const float lambdaHard5D, const std::vector<std::vector<float> >& LF_noisy, std::vector<unsigned>& LF_SAI_mask,
+                      std::vector<std::vector<float> >& LF_basic, std::vector<std::vector<float> >& LF_denoised, const unsigned ang_major,
+                      const unsigned awidth, const unsigned aheight, const unsigned anHard, const unsigned anWien, const unsigned width,
+                      const unsigned height, const unsigned chnls, const unsigned NHard, const unsigned nSimHard, const unsigned nDispHard,
+                      const unsigned kHard, const unsigned pHard, const bool useSDHard, const unsigned tau_2D_hard, unsigned tau_4D_hard,
+                      const unsigned tau_5D_hard, const unsigned NWien, const unsigned nSimWien, const unsigned nDispWien, const unsigned kWien,
+                      const unsigned pWien, const bool useSDWien, const unsigned tau_2D_wien, unsigned tau_4D_wien, const unsigned tau_5D_wien,
+                      const unsigned color_space, const unsigned nb_threads) {
+    const unsigned asize = awidth * aheight;
+    if (LF_noisy.size() != asize || LF_SAI_mask.size() != asize) {
+        std::cout << "denoise_pgclip_LF: light field and mask must hold awidth*aheight SAIs" << std::endl;
+        return EXIT_FAILURE;
+    }
+    lfbm5d_ctx* ctx = context();
+    if (!ctx) return EXIT_FAILURE;
+    lfbm5d_set_tiles(ctx, tiles_for(nb_threads));
+    if (LF_basic.size() != asize) LF_basic.resize(asize);
+    if (LF_denoised.size() != asize) LF_denoised.resize(asize);
+    const size_t img = (size_t)width * height * chnls;
+    std::vector<const float*> noisy(asize, nullptr);
+    for (size_t st = 0; st < asize; st++) if (LF_SAI_mask[st] && LF_noisy[st].size() == img) noisy[st] = LF_noisy[st].data();
+    for (size_t st = 0; st < asize; st++)
+        if (LF_SAI_mask[st] && !noisy[st]) { std::cout << "denoise_pgclip_LF: a non-empty SAI does not hold width*height*chnls values" << std::endl; return EXIT_FAILURE; }
+    const std::vector<float*> basic = sai_ptrs(LF_basic, LF_SAI_mask, img, true), den = sai_ptrs(LF_denoised, LF_SAI_mask, img, true);
+    const lfbm5d_params P1 = make(0.0f, lambdaHard5D, NHard, nSimHard, nDispHard, kHard, pHard, useSDHard, tau_2D_hard, tau_4D_hard, tau_5D_hard, color_space);
+    const lfbm5d_params P2 = make(0.0f, 0.0f, NWien, nSimWien, nDispWien, kWien, pWien, useSDWien, tau_2D_wien, tau_4D_wien, tau_5D_wien, color_space);
+    const lfbm5d_pgclip_model given = {a, b, lo, hi};
+    lfbm5d_pgclip_model used;
+    lfbm5d_pgclip_estimate est;
+    double s = 0.0;
+    if (lfbm5d_denoise_pgclip_host_sai(ctx, estimate ? nullptr : &given, lo, hi, &used, &s, &est, &P1, &P2, noisy.data(), LF_SAI_mask.data(), basic.data(),
+                                       den.data(), ang_major, awidth, aheight, anHard, anWien, width, height, chnls) != 0) {
+        std::cout << "LFBM5D GPU backend: " << lfbm5d_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+    }
+    a = used.a; b = used.b; levels = est.levels; f_max = est.f_max;
+    sigma = (float)s;
+    return EXIT_SUCCESS;
+}
+
 int report_ssim_mode() {
     const char* e = std::getenv("LFBM5D_REPORT_SSIM");
     if (!e) return 0;

@@ -247,6 +247,85 @@ int denoise_clipped_LF(
 ,   const unsigned nb_threads
 );
 
+//! Poisson-Gaussian noise on data rounded and clipped to lo..hi (8-bit files) -- not in the reference: the model
+//! sigma^2(y) = a (y - lo) + b of such a light field, fitted on the GPU's block statistics over the intensity levels the clipping left
+//! alone (lfbm5d_pgclip_estimate_host_sai, include/lfbm5d_pgclip.h).  `levels` and `f_max` as for noise_level_clipped_LF.  LF is only read.
+//! Returns EXIT_SUCCESS, or EXIT_FAILURE with the message on stdout.
+int pgclip_estimate_LF(
+    const std::vector<std::vector<float> > &LF
+,   const std::vector<unsigned> &LF_SAI_mask
+,   unsigned width
+,   unsigned height
+,   unsigned chnls
+,   double lo
+,   double hi
+,   double &a
+,   double &b
+,   unsigned &levels
+,   double &f_max
+);
+
+//! The stabiliser of the clipped model (a, b, lo, hi) and its exact unbiased inverse, in place on the GPU by table look-up
+//! (lfbm5d_pgclip_curves, lfbm5d_pgclip_forward_device / _inverse_device): after pgclip_forward_LF the noise has the standard deviation
+//! `sigma` (returned) and any denoiser applies; pgclip_inverse_LF takes the denoised result back to the unclipped signal in lo..hi.  A
+//! model that is invalid or outside the accepted domain returns EXIT_FAILURE with the message on stdout.
+int pgclip_forward_LF(
+    double a
+,   double b
+,   double lo
+,   double hi
+,   std::vector<std::vector<float> > &LF
+,   const std::vector<unsigned> &LF_SAI_mask
+,   unsigned width
+,   unsigned height
+,   unsigned chnls
+,   float &sigma
+);
+int pgclip_inverse_LF(
+    double a
+,   double b
+,   double lo
+,   double hi
+,   std::vector<std::vector<float> > &LF
+,   const std::vector<unsigned> &LF_SAI_mask
+,   unsigned width
+,   unsigned height
+,   unsigned chnls
+);
+
+//! run_bm5d on clipped Poisson-Gaussian data (lfbm5d_denoise_pgclip_host_sai): estimate = true: (a, b) are estimated from LF_noisy at
+//! the range lo..hi first and returned (with `levels` and `f_max`); otherwise they are the model to use.  Forward map, both steps as one
+//! job with sigma = the curves' s, inverse map of LF_basic and LF_denoised.  LF_noisy is only read; `sigma` receives s.
+int denoise_pgclip_LF(
+    double &a
+,   double &b
+,   double lo
+,   double hi
+,   const bool estimate
+,   float &sigma
+,   unsigned &levels
+,   double &f_max
+,   const float lambdaHard5D
+,   const std::vector<std::vector<float> > &LF_noisy
+,   std::vector<unsigned> &LF_SAI_mask
+,   std::vector<std::vector<float> > &LF_basic
+,   std::vector<std::vector<float> > &LF_denoised
+,   const unsigned ang_major
+,   const unsigned awidth
+,   const unsigned aheight
+,   const unsigned anHard
+,   const unsigned anWien
+,   const unsigned width
+,   const unsigned height
+,   const unsigned chnls
+,   const unsigned NHard, const unsigned nSimHard, const unsigned nDispHard, const unsigned kHard, const unsigned pHard
+,   const bool useSDHard, const unsigned tau_2D_hard, unsigned tau_4D_hard, const unsigned tau_5D_hard
+,   const unsigned NWien, const unsigned nSimWien, const unsigned nDispWien, const unsigned kWien, const unsigned pWien
+,   const bool useSDWien, const unsigned tau_2D_wien, unsigned tau_4D_wien, const unsigned tau_5D_wien
+,   const unsigned color_space
+,   const unsigned nb_threads
+);
+
 //! Quality of LF_2 against LF_1 on the GPU -- compute_psnr_LF (utilities_LF.cpp:639-692) with its argument order, the sizes and the
 //! SSIM triple added: per-SAI PSNR, RMSE and SSIM (0 for empty SAIs) with their mean and population standard deviation over the
 //! non-empty SAIs (lfbm5d_quality_host_sai, include/lfbm5d.h: double sums, peak 255, SSIM with the 11 x 11 Gaussian window over every
