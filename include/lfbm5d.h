@@ -987,6 +987,8 @@ int lfbm5d_device_count(void);
 #include "lfbm5d_photo.h"
 /* ---- clipped Poisson-Gaussian noise: censored fit, stabiliser and exact unbiased inverse (lfbm5d_pgclip_*) ---- */
 #include "lfbm5d_pgclip.h"
+/* ---- per-view noise levels: one sigma per SAI, one sigma per angular window (lfbm5d_views_*, lfbm5d_*_views_*) ---- */
+#include "lfbm5d_views.h"
 
 #ifdef __cplusplus
 }

@@ -34,8 +34,9 @@
  * float32 multiplication per value of every non-empty SAI), G <- G g.
  * Integer atomics only; ratios and gains on the host in double on integer histograms: the GPU equals the numpy model of
  * tests/photo_model.py bit for bit in every integer and float it returns, and repeated calls return the same bits.
- * Limits: gain only (no offset, no vignetting inside a view, no spatially varying gain); after the division a view's noise is sigma / g
- * and nothing downstream is told (the consistency check still calls a view bad that is merely noisier; gain_min / gain_max tell the
+ * Limits: gain only (no offset, no vignetting inside a view, no spatially varying gain); after the division a view's noise is sigma / g:
+ * the filter is told only through the jobs of include/lfbm5d_views.h (lfbm5d_views_from_gains turns the gains into their view table),
+ * the plain jobs and the consistency check are not (it still calls a view bad that is merely noisier; gain_min / gain_max tell the
  * caller); the common factor is free (lower median, or the anchor); one GPU; the defaults are one row of a sweep on one light field and
  * a translated view of it, both unclipped (profiles/photo_defaults.txt): it cannot weigh hi's guard against saturated values.
  */

@@ -603,6 +603,18 @@ def lib():
         L.lfbm5d_photo_host_sai.argtypes = [vp, qp, vp, up, vp, dp, up, ullp] + [C.c_uint] * 6 + [qr]
         L.lfbm5d_photo_apply_device.argtypes = [vp, fp, up, dp, C.c_uint, fp] + [C.c_uint] * 5
         L.lfbm5d_photo_apply_host_sai.argtypes = [vp, vp, up, dp, C.c_uint, vp] + [C.c_uint] * 5
+    if hasattr(L, "lfbm5d_denoise_views_device"):   # (absent from older builds loaded through LFBM5D_HIP_LIB for A/B runs)
+        dp, pp = C.POINTER(C.c_double), C.POINTER(Params)
+        L.lfbm5d_views_error.argtypes = []
+        L.lfbm5d_views_error.restype = C.c_char_p
+        L.lfbm5d_views_window_sigma.argtypes = [dp, up] + [C.c_uint] * 6 + [C.POINTER(C.c_float)]
+        L.lfbm5d_views_from_gains.argtypes = [C.c_double, C.POINTER(C.c_float), C.c_uint, up, C.c_uint, dp]
+        L.lfbm5d_denoise_views_device.argtypes = [vp, dp, dp, pp, pp, fp, up, fp, fp] + [C.c_uint] * 8
+        L.lfbm5d_denoise_views_host_sai.argtypes = [vp, dp, dp, pp, pp, fp, up, fp, fp] + [C.c_uint] * 8
+        L.lfbm5d_step1_views_device.argtypes = [vp, dp, dp, pp, fp, up, fp] + [C.c_uint] * 7
+        L.lfbm5d_step2_views_device.argtypes = [vp, dp, dp, pp, fp, up, fp, fp] + [C.c_uint] * 7
+        L.lfbm5d_bm3d_lf_views_device.argtypes = [vp, dp, dp, bp, bp, fp, up, fp, fp] + [C.c_uint] * 4
+        L.lfbm5d_last_window_sigmas.argtypes = [vp, C.POINTER(C.c_float), C.c_uint]
     L.lfbm5d_malloc.argtypes = [C.POINTER(vp), C.c_size_t]
     L.lfbm5d_free.argtypes = [vp]
     L.lfbm5d_memcpy_h2d.argtypes = [vp, vp, C.c_size_t]
@@ -960,6 +972,43 @@ def photo_solve(r, neighbours, fitted, anchor=None):
     return g
 
 
+def window_sigma(sigma_sai, awidth, aheight, ps, pt, an=1, ang_major=None, mask=None):
+    """The sigma of the angular window of half size `an` around SAI (ps, pt) under the view table `sigma_sai` [aheight * awidth], one noise
+    level per SAI (lfbm5d_views_window_sigma, include/lfbm5d_views.h): the table's value if the window's non-empty SAIs share one, else
+    the root mean square of theirs.  Host only, needs no GPU.  Returns a numpy float32."""
+    t = np.ascontiguousarray(np.asarray(sigma_sai, dtype=np.float64).reshape(-1))
+    if t.size != int(awidth) * int(aheight):
+        raise LfBm5dError("window_sigma: the view table needs one value per SAI")
+    m = None if mask is None else _u32(mask)
+    out = C.c_float()
+    if lib().lfbm5d_views_window_sigma(t.ctypes.data_as(C.POINTER(C.c_double)), None if m is None else m.ctypes.data_as(C.POINTER(C.c_uint)),
+                                       ROWMAJOR if ang_major is None else ang_major, int(awidth), int(aheight), int(ps), int(pt), int(an),
+                                       C.byref(out)) != 0:
+        raise LfBm5dError(lib().lfbm5d_views_error().decode())
+    return np.float32(out.value)
+
+
+def views_from_gains(sigma, gain, mask=None):
+    """The view table photometric equalisation leaves behind: sigma_v = sigma sqrt(mean_c g[v][c]^-2) for the gains `gain` [asize] or
+    [asize][C] it divided out (lfbm5d_views_from_gains, include/lfbm5d_views.h; Equalise.gain holds them).  Host only, needs no GPU.
+    Returns float64 [asize], 0 for empty SAIs."""
+    g = np.asarray(gain, dtype=np.float64)
+    if g.ndim == 1:
+        g = g[:, None]
+    if g.ndim != 2 or not 1 <= g.shape[1] <= 3:
+        raise LfBm5dError("views_from_gains: gains must be [asize] or [asize][C] with C = 1..3")
+    g = np.ascontiguousarray(g.astype(np.float32))
+    m = None if mask is None else _u32(mask)
+    if m is not None and m.size != g.shape[0]:
+        raise LfBm5dError("views_from_gains: the mask needs one value per SAI")
+    out = np.zeros(max(g.shape[0], 1), np.float64)
+    if lib().lfbm5d_views_from_gains(float(sigma), g.ctypes.data_as(C.POINTER(C.c_float)), g.shape[1],
+                                     None if m is None else m.ctypes.data_as(C.POINTER(C.c_uint)), g.shape[0],
+                                     out.ctypes.data_as(C.POINTER(C.c_double))) != 0:
+        raise LfBm5dError(lib().lfbm5d_views_error().decode())
+    return out[:g.shape[0]]
+
+
 def sr_defaults(scale, /, **changes):
     """lfbm5d_sr_defaults (host only): the SrParams the library starts from for `scale`; keyword arguments replace fields
     (kernel may be "bicubic" / "gaussian")."""
@@ -1201,6 +1250,72 @@ class Context:
         else:
             self._ck(self._L.lfbm5d_denoise_device(self._h, C.byref(P1), C.byref(P2), _dev_ptr(noisy), mp, _dev_ptr(basic),
                                                    _dev_ptr(denoised), *tail))
+
+    # ---- per-view noise levels (include/lfbm5d_views.h) ----
+    @staticmethod
+    def _view_table(sigma_sai, asize):
+        """(the table or NULL, the buffer the applied table is written to) of a *_views_* call."""
+        dp = C.POINTER(C.c_double)
+        used = np.zeros(max(asize, 1), np.float64)
+        if sigma_sai is None:
+            return None, None, used
+        t = np.ascontiguousarray(np.asarray(sigma_sai, dtype=np.float64).reshape(-1))
+        if t.size != asize:
+            raise LfBm5dError("the view table needs one value per SAI")
+        return t, t.ctypes.data_as(dp), used
+
+    def denoise_views(self, sigma_sai, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, Cc):
+        """denoise() with one noise level per SAI (lfbm5d_denoise_views_*): every angular window runs with its window sigma
+        (window_sigma(); P1.sigma / P2.sigma are ignored).  sigma_sai: [asize] in the units of sigma, or None: the per-SAI estimate
+        noise_level(..., per_sai=True) of `noisy` is taken first.  CUDA float32 tensors (device form), or float32 numpy arrays /
+        lists of per-SAI arrays (host form, in / out like denoise(); bit-identical).  Returns the table that was applied, float64
+        [asize] (0 for empty SAIs)."""
+        m = _u32(mask)
+        mp = m.ctypes.data_as(C.POINTER(C.c_uint))
+        t, tp, used = self._view_table(sigma_sai, m.size)
+        head = (self._h, tp, used.ctypes.data_as(C.POINTER(C.c_double)), C.byref(P1), C.byref(P2))
+        tail = (ang_major, awidth, aheight, an1, an2, int(W), int(H), int(Cc))
+        if isinstance(noisy, (list, tuple, np.ndarray)):
+            n, b, d = (self._host_sais(x) for x in (noisy, basic, denoised))
+            self._ck(self._L.lfbm5d_denoise_views_host_sai(*head, _sai_ptrs(n, m), mp, _sai_ptrs(b, m), _sai_ptrs(d, m), *tail))
+        else:
+            self._ck(self._L.lfbm5d_denoise_views_device(*head, _dev_ptr(noisy), mp, _dev_ptr(basic), _dev_ptr(denoised), *tail))
+        return used[:m.size]
+
+    def step1_views(self, sigma_sai, P, noisy, mask, basic, ang_major, awidth, aheight, an, W, H, Cc):
+        """step1() with a view table (lfbm5d_step1_views_device; CUDA tensors): see denoise_views().  Returns the table applied."""
+        m = _u32(mask)
+        t, tp, used = self._view_table(sigma_sai, m.size)
+        self._ck(self._L.lfbm5d_step1_views_device(self._h, tp, used.ctypes.data_as(C.POINTER(C.c_double)), C.byref(P), _dev_ptr(noisy),
+                                                   m.ctypes.data_as(C.POINTER(C.c_uint)), _dev_ptr(basic), ang_major, awidth, aheight, an,
+                                                   int(W), int(H), int(Cc)))
+        return used[:m.size]
+
+    def step2_views(self, sigma_sai, P, noisy, mask, basic, denoised, ang_major, awidth, aheight, an, W, H, Cc):
+        """step2() with a view table (lfbm5d_step2_views_device; CUDA tensors): see denoise_views().  Returns the table applied."""
+        m = _u32(mask)
+        t, tp, used = self._view_table(sigma_sai, m.size)
+        self._ck(self._L.lfbm5d_step2_views_device(self._h, tp, used.ctypes.data_as(C.POINTER(C.c_double)), C.byref(P), _dev_ptr(noisy),
+                                                   m.ctypes.data_as(C.POINTER(C.c_uint)), _dev_ptr(basic), _dev_ptr(denoised), ang_major,
+                                                   awidth, aheight, an, int(W), int(H), int(Cc)))
+        return used[:m.size]
+
+    def bm3d_lf_views(self, sigma_sai, hard, wien, noisy, mask, basic, denoised, W, H, Cc):
+        """bm3d_lf() with a view table (lfbm5d_bm3d_lf_views_device; CUDA tensors): SAI v is filtered with sigma_sai[v] in both steps
+        (hard.sigma / wien.sigma are ignored).  Returns the table applied."""
+        m = _u32(mask)
+        t, tp, used = self._view_table(sigma_sai, m.size)
+        self._ck(self._L.lfbm5d_bm3d_lf_views_device(self._h, tp, used.ctypes.data_as(C.POINTER(C.c_double)), C.byref(hard), C.byref(wien),
+                                                     _dev_ptr(noisy), m.ctypes.data_as(C.POINTER(C.c_uint)), _dev_ptr(basic),
+                                                     _dev_ptr(denoised), m.size, int(W), int(H), int(Cc)))
+        return used[:m.size]
+
+    def last_window_sigmas(self):
+        """The sigma applied to every window of the last step / denoise job, in the order of last_windows() (float32)."""
+        n = self._L.lfbm5d_last_window_sigmas(self._h, None, 0)
+        out = np.zeros(max(n, 1), np.float32)
+        self._L.lfbm5d_last_window_sigmas(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size)
+        return out[:max(n, 0)].copy()
 
     # ---- inner seam ----
     def core_pass(self, step, P, aw, ah, Wb, Hb, Cc, noisy, basic, num, den, mask, procSAI, cst, pst):
@@ -2074,6 +2189,11 @@ def equalise(noisy, mask, ang_major, awidth, aheight, width, height, chnls, retu
     return (ctx or _ctx()).equalise(noisy, mask, ang_major, awidth, aheight, width, height, chnls, return_hist=return_hist, **params)
 
 
+def denoise_views(sigma_sai, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls, ctx=None):
+    """Context.denoise_views on the process-wide context (or `ctx`): the two-step job with one noise level per SAI."""
+    return (ctx or _ctx()).denoise_views(sigma_sai, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls)
+
+
 def denoise_pg(model, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls, ctx=None):
     """Context.denoise_pg on the default context (device 0); returns the model that was used."""
     return (ctx or _ctx()).denoise_pg(model, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls)
@@ -2140,6 +2260,38 @@ def dropin_probe(noisy, mask, awidth, aheight, width, height, chnls, sigma, lamb
     if rc != 0:
         raise LfBm5dError("drop-in probe failed (message on stdout)")
     return ms, n_out, b_out, d_out
+
+
+def denoise_views_probe(noisy, mask, sigma_sai, awidth, aheight, width, height, chnls, lambda_, hard, wien, color_space="opp",
+                        ang_major=ROWMAJOR, an=(1, 1)):
+    """denoise_views_LF of the C++ drop-in (run_bm5d.h) on vector<vector<float>> light fields built from `noisy` [asize][C*H*W] (float32
+    numpy): (noisy, basic, denoised as the call leaves them, the table applied, the window sigmas).  sigma_sai None: the estimate.
+    hard / wien = (N, nSim, nDisp, k, p, tau_2D, tau_4D, tau_5D) with transform names, as in dropin_probe."""
+    import ctypes
+    D = ctypes.CDLL(os.path.join(_HERE, "liblfbm5d_dropin.so"))
+    dp = C.POINTER(C.c_double)
+    D.lfbm5d_denoise_views_probe.argtypes = ([C.c_void_p] * 2 + [dp, dp] + [C.c_void_p] * 3 + [C.c_uint] * 8 + [C.c_float, C.c_void_p, C.c_void_p,
+                                             C.c_uint, C.c_void_p, C.c_uint, C.POINTER(C.c_uint)])
+
+    def pk(t):
+        N, nSim, nDisp, k, p, t2, t4, t5 = t
+        return np.array([N, nSim, nDisp, k, p, 0, TAU[t2], TAU[t4], TAU[t5]], np.uint32)
+    noisy = np.ascontiguousarray(noisy, dtype=np.float32)
+    m = _u32(mask)
+    asize = m.size
+    t = None if sigma_sai is None else np.ascontiguousarray(np.asarray(sigma_sai, np.float64).reshape(-1))
+    used = np.zeros(max(asize, 1), np.float64)
+    outs = [np.zeros_like(noisy) for _ in range(3)]
+    h, w = pk(hard), pk(wien)
+    win = np.zeros(4 * asize + 8, np.float32)
+    n_win = C.c_uint()
+    rc = D.lfbm5d_denoise_views_probe(noisy.ctypes.data, m.ctypes.data, None if t is None else t.ctypes.data_as(dp), used.ctypes.data_as(dp),
+                                      outs[0].ctypes.data, outs[1].ctypes.data, outs[2].ctypes.data, ang_major, awidth, aheight, an[0], an[1],
+                                      width, height, chnls, float(lambda_), h.ctypes.data, w.ctypes.data, COLOR_SPACE[color_space],
+                                      win.ctypes.data, win.size, C.byref(n_win))
+    if rc != 0:
+        raise LfBm5dError("denoise_views_LF failed (its message is on stdout)")
+    return outs[0], outs[1], outs[2], used[:asize], win[:min(n_win.value, win.size)].copy()
 
 
 def superres_probe(low, mask, awidth, aheight, width, height, chnls, sr, lambda_, hard, color_space="opp", ang_major=ROWMAJOR, an=1):

@@ -221,6 +221,12 @@ int lfbm5d_last_windows(const lfbm5d_ctx* c, unsigned* out_sai, unsigned cap) {
     return (int)c->last_windows.size();
 }
 
+int lfbm5d_last_window_sigmas(const lfbm5d_ctx* c, float* out, unsigned cap) {
+    if (!c) return -1;
+    for (size_t i = 0; i < c->views.last.size() && i < cap && out; i++) out[i] = c->views.last[i];
+    return (int)c->views.last.size();
+}
+
 int lfbm5d_comm_ranks(const lfbm5d_ctx* c) {
     if (!c || !c->comm) return 0;
     int n = 0;
@@ -495,7 +501,8 @@ int run_bm3d_lf(lfbm5d_ctx* c, const lfbm5d_bm3d_params* Hd, const lfbm5d_bm3d_p
      * nWien > nHard the crop reaches rows and columns the second step never aggregates into, which the reference returns
      * as 0 / 0: no result to reproduce */
     if (Wn->nHW > Hd->nHW) return fail(c, "unsupported: BM3D with nWien > nHard (the reference's own result is undefined there: 0 / 0 in the cropped border)");
-    if (Hd->color_space != Wn->color_space || Hd->sigma != Wn->sigma) return fail(c, "BM3D: both steps share sigma and colour space");
+    const bool views = !c->views.table.empty();   /* a view table (include/lfbm5d_views.h): SAI v is filtered with sigma_v in both steps */
+    if (Hd->color_space != Wn->color_space || (!views && Hd->sigma != Wn->sigma)) return fail(c, "BM3D: both steps share sigma and colour space");
     const unsigned nP = Hd->nHW, Wb = W + 2 * nP, Hb = H + 2 * nP;
     const size_t img = (size_t)C * W * H, imgb = (size_t)C * Wb * Hb;
     /* The SAIs are independent images (bm3d_LF.cpp:106-121 is a plain loop): they are dealt to lanes -- contexts with a stream and
@@ -526,12 +533,14 @@ int run_bm3d_lf(lfbm5d_ctx* c, const lfbm5d_bm3d_params* Hd, const lfbm5d_bm3d_p
         HIPCK(c, x->t_num.reserve(imgb * sizeof(float)));
         float* const wn = x->w_noisy.as<float>(); float* const wb = x->w_basic.as<float>(); float* const wo = x->t_num.as<float>();
         float* noisy = d_noisy + st * img; float* basic = d_basic + st * img; float* deno = d_denoised + st * img;
+        lfbm5d_bm3d_params Hv = *Hd, Wv = *Wn;
+        if (views) Hv.sigma = Wv.sigma = (float)c->views.table[st];
         if (C == 3) HIPCK(c, launch_color(s, noisy, Hd->color_space, W * H, 1));
         HIPCK(c, launch_symetrize(s, noisy, wn, W, H, C, nP));
-        if (bm3d_step(x, 1, Hd, Wb, Hb, C, wn, nullptr, wo)) { if (x != c) c->err = x->err; return 1; }
+        if (bm3d_step(x, 1, &Hv, Wb, Hb, C, wn, nullptr, wo)) { if (x != c) c->err = x->err; return 1; }
         HIPCK(c, launch_unsymetrize(s, basic, wo, W, H, C, nP));
         HIPCK(c, launch_symetrize(s, basic, wb, W, H, C, nP));
-        if (bm3d_step(x, 2, Wn, Wb, Hb, C, wn, wb, wo)) { if (x != c) c->err = x->err; return 1; }
+        if (bm3d_step(x, 2, &Wv, Wb, Hb, C, wn, wb, wo)) { if (x != c) c->err = x->err; return 1; }
         HIPCK(c, launch_crop(s, deno, wo, W, H, C, nP, Wn->nHW));
         if (C == 3) {
             HIPCK(c, launch_color(s, deno, Hd->color_space, W * H, 0));

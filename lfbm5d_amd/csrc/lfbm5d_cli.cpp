@@ -98,6 +98,17 @@
  *                     it is an error (a gain changes the noise model and the clipping range), and so is any other value.  With a
  *                     ground truth LFBM5D_EQUALISE_ADD=<edge> (0 < edge <= 1) first multiplies the synthesised noisy views by a smooth
  *                     vignette, 1 at the centre view and <edge> at the corner views.  Unset, the output is unchanged;
+ *   LFBM5D_VIEW_SIGMA=auto | gains   one noise level per SAI (denoise_views_LF, run_bm5d.h; include/lfbm5d_views.h): every angular window
+ *                     is filtered with the root mean square of its views' levels, both steps as one job (LFBM3Ddenoising: every SAI with
+ *                     its own level, bm3d_views_LF).  `auto` takes the per-view blind estimate of the noisy light field where
+ *                     LFBM5D_SIGMA=auto takes the pooled one, after equalisation and impulse repair; the argument's sigma, or the
+ *                     pooled estimate, is only printed.  `gains` needs LFBM5D_EQUALISE and a numeric sigma (with LFBM5D_SIGMA=auto it is
+ *                     an error: use `auto`): sigma_v = sigma sqrt(mean over the channels of g^-2) for the gains that were divided out.
+ *                     Prints `Per-view noise levels: <n> SAIs, sigma <min>..<max> (pooled <rms>), from <estimate|gains>; window sigmas
+ *                     <min>..<max>`.  With LFBM5D_SIGMA=poisson*, LFBM5D_CLIP, LFBM5D_MISSING, LFBM5D_DEFECTS or LFBM5D_DETECT (their
+ *                     models and refinement steps assume one sigma) it is an error, and so is any other value.  With a ground truth
+ *                     LFBM5D_VIEW_SIGMA_ADD=<edge> (0 < edge <= 1) synthesises noise of sigma / g_v on view v in place of uniform
+ *                     noise, g the vignette of LFBM5D_EQUALISE_ADD: what a devignetted capture carries.  Unset, the output is unchanged;
  *   LFBM5D_REPORT_SSIM=1  the average SSIM next to every average PSNR on stdout and an SSIM block behind every PSNR block of the
  *                     results file, computed on the GPU on the images as the files hold them (cli_quality.h); any other value is an
  *                     error; unset, the output is unchanged.
@@ -302,7 +313,7 @@ void diff_LF(const vector<vector<float> >& A, const vector<vector<float> >& B, c
  * threads that start within one millisecond must not share one).  LFBM5D_SEED (tests, benchmarks) is ONE stream through the SAIs
  * in order: its uniforms are drawn in order, SAI by SAI, and only their Box-Muller transform is spread over the threads. */
 void add_noise_LF(const vector<vector<float> >& LF, const vector<unsigned>& mask, vector<vector<float> >& LF_noisy, float sigma,
-                  const double* pg = nullptr) {
+                  const double* pg = nullptr, const vector<double>* view_sigma = nullptr) {
     const char* seed = env("LFBM5D_SEED");
     if (pg) {   /* Poisson-Gaussian noise {a, b}: a * Poisson(y / a) + N(0, b), one <random> stream through the SAIs in order */
         timeval tp; gettimeofday(&tp, nullptr);
@@ -321,7 +332,10 @@ void add_noise_LF(const vector<vector<float> >& LF, const vector<unsigned>& mask
         }
         return;
     }
-    auto gauss = [sigma](double x, double y) { return (float)((double)sigma * sqrt(-2.0 * log(x)) * cos(2.0 * M_PI * y)); };
+    /* (LFBM5D_VIEW_SIGMA_ADD: SAI st draws with its own sigma) */
+    auto gauss = [sigma, view_sigma](size_t st, double x, double y) {
+        return (float)((view_sigma ? (*view_sigma)[st] : (double)sigma) * sqrt(-2.0 * log(x)) * cos(2.0 * M_PI * y));
+    };
     if (!seed) {
         parallel_sais((unsigned)LF.size(), [&](unsigned st) {
             if (!mask[st]) return true;
@@ -329,7 +343,7 @@ void add_noise_LF(const vector<vector<float> >& LF, const vector<unsigned>& mask
             Mt g(tp.tv_sec * 1000 + tp.tv_usec / 1000 + (unsigned long)getpid() + st);
             for (size_t q = 0; q < LF[st].size(); q++) {
                 const double x = g.res53(), y = g.res53();
-                LF_noisy[st][q] = LF[st][q] + gauss(x, y);
+                LF_noisy[st][q] = LF[st][q] + gauss(st, x, y);
             }
             return true;
         });
@@ -344,7 +358,7 @@ void add_noise_LF(const vector<vector<float> >& LF, const vector<unsigned>& mask
         for (size_t q = 0; q < 2 * n; q++) u[q] = g.res53();
         const unsigned parts = 16;
         parallel_sais(parts, [&](unsigned part) {
-            for (size_t q = n * part / parts; q < n * (part + 1) / parts; q++) LF_noisy[st][q] = LF[st][q] + gauss(u[2 * q], u[2 * q + 1]);
+            for (size_t q = n * part / parts; q < n * (part + 1) / parts; q++) LF_noisy[st][q] = LF[st][q] + gauss(st, u[2 * q], u[2 * q + 1]);
             return true;
         });
     }
@@ -679,15 +693,93 @@ bool equalise_mode(int& mode, double& add, int smode, bool gt) {
     return true;
 }
 
-/* LFBM5D_EQUALISE_ADD: view (s, t) times 1 - (1 - edge) rho^2, rho its angular distance from the centre, 1 at the corners */
-void add_vignette_LF(vector<vector<float> >& LF_noisy, const vector<unsigned>& mask, unsigned ang_major, unsigned aw, unsigned ah, double edge) {
+/* LFBM5D_VIEW_SIGMA / LFBM5D_VIEW_SIGMA_ADD: mode 0 when unset, 1 = auto, 2 = gains; add = 0 when unset; false (message printed) on a
+ * malformed value, a combination the header comment excludes, or LFBM5D_VIEW_SIGMA_ADD without a ground truth */
+bool view_sigma_mode(int& mode, double& add, int smode, bool gt) {
+    mode = 0; add = 0.0;
+    if (const char* e = env("LFBM5D_VIEW_SIGMA")) {
+        mode = !strcmp(e, "auto") ? 1 : !strcmp(e, "gains") ? 2 : 0;
+        if (!mode) {
+            cout << "LFBM5D_VIEW_SIGMA must be \"auto\" (estimate one noise level per view from the noisy light field) or \"gains\" (derive them "
+                    "from sigma and the gains of LFBM5D_EQUALISE), or unset; got \"" << e << "\"" << endl;
+            return false;
+        }
+        if (smode >= 2) {
+            cout << "LFBM5D_VIEW_SIGMA cannot be combined with LFBM5D_SIGMA=poisson (per-view signal-dependent models are not covered)" << endl;
+            return false;
+        }
+        if (env("LFBM5D_CLIP")) {
+            cout << "LFBM5D_VIEW_SIGMA cannot be combined with LFBM5D_CLIP (the clipped estimate and the declipping assume one sigma)" << endl;
+            return false;
+        }
+        if (env("LFBM5D_MISSING") || env("LFBM5D_DEFECTS") || env("LFBM5D_DETECT")) {
+            cout << "LFBM5D_VIEW_SIGMA cannot be combined with LFBM5D_MISSING, LFBM5D_DEFECTS or LFBM5D_DETECT (their refinement steps assume one sigma)" << endl;
+            return false;
+        }
+        if (mode == 2 && !env("LFBM5D_EQUALISE")) {
+            cout << "LFBM5D_VIEW_SIGMA=gains needs LFBM5D_EQUALISE (the gains it divides out)" << endl;
+            return false;
+        }
+        if (mode == 2 && smode == 1) {
+            cout << "LFBM5D_VIEW_SIGMA=gains needs a numeric sigma, not LFBM5D_SIGMA=auto: LFBM5D_VIEW_SIGMA=auto estimates every view's level" << endl;
+            return false;
+        }
+    }
+    if (const char* e = env("LFBM5D_VIEW_SIGMA_ADD")) {
+        char* q = nullptr;
+        add = strtod(e, &q);
+        if (q == e || *q || isspace((unsigned char)*e) || !(add > 0.0) || !(add <= 1.0)) {
+            cout << "LFBM5D_VIEW_SIGMA_ADD must be the vignette gain of the corner views, 0 < edge <= 1, or unset; got \"" << e << "\"" << endl;
+            return false;
+        }
+        if (!gt) { cout << "LFBM5D_VIEW_SIGMA_ADD needs a source light field to synthesise the noisy one from" << endl; return false; }
+        if (smode >= 2) { cout << "LFBM5D_VIEW_SIGMA_ADD cannot be combined with LFBM5D_SIGMA=poisson (the synthesised noise is Gaussian)" << endl; return false; }
+    }
+    return true;
+}
+
+/* the smooth vignette of LFBM5D_EQUALISE_ADD and LFBM5D_VIEW_SIGMA_ADD: view (s, t) gets 1 - (1 - edge) rho^2, rho its angular distance from
+ * the centre, 1 at the corners */
+double vignette_gain(unsigned s, unsigned t, unsigned aw, unsigned ah, double edge) {
     const double cs = (ah - 1) / 2.0, ct = (aw - 1) / 2.0, corner = cs * cs + ct * ct;
+    const double rho2 = corner > 0.0 ? ((s - cs) * (s - cs) + (t - ct) * (t - ct)) / corner : 0.0;
+    return 1.0 - (1.0 - edge) * rho2;
+}
+
+/* LFBM5D_VIEW_SIGMA_ADD: sigma_v = sigma / g_v */
+vector<double> vignette_sigmas(float sigma, unsigned ang_major, unsigned aw, unsigned ah, double edge) {
+    vector<double> out((size_t)aw * ah, 0.0);
+    for (unsigned s = 0; s < ah; s++)
+        for (unsigned t = 0; t < aw; t++)
+            out[ang_major == LFBM5D_ROWMAJOR ? s * aw + t : s + t * ah] = (double)sigma / vignette_gain(s, t, aw, ah, edge);
+    return out;
+}
+
+/* LFBM5D_VIEW_SIGMA: the line that reports the table the filter ran with */
+void print_view_sigmas(const vector<double>& table, const vector<unsigned>& mask, const vector<float>& window_sigmas, bool estimated) {
+    unsigned n = 0;
+    double lo = 0.0, hi = 0.0, sum = 0.0;
+    for (size_t st = 0; st < table.size(); st++) {
+        if (!mask[st]) continue;
+        lo = n ? std::min(lo, table[st]) : table[st]; hi = n ? std::max(hi, table[st]) : table[st];
+        sum += table[st] * table[st];
+        n++;
+    }
+    float wlo = 0.0f, whi = 0.0f;
+    for (size_t i = 0; i < window_sigmas.size(); i++) {
+        wlo = i ? std::min(wlo, window_sigmas[i]) : window_sigmas[i]; whi = i ? std::max(whi, window_sigmas[i]) : window_sigmas[i];
+    }
+    cout << endl << "Per-view noise levels: " << n << " SAIs, sigma " << lo << ".." << hi << " (pooled " << (n ? sqrt(sum / n) : 0.0) << "), from "
+         << (estimated ? "estimate" : "gains") << "; window sigmas " << wlo << ".." << whi << endl;
+}
+
+/* LFBM5D_EQUALISE_ADD: view (s, t) times its vignette gain */
+void add_vignette_LF(vector<vector<float> >& LF_noisy, const vector<unsigned>& mask, unsigned ang_major, unsigned aw, unsigned ah, double edge) {
     for (unsigned s = 0; s < ah; s++)
         for (unsigned t = 0; t < aw; t++) {
             const unsigned st = ang_major == LFBM5D_ROWMAJOR ? s * aw + t : s + t * ah;
             if (!mask[st]) continue;
-            const double rho2 = corner > 0.0 ? ((s - cs) * (s - cs) + (t - ct) * (t - ct)) / corner : 0.0;
-            const float g = (float)(1.0 - (1.0 - edge) * rho2);
+            const float g = (float)vignette_gain(s, t, aw, ah, edge);
             for (float& v : LF_noisy[st]) v = v * g;
         }
     cout << "Vignette [corner views x " << edge << "]" << endl;
@@ -916,6 +1008,8 @@ int main(int argc, char** argv) {
     int eq_mode = 0; double eq_add = 0.0;
     if (!equalise_mode(eq_mode, eq_add, smode, gt)) return EXIT_FAILURE;
     vector<double> eq_gains;
+    int vs_mode = 0; double vs_add = 0.0;
+    if (!view_sigma_mode(vs_mode, vs_add, smode, gt)) return EXIT_FAILURE;
     unsigned dsteps = 1;
     if (!disparity_steps_mode(dsteps, detect || !missing.empty() || eq_mode)) return EXIT_FAILURE;
     float occl = 0.0f;
@@ -935,9 +1029,11 @@ int main(int argc, char** argv) {
         cout << "Loading LF elapsed time = " << now_s() - t << "s." << endl;
         LF_noisy.assign(awh, vector<float>((size_t)W * H * C, 0.0f));
         if (smode == 3 || smode == 5) cout << endl << "Add noise [Poisson-Gaussian, a = " << pg[0] << ", b = " << pg[1] << "] ... " << flush;
+        else if (vs_add > 0.0) cout << endl << "Add noise [sigma = " << sigma << " / vignette, corner views x " << vs_add << "] ... " << flush;
         else cout << endl << "Add noise [sigma = " << sigma << "] ... " << flush;
         t = now_s();
-        add_noise_LF(LF, mask, LF_noisy, sigma, smode == 3 || smode == 5 ? pg : nullptr);
+        const vector<double> vs_sigmas = vs_add > 0.0 ? vignette_sigmas(sigma, ang_major, aw, ah, vs_add) : vector<double>();
+        add_noise_LF(LF, mask, LF_noisy, sigma, smode == 3 || smode == 5 ? pg : nullptr, vs_add > 0.0 ? &vs_sigmas : nullptr);
         cout << "done in " << now_s() - t << "s." << endl;
         if (eq_add > 0.0) add_vignette_LF(LF_noisy, mask, ang_major, aw, ah, eq_add);
         if (clip_add) clip_round_LF(LF_noisy, mask, clip_lo, clip_hi);
@@ -1005,6 +1101,15 @@ int main(int argc, char** argv) {
                         t2[0], t2[1], lambda, cs, nb_threads, sub) != EXIT_SUCCESS) return EXIT_FAILURE;
         if (pg_inverse_LF(pg[0], pg[1], LF_basic, mask, W, H, C) != EXIT_SUCCESS || pg_inverse_LF(pg[0], pg[1], LF_den, mask, W, H, C) != EXIT_SUCCESS)
             return EXIT_FAILURE;
+    } else
+    if (vs_mode) {   /* one noise level per SAI: every SAI is its own "window" */
+        vector<double> table;
+        if (vs_mode == 2 && views_from_gains((double)sigma, eq_gains, C, mask, table) != EXIT_SUCCESS) return EXIT_FAILURE;
+        if (bm3d_views_LF(table, LF_noisy, mask, LF_basic, LF_den, W, H, C, n[0], n[1], k[0], k[1], N[0], N[1], p[0], p[1], sd[0] != 0, sd[1] != 0,
+                          t2[0], t2[1], lambda, cs) != EXIT_SUCCESS) return EXIT_FAILURE;
+        vector<float> each;
+        for (size_t st = 0; st < table.size(); st++) if (mask[st]) each.push_back((float)table[st]);
+        print_view_sigmas(table, mask, each, vs_mode == 1);
     } else
     if (run_bm3d_LF(sigma, LF_noisy, mask, LF_basic, LF_den, W, H, C, n[0], n[1], k[0], k[1], N[0], N[1], p[0], p[1], sd[0] != 0, sd[1] != 0,
                     t2[0], t2[1], lambda, cs, nb_threads, sub) != EXIT_SUCCESS) return EXIT_FAILURE;
@@ -1096,6 +1201,8 @@ int main(int argc, char** argv) {
     int eq_mode = 0; double eq_add = 0.0;
     if (!equalise_mode(eq_mode, eq_add, smode, gt)) return EXIT_FAILURE;
     vector<double> eq_gains;
+    int vs_mode = 0; double vs_add = 0.0;
+    if (!view_sigma_mode(vs_mode, vs_add, smode, gt)) return EXIT_FAILURE;
     unsigned dsteps = 1;
     if (!disparity_steps_mode(dsteps, detect || !missing.empty() || eq_mode)) return EXIT_FAILURE;
     float occl = 0.0f;
@@ -1115,9 +1222,11 @@ int main(int argc, char** argv) {
         cout << "Loading LF elapsed time = " << now_s() - t << "s." << endl;
         LF_noisy.assign(awh, vector<float>((size_t)W * H * C, 0.0f));
         if (smode == 3 || smode == 5) cout << endl << "Add noise [Poisson-Gaussian, a = " << pg[0] << ", b = " << pg[1] << "] ... " << flush;
+        else if (vs_add > 0.0) cout << endl << "Add noise [sigma = " << sigma << " / vignette, corner views x " << vs_add << "] ... " << flush;
         else cout << endl << "Add noise [sigma = " << sigma << "] ... " << flush;
         t = now_s();
-        add_noise_LF(LF, mask, LF_noisy, sigma, smode == 3 || smode == 5 ? pg : nullptr);
+        const vector<double> vs_sigmas = vs_add > 0.0 ? vignette_sigmas(sigma, ang_major, aw, ah, vs_add) : vector<double>();
+        add_noise_LF(LF, mask, LF_noisy, sigma, smode == 3 || smode == 5 ? pg : nullptr, vs_add > 0.0 ? &vs_sigmas : nullptr);
         cout << "done in " << now_s() - t << "s." << endl;
         if (eq_add > 0.0) add_vignette_LF(LF_noisy, mask, ang_major, aw, ah, eq_add);
         if (clip_add) clip_round_LF(LF_noisy, mask, clip_lo, clip_hi);
@@ -1181,7 +1290,7 @@ int main(int argc, char** argv) {
      * inverse(estimate) between the calls: the two differ (0.015 dB on the test light field) because the reference's colour matrices are not
      * inverses of each other */
     const char* one_job_s = env("LFBM5D_ONE_JOB");
-    const bool one_job = smode >= 2 || clip_on || (one_job_s && *one_job_s && *one_job_s != '0');   /* the Poisson-Gaussian and the clipped path are one job */
+    const bool one_job = smode >= 2 || clip_on || vs_mode || (one_job_s && *one_job_s && *one_job_s != '0');   /* the Poisson-Gaussian, the clipped and the per-view path are one job */
     cout << endl << " ---> Running LFBM5D filter <--- " << endl << endl << (one_job ? "Steps 1 and 2 running as one job..." : "Step 1 running...") << endl;
     const double tb = now_s();
     double t1 = now_s();
@@ -1204,6 +1313,14 @@ int main(int argc, char** argv) {
                                nb_threads) != EXIT_SUCCESS) return EXIT_FAILURE;
         job = now_s() - t1;
         print_declipping(clip_lo, clip_hi, sigma);
+    } else if (vs_mode) {
+        vector<double> table; vector<float> window_sigmas;
+        if (vs_mode == 2 && views_from_gains((double)sigma, eq_gains, C, mask, table) != EXIT_SUCCESS) return EXIT_FAILURE;
+        if (denoise_views_LF(table, window_sigmas, lambda, LF_noisy, mask, LF_basic, LF_den, ang_major, aw, ah, anH, anW, W, H, C, N[0], nSim[0],
+                             nDisp[0], k[0], p[0], sd[0] != 0, t2[0], t4[0], t5[0], N[1], nSim[1], nDisp[1], k[1], p[1], sd[1] != 0, t2[1], t4[1],
+                             t5[1], cs, nb_threads) != EXIT_SUCCESS) return EXIT_FAILURE;
+        job = now_s() - t1;
+        print_view_sigmas(table, mask, window_sigmas, vs_mode == 1);
     } else if (one_job) {
         if (run_bm5d(sigma, lambda, LF_noisy, mask, LF_basic, LF_den, ang_major, aw, ah, anH, anW, W, H, C, N[0], nSim[0], nDisp[0], k[0], p[0],
                      sd[0] != 0, t2[0], t4[0], t5[0], N[1], nSim[1], nDisp[1], k[1], p[1], sd[1] != 0, t2[1], t4[1], t5[1], cs, nb_threads) != EXIT_SUCCESS)

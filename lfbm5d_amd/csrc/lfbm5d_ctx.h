@@ -106,6 +106,9 @@ struct lfbm5d_ctx {
     int pass_rank = 0, pass_world = 1;
     bool pass_reduce = false;
     std::vector<unsigned> last_windows;   /* processed SAI of every window of the last step, in order */
+    /* per-view noise levels (include/lfbm5d_views.h): the view table of the job that is running (empty: none; set and cleared by the
+     * lfbm5d_*_views_* entry points, lfbm5d_views.hip), and the sigma applied to every window of last_windows */
+    struct ViewSigmas { std::vector<double> table; std::vector<float> last; } views;
     lfbm5d_stats stats;
     /* per-pass work buffers (grow only) */
     DevBuf t_noisy, t_basic, t_tnum, t_tden, und_num, und_den;   /* tile mode: one tile of the window, the tiles' interiors */

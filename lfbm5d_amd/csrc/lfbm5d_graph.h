@@ -50,6 +50,20 @@ inline MaskedWindow mask_window(const plan::Window& w, const unsigned* h_mask) {
     return m;
 }
 
+/* The sigma of a window's passes: the job's own, or with a view table (include/lfbm5d_views.h) the window sigma. */
+inline float window_sigma(const lfbm5d_ctx* c, const lfbm5d_params* P, const plan::Window& w, const unsigned* h_mask) {
+    return c->views.table.empty() ? P->sigma : plan::window_sigma(c->views.table.data(), w, h_mask);
+}
+/* What lfbm5d_last_windows / lfbm5d_last_window_sigmas report after a completed graph: every node's processed SAI and sigma, in node
+ * order (windows of other ranks included: the sigma is a function of the table and the plan alone).  P, an: per step slot. */
+inline void record_graph_windows(lfbm5d_ctx* c, const plan::Graph& G, const plan::Grid& grid, const unsigned* h_mask,
+                                 const lfbm5d_params* const* P, const unsigned* an) {
+    for (const plan::Node& nd : G.nodes) {
+        c->last_windows.push_back(nd.pst);
+        c->views.last.push_back(window_sigma(c, P[nd.s], plan::window_at(grid, nd.ps, nd.pt, an[nd.s]), h_mask));
+    }
+}
+
 /* A lane = a context with its stream, per-pass work buffers and these window buffers (lane 0 is the job's own context).
  * lane_buffers sizes them for windows of win_floats floats; the padded sums only where the form keeps them. */
 struct Lane { lfbm5d_ctx* x; float* w_noisy; float* w_basic; float* w_num; float* w_den; unsigned* d_small; };

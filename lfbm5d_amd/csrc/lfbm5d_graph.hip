@@ -428,6 +428,7 @@ struct GraphRun {
                                      Lw.w_den, Lw.x->est.as<float>() + kEstLead, g.imgb, m.sl, W, H, C, g.nHW, Lw.d_small));
         lfbm5d_params Pw = *J.P[sl];
         Pw.tau_4D = nd.tau4;
+        Pw.sigma = window_sigma(c, J.P[sl], win, h_mask);
         Lw.x->gslot = sl;
         Lw.x->est_ready = true;
         if (direct) { Lw.x->direct.on = true; Lw.x->direct.num = S->g_num[sl]; Lw.x->direct.den = S->g_den[sl]; Lw.x->direct.lf_stride = img; Lw.x->direct.sai = m.sl; }

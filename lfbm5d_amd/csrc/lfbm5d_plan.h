@@ -22,6 +22,7 @@
 #define LFBM5D_PLAN_H
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 namespace lfbm5d {
@@ -71,6 +72,25 @@ inline Window window_at(const Grid& g, unsigned ps, unsigned pt, unsigned an) {
     for (unsigned si = 0; si < asw; si++)
         for (unsigned ti = 0; ti < asw; ti++) w.st[w.slots.index(si, ti)] = g.index(si + (unsigned)w.mins, ti + (unsigned)w.mint);
     return w;
+}
+
+/* The window sigma of include/lfbm5d_views.h: over the non-empty SAIs of the window in ascending slot order, (float)s if all their
+ * table values are the same double s, else (float)sqrt(mean of their squares), summed from +0 in that order in double.  0 for a window
+ * without a non-empty SAI.  The uniform branch is what makes a uniform table reproduce the plain job bit for bit: keep it. */
+inline float window_sigma(const double* sigma_sai, const Window& w, const unsigned* h_mask) {
+    double first = 0.0, sum = 0.0;
+    unsigned n = 0;
+    bool uniform = true;
+    for (unsigned st : w.st) {
+        if (h_mask && !h_mask[st]) continue;
+        const double v = sigma_sai[st];
+        if (n == 0) first = v;
+        else if (v != first) uniform = false;
+        sum += v * v;
+        n++;
+    }
+    if (n == 0) return 0.0f;
+    return uniform ? (float)first : (float)std::sqrt(sum / (double)n);
 }
 
 /* The sequence of windows a step processes, as the processed SAI of each: first the centre SAI if it is not empty, then

@@ -138,6 +138,7 @@ struct StepEngine {
         HIPCK(c, launch_symetrize_multi(s, g_den, img, L.w_den, imgb, m.sl, W, H, C, nHW));
         Pw = *P;
         Pw.tau_4D = tau_4D;
+        Pw.sigma = window_sigma(c, P, win, h_mask);   /* every pass of the window */
         unsigned rem_w = m.n_in;
         bool centre_next = m.mask_w[win.cst_w] != 0;
         std::vector<unsigned> h_tmp_w(Aw);
@@ -178,6 +179,7 @@ struct StepEngine {
         for (unsigned i = 0; i < Aw; i++) if (m.mask_w[i]) dirty.push_back(win.st[i]);
         c->stats.windows += 1;
         c->last_windows.push_back(grid.index(ps, pt));
+        c->views.last.push_back(Pw.sigma);
         return 0;
     }
 
@@ -321,7 +323,7 @@ int run_step(lfbm5d_ctx* c, int step, const lfbm5d_params* P, float* d_noisy, co
     /* sized for run_graph's use too (its lanes add kWinCounters words): a later, larger reserve would free the block the
      * engine's window buffers refer to */
     HIPCK(c, c->small.reserve((asize + 8 + kWinCounters) * sizeof(unsigned)));
-    c->last_windows.clear();
+    c->last_windows.clear(); c->views.last.clear();
     StepEngine E{c, step, P, h_mask, d_noisy, d_basic, d_out, grid, an, W, H, C};
     E.restart();
     if (lane_buffers(c, c, E.Aw * E.imgb, step == 2, true, asize, E.L)) return 1;
@@ -372,7 +374,8 @@ int run_step(lfbm5d_ctx* c, int step, const lfbm5d_params* P, float* d_noisy, co
         int complete = 1;
         if (E.run_as_graph(G, nranks, emu > 1, streamable ? io : nullptr, &complete)) return 1;
         if (complete) {
-            for (const plan::Node& nd : G.nodes) c->last_windows.push_back(nd.pst);
+            const unsigned an_of[1] = {an};
+            record_graph_windows(c, G, grid, h_mask, &P, an_of);
             graph_done = true;
         } else if (nranks > 1) {
             return fail(c, "a window needed more than its centre pass: set LFBM5D_STEP_SHARDING=rows for this light field");
@@ -473,7 +476,7 @@ static int run_denoise_whole(lfbm5d_ctx* c, const lfbm5d_params* P1, const lfbm5
         J.noisy[1] = c->n2.as<float>();
     }
     if (zeroed_sums(c, c, 2, asize * img, s, J.g_num, J.g_den)) return 1;
-    c->last_windows.clear();
+    c->last_windows.clear(); c->views.last.clear();
     int complete = 1;
     if (run_graph(c, J, G, h_mask, grid, W, H, C, nranks, emu > 1, &complete)) return 1;
     if (!complete) {
@@ -483,7 +486,7 @@ static int run_denoise_whole(lfbm5d_ctx* c, const lfbm5d_params* P1, const lfbm5
         HIPCK(c, hipMemcpyAsync(d_noisy, c->pristine.p, asize * img * sizeof(float), hipMemcpyDeviceToDevice, s));
         return two_calls();
     }
-    for (const plan::Node& nd : G.nodes) c->last_windows.push_back(nd.pst);
+    record_graph_windows(c, G, grid, h_mask, J.P, J.an);
     if (streamable) { HIPCK(c, hipStreamSynchronize(s)); return 0; }   /* (every SAI's outputs have been formed and delivered) */
     /* final estimate (bm5d.cpp:1106) and the closing inverse colour transforms of both steps' outputs (bm5d.cpp:1414-1418) */
     if (nranks == 1) HIPCK(c, launch_estimate_lf(s, J.g_num[1], J.g_den[1], d_basic, d_out, img, asize, d_mask));

@@ -1018,6 +1018,93 @@ extern "C" int lfbm5d_equalise_probe(const float* in_flat, const unsigned* mask,
     return 0;
 }
 
+/* run_bm5d with a view table (include/lfbm5d_views.h): the caller's vectors, one pointer per SAI */
+int denoise_views_LF(std::vector<double>& sigma_sai, std::vector<float>& window_sigmas, const float lambdaHard5D,
+                     std::vector<std::vector<float> >& LF_noisy, std::vector<unsigned>& LF_SAI_mask, std::vector<std::vector<float> >& LF_basic,
+                     std::vector<std::vector<float> >& LF_denoised, const unsigned ang_major, const unsigned awidth, const unsigned aheight,
+                     const unsigned anHard, const unsigned anWien, const unsigned width, const unsigned height, const unsigned chnls,
+                     const unsigned NHard, const unsigned nSimHard, const unsigned nDispHard, const unsigned kHard, const unsigned pHard,
+                     const bool useSDHard, const unsigned tau_2D_hard, unsigned tau_4D_hard, const unsigned tau_5D_hard, const unsigned NWien,
+                     const unsigned nSimWien, const unsigned nDispWien, const unsigned kWien, const unsigned pWien, const bool useSDWien,
+                     const unsigned tau_2D_wien, unsigned tau_4D_wien, const unsigned tau_5D_wien, const unsigned color_space,
+                     const unsigned nb_threads) {
+    const unsigned asize = awidth * aheight;
+    if (LF_noisy.size() != asize || LF_SAI_mask.size() != asize || (!sigma_sai.empty() && sigma_sai.size() != asize)) {
+        std::cout << "denoise_views_LF: light field, mask and view table must hold awidth*aheight SAIs" << std::endl;
+        return EXIT_FAILURE;
+    }
+    lfbm5d_ctx* ctx = context();
+    if (!ctx) return EXIT_FAILURE;
+    lfbm5d_set_tiles(ctx, tiles_for(nb_threads));
+    if (LF_basic.size() != asize) LF_basic.resize(asize);
+    if (LF_denoised.size() != asize) LF_denoised.resize(asize);
+    const size_t img = (size_t)width * height * chnls;
+    const std::vector<float*> noisy = sai_ptrs(LF_noisy, LF_SAI_mask, img, false), basic = sai_ptrs(LF_basic, LF_SAI_mask, img, true),
+                              den = sai_ptrs(LF_denoised, LF_SAI_mask, img, true);
+    if (!inputs_ok(noisy, LF_SAI_mask, "denoise_views_LF")) return EXIT_FAILURE;
+    const lfbm5d_params P1 = make(0.0f, lambdaHard5D, NHard, nSimHard, nDispHard, kHard, pHard, useSDHard, tau_2D_hard, tau_4D_hard, tau_5D_hard, color_space);
+    const lfbm5d_params P2 = make(0.0f, 0.0f, NWien, nSimWien, nDispWien, kWien, pWien, useSDWien, tau_2D_wien, tau_4D_wien, tau_5D_wien, color_space);
+    std::vector<double> used(asize, 0.0);
+    if (lfbm5d_denoise_views_host_sai(ctx, sigma_sai.empty() ? nullptr : sigma_sai.data(), used.data(), &P1, &P2, noisy.data(),
+                                      LF_SAI_mask.data(), basic.data(), den.data(), ang_major, awidth, aheight, anHard, anWien, width, height,
+                                      chnls) != 0) {
+        std::cout << "LFBM5D GPU backend: " << lfbm5d_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+    }
+    sigma_sai = used;
+    const int n = lfbm5d_last_window_sigmas(ctx, nullptr, 0);
+    window_sigmas.assign((size_t)std::max(n, 0), 0.0f);
+    if (n > 0) lfbm5d_last_window_sigmas(ctx, window_sigmas.data(), (unsigned)n);
+    return EXIT_SUCCESS;
+}
+
+int views_from_gains(const double sigma, const std::vector<double>& gains, const unsigned chnls, const std::vector<unsigned>& LF_SAI_mask,
+                     std::vector<double>& sigma_sai) {
+    const size_t asize = LF_SAI_mask.size();
+    if (gains.size() != 3 * asize || chnls < 1 || chnls > 3) {
+        std::cout << "views_from_gains: gains must hold 3 values per SAI of the mask, chnls 1..3" << std::endl;
+        return EXIT_FAILURE;
+    }
+    std::vector<float> g(asize * chnls);
+    for (size_t st = 0; st < asize; st++) for (unsigned c = 0; c < chnls; c++) g[st * chnls + c] = (float)gains[3 * st + c];
+    sigma_sai.assign(asize, 0.0);
+    if (lfbm5d_views_from_gains(sigma, g.data(), chnls, LF_SAI_mask.data(), (unsigned)asize, sigma_sai.data()) != 0) {
+        std::cout << lfbm5d_views_error() << std::endl;
+        return EXIT_FAILURE;
+    }
+    return EXIT_SUCCESS;
+}
+
+/* Test hook: denoise_views_LF on a vector<vector<float>> light field built from a flat copy [asize][chnls*height*width].  table [asize]
+ * or NULL (the estimate); used_out [asize]; hard / wien = {N, nSim, nDisp, k, p, useSD, tau_2D, tau_4D, tau_5D}; win_out [win_cap] receives
+ * the window sigmas, *n_win their count.  The light fields are copied to the non-NULL flat outputs. */
+extern "C" int lfbm5d_denoise_views_probe(const float* noisy_flat, const unsigned* mask, const double* table, double* used_out, float* noisy_out,
+                                          float* basic_out, float* denoised_out, unsigned ang_major, unsigned awidth, unsigned aheight,
+                                          unsigned anHard, unsigned anWien, unsigned width, unsigned height, unsigned chnls, float lambda,
+                                          const unsigned* hard, const unsigned* wien, unsigned color_space, float* win_out, unsigned win_cap,
+                                          unsigned* n_win) {
+    const size_t asize = (size_t)awidth * aheight, img = (size_t)width * height * chnls;
+    std::vector<unsigned> m(mask, mask + asize);
+    std::vector<std::vector<float> > LF_noisy(asize), LF_basic, LF_denoised;
+    for (size_t st = 0; st < asize; st++) if (m[st]) LF_noisy[st].assign(noisy_flat + st * img, noisy_flat + (st + 1) * img);
+    std::vector<double> t;
+    if (table) t.assign(table, table + asize);
+    std::vector<float> ws;
+    if (denoise_views_LF(t, ws, lambda, LF_noisy, m, LF_basic, LF_denoised, ang_major, awidth, aheight, anHard, anWien, width, height, chnls,
+                         hard[0], hard[1], hard[2], hard[3], hard[4], hard[5] != 0, hard[6], hard[7], hard[8],
+                         wien[0], wien[1], wien[2], wien[3], wien[4], wien[5] != 0, wien[6], wien[7], wien[8], color_space, 1) != EXIT_SUCCESS) return 1;
+    for (size_t st = 0; st < asize; st++) {
+        if (used_out) used_out[st] = t[st];
+        if (!m[st]) continue;
+        if (noisy_out) std::memcpy(noisy_out + st * img, LF_noisy[st].data(), img * sizeof(float));
+        if (basic_out) std::memcpy(basic_out + st * img, LF_basic[st].data(), img * sizeof(float));
+        if (denoised_out) std::memcpy(denoised_out + st * img, LF_denoised[st].data(), img * sizeof(float));
+    }
+    if (n_win) *n_win = (unsigned)ws.size();
+    for (size_t i = 0; i < ws.size() && i < win_cap && win_out; i++) win_out[i] = ws[i];
+    return 0;
+}
+
 /* run_bm3d_LF (src/bm3d_LF.h:10-35, bm3d_LF.cpp:75-125): BM3D on every SAI of the mask */
 #include "run_bm3d_lf.h"
 int run_bm3d_LF(const float sigma, std::vector<std::vector<float> >& LF_noisy, std::vector<unsigned>& LF_SAI_mask,
@@ -1052,6 +1139,51 @@ int run_bm3d_LF(const float sigma, std::vector<std::vector<float> >& LF_noisy, s
     unflatten(LF_noisy, LF_SAI_mask, img, noisy);
     unflatten(LF_basic, LF_SAI_mask, img, basic);
     unflatten(LF_denoised, LF_SAI_mask, img, den);
+    return EXIT_SUCCESS;
+}
+
+/* run_bm3d_LF with a view table: the device form on buffers staged here (the library has no host form of it) */
+int bm3d_views_LF(std::vector<double>& sigma_sai, std::vector<std::vector<float> >& LF_noisy, std::vector<unsigned>& LF_SAI_mask,
+                  std::vector<std::vector<float> >& LF_basic, std::vector<std::vector<float> >& LF_denoised, const unsigned width,
+                  const unsigned height, const unsigned chnls, const unsigned nHard, const unsigned nWien, const unsigned kHard,
+                  const unsigned kWien, const unsigned NHard, const unsigned NWien, const unsigned pHard, const unsigned pWien,
+                  const bool useSD_h, const bool useSD_w, const unsigned tau_2D_hard, const unsigned tau_2D_wien, const float lambdaHard3D,
+                  const unsigned color_space) {
+    const size_t asize = LF_noisy.size();
+    if (LF_SAI_mask.size() != asize || (!sigma_sai.empty() && sigma_sai.size() != asize)) {
+        std::cout << "bm3d_views_LF: light field, mask and view table must hold the same number of SAIs" << std::endl;
+        return EXIT_FAILURE;
+    }
+    lfbm5d_ctx* ctx = context();
+    if (!ctx) return EXIT_FAILURE;
+    if (LF_basic.size() != asize) LF_basic.resize(asize);
+    if (LF_denoised.size() != asize) LF_denoised.resize(asize);
+    const size_t img = (size_t)width * height * chnls, bytes = std::max<size_t>(1, asize * img) * sizeof(float);
+    Flat noisy, out = flat_alloc(asize * img);
+    flatten(LF_noisy, LF_SAI_mask, img, noisy);
+    lfbm5d_bm3d_params Hd, Wn;
+    Hd.sigma = 0.0f; Hd.lambda3D = lambdaHard3D; Hd.N = NHard; Hd.nHW = nHard; Hd.k = kHard; Hd.p = pHard;
+    Hd.useSD = useSD_h ? 1u : 0u; Hd.tau_2D = tau_2D_hard; Hd.color_space = color_space;
+    Wn = Hd; Wn.N = NWien; Wn.nHW = nWien; Wn.k = kWien; Wn.p = pWien; Wn.useSD = useSD_w ? 1u : 0u; Wn.tau_2D = tau_2D_wien;
+    struct Dev { void* p = nullptr; ~Dev() { if (p) lfbm5d_free(p); } } dn, db, dd;
+    if (lfbm5d_malloc(&dn.p, bytes) || lfbm5d_malloc(&db.p, bytes) || lfbm5d_malloc(&dd.p, bytes) || lfbm5d_memcpy_h2d(dn.p, noisy.get(), asize * img * sizeof(float))) {
+        std::cout << "bm3d_views_LF: no device memory for the light fields" << std::endl;
+        return EXIT_FAILURE;
+    }
+    std::vector<double> used(asize, 0.0);
+    std::cout << " - > Running BM3D filter on every SAI with its own sigma (GPU)" << std::endl;
+    if (lfbm5d_bm3d_lf_views_device(ctx, sigma_sai.empty() ? nullptr : sigma_sai.data(), used.data(), &Hd, &Wn, (float*)dn.p, LF_SAI_mask.data(),
+                                    (float*)db.p, (float*)dd.p, (unsigned)asize, width, height, chnls) != 0) {
+        std::cout << "LFBM5D GPU backend: " << lfbm5d_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+    }
+    sigma_sai = used;
+    std::vector<std::vector<float> >* const dst[3] = {&LF_noisy, &LF_basic, &LF_denoised};
+    void* const src[3] = {dn.p, db.p, dd.p};
+    for (int i = 0; i < 3; i++) {
+        if (lfbm5d_memcpy_d2h(out.get(), src[i], asize * img * sizeof(float))) { std::cout << "bm3d_views_LF: device-to-host copy failed" << std::endl; return EXIT_FAILURE; }
+        unflatten(*dst[i], LF_SAI_mask, img, out);
+    }
     return EXIT_SUCCESS;
 }
 

@@ -535,6 +535,61 @@ int apply_gains_LF(
 ,   const unsigned chnls
 );
 
+//! Per-view noise levels -- not in the reference: run_bm5d with one noise level per SAI (lfbm5d_denoise_views_host_sai,
+//! include/lfbm5d_views.h).  sigma_sai: one value per SAI in the units of `sigma`, or empty: the per-SAI blind estimate of LF_noisy is
+//! taken first; on return it holds the table that was applied (0 for empty SAIs).  Every angular window runs with the root mean square
+//! of its views' levels (their common value where they agree).  window_sigmas receives the sigma of every window that ran, the first
+//! step's windows, then the second's.  Everything else as run_bm5d.  Returns EXIT_SUCCESS, or EXIT_FAILURE with the message on stdout.
+int denoise_views_LF(
+    std::vector<double> &sigma_sai
+,   std::vector<float> &window_sigmas
+,   const float lambdaHard5D
+,   std::vector<std::vector<float> > &LF_noisy
+,   std::vector<unsigned> &LF_SAI_mask
+,   std::vector<std::vector<float> > &LF_basic
+,   std::vector<std::vector<float> > &LF_denoised
+,   const unsigned ang_major
+,   const unsigned awidth
+,   const unsigned aheight
+,   const unsigned anHard
+,   const unsigned anWien
+,   const unsigned width
+,   const unsigned height
+,   const unsigned chnls
+,   const unsigned NHard, const unsigned nSimHard, const unsigned nDispHard, const unsigned kHard, const unsigned pHard
+,   const bool useSDHard, const unsigned tau_2D_hard, unsigned tau_4D_hard, const unsigned tau_5D_hard
+,   const unsigned NWien, const unsigned nSimWien, const unsigned nDispWien, const unsigned kWien, const unsigned pWien
+,   const bool useSDWien, const unsigned tau_2D_wien, unsigned tau_4D_wien, const unsigned tau_5D_wien
+,   const unsigned color_space
+,   const unsigned nb_threads
+);
+
+//! The view table equalisation leaves behind: sigma_v = sigma sqrt(mean_c g_{v,c}^-2) over the stored channels (lfbm5d_views_from_gains);
+//! `gains` holds 3 doubles per SAI, as equalise_LF returns them.  Host only.  Returns EXIT_SUCCESS, or EXIT_FAILURE with the message on
+//! stdout.
+int views_from_gains(
+    const double sigma
+,   const std::vector<double> &gains
+,   const unsigned chnls
+,   const std::vector<unsigned> &LF_SAI_mask
+,   std::vector<double> &sigma_sai
+);
+
+//! run_bm3d_LF (run_bm3d_lf.h) with one noise level per SAI (lfbm5d_bm3d_lf_views_device): SAI v is filtered with sigma_sai[v] in both
+//! steps.  sigma_sai as for denoise_views_LF.
+int bm3d_views_LF(
+    std::vector<double> &sigma_sai
+,   std::vector<std::vector<float> > &LF_noisy
+,   std::vector<unsigned> &LF_SAI_mask
+,   std::vector<std::vector<float> > &LF_basic
+,   std::vector<std::vector<float> > &LF_denoised
+,   const unsigned width, const unsigned height, const unsigned chnls
+,   const unsigned nHard, const unsigned nWien, const unsigned kHard, const unsigned kWien
+,   const unsigned NHard, const unsigned NWien, const unsigned pHard, const unsigned pWien
+,   const bool useSD_h, const bool useSD_w, const unsigned tau_2D_hard, const unsigned tau_2D_wien
+,   const float lambdaHard3D, const unsigned color_space
+);
+
 //! Super-resolution -- not in the reference's master branch: the scheme of SR-LFBM5D (iterative back-projection regularised by the
 //! hard-thresholding step above) with the operators of include/lfbm5d.h, on the GPU (lfbm5d_superres_host_sai).  LF_low holds
 //! width x height SAIs and is only read; LF_high is (re)sized to scale*width x scale*height SAIs and filled.  kernel: 0 = bicubic,

@@ -112,6 +112,24 @@ def add_noise_mt19937(clean, sigma, seed=1, out=None):
     return res
 
 
+def add_view_noise(clean, sigma_sai, seed=1):
+    """Additive white Gaussian noise of standard deviation sigma_sai[v] on view v of `clean` ([A][...]): the generator, its seeding and
+    the two draws per sample of add_noise_mt19937 -- ONE MT19937 stream, drawn SAI after SAI in memory order -- with the SAI's own sigma
+    in z = sigma_v * sqrt(-2 ln a) * cos(2 pi b).  A uniform table returns add_noise_mt19937's result.  Returns float32."""
+    clean = np.ascontiguousarray(clean, dtype=np.float32)
+    sig = np.asarray(sigma_sai, dtype=np.float64).reshape(-1)
+    if clean.ndim < 1 or sig.size != clean.shape[0]:
+        raise ValueError("add_view_noise: sigma_sai needs one value per view")
+    res = np.empty_like(clean)
+    rs = np.random.RandomState(int(seed) & 0xFFFFFFFF)
+    for v in range(clean.shape[0]):
+        n = clean[v].size
+        u = rs.random_sample(2 * n)
+        z = float(sig[v]) * np.sqrt(-2.0 * np.log(u[0::2])) * np.cos(2.0 * np.pi * u[1::2])
+        res[v] = clean[v] + z.astype(np.float32).reshape(clean[v].shape)
+    return res
+
+
 def add_poisson_gaussian(clean, a, b, seed=1):
     """Poisson-Gaussian noise var(z | y) = a y + b on `clean` (any shape, nominally 0..255) from numpy's default_rng(seed):
     a * poisson(clean / a) + normal(0, sqrt(b)); a = 0 gives the Gaussian part alone.  Negative values of `clean` count as 0 for the
