@@ -972,6 +972,35 @@ int lfbm5d_last_group_list(lfbm5d_ctx* ctx, unsigned* n, unsigned* out, unsigned
  *       layout [slot][(2 nDisp+1)^2][strip][table row + lane][64], stereo_table_stride. */
 int lfbm5d_last_scan_version(const lfbm5d_ctx* ctx);
 
+/* The aggregation launch of a core pass (core:484-528) alone, on buffers the caller supplies: what a pass hands its aggregation
+ * kernel, spelled out.  For the tests that predict num / den bit for bit (tests/agg_model.py).  Device pointers unless marked host. */
+typedef struct lfbm5d_agg_debug {
+    float* num;                 /* [A][C][Hb][Wb] sums of the padded window, added to in place; direct form: [SAI][C][H][W], lf_stride apart */
+    float* den;
+    const float* filt;          /* filtered patches of the launch's groups: [g - ref_begin][N][A][C][k*k], or SAI-major [A][g - ref_begin][N][C][k*k] */
+    const float* wgt;           /* [n_refs_total][C] group weights */
+    const unsigned* aggpos;     /* [A][n_refs_total][N] (row << 16) | column of every patch in the padded window, 0xffffffff: absent; 16-byte aligned */
+    const unsigned* mask;       /* host, [A]: non-zero = the SAI of this slot is there */
+    const unsigned* proc;       /* host, [A]: non-zero = already processed (skipped) */
+    const unsigned* sai;        /* host, [A]: direct form, slot -> SAI of the light field (else unused, may be NULL) */
+    unsigned long long filt_sai_stride;   /* 0: group-major; > 0: SAI-major, floats per SAI */
+    unsigned long long filt_bytes;        /* size of filt */
+    unsigned long long lf_stride;         /* direct form: floats per SAI of num / den */
+    unsigned long long sums_floats;       /* size of num and of den, */
+    unsigned long long wgt_floats;        /* ... of wgt */
+    unsigned long long aggpos_words;      /* ... and of aggpos: the geometry below is checked against them */
+    unsigned n_refs_total;      /* reference patches of the pass (regular grid: n_ref_rows * n_ref_cols) */
+    unsigned ref_begin, n_groups;   /* the launch's groups: whole rows of the regular grid, any slice of an irregular list */
+    unsigned n_ref_rows, n_ref_cols;
+    unsigned Wb, Hb, C, A, k, N, pst, p, nSim, nDisp;
+    unsigned irregular;         /* the reference list is not the regular grid (nHW + i p, forced last index) */
+    unsigned wchan0;            /* every channel takes channel 0's weight */
+    unsigned direct;            /* tiles over the interior only, num / den are the light field's */
+} lfbm5d_agg_debug;
+/* Checks the arguments against what the kernel assumes (message via lfbm5d_last_error, nothing launched), then runs the launch on
+ * the context's stream with the context's options (agg_64bit, agg_scalar_scan) and the Kaiser window of patch size k, and waits. */
+int lfbm5d_debug_aggregate(lfbm5d_ctx* ctx, const lfbm5d_agg_debug* args);
+
 /* ---- device memory helpers so hosts without a HIP binding (ctypes, cgo, JNI) can stage data ---- */
 int lfbm5d_malloc(void** dptr, size_t bytes);
 int lfbm5d_free(void* dptr);

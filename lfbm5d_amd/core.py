@@ -54,6 +54,14 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class AggDebugStruct(C.Structure):
+    """lfbm5d_agg_debug: the aggregation launch of a core pass on buffers the caller supplies (include/lfbm5d.h)."""
+    _fields_ = ([(n, C.c_void_p) for n in ("num", "den", "filt", "wgt", "aggpos", "mask", "proc", "sai")]
+                + [(n, C.c_ulonglong) for n in ("filt_sai_stride", "filt_bytes", "lf_stride", "sums_floats", "wgt_floats", "aggpos_words")]
+                + [(n, C.c_uint) for n in ("n_refs_total", "ref_begin", "n_groups", "n_ref_rows", "n_ref_cols", "Wb", "Hb", "C", "A", "k",
+                                           "N", "pst", "p", "nSim", "nDisp", "irregular", "wchan0", "direct")])
+
+
 class NoiseLevelStruct(C.Structure):
     """lfbm5d_noise_level: the blind noise-level estimate (include/lfbm5d.h)."""
     _fields_ = [("sigma", C.c_double), ("sigma_channel", C.c_double * 3), ("components", C.c_uint), ("patch", C.c_uint),
@@ -485,6 +493,8 @@ def lib():
     L.lfbm5d_last_scores.restype = C.c_size_t
     L.lfbm5d_last_scan_version.argtypes = [vp]
     L.lfbm5d_last_scan_version.restype = C.c_int
+    if hasattr(L, "lfbm5d_debug_aggregate"):   # (absent from older builds loaded through LFBM5D_HIP_LIB for A/B runs)
+        L.lfbm5d_debug_aggregate.argtypes = [vp, C.POINTER(AggDebugStruct)]
     if hasattr(L, "lfbm5d_noise_level_device"):   # (absent from older builds loaded through LFBM5D_HIP_LIB for A/B runs)
         dp, np_ = C.POINTER(C.c_double), C.POINTER(NoiseLevelStruct)
         L.lfbm5d_noise_level_device.argtypes = [vp, fp, up] + [C.c_uint] * 5 + [np_, dp, dp]
@@ -2097,6 +2107,39 @@ class Context:
 
     def last_scan_version(self):
         return int(self._L.lfbm5d_last_scan_version(self._h))
+
+    def debug_aggregate(self, num, den, filt, wgt, aggpos, mask, proc, *, n_refs_total, ref_begin, n_groups, n_ref_rows, n_ref_cols,
+                        Wb, Hb, C_, A, k, N, pst, p, nSim, nDisp, filt_sai_stride=0, filt_bytes=None, irregular=0, wchan0=0,
+                        direct=0, lf_stride=0, sai=None):
+        """lfbm5d_debug_aggregate: the aggregation launch alone.  num, den, filt, wgt: float32 CUDA tensors, aggpos: an int32 CUDA
+        tensor holding the uint32 words; num and den are added to in place.  mask, proc, sai: sequences of A integers.  A None entry
+        among the tensors goes to the library as a NULL pointer (which it refuses)."""
+        import torch
+
+        def ptr(t, dtype):
+            if t is None:
+                return None, 0
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+                raise LfBm5dError("debug_aggregate takes contiguous CUDA tensors: float32 values, int32 positions")
+            torch.cuda.current_stream(t.device).synchronize()
+            return t.data_ptr(), t.numel()
+
+        a = AggDebugStruct()
+        (a.num, n_num), (a.den, n_den) = ptr(num, torch.float32), ptr(den, torch.float32)
+        a.filt, n_filt = ptr(filt, torch.float32)
+        a.wgt, a.wgt_floats = ptr(wgt, torch.float32)
+        a.aggpos, a.aggpos_words = ptr(aggpos, torch.int32)
+        a.sums_floats = min(n_num, n_den)
+        a.filt_bytes = 4 * n_filt if filt_bytes is None else min(int(filt_bytes), 4 * n_filt)
+        keep = [None if x is None else _u32(x) for x in (mask, proc, sai)]
+        a.mask, a.proc, a.sai = [None if x is None else x.ctypes.data for x in keep]
+        if any(x is not None and x.size < A for x in keep):
+            raise LfBm5dError("debug_aggregate: mask, proc and sai hold one entry per SAI slot")
+        a.filt_sai_stride, a.lf_stride = int(filt_sai_stride), int(lf_stride)
+        a.n_refs_total, a.ref_begin, a.n_groups, a.n_ref_rows, a.n_ref_cols = n_refs_total, ref_begin, n_groups, n_ref_rows, n_ref_cols
+        a.Wb, a.Hb, a.C, a.A, a.k, a.N, a.pst, a.p, a.nSim, a.nDisp = Wb, Hb, C_, A, k, N, pst, p, nSim, nDisp
+        a.irregular, a.wchan0, a.direct = int(irregular), int(wchan0), int(direct)
+        self._ck(self._L.lfbm5d_debug_aggregate(self._h, C.byref(a)))
 
 
 _default_ctx = None

@@ -84,6 +84,7 @@ void lfbm5d_destroy(lfbm5d_ctx* c) {
     c->inp.stats.release(); c->inp.state[0].release(); c->inp.state[1].release(); c->inp.flags.release();
     c->view.table.release(); c->view.stats.release(); c->view.disp.release(); c->view.set.release();
     c->consist.table.release(); c->consist.stats.release(); c->consist.pred.release(); c->consist.disp.release(); c->consist.flags.release();
+    c->dbg_agg.tb.release();
     c->photo.table.release(); c->photo.sweep_table.release(); c->photo.stats.release(); c->photo.pred.release(); c->photo.disp.release(); c->photo.x.release();
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     if (c->h_small) (void)hipHostFree(c->h_small);
@@ -672,6 +673,80 @@ size_t lfbm5d_last_scores(lfbm5d_ctx* c, float* h_scores, size_t n_floats) {
 }
 
 int lfbm5d_last_scan_version(const lfbm5d_ctx* c) { return c ? c->last_scan_version : 0; }
+
+int lfbm5d_debug_aggregate(lfbm5d_ctx* c, const lfbm5d_agg_debug* d) {
+    if (!c) return 1;
+    if (!d) return fail(c, "debug_aggregate: no arguments");
+    typedef unsigned long long u64;
+    /* what k_aggregate takes for granted (pass_impl guarantees it by construction) */
+    if (!d->num || !d->den || !d->filt || !d->wgt || !d->aggpos || !d->mask || !d->proc) return fail(c, "debug_aggregate: NULL pointer");
+    if (d->direct && !d->sai) return fail(c, "debug_aggregate: NULL pointer (direct form without a slot-to-SAI list)");
+    if (!is_pow2(d->N) || d->N > (unsigned)kMaxN3) return fail(c, "debug_aggregate: N must be a power of two <= 32");
+    if (d->k < 2 || d->k > (unsigned)kMaxK) return fail(c, "debug_aggregate: patch size k outside 2..32");
+    if (d->C != 1 && d->C != 3) return fail(c, "debug_aggregate: chnls must be 1 or 3");
+    if (d->A < 1 || d->A > (unsigned)kBigA || d->pst >= d->A) return fail(c, "debug_aggregate: A outside 1..289 or pst outside the window");
+    if (d->Wb > 65535u || d->Hb > 65535u) return fail(c, "debug_aggregate: Wb and Hb must be at most 65535 (positions are 16-bit pairs)");
+    if (d->nSim < 1 || d->nSim > 48 || d->nDisp > 24 || d->p < 1) return fail(c, "debug_aggregate: bad search window / step");
+    const unsigned nHW = d->nSim + d->nDisp, k2 = d->k * d->k;
+    if (d->Wb < 2 * nHW + d->k + 1 || d->Hb < 2 * nHW + d->k + 1) return fail(c, "debug_aggregate: window smaller than 2 nHW + k + 1");
+    if (!d->n_groups || d->ref_begin > d->n_refs_total || d->n_groups > d->n_refs_total - d->ref_begin)
+        return fail(c, "debug_aggregate: groups [ref_begin, ref_begin + n_groups) outside the reference list");
+    if (!d->irregular) {   /* the kernel derives its candidate ranges from the grid's geometry: the counts must be that grid's */
+        std::vector<unsigned> rows, cols;
+        ind_init(rows, d->Hb - d->k + 1, nHW, d->p);
+        ind_init(cols, d->Wb - d->k + 1, nHW, d->p);
+        if (d->n_ref_rows != rows.size() || d->n_ref_cols != cols.size() || (u64)d->n_ref_rows * d->n_ref_cols != d->n_refs_total)
+            return fail(c, "debug_aggregate: n_ref_rows / n_ref_cols / n_refs_total are not the reference grid of this window");
+        if (d->ref_begin % d->n_ref_cols || d->n_groups % d->n_ref_cols) return fail(c, "debug_aggregate: a launch on the regular grid covers whole rows");
+    }
+    /* sizes: the gathers of the 64-bit form (agg_64bit) are not bounds-checked by a buffer resource */
+    const u64 patch = (u64)d->C * k2, launch_patches = (u64)d->n_groups * d->N;
+    if (launch_patches * (d->filt_sai_stride ? 1u : d->A) * patch >= (1ull << 32)) return fail(c, "debug_aggregate: patch offsets beyond 32 bits");
+    if (d->filt_sai_stride ? (d->filt_sai_stride < launch_patches * patch || d->filt_bytes / sizeof(float) < d->filt_sai_stride * d->A)
+                           : d->filt_bytes / sizeof(float) < launch_patches * d->A * patch)
+        return fail(c, "debug_aggregate: filt is smaller than the launch's patches");
+    if (d->wgt_floats < (u64)d->n_refs_total * d->C) return fail(c, "debug_aggregate: wgt is smaller than [n_refs_total][C]");
+    if (d->aggpos_words < (u64)d->A * d->n_refs_total * d->N) return fail(c, "debug_aggregate: aggpos is smaller than [A][n_refs_total][N]");
+    if ((uintptr_t)d->aggpos % 16) return fail(c, "debug_aggregate: aggpos must be 16-byte aligned");
+    const u64 plane = d->direct ? (u64)(d->Wb - 2 * nHW) * (d->Hb - 2 * nHW) : (u64)d->Wb * d->Hb;
+    if (d->direct) {
+        if (d->lf_stride < d->C * plane) return fail(c, "debug_aggregate: lf_stride smaller than one SAI");
+        for (unsigned st = 0; st < d->A; st++)
+            if (d->sums_floats < d->C * plane || (u64)d->sai[st] > (d->sums_floats - d->C * plane) / d->lf_stride)
+                return fail(c, "debug_aggregate: num / den are smaller than the light field the SAI list addresses");
+    } else if (d->sums_floats < (u64)d->A * d->C * plane) return fail(c, "debug_aggregate: num / den are smaller than [A][C][Hb][Wb]");
+
+    (void)hipSetDevice(c->device);
+    if (c->dbg_agg.k != d->k) {   /* the product's own tables for this patch size: the Kaiser window is all the kernel reads of them */
+        GroupTables tb;
+        build_tables(tb, d->k, 3, 3);
+        HIPCK(c, c->dbg_agg.tb.reserve(sizeof(GroupTables)));
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        HIPCK(c, hipMemcpy(c->dbg_agg.tb.p, &tb, sizeof(tb), hipMemcpyHostToDevice));
+        c->dbg_agg.k = d->k;
+    }
+    AggArgs aa;
+    std::memset(&aa, 0, sizeof(aa));
+    aa.num = d->num; aa.den = d->den; aa.filt = d->filt; aa.filt_sai_stride = d->filt_sai_stride; aa.filt_bytes = d->filt_bytes;
+    aa.wgt = d->wgt; aa.aggpos = d->aggpos; aa.n_refs_total = d->n_refs_total; aa.tb = c->dbg_agg.tb.as<GroupTables>();
+    aa.ref_begin = d->ref_begin; aa.n_groups = d->n_groups; aa.n_ref_rows = d->n_ref_rows; aa.n_ref_cols = d->n_ref_cols;
+    aa.Wb = d->Wb; aa.Hb = d->Hb; aa.C = d->C; aa.A = d->A; aa.k = d->k; aa.N = d->N; aa.pst = d->pst; aa.p = d->p;
+    aa.nHW = nHW; aa.nSim = d->nSim; aa.nDisp = d->nDisp;
+    aa.mask_bits = sai_mask_none(); aa.proc_bits = sai_mask_none();
+    for (unsigned st = 0; st < d->A; st++) {
+        if (d->mask[st]) aa.mask_bits.set(st);
+        if (d->proc[st]) aa.proc_bits.set(st);
+    }
+    aa.irregular = d->irregular ? 1u : 0u; aa.wchan0 = d->wchan0 ? 1u : 0u;
+    aa.opt = c->opt->kernels;
+    if (d->direct) {
+        aa.direct = 1u; aa.lf_stride = d->lf_stride; aa.sai.n = d->A;
+        for (unsigned st = 0; st < d->A; st++) aa.sai.st[st] = d->sai[st];
+    }
+    HIPCK(c, launch_aggregate(c->stream, aa));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
 
 int lfbm5d_malloc(void** dptr, size_t bytes) { return hipMalloc(dptr, bytes) == hipSuccess ? 0 : 1; }
 int lfbm5d_free(void* dptr) { return hipFree(dptr) == hipSuccess ? 0 : 1; }

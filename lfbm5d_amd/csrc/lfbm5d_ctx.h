@@ -193,6 +193,8 @@ struct lfbm5d_ctx {
     /* ... whose score table was not filled in front of the table kernel (pass_impl): lfbm5d_last_scores writes `fill` into the
      * entries that kernel left out before it copies the table (launch_scores_patch), once */
     struct UnfilledScores { bool pending = false; unsigned n_rows = 0, n_cols = 0, W = 0, nSim = 0, nHW = 0, p = 0, last_r = 0, last_c = 0; float fill = 0; } unfilled;
+    /* lfbm5d_debug_aggregate: the transform tables (build_tables) of patch size `k`, apart from the passes' cached ones */
+    struct DebugAgg { DevBuf tb; unsigned k = 0; } dbg_agg;
 };
 
 namespace lfbm5d_host {
