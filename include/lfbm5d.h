@@ -1001,6 +1001,44 @@ typedef struct lfbm5d_agg_debug {
  * the context's stream with the context's options (agg_64bit, agg_scalar_scan) and the Kaiser window of patch size k, and waits. */
 int lfbm5d_debug_aggregate(lfbm5d_ctx* ctx, const lfbm5d_agg_debug* args);
 
+/* The group launch of a core pass (core:277-481 / :1054-1282) alone: gather, transforms, shrinkage, inverses and group weights on
+ * block-matching tables the caller supplies.  For the tests that compare every filtered patch with a model of the chain
+ * (tests/group_model.py).  Device pointers unless marked host. */
+typedef struct lfbm5d_group_debug {
+    const float* noisy;         /* [A][C][Hb][Wb] the padded window */
+    const float* basic;         /* the same of the pilot: step 2 only (else unused, may be NULL) */
+    const unsigned* refs;       /* [n_refs_total] reference patches, flat positions i * Wb + j */
+    const unsigned* self_idx;   /* [n_refs_total][N] the stack of every reference patch in the processed SAI */
+    const unsigned* self_cnt;   /* [n_refs_total] its size: a power of two in 1..N */
+    const unsigned* best;       /* [A][Wb*Hb] disparity match of every position (entry pst unused) */
+    const unsigned char* shape; /* [A][Wb*Hb] non-zero: the SAI belongs to the angular shape of the reference patch at this position */
+    float* filt;                /* out: the launch's groups [g - ref_begin][N][A][C][k*k], or SAI-major [A][g - ref_begin][N][C][k*k] */
+    float* wgt;                 /* out: [n_refs_total][C], the launch's rows are written */
+    unsigned* aggpos;           /* out: [A][n_refs_total][N], (row << 16) | column or 0xffffffff */
+    unsigned long long* counters;   /* host, out: [2] what the launch counted: sum of the stack sizes, shape-adaptive groups */
+    const unsigned* mask;       /* host, [A]: non-zero = the SAI of this slot is there */
+    const lfbm5d_params* params;   /* host: the pass's parameters (sigma, lambda, N, k, useSD, transforms, colour space) */
+    char* kernels;              /* host, out (may be NULL): the kernels launched, in order, names joined by '+' */
+    unsigned long long filt_sai_stride;   /* 0: group-major; > 0: SAI-major, floats per SAI (general kernels only) */
+    unsigned long long image_floats;      /* size of noisy (and basic), */
+    unsigned long long table_words;       /* ... of best and of shape (entries), */
+    unsigned long long filt_floats;       /* ... of filt, */
+    unsigned long long wgt_floats;        /* ... of wgt */
+    unsigned long long aggpos_words;      /* ... and of aggpos: the geometry below is checked against them */
+    unsigned long long kernels_cap;       /* bytes behind `kernels` (the text is cut to fit, always terminated) */
+    unsigned step;              /* 1: hard thresholding, 2: Wiener */
+    unsigned aw, ah;            /* the angular window, A = aw * ah */
+    unsigned Wb, Hb, C, pst;
+    unsigned fill_quirk;        /* 1 as in a centre pass: patches at columns >= Wb - k read as zeros; 0 as in a subset pass */
+    unsigned n_refs_total;
+    unsigned ref_begin, n_groups;   /* the launch's groups */
+    unsigned bm3d;              /* the per-SAI BM3D arithmetic (A = 1) */
+} lfbm5d_group_debug;
+/* Checks the arguments and the tables against what the kernels assume (message via lfbm5d_last_error, nothing launched), then runs
+ * launch_group as a pass does -- same thresholds, lambda rule, sigma table, scratch and options of the context -- on the context's
+ * stream, and waits.  The group list of the launch is read with lfbm5d_last_group_list. */
+int lfbm5d_debug_group(lfbm5d_ctx* ctx, const lfbm5d_group_debug* args);
+
 /* ---- device memory helpers so hosts without a HIP binding (ctypes, cgo, JNI) can stage data ---- */
 int lfbm5d_malloc(void** dptr, size_t bytes);
 int lfbm5d_free(void* dptr);

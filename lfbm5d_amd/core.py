@@ -62,6 +62,16 @@ class AggDebugStruct(C.Structure):
                                            "N", "pst", "p", "nSim", "nDisp", "irregular", "wchan0", "direct")])
 
 
+class GroupDebugStruct(C.Structure):
+    """lfbm5d_group_debug: the group launch of a core pass on tables and buffers the caller supplies (include/lfbm5d.h)."""
+    _fields_ = ([(n, C.c_void_p) for n in ("noisy", "basic", "refs", "self_idx", "self_cnt", "best", "shape", "filt", "wgt", "aggpos",
+                                           "counters", "mask", "params", "kernels")]
+                + [(n, C.c_ulonglong) for n in ("filt_sai_stride", "image_floats", "table_words", "filt_floats", "wgt_floats",
+                                                "aggpos_words", "kernels_cap")]
+                + [(n, C.c_uint) for n in ("step", "aw", "ah", "Wb", "Hb", "C", "pst", "fill_quirk", "n_refs_total", "ref_begin",
+                                           "n_groups", "bm3d")])
+
+
 class NoiseLevelStruct(C.Structure):
     """lfbm5d_noise_level: the blind noise-level estimate (include/lfbm5d.h)."""
     _fields_ = [("sigma", C.c_double), ("sigma_channel", C.c_double * 3), ("components", C.c_uint), ("patch", C.c_uint),
@@ -495,6 +505,8 @@ def lib():
     L.lfbm5d_last_scan_version.restype = C.c_int
     if hasattr(L, "lfbm5d_debug_aggregate"):   # (absent from older builds loaded through LFBM5D_HIP_LIB for A/B runs)
         L.lfbm5d_debug_aggregate.argtypes = [vp, C.POINTER(AggDebugStruct)]
+    if hasattr(L, "lfbm5d_debug_group"):
+        L.lfbm5d_debug_group.argtypes = [vp, C.POINTER(GroupDebugStruct)]
     if hasattr(L, "lfbm5d_noise_level_device"):   # (absent from older builds loaded through LFBM5D_HIP_LIB for A/B runs)
         dp, np_ = C.POINTER(C.c_double), C.POINTER(NoiseLevelStruct)
         L.lfbm5d_noise_level_device.argtypes = [vp, fp, up] + [C.c_uint] * 5 + [np_, dp, dp]
@@ -2140,6 +2152,60 @@ class Context:
         a.Wb, a.Hb, a.C, a.A, a.k, a.N, a.pst, a.p, a.nSim, a.nDisp = Wb, Hb, C_, A, k, N, pst, p, nSim, nDisp
         a.irregular, a.wchan0, a.direct = int(irregular), int(wchan0), int(direct)
         self._ck(self._L.lfbm5d_debug_aggregate(self._h, C.byref(a)))
+
+    def debug_group(self, step, P, aw, ah, Wb, Hb, C_, noisy, basic, refs, self_idx, self_cnt, best, shape, filt, wgt, aggpos, mask, pst,
+                    *, fill_quirk=1, n_refs_total, ref_begin=0, n_groups=None, filt_sai_stride=0, filt_floats=None, bm3d=0, null=()):
+        """lfbm5d_debug_group: the group launch alone.  noisy, basic, filt, wgt: float32 CUDA tensors; refs, self_idx, self_cnt, best,
+        aggpos: int32 CUDA tensors holding the uint32 words; shape: a uint8 CUDA tensor; mask: a sequence of A integers; P: Params.
+        filt, wgt and aggpos are written.  A None tensor goes to the library as a NULL pointer (which it refuses, `basic` in step 1
+        apart).  null: names of further fields of the struct to hand over as NULL (the refusal tests).  Returns (kernel text, sum of
+        the stack sizes, shape-adaptive groups)."""
+        import torch
+
+        def ptr(t, dtype):
+            if t is None:
+                return None, 0
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+                raise LfBm5dError("debug_group takes contiguous CUDA tensors: float32 values, int32 tables, uint8 shapes")
+            torch.cuda.current_stream(t.device).synchronize()
+            return t.data_ptr(), t.numel()
+
+        a = GroupDebugStruct()
+        a.noisy, n_noisy = ptr(noisy, torch.float32)
+        a.basic, n_basic = ptr(basic, torch.float32)
+        a.image_floats = n_noisy if basic is None else min(n_noisy, n_basic)
+        a.refs, n_refs = ptr(refs, torch.int32)
+        a.self_idx, n_idx = ptr(self_idx, torch.int32)
+        a.self_cnt, n_cnt = ptr(self_cnt, torch.int32)
+        a.best, n_best = ptr(best, torch.int32)
+        a.shape, n_shape = ptr(shape, torch.uint8)
+        a.table_words = min(n_best, n_shape)
+        a.filt, n_filt = ptr(filt, torch.float32)
+        a.filt_floats = n_filt if filt_floats is None else min(int(filt_floats), n_filt)
+        a.wgt, a.wgt_floats = ptr(wgt, torch.float32)
+        a.aggpos, a.aggpos_words = ptr(aggpos, torch.int32)
+        N = max(1, int(P.N))
+        if any(t is not None and n < need for t, n, need in ((refs, n_refs, n_refs_total), (self_cnt, n_cnt, n_refs_total),
+                                                             (self_idx, n_idx, n_refs_total * N))):
+            raise LfBm5dError("debug_group: refs, self_cnt and self_idx hold n_refs_total (x N) entries")
+        counters = (C.c_ulonglong * 2)(0, 0)
+        a.counters = C.addressof(counters)
+        keep = None if mask is None else _u32(mask)
+        if keep is not None and keep.size < aw * ah:
+            raise LfBm5dError("debug_group: mask holds one entry per SAI slot")
+        a.mask = None if keep is None else keep.ctypes.data
+        a.params = None if P is None else C.addressof(P)
+        text = C.create_string_buffer(512)
+        a.kernels, a.kernels_cap = C.addressof(text), 512
+        a.filt_sai_stride = int(filt_sai_stride)
+        a.step, a.aw, a.ah, a.Wb, a.Hb, a.C, a.pst, a.fill_quirk = step, aw, ah, Wb, Hb, C_, pst, int(fill_quirk)
+        a.n_refs_total, a.ref_begin = n_refs_total, ref_begin
+        a.n_groups = n_refs_total - ref_begin if n_groups is None else n_groups
+        a.bm3d = int(bm3d)
+        for name in null:
+            setattr(a, name, None)
+        self._ck(self._L.lfbm5d_debug_group(self._h, C.byref(a)))
+        return text.value.decode(), int(counters[0]), int(counters[1])
 
 
 _default_ctx = None

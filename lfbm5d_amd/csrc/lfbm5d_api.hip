@@ -748,6 +748,121 @@ int lfbm5d_debug_aggregate(lfbm5d_ctx* c, const lfbm5d_agg_debug* d) {
     return 0;
 }
 
+int lfbm5d_debug_group(lfbm5d_ctx* c, const lfbm5d_group_debug* d) {
+    if (!c) return 1;
+    if (!d) return fail(c, "debug_group: no arguments");
+    typedef unsigned long long u64;
+    if (d->kernels && d->kernels_cap) d->kernels[0] = 0;
+    /* what the group kernels take for granted (pass_impl guarantees it by construction, block matching by its search ranges) */
+    if (!d->noisy || !d->refs || !d->self_idx || !d->self_cnt || !d->best || !d->shape || !d->filt || !d->wgt || !d->aggpos || !d->counters ||
+        !d->mask || !d->params)
+        return fail(c, "debug_group: NULL pointer");
+    if (d->step != 1 && d->step != 2) return fail(c, "debug_group: step must be 1 or 2");
+    if (d->step == 2 && !d->basic) return fail(c, "debug_group: NULL pointer (step 2 needs the basic estimate)");
+    const lfbm5d_params* P = d->params;
+    if (validate(c, (int)d->step, P, d->aw, d->ah, d->C, d->bm3d != 0)) { c->err = "debug_group: " + c->err; return 1; }
+    if (!d->bm3d && P->N < 1) return fail(c, "debug_group: N must be a power of two <= 32");
+    const unsigned A = d->aw * d->ah, k = P->k, k2 = k * k, N = P->N, Wb = d->Wb, Hb = d->Hb, C = d->C, R = d->n_refs_total;
+    if (Wb > 65535u || Hb > 65535u) return fail(c, "debug_group: Wb and Hb must be at most 65535 (positions are 16-bit pairs)");
+    if (Wb < k || Hb < k) return fail(c, "debug_group: window smaller than a patch");
+    if (d->pst >= A || !d->mask[d->pst]) return fail(c, "debug_group: pst is not an SAI of the mask");
+    if (!d->n_groups || d->ref_begin > R || d->n_groups > R - d->ref_begin)
+        return fail(c, "debug_group: groups [ref_begin, ref_begin + n_groups) outside the reference list");
+    const u64 plane = (u64)Wb * Hb, patch = (u64)C * k2, launch_patches = (u64)d->n_groups * N;
+    if (launch_patches * (d->filt_sai_stride ? 1u : A) * patch >= (1ull << 32)) return fail(c, "debug_group: patch offsets beyond 32 bits");
+    if (d->image_floats < (u64)A * C * plane) return fail(c, "debug_group: noisy / basic are smaller than [A][C][Hb][Wb]");
+    if (d->table_words < (u64)A * plane) return fail(c, "debug_group: best / shape are smaller than [A][Wb*Hb]");
+    if (d->filt_sai_stride && (A == 9 || A == 1) && !(c->opt->kernels & kOptGroupGeneric))
+        return fail(c, "debug_group: SAI-major filt is written by the general kernels only (wider windows, option group_generic)");
+    if (d->filt_sai_stride ? (d->filt_sai_stride < launch_patches * patch || d->filt_floats < d->filt_sai_stride * A)
+                           : d->filt_floats < launch_patches * A * patch)
+        return fail(c, "debug_group: filt is smaller than the launch's patches");
+    if (d->wgt_floats < (u64)R * C) return fail(c, "debug_group: wgt is smaller than [n_refs_total][C]");
+    if (d->aggpos_words < (u64)A * R * N) return fail(c, "debug_group: aggpos is smaller than [A][n_refs_total][N]");
+
+    (void)hipSetDevice(c->device);
+    hipStream_t s = c->stream;
+    HIPCK(c, hipStreamSynchronize(s));
+    SaiMask mask_bits = sai_mask_none();
+    for (unsigned st = 0; st < A; st++) if (d->mask[st]) mask_bits.set(st);
+    {   /* the tables: every patch the launch gathers lies inside the window */
+        const unsigned g0 = d->ref_begin, ng = d->n_groups;
+        std::vector<unsigned> refs(ng), cnt(ng), idx((size_t)ng * N), best;
+        HIPCK(c, hipMemcpy(refs.data(), d->refs + g0, (size_t)ng * sizeof(unsigned), hipMemcpyDeviceToHost));
+        HIPCK(c, hipMemcpy(cnt.data(), d->self_cnt + g0, (size_t)ng * sizeof(unsigned), hipMemcpyDeviceToHost));
+        HIPCK(c, hipMemcpy(idx.data(), d->self_idx + (size_t)g0 * N, (size_t)ng * N * sizeof(unsigned), hipMemcpyDeviceToHost));
+        auto inside = [&](unsigned p) { return p < plane && p / Wb <= Hb - k && p % Wb <= Wb - k; };
+        for (unsigned g = 0; g < ng; g++) {
+            if (!inside(refs[g])) return fail(c, "debug_group: a reference patch lies outside [0, Hb-k] x [0, Wb-k]");
+            if (!is_pow2(cnt[g]) || cnt[g] > N) return fail(c, "debug_group: a stack size (self_cnt) is not a power of two in 1..N");
+            for (unsigned n = 0; n < cnt[g]; n++)
+                if (!inside(idx[(size_t)g * N + n])) return fail(c, "debug_group: a stack entry (self_idx) lies outside [0, Hb-k] x [0, Wb-k]");
+        }
+        if (mask_bits.count() > 1) {
+            best.resize((size_t)A * plane);
+            HIPCK(c, hipMemcpy(best.data(), d->best, best.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+            for (unsigned st = 0; st < A; st++) {
+                if (st == d->pst || !mask_bits.test(st)) continue;
+                for (unsigned g = 0; g < ng; g++)
+                    for (unsigned n = 0; n < cnt[g]; n++)
+                        if (!inside(best[(size_t)st * plane + idx[(size_t)g * N + n]]))
+                            return fail(c, "debug_group: a disparity match (best) of a stack entry lies outside [0, Hb-k] x [0, Wb-k]");
+            }
+        }
+    }
+    const unsigned Nst = N > 1 ? N : 1;
+    HIPCK(c, c->gpos.reserve((size_t)A * R * Nst * sizeof(unsigned)));
+    HIPCK(c, c->gofs.reserve((size_t)A * R * Nst * sizeof(unsigned)));
+    HIPCK(c, c->gok.reserve((size_t)R * Nst * sizeof(unsigned)));
+    HIPCK(c, c->sa_list.reserve((size_t)(4 * (size_t)R + 1) * sizeof(unsigned)));
+    HIPCK(c, c->gshape.reserve((size_t)R * (A > (unsigned)kMaxA ? kShapeInfoBigBytes : kShapeInfoBytes)));
+    if (c->dbg_group.key[0] != k || c->dbg_group.key[1] != d->aw || c->dbg_group.key[2] != d->ah) {
+        GroupTables tb;
+        build_tables(tb, k, d->aw, d->ah);
+        HIPCK(c, c->dbg_group.tb.reserve(sizeof(GroupTables)));
+        HIPCK(c, hipMemcpy(c->dbg_group.tb.p, &tb, sizeof(tb), hipMemcpyHostToDevice));
+        c->dbg_group.key[0] = k; c->dbg_group.key[1] = d->aw; c->dbg_group.key[2] = d->ah;
+    }
+    if (!c->counters.p) {   /* (as pass_impl) */
+        HIPCK(c, c->counters.reserve(32 * sizeof(unsigned long long)));
+        HIPCK(c, hipMemset(c->counters.p, 0, 32 * sizeof(unsigned long long)));
+    }
+    /* the launch counts into the context's counters like a pass; they are put back afterwards, so that the stats of the passes stay theirs */
+    unsigned long long* const d_counters = c->counters.as<unsigned long long>() + 16 * c->gslot;
+    unsigned long long before[2], after[2];
+    HIPCK(c, hipMemcpy(before, d_counters, sizeof(before), hipMemcpyDeviceToHost));
+    GroupArgs ga;
+    std::memset(&ga, 0, sizeof(ga));
+    ga.noisy = d->noisy; ga.basic = d->basic;
+    ga.refs = d->refs; ga.self_idx = d->self_idx; ga.self_cnt = d->self_cnt; ga.best = d->best; ga.shape = d->shape;
+    ga.tb = c->dbg_group.tb.as<GroupTables>();
+    ga.wgt = d->wgt; ga.aggpos = d->aggpos; ga.gpos = c->gpos.as<unsigned>(); ga.gofs = c->gofs.as<unsigned>(); ga.gok = c->gok.as<unsigned>();
+    ga.sa_list = c->sa_list.as<unsigned>(); ga.gshape = c->gshape.p; ga.n_refs_total = R; ga.counters = d_counters;
+    ga.ref_begin = d->ref_begin; ga.n_groups = d->n_groups;
+    ga.Wb = Wb; ga.Hb = Hb; ga.C = C; ga.A = A; ga.k = k; ga.N = Nst; ga.pst = d->pst;
+    ga.mask_bits = mask_bits; ga.proc_bits = sai_mask_none();
+    ga.step = (int)d->step; ga.fill_quirk = d->fill_quirk ? 1u : 0u; ga.bm3d = d->bm3d ? 1u : 0u;
+    if (group_args_of_pass(c, ga, P)) return 1;
+    /* filt is indexed by the absolute group number, as in a band of a pass */
+    const size_t per_group = (size_t)Nst * A * patch;
+    ga.filt_sai_stride = d->filt_sai_stride;
+    ga.filt = d->filt - (size_t)d->ref_begin * (d->filt_sai_stride ? per_group / A : per_group);
+    std::string trace;
+    hipError_t e = launch_group(s, ga, &trace);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = hipMemcpy(after, d_counters, sizeof(after), hipMemcpyDeviceToHost);
+    const hipError_t e_back = hipMemcpy(d_counters, before, sizeof(before), hipMemcpyHostToDevice);   /* also when the launch failed */
+    if (e != hipSuccess) return fail(c, std::string("debug_group: launch_group: ") + hipGetErrorString(e));
+    HIPCK(c, e_back);
+    d->counters[0] = after[0] - before[0]; d->counters[1] = after[1] - before[1];
+    if (d->kernels && d->kernels_cap) {
+        const size_t n = std::min<size_t>(trace.size(), (size_t)d->kernels_cap - 1);
+        std::memcpy(d->kernels, trace.data(), n);
+        d->kernels[n] = 0;
+    }
+    return 0;
+}
+
 int lfbm5d_malloc(void** dptr, size_t bytes) { return hipMalloc(dptr, bytes) == hipSuccess ? 0 : 1; }
 int lfbm5d_free(void* dptr) { return hipFree(dptr) == hipSuccess ? 0 : 1; }
 int lfbm5d_memcpy_h2d(void* dst, const void* src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess ? 0 : 1; }

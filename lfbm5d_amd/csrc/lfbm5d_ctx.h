@@ -195,6 +195,8 @@ struct lfbm5d_ctx {
     struct UnfilledScores { bool pending = false; unsigned n_rows = 0, n_cols = 0, W = 0, nSim = 0, nHW = 0, p = 0, last_r = 0, last_c = 0; float fill = 0; } unfilled;
     /* lfbm5d_debug_aggregate: the transform tables (build_tables) of patch size `k`, apart from the passes' cached ones */
     struct DebugAgg { DevBuf tb; unsigned k = 0; } dbg_agg;
+    /* lfbm5d_debug_group: likewise, for patch size and window key[0..2] */
+    struct DebugGroup { DevBuf tb; unsigned key[3] = {0, 0, 0}; } dbg_group;
 };
 
 namespace lfbm5d_host {
@@ -220,6 +222,8 @@ void ind_init(std::vector<unsigned>& v, unsigned max_size, unsigned N, unsigned 
 void build_tables(GroupTables& t, unsigned k, unsigned aw, unsigned ah);
 bool is_pow2(unsigned n);
 int validate(lfbm5d_ctx* c, int step, const lfbm5d_params* P, unsigned aw, unsigned ah, unsigned C, bool bm3d = false);
+/* the part of GroupArgs that follows from the pass's parameters (thresholds, lambda rule, sigma table, options, scratch) */
+int group_args_of_pass(lfbm5d_ctx* c, lfbm5d::GroupArgs& ga, const lfbm5d_params* P);
 int fold_counters(lfbm5d_ctx* c, const lfbm5d_params* P, unsigned A, unsigned C, int step, int slot = 0);
 /* A lane's (or an emulated rank's) counters and event times into the job's context: every field a pass adds to.  Not added:
  * windows, messages, lane_windows -- the job counts those on its own context as it enqueues, a lane's are zero; ms_comm -- the

@@ -18,12 +18,22 @@ namespace lfbm5d {
 /* dispatch pieces of launch_group (lfbm5d_group_generic.hip): the dedicated kernels of the hard-thresholding step
  * (lfbm5d_group_ht.hip) and of the Wiener step / 8x8 patches / per-SAI BM3D (lfbm5d_group_wiener.hip).  *launched = false: the
  * configuration is not theirs */
-hipError_t launch_group_ht(hipStream_t s, const GroupArgs& a, bool all_sa, bool* launched);
-hipError_t launch_group_wiener(hipStream_t s, const GroupArgs& a, bool all_sa, bool* launched);
-hipError_t launch_group_wide(hipStream_t s, const GroupArgs& a, bool* launched);   /* lfbm5d_group_wide.hip: HT, tau_2D = id, 5x5 / 7x7 windows */
+hipError_t launch_group_ht(hipStream_t s, const GroupArgs& a, bool all_sa, bool* launched, std::string* trace);
+hipError_t launch_group_wiener(hipStream_t s, const GroupArgs& a, bool all_sa, bool* launched, std::string* trace);
+hipError_t launch_group_wide(hipStream_t s, const GroupArgs& a, bool* launched, std::string* trace);   /* lfbm5d_group_wide.hip: HT, tau_2D = id, 5x5 / 7x7 windows */
 hipError_t prepare_group_wide();
 /* lfbm5d_group_slab.hip: stacks beyond the LDS (Wiener k = 12 / 16, N = 32, 5x5 / 7x7 windows with a 2-D transform) */
-hipError_t launch_group_slab(hipStream_t s, const GroupArgs& a, bool* launched);
+hipError_t launch_group_slab(hipStream_t s, const GroupArgs& a, bool* launched, std::string* trace);
+/* Every launch of the group stage goes through LFBM5D_LAUNCH: with a trace (lfbm5d_debug_group; NULL in ordinary passes) the
+ * kernel's name as the dispatcher spells it is appended, names joined by '+'. */
+inline void group_note(std::string* trace, const char* name) {
+    if (!trace) return;
+    std::string n(name);
+    if (!n.empty() && n.front() == '(' && n.back() == ')') n = n.substr(1, n.size() - 2);
+    if (!trace->empty()) *trace += '+';
+    *trace += n;
+}
+#define LFBM5D_LAUNCH(trace, kern, ...) do { group_note(trace, #kern); hipLaunchKernelGGL(kern, __VA_ARGS__); } while (0)
 hipError_t prepare_group_slab();
 bool group_uses_slab(const GroupArgs& a);
 size_t group_slab_scratch_bytes(const GroupArgs& a);

@@ -368,24 +368,24 @@ size_t group_scratch_bytes(const GroupArgs& a) {
     if (!group_uses_generic(a) || (group_lds_bytes(a) <= (size_t)kGenericLdsLimit && a.A <= (unsigned)kMaxA)) return 0;
     return (size_t)kBigBlocks * (a.step == 2 ? 2 : 1) * a.N * a.A * a.k * a.k * sizeof(float);
 }
-hipError_t launch_group(hipStream_t s, const GroupArgs& a) {
+hipError_t launch_group(hipStream_t s, const GroupArgs& a, std::string* trace) {
     /* geometry pre-pass: patch positions, aggregation positions, angular shapes */
-    hipLaunchKernelGGL(k_group_pos, grid1d((size_t)a.n_groups * a.N), dim3(256), 0, s, a);
+    LFBM5D_LAUNCH(trace, k_group_pos, grid1d((size_t)a.n_groups * a.N), dim3(256), 0, s, a);
     const bool bigA = a.A > (unsigned)kMaxA;
-    if (bigA) hipLaunchKernelGGL(k_group_shape<true>, grid1d(a.n_groups), dim3(256), 0, s, a);
-    else      hipLaunchKernelGGL(k_group_shape<false>, grid1d(a.n_groups), dim3(256), 0, s, a);
+    if (bigA) LFBM5D_LAUNCH(trace, k_group_shape<true>, grid1d(a.n_groups), dim3(256), 0, s, a);
+    else      LFBM5D_LAUNCH(trace, k_group_shape<false>, grid1d(a.n_groups), dim3(256), 0, s, a);
     /* a window with an empty SAI: tau_4D is the shape-adaptive transform (bm5d.cpp:276-280) and every group uses it */
     const bool all_sa = a.tau4 == 6 && !a.mask_bits.holds_all(a.A) && !(a.opt & kOptNoSaKernels);
     /* option group_generic: test hook, every configuration through the generic LDS kernel (the dedicated kernels' cross-check) */
     if (!(a.opt & kOptGroupGeneric)) {
         bool launched = false;
-        hipError_t e = launch_group_ht(s, a, all_sa, &launched);
+        hipError_t e = launch_group_ht(s, a, all_sa, &launched, trace);
         if (launched) return e;
-        e = launch_group_wiener(s, a, all_sa, &launched);
+        e = launch_group_wiener(s, a, all_sa, &launched, trace);
         if (launched) return e;
-        e = launch_group_wide(s, a, &launched);
+        e = launch_group_wide(s, a, &launched, trace);
         if (launched) return e;
-        e = launch_group_slab(s, a, &launched);
+        e = launch_group_slab(s, a, &launched, trace);
         if (launched) return e;
     }
     const size_t lds = group_lds_bytes(a);
@@ -396,15 +396,15 @@ hipError_t launch_group(hipStream_t s, const GroupArgs& a) {
         const unsigned tf = (unsigned)group_tmp_floats(a);
         const size_t ltmp = (size_t)tf * sizeof(float) + (bigA ? (size_t)a.N * a.A * sizeof(unsigned) : 0);
         if (bigA) {
-            if (a.step == 2) hipLaunchKernelGGL((k_group_big<2, true>), dim3(blocks), dim3(kThreads), ltmp, s, a, a.scratch, slice, tf);
-            else             hipLaunchKernelGGL((k_group_big<1, true>), dim3(blocks), dim3(kThreads), ltmp, s, a, a.scratch, slice, tf);
+            if (a.step == 2) LFBM5D_LAUNCH(trace, (k_group_big<2, true>), dim3(blocks), dim3(kThreads), ltmp, s, a, a.scratch, slice, tf);
+            else             LFBM5D_LAUNCH(trace, (k_group_big<1, true>), dim3(blocks), dim3(kThreads), ltmp, s, a, a.scratch, slice, tf);
         }
-        else if (a.step == 2) hipLaunchKernelGGL((k_group_big<2, false>), dim3(blocks), dim3(kThreads), ltmp, s, a, a.scratch, slice, tf);
-        else                  hipLaunchKernelGGL((k_group_big<1, false>), dim3(blocks), dim3(kThreads), ltmp, s, a, a.scratch, slice, tf);
+        else if (a.step == 2) LFBM5D_LAUNCH(trace, (k_group_big<2, false>), dim3(blocks), dim3(kThreads), ltmp, s, a, a.scratch, slice, tf);
+        else                  LFBM5D_LAUNCH(trace, (k_group_big<1, false>), dim3(blocks), dim3(kThreads), ltmp, s, a, a.scratch, slice, tf);
         return hipGetLastError();
     }
-    if (a.step == 2) hipLaunchKernelGGL(k_group<2>, dim3(a.n_groups, a.C), dim3(kThreads), lds, s, a);
-    else             hipLaunchKernelGGL(k_group<1>, dim3(a.n_groups, a.C), dim3(kThreads), lds, s, a);
+    if (a.step == 2) LFBM5D_LAUNCH(trace, k_group<2>, dim3(a.n_groups, a.C), dim3(kThreads), lds, s, a);
+    else             LFBM5D_LAUNCH(trace, k_group<1>, dim3(a.n_groups, a.C), dim3(kThreads), lds, s, a);
     return hipGetLastError();
 }
 } /* namespace lfbm5d */

@@ -695,26 +695,26 @@ hipError_t prepare_group_ht() {
     return hipSuccess;
 }
 
-hipError_t launch_group_ht(hipStream_t s, const GroupArgs& a, bool all_sa, bool* launched) {
+hipError_t launch_group_ht(hipStream_t s, const GroupArgs& a, bool all_sa, bool* launched, std::string* trace) {
     *launched = true;
     /* no 2-D transform and a stack small enough for registers: register-resident kernel */
     if (a.tau2 == 4 && a.N <= 8 && a.k * a.k <= 256 && a.step == 1 && a.A == 9 && (size_t)a.A * a.C * a.Wb * a.Hb * 4 < 0x7fffffffull) {   /* 32-bit byte offsets into the window */
         const unsigned threads = ((a.k * a.k + 63) / 64) * 64;
         const unsigned gx = ((a.n_groups + 7) / 8) * 8;   /* xcd_group_index */
         if (all_sa) {
-            if (a.tau5 == 9) hipLaunchKernelGGL(k_group_id_haar_sa, dim3(gx, a.C), dim3(threads), 0, s, a);
-            else             hipLaunchKernelGGL(k_group_id_any_sa, dim3(gx, a.C), dim3(threads), 0, s, a);
+            if (a.tau5 == 9) LFBM5D_LAUNCH(trace, k_group_id_haar_sa, dim3(gx, a.C), dim3(threads), 0, s, a);
+            else             LFBM5D_LAUNCH(trace, k_group_id_any_sa, dim3(gx, a.C), dim3(threads), 0, s, a);
         }
         else {
             if (!a.sa_list) return hipErrorInvalidValue;
             /* kOptHtReferenceOrder (test hook): the reference-order kernel */
             const bool fast = a.tau5 == 9 && (a.tau4 == 5 || a.tau4 == 6) && a.C <= 3 && !(a.opt & kOptHtReferenceOrder);
-            if (fast)             hipLaunchKernelGGL(k_group_id_haar_fast, dim3(gx, a.C), dim3(threads), 0, s, a);
-            else if (a.tau5 == 9) hipLaunchKernelGGL(k_group_id_haar, dim3(gx, a.C), dim3(threads), 0, s, a);
-            else                  hipLaunchKernelGGL(k_group_id_any, dim3(gx, a.C), dim3(threads), 0, s, a);
+            if (fast)             LFBM5D_LAUNCH(trace, k_group_id_haar_fast, dim3(gx, a.C), dim3(threads), 0, s, a);
+            else if (a.tau5 == 9) LFBM5D_LAUNCH(trace, k_group_id_haar, dim3(gx, a.C), dim3(threads), 0, s, a);
+            else                  LFBM5D_LAUNCH(trace, k_group_id_any, dim3(gx, a.C), dim3(threads), 0, s, a);
             if (a.tau4 == 6 || fast) {   /* what the kernel above has left: shape-adaptive groups (k_group_shape's entries), guard-band cases */
-                if (a.tau5 == 9) hipLaunchKernelGGL(k_group_id_haar_list, dim3(kSaListBlocks), dim3(threads), 0, s, a);
-                else             hipLaunchKernelGGL(k_group_id_any_list, dim3(kSaListBlocks), dim3(threads), 0, s, a);
+                if (a.tau5 == 9) LFBM5D_LAUNCH(trace, k_group_id_haar_list, dim3(kSaListBlocks), dim3(threads), 0, s, a);
+                else             LFBM5D_LAUNCH(trace, k_group_id_any_list, dim3(kSaListBlocks), dim3(threads), 0, s, a);
             }
         }
         return hipGetLastError();
@@ -726,20 +726,20 @@ hipError_t launch_group_ht(hipStream_t s, const GroupArgs& a, bool all_sa, bool*
             const dim3 grid8((a.n_groups + kT16Groups - 1) / kT16Groups, a.C);
             const size_t l1 = (size_t)kT16Groups * 9 * kT16Patch * sizeof(float);
             if (all_sa) {
-                if (a.tau2 == 7) hipLaunchKernelGGL(k_group_bior16_n1_sa, grid8, block, l1, s, a);
-                else             hipLaunchKernelGGL(k_group_dct16_n1_sa, grid8, block, l1, s, a);
+                if (a.tau2 == 7) LFBM5D_LAUNCH(trace, k_group_bior16_n1_sa, grid8, block, l1, s, a);
+                else             LFBM5D_LAUNCH(trace, k_group_dct16_n1_sa, grid8, block, l1, s, a);
             }
-            else if (a.tau2 == 7) hipLaunchKernelGGL(k_group_bior16_n1, grid8, block, l1, s, a);
-            else                  hipLaunchKernelGGL(k_group_dct16_n1, grid8, block, l1, s, a);
+            else if (a.tau2 == 7) LFBM5D_LAUNCH(trace, k_group_bior16_n1, grid8, block, l1, s, a);
+            else                  LFBM5D_LAUNCH(trace, k_group_dct16_n1, grid8, block, l1, s, a);
             return hipGetLastError();
         }
         if (a.tau2 == 7) {
             /* two rounds through a work area of 40 patches: groups of fewer than eight matches fit it whole (N <= 4: 36 patches) */
-            if (a.tau5 == 9) hipLaunchKernelGGL(k_group_bior16_haar, grid, block, std::min(lb, (size_t)kT16Half * kT16Patch * sizeof(float)), s, a);
-            else             hipLaunchKernelGGL(k_group_bior16_any, grid, block, lb, s, a);
+            if (a.tau5 == 9) LFBM5D_LAUNCH(trace, k_group_bior16_haar, grid, block, std::min(lb, (size_t)kT16Half * kT16Patch * sizeof(float)), s, a);
+            else             LFBM5D_LAUNCH(trace, k_group_bior16_any, grid, block, lb, s, a);
         } else {
-            if (a.tau5 == 9) hipLaunchKernelGGL(k_group_dct16_haar, grid, block, std::min(lb, (size_t)kT16Half * kT16Patch * sizeof(float)), s, a);
-            else             hipLaunchKernelGGL(k_group_dct16_any, grid, block, lb, s, a);
+            if (a.tau5 == 9) LFBM5D_LAUNCH(trace, k_group_dct16_haar, grid, block, std::min(lb, (size_t)kT16Half * kT16Patch * sizeof(float)), s, a);
+            else             LFBM5D_LAUNCH(trace, k_group_dct16_any, grid, block, lb, s, a);
         }
         return hipGetLastError();
     }

@@ -617,12 +617,12 @@ hipError_t prepare_group_slab() {
 }
 
 template <int WA, int MAXN>
-static void launch_slab(hipStream_t s, const GroupArgs& a, unsigned blocks, size_t lds, unsigned long long slice, int ls) {
-    if (a.step == 2) hipLaunchKernelGGL((k_group_slab<2, WA, MAXN>), dim3(blocks), dim3(kThreads), lds, s, a, a.scratch, slice, ls);
-    else             hipLaunchKernelGGL((k_group_slab<1, WA, MAXN>), dim3(blocks), dim3(kThreads), lds, s, a, a.scratch, slice, ls);
+static void launch_slab(hipStream_t s, const GroupArgs& a, unsigned blocks, size_t lds, unsigned long long slice, int ls, std::string* trace) {
+    if (a.step == 2) LFBM5D_LAUNCH(trace, (k_group_slab<2, WA, MAXN>), dim3(blocks), dim3(kThreads), lds, s, a, a.scratch, slice, ls);
+    else             LFBM5D_LAUNCH(trace, (k_group_slab<1, WA, MAXN>), dim3(blocks), dim3(kThreads), lds, s, a, a.scratch, slice, ls);
 }
 
-hipError_t launch_group_slab(hipStream_t s, const GroupArgs& a, bool* launched) {
+hipError_t launch_group_slab(hipStream_t s, const GroupArgs& a, bool* launched, std::string* trace) {
     *launched = false;
     if (!group_uses_slab(a)) return hipSuccess;
     const unsigned long long slice = (unsigned long long)(a.step == 2 ? 2 : 1) * a.N * a.A * a.k * a.k;
@@ -632,16 +632,16 @@ hipError_t launch_group_slab(hipStream_t s, const GroupArgs& a, bool* launched) 
     const int ls = slab_log2(a);
     const size_t lds = slab_lds_bytes(a);
     const bool n16 = a.N <= 16;
-#define LFBM5D_LS(WA) do { if (n16) launch_slab<WA, 16>(s, a, blocks, lds, slice, ls); else launch_slab<WA, 32>(s, a, blocks, lds, slice, ls); } while (0)
+#define LFBM5D_LS(WA) do { if (n16) launch_slab<WA, 16>(s, a, blocks, lds, slice, ls, trace); else launch_slab<WA, 32>(s, a, blocks, lds, slice, ls, trace); } while (0)
     switch (slab_window_side(a.A)) {
         case 3: LFBM5D_LS(3); break;
         case 5: LFBM5D_LS(5); break;
         case 7: LFBM5D_LS(7); break;
         case 9: LFBM5D_LS(9); break;
-        case 11: launch_slab<11, 16>(s, a, blocks, lds, slice, ls); break;
-        case 13: launch_slab<13, 16>(s, a, blocks, lds, slice, ls); break;
-        case 15: launch_slab<15, 16>(s, a, blocks, lds, slice, ls); break;
-        default: launch_slab<17, 16>(s, a, blocks, lds, slice, ls); break;
+        case 11: launch_slab<11, 16>(s, a, blocks, lds, slice, ls, trace); break;
+        case 13: launch_slab<13, 16>(s, a, blocks, lds, slice, ls, trace); break;
+        case 15: launch_slab<15, 16>(s, a, blocks, lds, slice, ls, trace); break;
+        default: launch_slab<17, 16>(s, a, blocks, lds, slice, ls, trace); break;
     }
 #undef LFBM5D_LS
     return hipGetLastError();

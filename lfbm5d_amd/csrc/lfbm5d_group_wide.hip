@@ -396,15 +396,15 @@ hipError_t prepare_group_wide() {
 }
 
 template <int AW>
-static void launch_idw(hipStream_t s, const GroupArgs& a, bool split) {
+static void launch_idw(hipStream_t s, const GroupArgs& a, bool split, std::string* trace) {
     constexpr int SLAB = WideSlab<AW>::value;
     const unsigned gx = ((a.n_groups + 7) / 8) * 8;   /* xcd_group_index */
     const size_t lds = (size_t)a.N * AW * AW * SLAB * sizeof(float);
-    if (split) hipLaunchKernelGGL((k_group_idw<AW, SLAB, true>), dim3(gx, a.C, (a.k * a.k + SLAB * wide_spw<AW>() - 1) / (SLAB * wide_spw<AW>())), dim3(256), lds, s, a);
-    else       hipLaunchKernelGGL((k_group_idw<AW, SLAB, false>), dim3(gx, a.C), dim3(256), lds, s, a);
+    if (split) LFBM5D_LAUNCH(trace, (k_group_idw<AW, SLAB, true>), dim3(gx, a.C, (a.k * a.k + SLAB * wide_spw<AW>() - 1) / (SLAB * wide_spw<AW>())), dim3(256), lds, s, a);
+    else       LFBM5D_LAUNCH(trace, (k_group_idw<AW, SLAB, false>), dim3(gx, a.C), dim3(256), lds, s, a);
 }
 
-hipError_t launch_group_wide(hipStream_t s, const GroupArgs& a, bool* launched) {
+hipError_t launch_group_wide(hipStream_t s, const GroupArgs& a, bool* launched, std::string* trace) {
     *launched = false;
     int aw = 0;
     for (int w = 5; w <= 17; w += 2) if (a.A == (unsigned)(w * w)) aw = w;
@@ -416,15 +416,15 @@ hipError_t launch_group_wide(hipStream_t s, const GroupArgs& a, bool* launched) 
         if (e != hipSuccess) return e;
     }
     switch (aw) {
-        case 5: launch_idw<5>(s, a, split); break;
-        case 7: launch_idw<7>(s, a, split); break;
-        case 9: launch_idw<9>(s, a, split); break;
-        case 11: launch_idw<11>(s, a, split); break;
-        case 13: launch_idw<13>(s, a, split); break;
-        case 15: launch_idw<15>(s, a, split); break;
-        default: launch_idw<17>(s, a, split); break;
+        case 5: launch_idw<5>(s, a, split, trace); break;
+        case 7: launch_idw<7>(s, a, split, trace); break;
+        case 9: launch_idw<9>(s, a, split, trace); break;
+        case 11: launch_idw<11>(s, a, split, trace); break;
+        case 13: launch_idw<13>(s, a, split, trace); break;
+        case 15: launch_idw<15>(s, a, split, trace); break;
+        default: launch_idw<17>(s, a, split, trace); break;
     }
-    if (split) hipLaunchKernelGGL(k_group_idw_weight, grid1d((size_t)a.n_groups * a.C), dim3(256), 0, s, a);
+    if (split) LFBM5D_LAUNCH(trace, k_group_idw_weight, grid1d((size_t)a.n_groups * a.C), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -1592,12 +1592,12 @@ hipError_t prepare_group_wiener() {
     return hipSuccess;
 }
 
-hipError_t launch_group_wiener(hipStream_t s, const GroupArgs& a, bool all_sa, bool* launched) {
+hipError_t launch_group_wiener(hipStream_t s, const GroupArgs& a, bool all_sa, bool* launched, std::string* trace) {
     *launched = true;
     if (a.tau2 == 7 && a.k == 8 && a.A == 9 && a.step == 2 && a.N <= (unsigned)kMaxN) {   /* 8x8 bior1.5, Wiener step: round 1's kernel with the wavelet in its 2-D stage */
         const size_t l8 = (size_t)2 * 64 * ((a.N * 9) | 1) * sizeof(float);
-        if (a.tau5 == 9) hipLaunchKernelGGL((k_group_dct8w<true>), dim3(a.n_groups, a.C), dim3(kDct8wThreads), l8, s, a);
-        else             hipLaunchKernelGGL((k_group_dct8w<false>), dim3(a.n_groups, a.C), dim3(kDct8wThreads), l8, s, a);
+        if (a.tau5 == 9) LFBM5D_LAUNCH(trace, (k_group_dct8w<true>), dim3(a.n_groups, a.C), dim3(kDct8wThreads), l8, s, a);
+        else             LFBM5D_LAUNCH(trace, (k_group_dct8w<false>), dim3(a.n_groups, a.C), dim3(kDct8wThreads), l8, s, a);
         return hipGetLastError();
     }
     if (a.tau2 == 5 && a.k == 8 && a.A == 9 && a.N <= (unsigned)kMaxN) {   /* 8x8 DCT */
@@ -1607,26 +1607,26 @@ hipError_t launch_group_wiener(hipStream_t s, const GroupArgs& a, bool all_sa, b
             /* the README's Wiener step: k_group_dct8w3.  Its two-image predecessor k_group_dct8w2 stays for Hadamard / DCT fibres and for
              * windows of 1.9 GB and more (32-bit offsets); option dct8w_v2: test hook, that kernel for every configuration.  */
             if (a.tau5 == 9 && (size_t)9 * a.C * a.Wb * a.Hb * 4 < 0x70000000ull && !(a.opt & kOptDct8wV2)) {
-                if (all_sa) hipLaunchKernelGGL(k_group_dct8w3<true>, dim3(gx, a.C), dim3(kDct8w3Threads), kW3Lds, s, a);
+                if (all_sa) LFBM5D_LAUNCH(trace, k_group_dct8w3<true>, dim3(gx, a.C), dim3(kDct8w3Threads), kW3Lds, s, a);
                 else if (a.tau4 == 5 || a.tau4 == 6) {
                     if (!a.sa_list) return hipErrorInvalidValue;
-                    hipLaunchKernelGGL(k_group_dct8w3_u, dim3(gx, a.C), dim3(kDct8w3Threads), kW3Lds, s, a);
-                    if (a.tau4 == 6) hipLaunchKernelGGL(k_group_dct8w3_list, dim3(kW3ListBlocks, a.C), dim3(kDct8w3Threads), kW3Lds, s, a);   /* the groups skipped above (usually none) */
+                    LFBM5D_LAUNCH(trace, k_group_dct8w3_u, dim3(gx, a.C), dim3(kDct8w3Threads), kW3Lds, s, a);
+                    if (a.tau4 == 6) LFBM5D_LAUNCH(trace, k_group_dct8w3_list, dim3(kW3ListBlocks, a.C), dim3(kDct8w3Threads), kW3Lds, s, a);   /* the groups skipped above (usually none) */
                 }
-                else        hipLaunchKernelGGL(k_group_dct8w3<false>, dim3(gx, a.C), dim3(kDct8w3Threads), kW3Lds, s, a);   /* tau_4D = id */
+                else        LFBM5D_LAUNCH(trace, k_group_dct8w3<false>, dim3(gx, a.C), dim3(kDct8w3Threads), kW3Lds, s, a);   /* tau_4D = id */
             }
-            else if (a.tau5 == 9) hipLaunchKernelGGL((k_group_dct8w2<true>), dim3(gx, a.C), dim3(kDct8w2Threads), l8, s, a);
-            else                  hipLaunchKernelGGL((k_group_dct8w2<false>), dim3(gx, a.C), dim3(kDct8w2Threads), l8, s, a);
+            else if (a.tau5 == 9) LFBM5D_LAUNCH(trace, (k_group_dct8w2<true>), dim3(gx, a.C), dim3(kDct8w2Threads), l8, s, a);
+            else                  LFBM5D_LAUNCH(trace, (k_group_dct8w2<false>), dim3(gx, a.C), dim3(kDct8w2Threads), l8, s, a);
             return hipGetLastError();
         }
-        hipLaunchKernelGGL(k_group_dct8, dim3(a.n_groups, a.C), dim3(kDct8Threads), l8, s, a);   /* hard-thresholding step: one thread per patch for the 2-D stage */
+        LFBM5D_LAUNCH(trace, k_group_dct8, dim3(a.n_groups, a.C), dim3(kDct8Threads), l8, s, a);   /* hard-thresholding step: one thread per patch for the 2-D stage */
         return hipGetLastError();
     }
     if (a.bm3d && a.A == 1 && a.k == 8 && a.tau5 == 8 && (a.tau2 == 5 || a.tau2 == 7)) {   /* per-SAI BM3D, 8x8 patches: a group per wavefront */
         const dim3 grid((a.n_groups + kBm3dWaves - 1) / kBm3dWaves, a.C), block(64 * kBm3dWaves);
         const size_t lb = (size_t)kBm3dWaves * 64 * (kMaxN3 + 1) * (a.step == 2 ? sizeof(v2f) : sizeof(float));
-        if (a.step == 2) { if (a.tau2 == 7) hipLaunchKernelGGL((k_group_bm3d8<2, true>), grid, block, lb, s, a); else hipLaunchKernelGGL((k_group_bm3d8<2, false>), grid, block, lb, s, a); }
-        else             { if (a.tau2 == 7) hipLaunchKernelGGL((k_group_bm3d8<1, true>), grid, block, lb, s, a); else hipLaunchKernelGGL((k_group_bm3d8<1, false>), grid, block, lb, s, a); }
+        if (a.step == 2) { if (a.tau2 == 7) LFBM5D_LAUNCH(trace, (k_group_bm3d8<2, true>), grid, block, lb, s, a); else LFBM5D_LAUNCH(trace, (k_group_bm3d8<2, false>), grid, block, lb, s, a); }
+        else             { if (a.tau2 == 7) LFBM5D_LAUNCH(trace, (k_group_bm3d8<1, true>), grid, block, lb, s, a); else LFBM5D_LAUNCH(trace, (k_group_bm3d8<1, false>), grid, block, lb, s, a); }
         return hipGetLastError();
     }
     *launched = false;

@@ -7,6 +7,7 @@
 #define LFBM5D_KERNELS_H
 
 #include <hip/hip_runtime.h>
+#include <string>
 #include <vector>
 
 #include "lfbm5d_options.h"
@@ -381,7 +382,8 @@ hipError_t launch_stereo_argmin(hipStream_t s, const float* tables, const unsign
                                 unsigned W, unsigned H, unsigned k, unsigned nDisp, float thr,
                                 unsigned* best, unsigned char* shape);
 hipError_t prepare_group_kernels();   /* once per device: LDS limits of the group kernels */
-hipError_t launch_group(hipStream_t s, const GroupArgs& a);
+/* trace (lfbm5d_debug_group; NULL in a pass): receives the names of the kernels launched, joined by + */
+hipError_t launch_group(hipStream_t s, const GroupArgs& a, std::string* trace = nullptr);
 size_t group_lds_bytes(const GroupArgs& a);
 /* HBM scratch (bytes) launch_group needs for this configuration: 0 unless the generic path's stacks exceed the LDS */
 size_t group_scratch_bytes(const GroupArgs& a);

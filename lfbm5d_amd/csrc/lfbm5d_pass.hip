@@ -169,6 +169,42 @@ int validate(lfbm5d_ctx* c, int step, const lfbm5d_params* P, unsigned aw, unsig
     return 0;
 }
 
+/* What a group launch takes from the pass's parameters rather than from its buffers: the transforms, the hard threshold's lambda
+ * (core:206-207), the sigma table, the thresholds of the fast hard-thresholding chain, the context's kernel options and the HBM
+ * scratch of the general forms.  ga holds the geometry already (Wb, Hb, C, A, k, N, step, bm3d).  One function for pass_impl and
+ * lfbm5d_debug_group: the seam launches with the pass's own numbers. */
+int group_args_of_pass(lfbm5d_ctx* c, GroupArgs& ga, const lfbm5d_params* P) {
+    const int step = ga.step;
+    const unsigned k = ga.k, A = ga.A;
+    float sig[3] = {0, 0, 0};
+    if (sigma_table(P->sigma, ga.C, P->color_space, sig)) return fail(c, "bad color space");
+    float lambda = P->lambda;
+    if (!ga.bm3d && step == 1 && P->tau_2D == LFBM5D_ID && P->tau_4D == LFBM5D_DCT) lambda /= (float)kSqrt2; /* core:206-207 */
+    ga.tau2 = P->tau_2D; ga.tau4 = P->tau_4D; ga.tau5 = P->tau_5D; ga.useSD = P->useSD;
+    ga.lambda = lambda;
+    for (int i = 0; i < 3; i++) ga.sigma[i] = sig[i];
+    if (A == 9 && step == 1) {   /* thresholds of the unnormalised transform chain (3x3 windows, Haar fibres): GroupArgs::ht3_T */
+        GroupTables ht;   /* (the same constants as the device table's) */
+        build_tables(ht, k, 3, 3);
+        for (int ch = 0; ch < 3; ch++) {
+            const float T = lambda * sig[ch] * 1.41421356237309505f;   /* the kernels' own float expression (core:2431) */
+            for (int st = 0; st < 9; st++)
+                for (int l = 0; l < 4; l++) ga.ht3_T[ch][st][l] = (float)((double)T / ((double)ht.ht3_f[st] * std::pow(2.0, -0.5 * l)));
+            for (int st = 0; st < 9; st++) {   /* floor of the guard band: Tq K M >= kHtGuardAbs[st][l] M at every level l */
+                double K = 0.0;
+                for (int l = 0; l < 4; l++) K = std::max(K, (double)kHtGuardAbs[st][l] / (double)ga.ht3_T[ch][st][l]);
+                ga.ht3_K[ch][st] = std::nextafter((float)std::min(K, 1e30), INFINITY);
+            }
+        }
+    }
+    ga.opt = c->opt->kernels;
+    if (const size_t sb = group_scratch_bytes(ga)) {   /* generic path with stacks beyond the 160 KiB LDS: HBM scratch slices */
+        HIPCK(c, c->gscratch.reserve(sb));
+        ga.scratch = c->gscratch.as<float>(); ga.scratch_floats = sb / sizeof(float);
+    }
+    return 0;
+}
+
 /* ------------------------------------------------------------------------------------------ */
 /* One core pass                                                                                */
 /* ------------------------------------------------------------------------------------------ */
@@ -197,8 +233,6 @@ int pass_impl(lfbm5d_ctx* c, int step, const lfbm5d_params* P, unsigned aw, unsi
                                              : (sig[0] < 35.0f ? 400.f : 3500.f))                           /* bm3d.cpp:531 */
                                 : (C == 1 ? 3.f : 1.f) * (sig[0] < 35.0f ? (step == 1 ? 3000 : 2000) : 5000); /* core:146/:915 */
     const float thr = tauMatch * k * k;                                                                  /* core:3315 */
-    float lambda = P->lambda;
-    if (!bm3d && step == 1 && P->tau_2D == LFBM5D_ID && P->tau_4D == LFBM5D_DCT) lambda /= (float)kSqrt2; /* core:206-207 */
     SaiMask mask_bits = sai_mask_none(), proc_bits = sai_mask_none();
     for (unsigned st = 0; st < A; st++) { if (h_mask[st]) mask_bits.set(st); if (h_proc[st]) proc_bits.set(st); }
     if (pst >= A || cst >= A) return fail(c, "cst / pst outside the angular window");
@@ -473,29 +507,8 @@ int pass_impl(lfbm5d_ctx* c, int step, const lfbm5d_params* P, unsigned aw, unsi
     ga.ref_begin = ref_begin; ga.n_groups = n_groups;
     ga.Wb = Wb; ga.Hb = Hb; ga.C = C; ga.A = A; ga.k = k; ga.N = Nst; ga.pst = pst;
     ga.mask_bits = mask_bits; ga.proc_bits = proc_bits;
-    ga.tau2 = P->tau_2D; ga.tau4 = P->tau_4D; ga.tau5 = P->tau_5D; ga.useSD = P->useSD;
-    ga.step = step; ga.lambda = lambda; ga.fill_quirk = centre ? 1u : 0u;
-    for (int i = 0; i < 3; i++) ga.sigma[i] = sig[i];
-    if (A == 9 && step == 1) {   /* thresholds of the unnormalised transform chain (3x3 windows, Haar fibres): GroupArgs::ht3_T */
-        GroupTables ht;   /* (the same constants as the device table's) */
-        build_tables(ht, k, 3, 3);
-        for (int ch = 0; ch < 3; ch++) {
-            const float T = lambda * sig[ch] * 1.41421356237309505f;   /* the kernels' own float expression (core:2431) */
-            for (int st = 0; st < 9; st++)
-                for (int l = 0; l < 4; l++) ga.ht3_T[ch][st][l] = (float)((double)T / ((double)ht.ht3_f[st] * std::pow(2.0, -0.5 * l)));
-            for (int st = 0; st < 9; st++) {   /* floor of the guard band: Tq K M >= kHtGuardAbs[st][l] M at every level l */
-                double K = 0.0;
-                for (int l = 0; l < 4; l++) K = std::max(K, (double)kHtGuardAbs[st][l] / (double)ga.ht3_T[ch][st][l]);
-                ga.ht3_K[ch][st] = std::nextafter((float)std::min(K, 1e30), INFINITY);
-            }
-        }
-    }
-    ga.bm3d = bm3d ? 1u : 0u;
-    ga.opt = c->opt->kernels;
-    if (const size_t sb = group_scratch_bytes(ga)) {   /* generic path with stacks beyond the 160 KiB LDS: HBM scratch slices */
-        HIPCK(c, c->gscratch.reserve(sb));
-        ga.scratch = c->gscratch.as<float>(); ga.scratch_floats = sb / sizeof(float);
-    }
+    ga.step = step; ga.fill_quirk = centre ? 1u : 0u; ga.bm3d = bm3d ? 1u : 0u;
+    if (group_args_of_pass(c, ga, P)) return 1;
     AggArgs aa;
     std::memset(&aa, 0, sizeof(aa));
     aa.num = d_num; aa.den = d_den; aa.wgt = ga.wgt; aa.aggpos = ga.aggpos; aa.n_refs_total = R; aa.refs = ga.refs;

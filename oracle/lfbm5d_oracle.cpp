@@ -1604,6 +1604,51 @@ int orc_pass(int step, const orc_params* P, unsigned aw, unsigned ah, unsigned W
                      ref_row_begin, ref_row_end, stats);
 }
 
+/* process_group on tables the caller supplies: the PassCtx is set up as pass_impl sets it up (sigma table, lambda rule, norms) */
+int orc_group(int step, const orc_params* P, unsigned aw, unsigned ah, unsigned Wb, unsigned Hb, unsigned C,
+              const float* noisy, const float* basic, const unsigned* mask, unsigned pst, int fill_quirk,
+              const unsigned* refs, const unsigned* self_idx, const unsigned* self_cnt, const unsigned* best,
+              const unsigned char* shape, unsigned ref_begin, unsigned n_groups,
+              float* patches, float* w, unsigned* nSx, unsigned* use_sadct) {
+    if (C > 3 || (step == 2 && !basic)) return 1;
+    PassCtx cx;
+    cx.step = step; cx.P = P; cx.aw = aw; cx.ah = ah; cx.A = aw * ah; cx.Wb = Wb; cx.Hb = Hb; cx.C = C;
+    cx.k = P->k; cx.k2 = P->k * P->k; cx.N = P->N ? P->N : 1; cx.nHW = P->nSim + P->nDisp;
+    cx.noisy = noisy; cx.basic = basic; cx.mask = mask; cx.pst = pst; cx.centre = fill_quirk != 0;
+    if (sigma_table(P->sigma, C, P->color_space, cx.sigma)) return 1;
+    cx.lambda = P->lambda;
+    if (step == 1 && P->tau_2D == ORC_ID && P->tau_4D == ORC_DCT) cx.lambda /= (float)kSqrt2; /* core:206-207 */
+    dct2d_norms(cx.k, cx.n2.cn, cx.n2.cni); cx.n2.k = cx.k;
+    dct4d_norms(aw, ah, cx.n4.cn, cx.n4.cni); cx.n4.aw = aw; cx.n4.ah = ah;
+    const unsigned A = cx.A;
+    const size_t plane = (size_t)Wb * Hb;
+    std::vector<std::vector<unsigned> > bestv(A);
+    std::vector<std::vector<unsigned char> > shapev(A);
+    for (unsigned st = 0; st < A; st++) {
+        if (st == pst || !mask[st]) continue;
+        bestv[st].assign(best + st * plane, best + (st + 1) * plane);
+        shapev[st].assign(shape + st * plane, shape + (st + 1) * plane);
+    }
+    cx.self_idx = self_idx; cx.self_cnt = self_cnt; cx.best = &bestv; cx.shape = &shapev;
+    const size_t per_group = (size_t)A * C * cx.N * cx.k2;
+    #pragma omp parallel for schedule(dynamic, 1) num_threads(g_threads > 0 ? g_threads : omp_get_max_threads())
+    for (int i = 0; i < (int)n_groups; i++) {
+        const unsigned g = ref_begin + (unsigned)i;
+        GroupOut go;
+        process_group(cx, g, refs[g], go);
+        nSx[i] = go.nSx; use_sadct[i] = go.use_sadct ? 1u : 0u;
+        for (unsigned c = 0; c < C; c++) w[(size_t)i * C + c] = go.w[c];
+        /* [st][c][n < nSx][k2] of the group, the stack padded to N with zeros */
+        float* out = patches + (size_t)i * per_group;
+        std::fill(out, out + per_group, 0.0f);
+        for (unsigned st = 0; st < A; st++)
+            for (unsigned c = 0; c < C; c++)
+                std::memcpy(out + (((size_t)st * C + c) * cx.N) * cx.k2, &go.patches[(((size_t)st * C + c) * go.nSx) * cx.k2],
+                            (size_t)go.nSx * cx.k2 * sizeof(float));
+    }
+    return 0;
+}
+
 int orc_run_step1(const orc_params* P, float* LF_noisy, const unsigned* mask, float* LF_basic,
                   unsigned ang_major, unsigned awidth, unsigned aheight, unsigned an, unsigned W,
                   unsigned H, unsigned C, int max_windows, orc_stats* stats) {

@@ -131,6 +131,17 @@ int orc_pass(int step, const orc_params* P, unsigned aw, unsigned ah,
              const unsigned* mask, const unsigned* procSAI, unsigned cst, unsigned pst,
              int ref_row_begin, int ref_row_end, orc_stats* stats);
 
+/* ---- the group stage of a pass alone (core:277-481 / :1054-1282), on block-matching tables the caller supplies ----
+ * refs[R], self_idx[R][N], self_cnt[R], best[A][Wb*Hb], shape[A][Wb*Hb] as orc_pass builds them (entries of empty SAIs and of pst
+ * are not read); fill_quirk != 0: the centre path's zero patches at columns >= Wb - k.  For the groups [ref_begin, ref_begin +
+ * n_groups): patches[i][st][c][N][k*k] pixel-domain filtered patches (stack entries beyond nSx zero), w[i][C] the group weights,
+ * nSx[i], use_sadct[i]. */
+int orc_group(int step, const orc_params* P, unsigned aw, unsigned ah, unsigned Wb, unsigned Hb, unsigned C,
+              const float* noisy, const float* basic, const unsigned* mask, unsigned pst, int fill_quirk,
+              const unsigned* refs, const unsigned* self_idx, const unsigned* self_cnt, const unsigned* best,
+              const unsigned char* shape, unsigned ref_begin, unsigned n_groups,
+              float* patches, float* w, unsigned* nSx, unsigned* use_sadct);
+
 /* ---- whole steps (run_bm5d_1st_step / run_bm5d_2nd_step, nb_threads == 1 semantics) ----
  * LF buffers are [awidth*aheight][C*W*H] contiguous, mutated in place exactly like the reference
  * (colour forward at entry, inverse at exit).  max_windows > 0 stops after that many angular

@@ -79,6 +79,8 @@ def lib():
     L.orc_pass.argtypes = [C.c_int, C.POINTER(Params), C.c_uint, C.c_uint, C.c_uint, C.c_uint,
                            C.c_uint, _f32p, C.c_void_p, _f32p, _f32p, _u32p, _u32p, C.c_uint,
                            C.c_uint, C.c_int, C.c_int, C.POINTER(Stats)]
+    L.orc_group.argtypes = [C.c_int, C.POINTER(Params), C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint, _f32p, C.c_void_p, _u32p,
+                            C.c_uint, C.c_int, _u32p, _u32p, _u32p, _u32p, _u8p, C.c_uint, C.c_uint, _f32p, _f32p, _u32p, _u32p]
     L.orc_run_step1.argtypes = [C.POINTER(Params), _f32p, _u32p, _f32p, C.c_uint, C.c_uint, C.c_uint,
                                 C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_int, C.POINTER(Stats)]
     L.orc_run_step2.argtypes = [C.POINTER(Params), _f32p, _u32p, _f32p, _f32p, C.c_uint, C.c_uint,
@@ -244,3 +246,28 @@ def last_weights(n_groups, Cc):
     n = lib().orc_last_weights(out, out.size)
     assert n >= out.size
     return out.reshape(n_groups, Cc)
+
+
+def group(step, P, aw, ah, Wb, Hb, Cc, noisy, basic, mask, pst, fill_quirk, refs, self_idx, self_cnt, best, shape, ref_begin=0,
+          n_groups=None):
+    """orc_group: process_group of the groups [ref_begin, ref_begin + n_groups) on the caller's block-matching tables.  Returns
+    patches [g][st][c][N][k*k] (stack entries beyond nSx zero), w [g][C], nSx [g], use_sadct [g]."""
+    L = lib()
+    A, N, k2 = aw * ah, max(1, P.N), P.k * P.k
+    refs = np.ascontiguousarray(refs, np.uint32)
+    n_groups = len(refs) - ref_begin if n_groups is None else n_groups
+    patches = np.zeros((n_groups, A, Cc, N, k2), np.float32)
+    w = np.zeros((n_groups, Cc), np.float32)
+    nSx, sa = np.zeros(n_groups, np.uint32), np.zeros(n_groups, np.uint32)
+    b = None
+    if basic is not None:
+        basic = np.ascontiguousarray(basic, np.float32)
+        b = basic.ctypes.data_as(C.c_void_p)
+    rc = L.orc_group(step, C.byref(P), aw, ah, Wb, Hb, Cc, np.ascontiguousarray(noisy, np.float32).reshape(-1), b,
+                     np.ascontiguousarray(mask, np.uint32), pst, int(fill_quirk), refs,
+                     np.ascontiguousarray(self_idx, np.uint32).reshape(-1), np.ascontiguousarray(self_cnt, np.uint32),
+                     np.ascontiguousarray(best, np.uint32).reshape(-1), np.ascontiguousarray(shape, np.uint8).reshape(-1),
+                     ref_begin, n_groups, patches.reshape(-1), w.reshape(-1), nSx, sa)
+    if rc:
+        raise RuntimeError("orc_group failed")
+    return patches, w, nSx, sa

@@ -31,17 +31,20 @@ def test_struct_layouts_match_header():
     assert C.sizeof(core.Stats) == 5 * 8 + 6 * 8 + 4 * 8
     # lfbm5d_agg_debug: 8 pointers, 6 sizes, 18 unsigned -- and the header's fields in the header's order, with matching widths
     assert C.sizeof(core.AggDebugStruct) == 8 * 8 + 6 * 8 + 18 * 4
+    # lfbm5d_group_debug: 14 pointers, 7 sizes, 12 unsigned
+    assert C.sizeof(core.GroupDebugStruct) == 14 * 8 + 7 * 8 + 12 * 4
     src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "lfbm5d.h")).read(), flags=re.S)
-    body = re.search(r"typedef struct lfbm5d_agg_debug \{(.*?)\} lfbm5d_agg_debug;", src, flags=re.S).group(1)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if decl:
-            ctype = C.c_void_p if "*" in decl else (C.c_ulonglong if decl.startswith("unsigned long long") else C.c_uint)
-            assert ctype is not C.c_uint or decl.startswith("unsigned "), decl
-            names = re.sub(r"^(const\s+)?(unsigned long long|unsigned|float)\s*\*?", "", decl)
-            fields += [(n.strip(), ctype) for n in names.split(",")]
-    assert fields == list(core.AggDebugStruct._fields_)
+    for name, struct in (("lfbm5d_agg_debug", core.AggDebugStruct), ("lfbm5d_group_debug", core.GroupDebugStruct)):
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), src, flags=re.S).group(1)
+        fields = []
+        for decl in body.split(";"):
+            decl = decl.strip()
+            if decl:
+                ctype = C.c_void_p if "*" in decl else (C.c_ulonglong if decl.startswith("unsigned long long") else C.c_uint)
+                assert ctype is not C.c_uint or decl.startswith("unsigned "), decl
+                names = re.sub(r"^(const\s+)?(unsigned long long|unsigned char|unsigned|float|char|lfbm5d_params)\s*\*?", "", decl)
+                fields += [(n.strip(), ctype) for n in names.split(",")]
+        assert fields == list(struct._fields_), name
 
 
 def test_shard_rows_partition():
