@@ -1056,6 +1056,8 @@ int lfbm5d_device_count(void);
 #include "lfbm5d_pgclip.h"
 /* ---- per-view noise levels: one sigma per SAI, one sigma per angular window (lfbm5d_views_*, lfbm5d_*_views_*) ---- */
 #include "lfbm5d_views.h"
+/* ---- joint repair of defects and missing views by a mask-aware plane sweep (lfbm5d_repair_*) ---- */
+#include "lfbm5d_repair.h"
 
 #ifdef __cplusplus
 }

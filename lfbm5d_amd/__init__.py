@@ -15,6 +15,7 @@ from .core import (Context, Params, Bm3dParams, Stats, run_bm5d_1st_step, run_bm
                    InpaintParamsStruct, InpaintResultStruct, Inpaint, inpaint_params, inpaint,
                    ViewParamsStruct, ViewResultStruct, ViewOcclResultStruct, ViewSynth, view_params, view_synth, view_occl_default,
                    ConsistParamsStruct, ConsistResultStruct, Consist, consist_params, consist,
+                   RepairParamsStruct, RepairResultStruct, Repair, repair_params, repair,
                    PhotoParamsStruct, PhotoResultStruct, Equalise, photo_params, photo_edges, photo_ratio, photo_solve, equalise,
                    ClipEstimateStruct, ClipNoiseLevel, clip_fit, noise_level_clipped, denoise_clipped,
                    PgclipModelStruct, PgclipEstimateStruct, PgclipCurvesStruct, PgclipEstimate, PgclipCurves, pgclip_fit, pgclip_curves,
@@ -31,6 +32,7 @@ __all__ = ["Context", "Params", "Bm3dParams", "Stats", "run_bm5d_1st_step", "run
            "InpaintParamsStruct", "InpaintResultStruct", "Inpaint", "inpaint_params", "inpaint",
            "ViewParamsStruct", "ViewResultStruct", "ViewOcclResultStruct", "ViewSynth", "view_params", "view_synth", "view_occl_default",
            "ConsistParamsStruct", "ConsistResultStruct", "Consist", "consist_params", "consist",
+           "RepairParamsStruct", "RepairResultStruct", "Repair", "repair_params", "repair",
            "PhotoParamsStruct", "PhotoResultStruct", "Equalise", "photo_params", "photo_edges", "photo_ratio", "photo_solve", "equalise",
            "ClipEstimateStruct", "ClipNoiseLevel", "clip_fit", "noise_level_clipped", "denoise_clipped",
            "PgclipModelStruct", "PgclipEstimateStruct", "PgclipCurvesStruct", "PgclipEstimate", "PgclipCurves", "pgclip_fit", "pgclip_curves",

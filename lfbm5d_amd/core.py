@@ -174,6 +174,19 @@ class ViewResultStruct(C.Structure):
                 ("disparity_hist", C.c_ulonglong * 17)]
 
 
+class RepairParamsStruct(C.Structure):
+    """lfbm5d_repair_params: the mask-aware sweep, min_valid and the refinement schedule of the joint repair (include/lfbm5d_repair.h)."""
+    _fields_ = [("max_disparity", C.c_uint), ("box_radius", C.c_uint), ("ang_radius", C.c_uint), ("min_valid", C.c_uint),
+                ("iterations", C.c_uint), ("sigma_start", C.c_float), ("sigma_end", C.c_float), ("sigma_noise", C.c_float)]
+
+
+class RepairResultStruct(C.Structure):
+    """lfbm5d_repair_result: counts of one joint fill (include/lfbm5d_repair.h)."""
+    _fields_ = [("missing", C.c_uint), ("targets", C.c_uint), ("swept", C.c_uint), ("passes", C.c_uint), ("values", C.c_ulonglong),
+                ("flagged", C.c_ulonglong), ("unsound", C.c_ulonglong * 3), ("views", C.c_ulonglong * 3), ("rim", C.c_ulonglong * 3),
+                ("left", C.c_ulonglong * 3), ("positions", C.c_ulonglong), ("disparity_hist", C.c_ulonglong * 17)]
+
+
 class ViewOcclResultStruct(C.Structure):
     """lfbm5d_view_occl_result: positions per set chosen by the occlusion-aware synthesis (include/lfbm5d_occl.h)."""
     _fields_ = [("set_hist", C.c_ulonglong * 5)]
@@ -286,6 +299,30 @@ class ViewSynth(NamedTuple):
     steps_hist: tuple = None
     set_hist: tuple = None
     sets: object = None
+
+
+class Repair(NamedTuple):
+    """Result of Context.repair_fill / Context.repair / repair: the repaired light field (a tensor or an array like the input), the code
+    planes (uint8 like the light field: 0 sound, 1 filled from the other views, 2 filled from the rim of its own plane, 3 left; None
+    unless asked for), the disparity planes (int8 [asize][H*W], d* at the unsound positions of the swept targets; None unless asked
+    for), the SAIs marked missing, the targets and those of them with a source, the passes of the rim fill, the values of the non-empty
+    SAIs, the non-zero flags, the counts per stored channel, the positions the sweep wrote at and those positions per disparity
+    (index d + 8)."""
+    out: object
+    codes: object
+    disparity: object
+    missing: int
+    targets: int
+    swept: int
+    passes: int
+    values: int
+    flagged: int
+    unsound: tuple
+    views: tuple
+    rim: tuple
+    left: tuple
+    positions: int
+    disparity_hist: tuple
 
 
 class Inpaint(NamedTuple):
@@ -605,6 +642,13 @@ def lib():
         L.lfbm5d_view_fill_occl_device.argtypes = [vp, wp, C.c_uint, C.c_float, fp, up, up, fp, vp, vp] + [C.c_uint] * 6 + [wr, ullp, orp]
         L.lfbm5d_view_occl_device.argtypes = [vp, wp, C.c_uint, C.c_float, pp, fp, up, up, fp, vp, vp] + [C.c_uint] * 7 + [wr, ullp, orp]
         L.lfbm5d_view_occl_host_sai.argtypes = [vp, wp, C.c_uint, C.c_float, pp, vp, up, up, vp, vp, vp] + [C.c_uint] * 7 + [wr, ullp, orp]
+    if hasattr(L, "lfbm5d_repair_device"):   # (absent from older builds loaded through LFBM5D_HIP_LIB for A/B runs)
+        jp, jr, pp = C.POINTER(RepairParamsStruct), C.POINTER(RepairResultStruct), C.POINTER(Params)
+        L.lfbm5d_repair_defaults.argtypes = [jp]
+        L.lfbm5d_repair_defaults.restype = None
+        L.lfbm5d_repair_fill_device.argtypes = [vp, jp, fp, vp, up, up, fp, vp, vp] + [C.c_uint] * 6 + [jr]
+        L.lfbm5d_repair_device.argtypes = [vp, jp, pp, fp, vp, up, up, fp, vp, vp] + [C.c_uint] * 7 + [jr]
+        L.lfbm5d_repair_host_sai.argtypes = [vp, jp, pp, vp, vp, up, up, vp, vp, vp] + [C.c_uint] * 7 + [jr]
     if hasattr(L, "lfbm5d_consist_device"):   # (absent from older builds loaded through LFBM5D_HIP_LIB for A/B runs)
         cp, cr = C.POINTER(ConsistParamsStruct), C.POINTER(ConsistResultStruct)
         dp, ullp = C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)
@@ -914,6 +958,21 @@ def view_params(max_disparity=None, box_radius=None, ang_radius=None, iterations
     P = ViewParamsStruct()
     lib().lfbm5d_view_defaults(C.byref(P))
     for name, v in (("max_disparity", max_disparity), ("box_radius", box_radius), ("ang_radius", ang_radius), ("iterations", iterations)):
+        if v is not None:
+            setattr(P, name, int(v))
+    for name, v in (("sigma_start", sigma_start), ("sigma_end", sigma_end), ("sigma_noise", sigma_noise)):
+        if v is not None:
+            setattr(P, name, float(v))
+    return P
+
+
+def repair_params(max_disparity=None, box_radius=None, ang_radius=None, min_valid=None, iterations=None, sigma_start=None, sigma_end=None,
+                  sigma_noise=None):
+    """lfbm5d_repair_params from the defaults of the library (lfbm5d_repair_defaults, host only); None keeps a default."""
+    P = RepairParamsStruct()
+    lib().lfbm5d_repair_defaults(C.byref(P))
+    for name, v in (("max_disparity", max_disparity), ("box_radius", box_radius), ("ang_radius", ang_radius), ("min_valid", min_valid),
+                    ("iterations", iterations)):
         if v is not None:
             setattr(P, name, int(v))
     for name, v in (("sigma_start", sigma_start), ("sigma_end", sigma_end), ("sigma_noise", sigma_noise)):
@@ -1904,6 +1963,78 @@ class Context:
                 self._ck(self._L.lfbm5d_view_steps_device(self._h, C.byref(vp), steps, *args, shp))
         return self._view_result(out, dp, res, sh, occl, sp)
 
+    # ---- joint repair ----
+    @staticmethod
+    def _repair_result(out, codes, disp, res, C_):
+        return Repair(out, codes, disp, int(res.missing), int(res.targets), int(res.swept), int(res.passes), int(res.values), int(res.flagged),
+                      tuple(res.unsound[:C_]), tuple(res.views[:C_]), tuple(res.rim[:C_]), tuple(res.left[:C_]), int(res.positions),
+                      tuple(res.disparity_hist))
+
+    def repair_fill(self, noisy, flags, missing, mask, ang_major, awidth, aheight, width, height, chnls, max_disparity=None, box_radius=None,
+                    ang_radius=None, min_valid=None, return_codes=False, return_disparity=False, out=None, codes_out=None,
+                    disparity_out=None):
+        """The joint fill of lfbm5d_repair_fill_device on CUDA tensors (include/lfbm5d_repair.h): noisy float32 [asize][C*H*W], flags
+        uint8 of that shape (non-zero = defective) or None, missing [asize] (non-zero = the whole SAI) or None.  The inputs are only
+        read; out / codes_out / disparity_out (int8 [asize][H*W]): optional tensors to write into, distinct from the inputs; planes of
+        empty SAIs of a fresh result are copies of the input's.  Returns a Repair."""
+        import torch
+        m = _u32(mask)
+        ms = None if missing is None else _u32(missing)
+        C_ = int(chnls)
+        rp = repair_params(max_disparity, box_radius, ang_radius, min_valid)
+        res = RepairResultStruct()
+        out = self._dev_out(noisy, out, m)
+        co = self._dev_planes(noisy, codes_out, return_codes, noisy.shape, torch.uint8)
+        dp = self._dev_planes(noisy, disparity_out, return_disparity, (m.size, int(width) * int(height)), torch.int8)
+        up = C.POINTER(C.c_uint)
+        rc = self._L.lfbm5d_repair_fill_device(self._h, C.byref(rp), _dev_ptr(noisy), None if flags is None else _dev_ptr(flags, np.uint8),
+                                               m.ctypes.data_as(up), None if ms is None else ms.ctypes.data_as(up), _dev_ptr(out),
+                                               None if co is None else _dev_ptr(co, np.uint8), None if dp is None else _dev_ptr(dp, np.int8),
+                                               ang_major, awidth, aheight, int(width), int(height), C_, C.byref(res))
+        self._ck(rc)
+        return self._repair_result(out, co, dp, res, C_)
+
+    def repair(self, noisy, flags, missing, mask, P, ang_major, awidth, aheight, an, width, height, chnls, max_disparity=None,
+               box_radius=None, ang_radius=None, min_valid=None, iterations=None, sigma_start=None, sigma_end=None, sigma_noise=None,
+               return_codes=False, return_disparity=False, out=None, codes_out=None, disparity_out=None):
+        """Joint repair (lfbm5d_repair_*, include/lfbm5d_repair.h): the values `flags` names (uint8 like noisy, non-zero = defective; or
+        None), every value that is not finite and every value of the SAIs `missing` marks (or None) are filled from the other views by a
+        plane sweep that skips unsound source values, what it cannot reach from the rim of its own plane, and the fill is refined by
+        `iterations` hard-thresholding steps (P, its sigma replaced by the schedule sigma_start -> sigma_end, not below sigma_noise) with
+        the sound values put back after every step; iterations = 0 is the fill alone, None the library's defaults.  noisy: a CUDA float32
+        tensor [asize][C*H*W] with a uint8 CUDA tensor of flags (device form), or float32 / uint8 numpy arrays of that shape or lists of
+        per-SAI arrays (host form, staged through HBM; identical results).  The inputs are only read.  Returns a Repair."""
+        m = _u32(mask)
+        ms = None if missing is None else _u32(missing)
+        asize, C_ = m.size, int(chnls)
+        rp = repair_params(max_disparity, box_radius, ang_radius, min_valid, iterations, sigma_start, sigma_end, sigma_noise)
+        res = RepairResultStruct()
+        up = C.POINTER(C.c_uint)
+        mp, msp = m.ctypes.data_as(up), None if ms is None else ms.ctypes.data_as(up)
+        tail = (ang_major, awidth, aheight, an, int(width), int(height), C_, C.byref(res))
+        if isinstance(noisy, (list, tuple, np.ndarray)):
+            arrays = self._host_sais(noisy)
+            out, outs = self._host_out(arrays, out)
+            fin = None if flags is None else [None if a is None else np.ascontiguousarray(a, np.uint8) for a in flags]
+            co = self._host_planes(arrays, codes_out, return_codes, np.uint8)
+            dp = self._host_planes(arrays, disparity_out, return_disparity, np.int8, int(width) * int(height))
+            rc = self._L.lfbm5d_repair_host_sai(self._h, C.byref(rp), C.byref(P), _sai_ptrs(arrays, m),
+                                                None if fin is None else _sai_ptrs(fin, m, np.uint8), mp, msp, _sai_ptrs(outs, m),
+                                                None if co is None else _sai_ptrs(co, m, np.uint8),
+                                                None if dp is None else _sai_ptrs(dp, m, np.int8), *tail)
+            self._ck(rc)
+            out, co, dp = self._stacked(noisy, out), self._stacked(noisy, co), self._stacked(noisy, dp, False)
+        else:
+            import torch
+            out = self._dev_out(noisy, out, m)
+            co = self._dev_planes(noisy, codes_out, return_codes, noisy.shape, torch.uint8)
+            dp = self._dev_planes(noisy, disparity_out, return_disparity, (asize, int(width) * int(height)), torch.int8)
+            rc = self._L.lfbm5d_repair_device(self._h, C.byref(rp), C.byref(P), _dev_ptr(noisy), None if flags is None else _dev_ptr(flags, np.uint8),
+                                              mp, msp, _dev_ptr(out), None if co is None else _dev_ptr(co, np.uint8),
+                                              None if dp is None else _dev_ptr(dp, np.int8), *tail)
+            self._ck(rc)
+        return self._repair_result(out, co, dp, res, C_)
+
     # ---- consistency check ----
     def consist(self, noisy, mask, ang_major, awidth, aheight, width, height, chnls, exclude=None, return_disparity=False,
                 flags_out=None, disparity_out=None, fill_nonfinite=True, disparity_steps=1, **params):
@@ -2288,6 +2419,12 @@ def view_synth(noisy, mask, missing, P, ang_major, awidth, aheight, an, width, h
     return (ctx or _ctx()).view_synth(noisy, mask, missing, P, ang_major, awidth, aheight, an, width, height, chnls, **more)
 
 
+def repair(noisy, flags, missing, mask, P, ang_major, awidth, aheight, an, width, height, chnls, ctx=None, **more):
+    """Context.repair on the default context (device 0): defective values and missing SAIs repaired together by a mask-aware plane
+    sweep, refined by the hard-thresholding step."""
+    return (ctx or _ctx()).repair(noisy, flags, missing, mask, P, ang_major, awidth, aheight, an, width, height, chnls, **more)
+
+
 def consist(noisy, mask, ang_major, awidth, aheight, width, height, chnls, ctx=None, **more):
     """Context.consist on the default context (device 0): defective values and bad SAIs found by cross-view consistency."""
     return (ctx or _ctx()).consist(noisy, mask, ang_major, awidth, aheight, width, height, chnls, **more)
@@ -2535,3 +2672,32 @@ def equalise_probe(noisy, mask, awidth, aheight, width, height, chnls, max_dispa
                                ppd.ctypes.data, gain.ctypes.data, state.ctypes.data, counts.ctypes.data, figures.ctypes.data, int(bool(restore))) != 0:
         raise LfBm5dError("equalise_LF failed (message on stdout)")
     return (out, gain, state.astype(np.int64), *(int(v) for v in counts), *(float(v) for v in figures))
+
+
+def repair_probe(noisy, flags, mask, missing, awidth, aheight, width, height, chnls, lambda_, hard, max_disparity=-1, box_radius=-1,
+                 ang_radius=-1, min_valid=-1, iterations=-1, sigma_start=0.0, sigma_end=0.0, sigma_noise=0.0, color_space="opp",
+                 ang_major=ROWMAJOR, an=1):
+    """The C++ drop-in's repair_LF (liblfbm5d_dropin.so, run_bm5d.h) on vector<vector<float>> light fields built from `noisy` and `flags`
+    [asize][chnls*height*width] (flags or missing None: an empty vector); hard = (N, nSim, nDisp, k, p, tau_2D, tau_4D, tau_5D[, useSD]).
+    Returns (the repaired light field, counts = (values, flagged, missing, from other views, from the rim, left), dmin, dmax)."""
+    path = os.path.join(os.path.dirname(library_path()), "liblfbm5d_dropin.so")
+    if not os.path.exists(path):
+        raise LfBm5dError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
+    D = C.CDLL(path)
+    D.lfbm5d_repair_probe.argtypes = [C.c_void_p] * 5 + [C.c_uint] * 7 + [C.c_void_p] * 3 + [C.c_uint, C.c_void_p, C.c_void_p]
+    t = tuple(hard)
+    hv = np.array([t[0], t[1], t[2], t[3], t[4], int(t[8]) if len(t) > 8 else 0, _TAU[t[5]], _TAU[t[6]], _TAU[t[7]]], np.uint32)
+    noisy = np.ascontiguousarray(noisy, np.float32)
+    fl = None if flags is None else np.ascontiguousarray(flags, np.uint8)
+    m, ms = _u32(mask), None if missing is None else _u32(missing)
+    out = noisy.copy()
+    rpi = np.array([max_disparity, box_radius, ang_radius, min_valid, iterations], np.int32)
+    rpf = np.array([sigma_start, sigma_end, sigma_noise, lambda_], np.float32)
+    res, rng = np.zeros(6, np.uint64), np.zeros(2, np.int32)
+    rc = D.lfbm5d_repair_probe(noisy.ctypes.data, None if fl is None else fl.ctypes.data, m.ctypes.data, None if ms is None else ms.ctypes.data,
+                               out.ctypes.data, ang_major, awidth, aheight, an, width, height, chnls, rpi.ctypes.data, rpf.ctypes.data,
+                               hv.ctypes.data, _CS[color_space] if isinstance(color_space, str) else int(color_space),
+                               res.ctypes.data, rng.ctypes.data)
+    if rc != 0:
+        raise LfBm5dError("repair_LF failed (message on stdout)")
+    return out, tuple(int(v) for v in res), int(rng[0]), int(rng[1])

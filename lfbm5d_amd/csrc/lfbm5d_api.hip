@@ -86,6 +86,8 @@ void lfbm5d_destroy(lfbm5d_ctx* c) {
     c->consist.table.release(); c->consist.stats.release(); c->consist.pred.release(); c->consist.disp.release(); c->consist.flags.release();
     c->dbg_agg.tb.release();
     c->photo.table.release(); c->photo.sweep_table.release(); c->photo.stats.release(); c->photo.pred.release(); c->photo.disp.release(); c->photo.x.release();
+    c->repair.valid.release(); c->repair.mid.release(); c->repair.rem.release(); c->repair.tiles.release(); c->repair.table.release();
+    c->repair.stats.release(); c->repair.codes.release(); c->repair.host.release();
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     if (c->h_small) (void)hipHostFree(c->h_small);
     if (c->stream) (void)hipStreamDestroy(c->stream);

@@ -68,6 +68,16 @@
  *                     LFBM5D_MISSING's format into <dir>/missing.txt (empty when none is bad), so that a camera's fixed map can be
  *                     reused.  Together with LFBM5D_DEFECTS or LFBM5D_MISSING it is an error (there is no combined loop).  The files
  *                     hold 8-bit values, so nothing here is non-finite.  Unset, the output is unchanged;
+ *   LFBM5D_REPAIR=joint   joint repair (repair_LF, run_bm5d.h; include/lfbm5d_repair.h): what LFBM5D_DEFECTS, LFBM5D_MISSING -- together
+ *                     or alone under this variable -- or LFBM5D_DETECT name goes to one job in place of the two stages: a plane sweep that
+ *                     skips unsound source values fills flagged values and missing SAIs from the other views, the rim fill takes the
+ *                     rest, one loop refines both with this command's hard-thresholding parameters and sigma_noise = sigma.
+ *                     LFBM5D_REPAIR_ITER=<K> replaces the library's number of refinement steps (LFBM5D_DEFECTS_ITER and
+ *                     LFBM5D_MISSING_ITER are not looked at).  It prints `Joint repair: <n> of <N> values flagged (<pct> %), <b> of <A> SAIs
+ *                     missing; <v> values from other views, <r> from the rim, <l> left; disparities <dmin>..<dmax>, <K> refinement
+ *                     steps`.  Errors that stop the command before it reads a file: any other value, LFBM5D_REPAIR_ITER alone, none of
+ *                     the three variables above, LFBM5D_DISPARITY_STEPS other than 1, LFBM5D_OCCLUSION, LFBM5D_SIGMA=poisson*,
+ *                     LFBM5D_VIEW_SIGMA.  Unset, every command behaves as before, its rejections included;
  *   LFBM5D_OCCLUSION=auto|<ratio>   the occlusion-aware plane sweep (include/lfbm5d_occl.h) in every view synthesis the command runs
  *                     (LFBM5D_MISSING, and the bad SAIs LFBM5D_DETECT hands over): `auto` is the library's ratio, <ratio> a finite
  *                     number >= 1.  The `View synthesis:` line then ends `, occlusion ratio <ratio>: <pct> % of the positions from a
@@ -590,7 +600,8 @@ bool inpaint_defects_LF(vector<vector<float> >& LF_noisy, const vector<vector<un
 }
 
 /* LFBM5D_MISSING / LFBM5D_MISSING_ITER: missing stays empty when unset, else one entry per SAI (non-zero = to be reconstructed);
- * iter < 0: the library's number of steps; false (message printed) on a malformed value or together with LFBM5D_DEFECTS */
+ * iter < 0: the library's number of steps; false (message printed) on a malformed value or together with LFBM5D_DEFECTS (unless
+ * LFBM5D_REPAIR is set, which repair_mode() has checked by then) */
 bool missing_mode(vector<unsigned>& missing, int& iter, unsigned ang_major, unsigned aw, unsigned ah, unsigned s0, unsigned t0) {
     missing.clear(); iter = -1;
     if (const char* e = env("LFBM5D_MISSING_ITER")) {
@@ -604,7 +615,7 @@ bool missing_mode(vector<unsigned>& missing, int& iter, unsigned ang_major, unsi
     }
     const char* e = env("LFBM5D_MISSING");
     if (!e) return true;
-    if (env("LFBM5D_DEFECTS")) { cout << "LFBM5D_MISSING cannot be combined with LFBM5D_DEFECTS (there is no combined loop): run them one after the other" << endl; return false; }
+    if (env("LFBM5D_DEFECTS") && !env("LFBM5D_REPAIR")) { cout << "LFBM5D_MISSING cannot be combined with LFBM5D_DEFECTS (there is no combined loop): run them one after the other" << endl; return false; }
     missing.assign((size_t)aw * ah, 0u);
     const char* p = e;
     bool ok = *p != 0;
@@ -657,6 +668,62 @@ bool synthesise_missing_LF(vector<vector<float> >& LF_noisy, const vector<unsign
         cout << txt;
     }
     if (report) cout << endl;
+    return true;
+}
+
+/* LFBM5D_REPAIR / LFBM5D_REPAIR_ITER: joint = false when unset; iter < 0: the library's number of steps; false (message printed) on a
+ * malformed value, LFBM5D_REPAIR_ITER alone, nothing to hand to the job, or a combination the header comment excludes.  Ahead of every
+ * other *_mode(): missing_mode() admits LFBM5D_DEFECTS beside LFBM5D_MISSING only under it. */
+bool repair_mode(bool& joint, int& iter, int smode) {
+    joint = false; iter = -1;
+    const char* e = env("LFBM5D_REPAIR");
+    const char* it = env("LFBM5D_REPAIR_ITER");
+    if (!e) {
+        if (it) { cout << "LFBM5D_REPAIR_ITER needs LFBM5D_REPAIR" << endl; return false; }
+        return true;
+    }
+    if (strcmp(e, "joint")) {
+        cout << "LFBM5D_REPAIR must be \"joint\" (defects and missing views repaired together by one mask-aware sweep and one loop), or unset; got \""
+             << e << "\"" << endl;
+        return false;
+    }
+    if (it) {
+        char* q = nullptr;
+        const long v = strtol(it, &q, 10);
+        if (q == it || *q || isspace((unsigned char)*it) || v < 0 || v > 1000) {
+            cout << "LFBM5D_REPAIR_ITER must be a number of refinement steps 0 <= K <= 1000, or unset; got \"" << it << "\"" << endl;
+            return false;
+        }
+        iter = (int)v;
+    }
+    if (!env("LFBM5D_DEFECTS") && !env("LFBM5D_MISSING") && !env("LFBM5D_DETECT")) {
+        cout << "LFBM5D_REPAIR needs LFBM5D_DEFECTS, LFBM5D_MISSING or LFBM5D_DETECT" << endl;
+        return false;
+    }
+    if (const char* d = env("LFBM5D_DISPARITY_STEPS"))
+        if (strcmp(d, "1")) { cout << "LFBM5D_REPAIR cannot be combined with LFBM5D_DISPARITY_STEPS other than 1 (the joint sweep takes integer disparities only)" << endl; return false; }
+    if (env("LFBM5D_OCCLUSION")) { cout << "LFBM5D_REPAIR cannot be combined with LFBM5D_OCCLUSION (the joint sweep does not reason about occlusions)" << endl; return false; }
+    if (smode >= 2) { cout << "LFBM5D_REPAIR cannot be combined with LFBM5D_SIGMA=poisson (the refinement steps assume one sigma)" << endl; return false; }
+    if (env("LFBM5D_VIEW_SIGMA")) { cout << "LFBM5D_REPAIR cannot be combined with LFBM5D_VIEW_SIGMA (the refinement steps assume one sigma)" << endl; return false; }
+    joint = true;
+    return true;
+}
+
+/* LFBM5D_REPAIR=joint: the fill (steps = 0) or the fill and the refinement loop, in place; flags and missing may be empty; hard as for
+ * inpaint_defects_LF.  report: print the line of the header comment, with the steps that are still to come. */
+bool repair_joint_LF(vector<vector<float> >& LF_noisy, const vector<vector<unsigned char> >& flags, const vector<unsigned>& mask,
+                     const vector<unsigned>& missing, unsigned ang_major, unsigned aw, unsigned ah, unsigned an, unsigned W, unsigned H, unsigned C,
+                     unsigned steps, unsigned steps_to_come, float sigma_noise, float lambda, const unsigned* hard, unsigned cs, bool report) {
+    unsigned long long r[6];   /* values, flagged, missing, from other views, from the rim, left */
+    int dmin = 0, dmax = 0;
+    if (repair_LF(LF_noisy, flags, mask, missing, ang_major, aw, ah, an, W, H, C, -1, -1, -1, -1, (int)steps, 0.0f, 0.0f, sigma_noise, lambda, hard[0],
+                  hard[1], hard[2], hard[3], hard[4], hard[5] != 0, hard[6], hard[7], hard[8], cs, r, dmin, dmax) != EXIT_SUCCESS) return false;
+    unsigned all = 0;
+    for (size_t st = 0; st < mask.size(); st++) if (mask[st]) all++;
+    if (report)
+        cout << endl << "Joint repair: " << r[1] << " of " << r[0] << " values flagged (" << 100.0 * (double)r[1] / (double)r[0] << " %), " << r[2]
+             << " of " << all << " SAIs missing; " << r[3] << " values from other views, " << r[4] << " from the rim, " << r[5]
+             << " left; disparities " << dmin << ".." << dmax << ", " << steps_to_come << " refinement steps" << endl;
     return true;
 }
 
@@ -999,6 +1066,8 @@ int main(int argc, char** argv) {
     if (qmode < 0) return EXIT_FAILURE;
     double imp_k = -1.0, imp_add = 0.0;
     if (!impulse_mode(imp_k, imp_add)) return EXIT_FAILURE;
+    bool joint = false; int rep_iter = -1;
+    if (!repair_mode(joint, rep_iter, smode)) return EXIT_FAILURE;
     const char* def_dir = nullptr; int def_iter = -1;
     if (!defects_mode(def_dir, def_iter)) return EXIT_FAILURE;
     vector<unsigned> missing; int miss_iter = -1;
@@ -1050,6 +1119,16 @@ int main(int argc, char** argv) {
     vector<vector<unsigned char> > detected;
     if (detect && !detect_LF(LF_noisy, mask, det_k, det_save, name, sep, ang_major, aw, ah, s0, t0, W, H, C, missing, detected, dsteps)) return EXIT_FAILURE;
     vector<unsigned> est_mask = mask;   /* the sigma estimate does not look at reconstructed SAIs */
+    if (joint && (def_dir || !detected.empty() || !missing.empty())) {   /* one joint fill in place of the two below */
+        vector<vector<unsigned char> > defects;
+        const unsigned hard[9] = {8, 8, 3, 8, 3, 0, LFBM5D_DCT, LFBM5D_SADCT, LFBM5D_HAAR};
+        if (!def_dir) defects.swap(detected);
+        else if (!load_defects(def_dir, name, sep, defects, mask, ang_major, aw, ah, s0, t0, W, H, C)) return EXIT_FAILURE;
+        if (!repair_joint_LF(LF_noisy, defects, mask, missing, ang_major, aw, ah, 1, W, H, C, 0, 0, 0.0f, lambda, hard, (unsigned)cs, true)) return EXIT_FAILURE;
+        cout << "Joint repair: the fill alone (the refinement steps run in LFBM5Ddenoising)" << endl;
+        for (size_t st = 0; st < missing.size(); st++) if (missing[st]) est_mask[st] = 0;
+        missing.clear(); def_dir = nullptr; detected.clear();
+    }
     if (!missing.empty()) {   /* the synthesis alone, for the same reason as the fill alone below */
         const unsigned hard[9] = {8, 8, 3, 8, 3, 0, LFBM5D_DCT, LFBM5D_SADCT, LFBM5D_HAAR};
         if (!synthesise_missing_LF(LF_noisy, mask, missing, ang_major, aw, ah, 1, W, H, C, 0, 0, 0.0f, lambda, hard, (unsigned)cs, true, dsteps, occl)) return EXIT_FAILURE;
@@ -1192,6 +1271,8 @@ int main(int argc, char** argv) {
     if (qmode < 0) return EXIT_FAILURE;
     double imp_k = -1.0, imp_add = 0.0;
     if (!impulse_mode(imp_k, imp_add)) return EXIT_FAILURE;
+    bool joint = false; int rep_iter = -1;
+    if (!repair_mode(joint, rep_iter, smode)) return EXIT_FAILURE;
     const char* def_dir = nullptr; int def_iter = -1;
     if (!defects_mode(def_dir, def_iter)) return EXIT_FAILURE;
     vector<unsigned> missing; int miss_iter = -1;
@@ -1246,8 +1327,19 @@ int main(int argc, char** argv) {
     vector<unsigned> est_mask = mask;   /* the sigma estimate does not look at reconstructed SAIs */
     unsigned view_steps = 0;
     if (detect && !detect_LF(LF_noisy, mask, det_k, det_save, name, sep, ang_major, aw, ah, s0, t0, W, H, C, missing, defects, dsteps)) return EXIT_FAILURE;
-    const bool have_defects = def_dir || !defects.empty();
-    if (!missing.empty()) {
+    unsigned rep_steps = 0;
+    const bool joint_job = joint && (def_dir || !defects.empty() || !missing.empty());
+    if (joint_job) {   /* one joint fill now, one loop behind the sigma estimate, in place of the two stages below */
+        lfbm5d_repair_params rp;
+        lfbm5d_repair_defaults(&rp);
+        rep_steps = rep_iter >= 0 ? (unsigned)rep_iter : rp.iterations;
+        if (def_dir && !load_defects(def_dir, name, sep, defects, mask, ang_major, aw, ah, s0, t0, W, H, C)) return EXIT_FAILURE;
+        if (!repair_joint_LF(LF_noisy, defects, mask, missing, ang_major, aw, ah, anH, W, H, C, 0, rep_steps, 0.0f, lambda, def_hard, (unsigned)cs, true))
+            return EXIT_FAILURE;
+        for (size_t st = 0; st < missing.size(); st++) if (missing[st]) est_mask[st] = 0;
+    }
+    const bool have_defects = !joint_job && (def_dir || !defects.empty());
+    if (!joint_job && !missing.empty()) {
         lfbm5d_view_params vp;
         lfbm5d_view_defaults(&vp);
         view_steps = smode >= 2 ? 0u : miss_iter >= 0 ? (unsigned)miss_iter : vp.iterations;
@@ -1268,6 +1360,8 @@ int main(int argc, char** argv) {
     if (imp_k >= 0.0 && !repair_impulses_LF(LF_noisy, mask, W, H, C, imp_k)) return EXIT_FAILURE;
     if (smode == 1 && !(clip_on ? estimate_sigma_clipped_LF(LF_noisy, est_mask, W, H, C, clip_lo, clip_hi, sigma)
                                 : estimate_sigma_LF(LF_noisy, est_mask, W, H, C, sigma))) return EXIT_FAILURE;
+    if (rep_steps && !repair_joint_LF(LF_noisy, defects, mask, missing, ang_major, aw, ah, anH, W, H, C, rep_steps, rep_steps, sigma, lambda, def_hard,
+                                      (unsigned)cs, false)) return EXIT_FAILURE;
     if (view_steps && !synthesise_missing_LF(LF_noisy, mask, missing, ang_major, aw, ah, anH, W, H, C, view_steps, view_steps, sigma, lambda, def_hard,
                                              (unsigned)cs, false, dsteps, occl)) return EXIT_FAILURE;
     if (def_steps && !inpaint_defects_LF(LF_noisy, defects, mask, ang_major, aw, ah, anH, W, H, C, def_steps, def_steps, sigma, lambda, def_hard,

@@ -7,7 +7,7 @@
  *                      streamed host seam
  *   lfbm5d_steps.hip   run_bm5d_1st_step / run_bm5d_2nd_step / both as one job on device buffers: schedule forms, tile mode
  *   lfbm5d_api.hip     the C-ABI of include/lfbm5d.h: context, options, communicators, host entry points, BM3D, inspection
- *   lfbm5d_side.h      the host frame of the side stages (lfbm5d_noise / quality / resample / pg / impulse / inpaint / view / consist / photo.hip):
+ *   lfbm5d_side.h      the host frame of the side stages (lfbm5d_noise / quality / resample / pg / impulse / inpaint / view / consist / photo / repair.hip):
  *                      SAI list, argument checks, staging of per-SAI host planes, the refinement loop, the sweep's source rows
  *   lfbm5d_side_values.h   what those stages share per value, host-and-device and free of HIP headers: tile, mirror, bit tests, key
  *                      layout, thresholds, the loop's sigma schedule
@@ -182,6 +182,10 @@ struct lfbm5d_ctx {
      * the leave-one-out source lists, histograms and counters, the prediction light field, the sweep's disparity planes, the host
      * form's output light field */
     struct PhotoBufs { DevBuf table, sweep_table, stats, pred, disp, x; std::vector<unsigned> planes_host; std::vector<float> factors_host; } photo;
+    /* joint repair (lfbm5d_repair.hip): the validity planes, the sweep's copy of the input and the flags of what is still unsound, the
+     * unsound positions per tile, the source lists with the float tables and the missing list, the counters, the code planes when the
+     * caller wants none, the host form's flag, code and disparity planes */
+    struct RepairBufs { DevBuf valid, mid, rem, tiles, table, stats, codes, host; } repair;
     /* window lanes (run_graph; the per-SAI BM3D steps): extra contexts on the same device, each with its own stream, window
      * buffers and per-pass work buffers; owned by this context */
     std::vector<lfbm5d_ctx*> lanes;

@@ -816,6 +816,93 @@ extern "C" int lfbm5d_view_synth_occl_probe(const float* in_flat, const unsigned
 }
 
 /* consistency check on the caller's vectors (one pointer per SAI; the library stages in and out) */
+/* joint repair on the caller's vectors, in place for the caller (one pointer per SAI; the library stages in and out apart) */
+int repair_LF(std::vector<std::vector<float> >& LF, const std::vector<std::vector<unsigned char> >& flags, const std::vector<unsigned>& LF_SAI_mask,
+              const std::vector<unsigned>& missing, const unsigned ang_major, const unsigned awidth, const unsigned aheight, const unsigned anHard,
+              const unsigned width, const unsigned height, const unsigned chnls, const int maxDisparity, const int boxRadius, const int angRadius,
+              const int minValid, const int iterations, const float sigmaStart, const float sigmaEnd, const float sigmaNoise,
+              const float lambdaHard5D, const unsigned NHard, const unsigned nSim, const unsigned nDisp, const unsigned kHard,
+              const unsigned pHard, const bool useSD, const unsigned tau_2D, unsigned tau_4D, const unsigned tau_5D, const unsigned color_space,
+              unsigned long long counts[6], int& dmin, int& dmax) {
+    const unsigned asize = awidth * aheight;
+    lfbm5d_repair_result result;
+    std::memset(&result, 0, sizeof(result));
+    std::memset(counts, 0, 6 * sizeof(unsigned long long));
+    dmin = dmax = 0;
+    if (LF.size() != asize || LF_SAI_mask.size() != asize || (!flags.empty() && flags.size() != asize) || (!missing.empty() && missing.size() != asize)) {
+        std::cout << "repair_LF: light field and mask must hold awidth*aheight SAIs, flags and missing that many or none" << std::endl;
+        return EXIT_FAILURE;
+    }
+    lfbm5d_repair_params rp;
+    lfbm5d_repair_defaults(&rp);
+    if (maxDisparity >= 0) rp.max_disparity = (unsigned)maxDisparity;
+    if (boxRadius >= 0) rp.box_radius = (unsigned)boxRadius;
+    if (angRadius >= 0) rp.ang_radius = (unsigned)angRadius;
+    if (minValid >= 0) rp.min_valid = (unsigned)minValid;
+    if (iterations >= 0) rp.iterations = (unsigned)iterations;
+    if (sigmaStart != 0.0f) rp.sigma_start = sigmaStart;
+    if (sigmaEnd != 0.0f) rp.sigma_end = sigmaEnd;
+    rp.sigma_noise = sigmaNoise;
+    lfbm5d_ctx* ctx = context();
+    if (!ctx) return EXIT_FAILURE;
+    const size_t img = (size_t)width * height * chnls;
+    std::vector<float*> p(asize, nullptr);
+    std::vector<const unsigned char*> f(asize, nullptr);
+    for (size_t st = 0; st < asize; st++)
+        if (LF_SAI_mask[st]) {
+            if (LF[st].size() != img || (!flags.empty() && flags[st].size() != img)) {
+                std::cout << "repair_LF: a non-empty SAI does not hold width*height*chnls values and flags" << std::endl;
+                return EXIT_FAILURE;
+            }
+            p[st] = LF[st].data();
+            if (!flags.empty()) f[st] = flags[st].data();
+        }
+    const lfbm5d_params P = make(0.0f, lambdaHard5D, NHard, nSim, nDisp, kHard, pHard, useSD, tau_2D, tau_4D, tau_5D, color_space);
+    const int rc = lfbm5d_repair_host_sai(ctx, &rp, &P, p.data(), flags.empty() ? nullptr : f.data(), LF_SAI_mask.data(),
+                                          missing.empty() ? nullptr : missing.data(), p.data(), nullptr, nullptr, ang_major, awidth, aheight, anHard,
+                                          width, height, chnls, &result);
+    counts[0] = result.values; counts[1] = result.flagged; counts[2] = result.missing;
+    for (unsigned c = 0; c < 3; c++) { counts[3] += result.views[c]; counts[4] += result.rim[c]; counts[5] += result.left[c]; }
+    bool any = false;
+    for (int d = -8; d <= 8; d++)
+        if (result.disparity_hist[d + 8]) { if (!any) dmin = d; dmax = d; any = true; }
+    if (rc != 0) {
+        std::cout << "LFBM5D GPU backend: " << lfbm5d_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+    }
+    return EXIT_SUCCESS;
+}
+
+/* Test hook: repair_LF on vector<vector<float>> light fields built from flat copies [asize][chnls*height*width] (flags_flat or NULL,
+ * missing or NULL); the result goes to out_flat.  rpi = {maxDisparity, boxRadius, angRadius, minValid, iterations}, rpf = {sigmaStart,
+ * sigmaEnd, sigmaNoise, lambda}, hard = {N, nSim, nDisp, k, p, useSD, tau_2D, tau_4D, tau_5D}; counts [6] as repair_LF's;
+ * range = {dmin, dmax}. */
+extern "C" int lfbm5d_repair_probe(const float* in_flat, const unsigned char* flags_flat, const unsigned* mask, const unsigned* missing,
+                                   float* out_flat, unsigned ang_major, unsigned awidth, unsigned aheight, unsigned an, unsigned width,
+                                   unsigned height, unsigned chnls, const int* rpi, const float* rpf, const unsigned* hard, unsigned color_space,
+                                   unsigned long long* counts, int* range) {
+    const size_t asize = (size_t)awidth * aheight, img = (size_t)width * height * chnls;
+    std::vector<unsigned> m(mask, mask + asize), ms;
+    if (missing) ms.assign(missing, missing + asize);
+    std::vector<std::vector<float> > LF(asize);
+    std::vector<std::vector<unsigned char> > fl(flags_flat ? asize : 0);
+    for (size_t st = 0; st < asize; st++)
+        if (m[st]) {
+            LF[st].assign(in_flat + st * img, in_flat + (st + 1) * img);
+            if (flags_flat) fl[st].assign(flags_flat + st * img, flags_flat + (st + 1) * img);
+        }
+    unsigned long long r[6];
+    int dmin = 0, dmax = 0;
+    const int rc = repair_LF(LF, fl, m, ms, ang_major, awidth, aheight, an, width, height, chnls, rpi[0], rpi[1], rpi[2], rpi[3], rpi[4], rpf[0],
+                             rpf[1], rpf[2], rpf[3], hard[0], hard[1], hard[2], hard[3], hard[4], hard[5] != 0, hard[6], hard[7], hard[8],
+                             color_space, r, dmin, dmax);
+    if (counts) std::memcpy(counts, r, sizeof(r));
+    if (range) { range[0] = dmin; range[1] = dmax; }
+    if (rc != EXIT_SUCCESS) return 1;
+    for (size_t st = 0; st < asize; st++) if (m[st]) std::memcpy(out_flat + st * img, LF[st].data(), img * sizeof(float));
+    return 0;
+}
+
 int consist_LF(const std::vector<std::vector<float> >& LF, const std::vector<unsigned>& LF_SAI_mask, const std::vector<unsigned>& exclude,
                const unsigned ang_major, const unsigned awidth, const unsigned aheight, const unsigned width, const unsigned height,
                const unsigned chnls, const int maxDisparity, const int boxRadius, const int angRadius, const int minSources, const int maxRounds,

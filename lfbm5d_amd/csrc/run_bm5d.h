@@ -440,6 +440,52 @@ int view_synth_LF(
 ,   unsigned long long *set_hist = nullptr
 );
 
+//! Joint repair -- not in the reference: the values that `flags` names (one uint8 plane per non-empty SAI, non-zero = defective; an empty
+//! vector: no flags), every value that is not finite and every value of the SAIs that `missing` marks (non-zero; an empty vector: none;
+//! they must be non-empty in LF_SAI_mask and hold width*height*chnls values, which are not used) are filled on the GPU from the other
+//! views by a plane sweep that skips unsound source values, what it cannot reach from the rim of its own plane, and the fill is refined
+//! by `iterations` hard-thresholding steps whose sigma falls from sigmaStart to sigmaEnd but not below sigmaNoise, the sound values
+//! being put back after every step (lfbm5d_repair_host_sai, include/lfbm5d_repair.h).  LF is repaired in place.  maxDisparity,
+//! boxRadius, angRadius, minValid, iterations < 0, sigmaStart = 0, sigmaEnd = 0: the library's defaults (lfbm5d_repair_defaults);
+//! iterations = 0: the fill alone.  `counts` receives the values of the non-empty SAIs, the non-zero flags, the SAIs marked missing and the
+//! values filled from other views, filled from the rim and left, over all channels; dmin..dmax is the range of the disparities chosen (0..0 when the sweep
+//! wrote nothing).  Returns EXIT_SUCCESS, or EXIT_FAILURE with the message on stdout.
+int repair_LF(
+    std::vector<std::vector<float> > &LF
+,   const std::vector<std::vector<unsigned char> > &flags
+,   const std::vector<unsigned> &LF_SAI_mask
+,   const std::vector<unsigned> &missing
+,   const unsigned ang_major
+,   const unsigned awidth
+,   const unsigned aheight
+,   const unsigned anHard
+,   const unsigned width
+,   const unsigned height
+,   const unsigned chnls
+,   const int      maxDisparity
+,   const int      boxRadius
+,   const int      angRadius
+,   const int      minValid
+,   const int      iterations
+,   const float    sigmaStart
+,   const float    sigmaEnd
+,   const float    sigmaNoise
+,   const float    lambdaHard5D
+,   const unsigned NHard
+,   const unsigned nSim
+,   const unsigned nDisp
+,   const unsigned kHard
+,   const unsigned pHard
+,   const bool     useSD
+,   const unsigned tau_2D
+,         unsigned tau_4D
+,   const unsigned tau_5D
+,   const unsigned color_space
+,   unsigned long long counts[6]
+,   int &dmin
+,   int &dmax
+);
+
 //! Consistency check -- not in the reference: every usable SAI is predicted on the GPU from its angular neighbours by the view synthesis'
 //! plane sweep with the SAI itself left out; a value is flagged (1) when its residual exceeds k times the light field's median residual
 //! and `spread` times the sources' own disagreement, or (2) when it is not finite; an SAI is bad when its median residual stands out
