@@ -1039,6 +1039,78 @@ typedef struct lfbm5d_group_debug {
  * stream, and waits.  The group list of the launch is read with lfbm5d_last_group_list. */
 int lfbm5d_debug_group(lfbm5d_ctx* ctx, const lfbm5d_group_debug* args);
 
+/* The kernels of the window schedule (lfbm5d_window.hip) alone, one launcher per call, on buffers the caller supplies: colour
+ * transforms, mirror padding and cropping, estimates, coverage counts, the two ends of a window, the per-SAI finalisation and
+ * output kernels, the tile and band copies.  For the tests that predict every one of them bit for bit (tests/window_model.py).
+ * `op` selects the launcher; the table says which fields it reads (everything else is ignored):
+ *   COLOR             noisy in place, [n_sai][lf_stride] holding [3][H][W]; dmask (may be NULL); cs; forward
+ *   COLOR_ROUNDTRIP   noisy -> out (out == noisy allowed), likewise
+ *   SYMETRIZE         noisy [C][H][W] -> w_noisy [C][H + 2 N][W + 2 N]
+ *   CROP              w_noisy [C][H + 2 N][W + 2 N] -> out [C][H][W], the crop at (off, off); off == N: unsymetrize
+ *   SYMETRIZE_MULTI   noisy [SAI][lf_stride] -> w_noisy [slot][w_stride], slot i <- SAI list[i]
+ *   UNSYMETRIZE_MULTI w_noisy [slot][w_stride] -> out [SAI][lf_stride], SAI list[i] <- slot i
+ *   ESTIMATE          est[i] = den[i] ? num[i] / den[i] : sub[i] on n elements
+ *   ESTIMATE_MULTI    w_num, w_den, w_noisy (the substitute) [slot][C][n] -> est [slot][n], channel 0 of the slots of slot_mask
+ *   ESTIMATE_LF       num, den, sub -> out, [n_sai][n]; dmask (may be NULL)
+ *   WINDOW_BEGIN      noisy, basic (may be NULL), num, den [SAI][lf_stride] -> w_noisy, w_basic, w_num, w_den [slot][w_stride] and
+ *                     est [slot][(H + 2 N)(W + 2 N)]; counters[0 .. 32) cleared; direct form: w_num == w_den == NULL
+ *   WINDOW_END        w_num, w_den -> num, den (of SAI list[i]), the coverage count added to counters[0 .. 32); patch side k;
+ *                     direct form (w_num == w_den == NULL): the count alone, from den
+ *   FINALIZE          num, den, sub -> basic, the SAIs list[0 .. n_list) of [SAI][lf_stride] holding [3][H][W]; cs; colour
+ *   OUTPUT            num, den, sub -> out; basic in place (may be NULL); noisy -> noisy_dst; likewise (sub == basic, noisy == noisy_dst allowed)
+ *   COUNT_ZEROS       den [n_sai][n]: counters[i] += exact zeros of segment i
+ *   COUNT_DENOISED    w_den [slot][w_stride] holding [C][H + 2 N][W + 2 N], the slots of slot_mask: counters[0] += the coverage count; k
+ *   COPY_RECT         w_noisy (slots w_stride apart, [C][sH][sW]) -> out (slots lf_stride apart, [C][H][W]): the rw x rh rectangle at
+ *                     (sx0, sy0) to (dx0, dy0), the slots of slot_mask
+ *   COPY_ROWS         w_noisy (n_sai planes of sH rows of W) rows [sy0, sy0 + rh) -> out (planes of H rows) rows dy0 ...
+ * Device pointers unless marked host. */
+enum lfbm5d_window_op {
+    LFBM5D_WOP_COLOR = 0, LFBM5D_WOP_COLOR_ROUNDTRIP = 1, LFBM5D_WOP_SYMETRIZE = 2, LFBM5D_WOP_CROP = 3, LFBM5D_WOP_SYMETRIZE_MULTI = 4,
+    LFBM5D_WOP_UNSYMETRIZE_MULTI = 5, LFBM5D_WOP_ESTIMATE = 6, LFBM5D_WOP_ESTIMATE_MULTI = 7, LFBM5D_WOP_ESTIMATE_LF = 8,
+    LFBM5D_WOP_WINDOW_BEGIN = 9, LFBM5D_WOP_WINDOW_END = 10, LFBM5D_WOP_FINALIZE = 11, LFBM5D_WOP_OUTPUT = 12, LFBM5D_WOP_COUNT_ZEROS = 13,
+    LFBM5D_WOP_COUNT_DENOISED = 14, LFBM5D_WOP_COPY_RECT = 15, LFBM5D_WOP_COPY_ROWS = 16
+};
+typedef struct lfbm5d_window_debug {
+    float* noisy;               /* the light-field side: lf_stride floats per SAI, lf_floats each */
+    float* basic;
+    float* num;
+    float* den;
+    float* sub;
+    float* out;
+    float* noisy_dst;
+    float* w_noisy;             /* the window side: w_stride floats per slot, w_floats each */
+    float* w_basic;
+    float* w_num;
+    float* w_den;
+    float* est;                 /* est_floats */
+    unsigned* counters;         /* counter_words */
+    const unsigned* dmask;      /* [n_sai] SAI mask on the device (0 = skip), dmask_words; NULL: every SAI */
+    const unsigned* list;       /* host, [n_list]: slot -> SAI of the light field, 0xffffffff: empty slot */
+    const unsigned* slot_mask;  /* host, [n_list]: non-zero = the slot is there */
+    unsigned long long lf_stride;
+    unsigned long long w_stride;
+    unsigned long long lf_floats;
+    unsigned long long w_floats;
+    unsigned long long est_floats;
+    unsigned long long n;       /* elements (ESTIMATE), per slot (ESTIMATE_MULTI), per segment (ESTIMATE_LF, COUNT_ZEROS) */
+    unsigned op;
+    unsigned W, H, C, N, k, off;
+    unsigned cs, forward, colour;
+    unsigned n_sai;             /* SAIs, segments or planes of the ops without a list */
+    unsigned n_list;            /* entries of list / slot_mask */
+    unsigned sW, sH, sx0, sy0, dx0, dy0, rw, rh;
+    unsigned counter_words, dmask_words;
+} lfbm5d_window_debug;
+/* Checks the arguments against what the kernels take for granted (message via lfbm5d_last_error, nothing launched): pointers, C,
+ * sizes of 0, the colour space, N <= W and N <= H where the op mirrors, k <= W and k <= H where it counts, at most 289 slots, list entries inside the
+ * light field the buffer sizes imply, strides of at least one image, every buffer against the geometry, rectangles and row ranges
+ * inside their images.  Then runs the one launcher on the context's stream, and waits. */
+int lfbm5d_debug_window(lfbm5d_ctx* ctx, const lfbm5d_window_debug* args);
+
+/* The noise level of every channel behind the forward colour transform (utilities.cpp:633-684), as the passes take it: out[0 .. C).
+ * Host only, no context.  Returns non-zero for an unknown colour space. */
+int lfbm5d_sigma_table(float sigma, unsigned C, unsigned color_space, float* out);
+
 /* ---- device memory helpers so hosts without a HIP binding (ctypes, cgo, JNI) can stage data ---- */
 int lfbm5d_malloc(void** dptr, size_t bytes);
 int lfbm5d_free(void* dptr);

@@ -72,6 +72,20 @@ class GroupDebugStruct(C.Structure):
                                            "n_groups", "bm3d")])
 
 
+WINDOW_OPS = ("color", "color_roundtrip", "symetrize", "crop", "symetrize_multi", "unsymetrize_multi", "estimate", "estimate_multi",
+              "estimate_lf", "window_begin", "window_end", "finalize", "output", "count_zeros", "count_denoised", "copy_rect", "copy_rows")
+_WINDOW_LF = ("noisy", "basic", "num", "den", "sub", "out", "noisy_dst")   # the light-field side of lfbm5d_window_debug
+_WINDOW_W = ("w_noisy", "w_basic", "w_num", "w_den")                        # ... and the window side
+
+
+class WindowDebugStruct(C.Structure):
+    """lfbm5d_window_debug: one launcher of the window-schedule kernels on buffers the caller supplies (include/lfbm5d.h)."""
+    _fields_ = ([(n, C.c_void_p) for n in _WINDOW_LF + _WINDOW_W + ("est", "counters", "dmask", "list", "slot_mask")]
+                + [(n, C.c_ulonglong) for n in ("lf_stride", "w_stride", "lf_floats", "w_floats", "est_floats", "n")]
+                + [(n, C.c_uint) for n in ("op", "W", "H", "C", "N", "k", "off", "cs", "forward", "colour", "n_sai", "n_list", "sW", "sH",
+                                           "sx0", "sy0", "dx0", "dy0", "rw", "rh", "counter_words", "dmask_words")])
+
+
 class NoiseLevelStruct(C.Structure):
     """lfbm5d_noise_level: the blind noise-level estimate (include/lfbm5d.h)."""
     _fields_ = [("sigma", C.c_double), ("sigma_channel", C.c_double * 3), ("components", C.c_uint), ("patch", C.c_uint),
@@ -544,6 +558,9 @@ def lib():
         L.lfbm5d_debug_aggregate.argtypes = [vp, C.POINTER(AggDebugStruct)]
     if hasattr(L, "lfbm5d_debug_group"):
         L.lfbm5d_debug_group.argtypes = [vp, C.POINTER(GroupDebugStruct)]
+    if hasattr(L, "lfbm5d_debug_window"):
+        L.lfbm5d_debug_window.argtypes = [vp, C.POINTER(WindowDebugStruct)]
+        L.lfbm5d_sigma_table.argtypes = [C.c_float, C.c_uint, C.c_uint, fp]
     if hasattr(L, "lfbm5d_noise_level_device"):   # (absent from older builds loaded through LFBM5D_HIP_LIB for A/B runs)
         dp, np_ = C.POINTER(C.c_double), C.POINTER(NoiseLevelStruct)
         L.lfbm5d_noise_level_device.argtypes = [vp, fp, up] + [C.c_uint] * 5 + [np_, dp, dp]
@@ -801,6 +818,14 @@ def quality_summary(mse_sai, ssim_sai, mask, peak=255.0):
     if ssim is not None:
         ssim[m == 0] = 0.0
     return _quality_result(res, mse, ssim, m, peak)
+
+
+def sigma_table(sigma, chnls, color_space):
+    """lfbm5d_sigma_table (host only, no GPU): the noise level of every channel behind the forward colour transform, float32 [chnls]."""
+    out = np.zeros(3, np.float32)
+    if lib().lfbm5d_sigma_table(float(sigma), int(chnls), int(color_space), out.ctypes.data_as(C.POINTER(C.c_float))) != 0:
+        raise LfBm5dError("lfbm5d_sigma_table: unknown colour space")
+    return out[:chnls]
 
 
 def pg_fit(hist, sum_m):
@@ -2337,6 +2362,46 @@ class Context:
             setattr(a, name, None)
         self._ck(self._L.lfbm5d_debug_group(self._h, C.byref(a)))
         return text.value.decode(), int(counters[0]), int(counters[1])
+
+    def debug_window(self, op, *, list=None, slot_mask=None, **f):
+        """lfbm5d_debug_window: one launcher of the window-schedule kernels alone.  op: a name of WINDOW_OPS.  The buffers go by the
+        names of lfbm5d_window_debug (include/lfbm5d.h has the table of what each op reads): float32 CUDA tensors, `counters` and
+        `dmask` int32 CUDA tensors holding the uint32 words; a None buffer goes to the library as a NULL pointer.  list, slot_mask:
+        sequences of integers.  Everything else (W, H, C, N, k, off, cs, forward, colour, n_sai, n, strides, rectangle) by keyword;
+        the sizes the library checks the geometry against are taken from the tensors (the smallest of each side), unless given."""
+        import torch
+
+        a = WindowDebugStruct()
+        a.op = WINDOW_OPS.index(op)
+        sizes = {"lf_floats": [], "w_floats": []}
+        for name in _WINDOW_LF + _WINDOW_W + ("est", "counters", "dmask"):
+            t = f.pop(name, None)
+            if t is None:
+                continue
+            dtype = torch.int32 if name in ("counters", "dmask") else torch.float32
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+                raise LfBm5dError("debug_window takes contiguous CUDA tensors: float32 values, int32 counters and masks")
+            torch.cuda.current_stream(t.device).synchronize()
+            setattr(a, name, t.data_ptr())
+            if name in _WINDOW_LF:
+                sizes["lf_floats"].append(t.numel())
+            elif name in _WINDOW_W:
+                sizes["w_floats"].append(t.numel())
+            else:
+                setattr(a, {"est": "est_floats", "counters": "counter_words", "dmask": "dmask_words"}[name], t.numel())
+        for key, v in sizes.items():
+            setattr(a, key, min(v) if v else 0)
+        keep = [None if x is None else _u32(x) for x in (list, slot_mask)]
+        a.list, a.slot_mask = [None if x is None else x.ctypes.data for x in keep]
+        n_list = f.pop("n_list", None)
+        a.n_list = max((x.size for x in keep if x is not None), default=0) if n_list is None else int(n_list)
+        if any(x is not None and x.size < a.n_list for x in keep):
+            raise LfBm5dError("debug_window: list and slot_mask hold n_list entries")
+        for key, v in f.items():
+            if key not in dict(WindowDebugStruct._fields_) or key in ("list", "slot_mask", "op"):
+                raise LfBm5dError("debug_window: unknown field " + key)
+            setattr(a, key, int(v))
+        self._ck(self._L.lfbm5d_debug_window(self._h, C.byref(a)))
 
 
 _default_ctx = None

@@ -507,6 +507,7 @@ int run_bm3d_lf(lfbm5d_ctx* c, const lfbm5d_bm3d_params* Hd, const lfbm5d_bm3d_p
     const bool views = !c->views.table.empty();   /* a view table (include/lfbm5d_views.h): SAI v is filtered with sigma_v in both steps */
     if (Hd->color_space != Wn->color_space || (!views && Hd->sigma != Wn->sigma)) return fail(c, "BM3D: both steps share sigma and colour space");
     const unsigned nP = Hd->nHW, Wb = W + 2 * nP, Hb = H + 2 * nP;
+    if (check_padding(c, W, H, nP)) return 1;
     const size_t img = (size_t)C * W * H, imgb = (size_t)C * Wb * Hb;
     /* The SAIs are independent images (bm3d_LF.cpp:106-121 is a plain loop): they are dealt to lanes -- contexts with a stream and
      * work buffers of their own -- so that the kernels of several SAIs are in flight together.  One SAI's launches are small (a
@@ -863,6 +864,185 @@ int lfbm5d_debug_group(lfbm5d_ctx* c, const lfbm5d_group_debug* d) {
         d->kernels[n] = 0;
     }
     return 0;
+}
+
+int lfbm5d_debug_window(lfbm5d_ctx* c, const lfbm5d_window_debug* d) {
+    if (!c) return 1;
+    if (!d) return fail(c, "debug_window: no arguments");
+    typedef unsigned long long u64;
+    const unsigned op = d->op, W = d->W, H = d->H, C = d->C, N = d->N, k = d->k;
+    if (op > LFBM5D_WOP_COPY_ROWS) return fail(c, "debug_window: unknown op");
+    /* what the kernels of lfbm5d_window.hip take for granted (the steps guarantee it by construction) */
+    const bool flat = op == LFBM5D_WOP_ESTIMATE || op == LFBM5D_WOP_ESTIMATE_MULTI || op == LFBM5D_WOP_ESTIMATE_LF || op == LFBM5D_WOP_COUNT_ZEROS;
+    const bool three = op == LFBM5D_WOP_COLOR || op == LFBM5D_WOP_COLOR_ROUNDTRIP || op == LFBM5D_WOP_FINALIZE || op == LFBM5D_WOP_OUTPUT;
+    const bool mirrors = op == LFBM5D_WOP_SYMETRIZE || op == LFBM5D_WOP_SYMETRIZE_MULTI || op == LFBM5D_WOP_WINDOW_BEGIN;
+    const bool padded = mirrors || op == LFBM5D_WOP_CROP || op == LFBM5D_WOP_UNSYMETRIZE_MULTI || op == LFBM5D_WOP_WINDOW_END || op == LFBM5D_WOP_COUNT_DENOISED;
+    const bool counts = op == LFBM5D_WOP_WINDOW_END || op == LFBM5D_WOP_COUNT_DENOISED;
+    const bool listed = op == LFBM5D_WOP_SYMETRIZE_MULTI || op == LFBM5D_WOP_UNSYMETRIZE_MULTI || op == LFBM5D_WOP_WINDOW_BEGIN ||
+                        op == LFBM5D_WOP_WINDOW_END || op == LFBM5D_WOP_FINALIZE || op == LFBM5D_WOP_OUTPUT;
+    const bool masked = op == LFBM5D_WOP_ESTIMATE_MULTI || op == LFBM5D_WOP_COUNT_DENOISED || op == LFBM5D_WOP_COPY_RECT;
+    {   /* the pointers the op cannot do without (the optional ones: basic, dmask, the window sums of the direct form) */
+        bool null = false;
+        switch (op) {
+        case LFBM5D_WOP_COLOR: null = !d->noisy; break;
+        case LFBM5D_WOP_COLOR_ROUNDTRIP: null = !d->noisy || !d->out; break;
+        case LFBM5D_WOP_SYMETRIZE: case LFBM5D_WOP_SYMETRIZE_MULTI: null = !d->noisy || !d->w_noisy; break;
+        case LFBM5D_WOP_CROP: case LFBM5D_WOP_UNSYMETRIZE_MULTI: case LFBM5D_WOP_COPY_RECT: case LFBM5D_WOP_COPY_ROWS: null = !d->w_noisy || !d->out; break;
+        case LFBM5D_WOP_ESTIMATE: null = !d->num || !d->den || !d->sub || !d->est; break;
+        case LFBM5D_WOP_ESTIMATE_MULTI: null = !d->w_num || !d->w_den || !d->w_noisy || !d->est; break;
+        case LFBM5D_WOP_ESTIMATE_LF: null = !d->num || !d->den || !d->sub || !d->out; break;
+        case LFBM5D_WOP_WINDOW_BEGIN: null = !d->noisy || !d->num || !d->den || !d->w_noisy || !d->est || !d->counters; break;
+        case LFBM5D_WOP_WINDOW_END: null = !d->num || !d->den || !d->counters; break;
+        case LFBM5D_WOP_FINALIZE: null = !d->num || !d->den || !d->sub || !d->basic; break;
+        case LFBM5D_WOP_OUTPUT: null = !d->num || !d->den || !d->sub || !d->out || !d->noisy || !d->noisy_dst; break;
+        case LFBM5D_WOP_COUNT_ZEROS: null = !d->den || !d->counters; break;
+        case LFBM5D_WOP_COUNT_DENOISED: null = !d->w_den || !d->counters; break;
+        }
+        if (null) return fail(c, "debug_window: NULL pointer");
+        if (listed && !d->list) return fail(c, "debug_window: NULL pointer (the SAI list)");
+        if (masked && !d->slot_mask) return fail(c, "debug_window: NULL pointer (the slot mask)");
+    }
+    if (op != LFBM5D_WOP_ESTIMATE && op != LFBM5D_WOP_ESTIMATE_LF && op != LFBM5D_WOP_COUNT_ZEROS && op != LFBM5D_WOP_COPY_ROWS) {
+        if (C != 1 && C != 3) return fail(c, "debug_window: chnls must be 1 or 3");
+        if (three && C != 3) return fail(c, "debug_window: this op works on three channels");
+    }
+    if (!flat) {
+        if (!W || !H) return fail(c, "debug_window: W and H must not be 0");
+        if (W > 65535u || H > 65535u || N > 65535u) return fail(c, "debug_window: W, H and N must be at most 65535");
+    } else if (!d->n || d->n >= (1ull << 32)) return fail(c, "debug_window: n must be 1 .. 2^32 - 1");
+    if (three && d->cs > LFBM5D_OPP && (d->colour || op == LFBM5D_WOP_COLOR || op == LFBM5D_WOP_COLOR_ROUNDTRIP))
+        return fail(c, "debug_window: the colour kernels know yuv, ycbcr and opp");
+    if (mirrors && (N > W || N > H)) return fail(c, "debug_window: the padding N is larger than the image (the mirror reflects once)");
+    if (counts && (k < 1 || k > W || k > H)) return fail(c, "debug_window: patch size k outside 1 .. min(W, H)");
+    if ((listed || masked) && d->n_list > (unsigned)kBigA) return fail(c, "debug_window: more than 289 slots");
+    if ((listed || masked) && !d->n_list) return fail(c, "debug_window: no slots");
+    const bool per_sai = op == LFBM5D_WOP_COLOR || op == LFBM5D_WOP_COLOR_ROUNDTRIP || op == LFBM5D_WOP_ESTIMATE_LF || op == LFBM5D_WOP_COUNT_ZEROS ||
+                         op == LFBM5D_WOP_COPY_ROWS;
+    if (per_sai && (!d->n_sai || d->n_sai > 65535u)) return fail(c, "debug_window: n_sai must be 1 .. 65535");
+    const u64 img = (u64)C * W * H, imgb = (u64)C * (W + 2 * N) * (H + 2 * N), planeb = (u64)(W + 2 * N) * (H + 2 * N);
+    if (three && img >= (1ull << 32)) return fail(c, "debug_window: image beyond 32-bit offsets");
+
+    /* the light field a list addresses: its SAI count follows from the size of the buffers */
+    auto lf_holds = [&](u64 n_sai_) { return n_sai_ && d->lf_floats >= img && (n_sai_ - 1) <= (d->lf_floats - img) / std::max<u64>(d->lf_stride, 1); };
+    u64 lf_sais = 0;
+    if (listed || op == LFBM5D_WOP_COLOR || op == LFBM5D_WOP_COLOR_ROUNDTRIP) {
+        if (d->lf_stride < img) return fail(c, "debug_window: lf_stride smaller than one image");
+        if (d->lf_floats < img) return fail(c, "debug_window: a light-field buffer is smaller than the geometry says");
+        lf_sais = (d->lf_floats - img) / d->lf_stride + 1;
+    }
+    if (listed) {
+        const bool plain = op == LFBM5D_WOP_FINALIZE || op == LFBM5D_WOP_OUTPUT;
+        for (unsigned i = 0; i < d->n_list; i++) {
+            if (d->list[i] == 0xffffffffu) { if (plain) return fail(c, "debug_window: an empty slot (0xffffffff) in a list this op does not test"); }
+            else if (d->list[i] >= lf_sais) return fail(c, "debug_window: a list entry lies outside the light field");
+        }
+    }
+    const char* const small_msg = "debug_window: a buffer is smaller than the geometry says";
+    SaiList L; std::memset(&L, 0, sizeof(L));
+    SaiMask bits = sai_mask_none();
+    if (listed) { L.n = d->n_list; for (unsigned i = 0; i < d->n_list; i++) L.st[i] = d->list[i]; }
+    if (masked) for (unsigned i = 0; i < d->n_list; i++) if (d->slot_mask[i]) bits.set(i);
+    if (d->dmask && (op == LFBM5D_WOP_COLOR || op == LFBM5D_WOP_COLOR_ROUNDTRIP || op == LFBM5D_WOP_ESTIMATE_LF) && d->dmask_words < d->n_sai)
+        return fail(c, "debug_window: dmask is smaller than n_sai");
+    if (padded && listed && !(op == LFBM5D_WOP_WINDOW_END && !d->w_num && !d->w_den) && d->w_stride < imgb)
+        return fail(c, "debug_window: w_stride smaller than one padded image");
+
+    (void)hipSetDevice(c->device);
+    hipStream_t s = c->stream;
+    hipError_t e = hipSuccess;
+    switch (op) {
+    case LFBM5D_WOP_COLOR:
+        if (!lf_holds(d->n_sai)) return fail(c, small_msg);
+        e = launch_color_lf(s, d->noisy, d->lf_stride, d->n_sai, d->dmask, d->cs, W * H, d->forward ? 1 : 0);
+        break;
+    case LFBM5D_WOP_COLOR_ROUNDTRIP:
+        if (!lf_holds(d->n_sai)) return fail(c, small_msg);
+        e = launch_color_roundtrip_lf(s, d->noisy, d->out, d->lf_stride, d->n_sai, d->dmask, d->cs, W * H);
+        break;
+    case LFBM5D_WOP_SYMETRIZE:
+        if (d->lf_floats < img || d->w_floats < imgb) return fail(c, small_msg);
+        e = launch_symetrize(s, d->noisy, d->w_noisy, W, H, C, N);
+        break;
+    case LFBM5D_WOP_CROP:
+        if (d->off > 2 * N) return fail(c, "debug_window: the crop at off leaves the padded image");
+        if (d->lf_floats < img || d->w_floats < imgb) return fail(c, small_msg);
+        e = launch_crop(s, d->out, d->w_noisy, W, H, C, N, d->off);
+        break;
+    case LFBM5D_WOP_SYMETRIZE_MULTI:
+        if (d->w_floats < (u64)(L.n - 1) * d->w_stride + imgb) return fail(c, small_msg);
+        e = launch_symetrize_multi(s, d->noisy, d->lf_stride, d->w_noisy, d->w_stride, L, W, H, C, N);
+        break;
+    case LFBM5D_WOP_UNSYMETRIZE_MULTI:
+        if (d->w_floats < (u64)(L.n - 1) * d->w_stride + imgb) return fail(c, small_msg);
+        e = launch_unsymetrize_multi(s, d->out, d->lf_stride, d->w_noisy, d->w_stride, L, W, H, C, N);
+        break;
+    case LFBM5D_WOP_ESTIMATE:
+        if (d->lf_floats < d->n || d->est_floats < d->n) return fail(c, small_msg);
+        e = launch_estimate(s, d->num, d->den, d->sub, d->est, d->n);
+        break;
+    case LFBM5D_WOP_ESTIMATE_MULTI:
+        if (d->w_floats < (u64)d->n_list * C * d->n || d->est_floats < (u64)d->n_list * d->n) return fail(c, small_msg);
+        e = launch_estimate_multi(s, d->w_num, d->w_den, d->w_noisy, d->est, d->n, C, d->n_list, bits);
+        break;
+    case LFBM5D_WOP_ESTIMATE_LF:
+        if (d->lf_floats < (u64)d->n_sai * d->n) return fail(c, small_msg);
+        e = launch_estimate_lf(s, d->num, d->den, d->sub, d->out, d->n, d->n_sai, d->dmask);
+        break;
+    case LFBM5D_WOP_WINDOW_BEGIN: {
+        if ((d->w_num == nullptr) != (d->w_den == nullptr)) return fail(c, "debug_window: NULL pointer (the direct form leaves out w_num AND w_den)");
+        if (d->basic && !d->w_basic) return fail(c, "debug_window: NULL pointer (basic without w_basic)");
+        if (d->w_floats < (u64)(L.n - 1) * d->w_stride + imgb || d->est_floats < (u64)L.n * planeb || d->counter_words < kWinCounters) return fail(c, small_msg);
+        e = launch_window_begin(s, d->noisy, d->basic, d->num, d->den, d->lf_stride, d->w_noisy, d->basic ? d->w_basic : nullptr, d->w_num, d->w_den,
+                                d->est, d->w_stride, L, W, H, C, N, d->counters);
+        break;
+    }
+    case LFBM5D_WOP_WINDOW_END:
+        if ((d->w_num == nullptr) != (d->w_den == nullptr)) return fail(c, "debug_window: NULL pointer (the direct form leaves out w_num AND w_den)");
+        if ((d->w_num && d->w_floats < (u64)(L.n - 1) * d->w_stride + imgb) || d->counter_words < kWinCounters) return fail(c, small_msg);
+        e = launch_window_end(s, d->num, d->den, d->lf_stride, d->w_num, d->w_den, d->w_stride, L, W, H, C, N, k, d->counters);
+        break;
+    case LFBM5D_WOP_FINALIZE:
+        e = launch_finalize_multi(s, d->num, d->den, d->sub, d->basic, d->lf_stride, L, d->cs, W * H, d->colour ? 1 : 0);
+        break;
+    case LFBM5D_WOP_OUTPUT:
+        e = launch_output_multi(s, d->num, d->den, d->sub, d->out, d->basic, d->noisy, d->noisy_dst, d->lf_stride, L, d->cs, W * H, d->colour ? 1 : 0);
+        break;
+    case LFBM5D_WOP_COUNT_ZEROS:
+        if (d->lf_floats < (u64)d->n_sai * d->n || d->counter_words < d->n_sai) return fail(c, small_msg);
+        e = launch_count_zeros(s, d->den, d->n, d->n_sai, d->counters);
+        break;
+    case LFBM5D_WOP_COUNT_DENOISED:
+        if (d->w_stride < imgb) return fail(c, "debug_window: w_stride smaller than one padded image");
+        if (d->w_floats < (u64)(d->n_list - 1) * d->w_stride + imgb || d->counter_words < 1) return fail(c, small_msg);
+        e = launch_count_denoised(s, d->w_den, d->w_stride, d->n_list, bits, W, H, C, N, k, d->counters);
+        break;
+    case LFBM5D_WOP_COPY_RECT: {
+        if (!d->sW || !d->sH || d->sW > 65535u || d->sH > 65535u) return fail(c, "debug_window: sW and sH must be 1 .. 65535");
+        if (!d->rw || !d->rh) return fail(c, "debug_window: empty rectangle");
+        if (d->rw > W || d->dx0 > W - d->rw || d->rh > H || d->dy0 > H - d->rh || d->rw > d->sW || d->sx0 > d->sW - d->rw || d->rh > d->sH || d->sy0 > d->sH - d->rh)
+            return fail(c, "debug_window: the rectangle lies outside its image");
+        const u64 simg = (u64)C * d->sW * d->sH;
+        if (d->lf_stride < img || d->w_stride < simg) return fail(c, "debug_window: a stride is smaller than one image");
+        if (d->lf_floats < (u64)(d->n_list - 1) * d->lf_stride + img || d->w_floats < (u64)(d->n_list - 1) * d->w_stride + simg) return fail(c, small_msg);
+        e = launch_copy_rect(s, d->out, d->lf_stride, W, H, d->dx0, d->dy0, d->w_noisy, d->w_stride, d->sW, d->sH, d->sx0, d->sy0, d->rw, d->rh, C,
+                             d->n_list, bits);
+        break;
+    }
+    case LFBM5D_WOP_COPY_ROWS:
+        if (!d->sH || d->sH > 65535u) return fail(c, "debug_window: sH must be 1 .. 65535");
+        if (d->rh > d->sH || d->sy0 > d->sH - d->rh || d->rh > H || d->dy0 > H - d->rh) return fail(c, "debug_window: the rows lie outside their image");
+        if (d->w_floats < (u64)d->n_sai * d->sH * W || d->lf_floats < (u64)d->n_sai * H * W) return fail(c, small_msg);
+        e = launch_copy_rows(s, d->w_noisy, d->sH, d->sy0, d->out, H, d->dy0, d->rh, W, d->n_sai);
+        break;
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(c, std::string("debug_window: ") + hipGetErrorString(e));
+    return 0;
+}
+
+int lfbm5d_sigma_table(float sigma, unsigned C, unsigned color_space, float* out) {
+    if (!out) return 1;
+    return sigma_table(sigma, C, color_space, out);
 }
 
 int lfbm5d_malloc(void** dptr, size_t bytes) { return hipMalloc(dptr, bytes) == hipSuccess ? 0 : 1; }

@@ -226,6 +226,8 @@ void ind_init(std::vector<unsigned>& v, unsigned max_size, unsigned N, unsigned 
 void build_tables(GroupTables& t, unsigned k, unsigned aw, unsigned ah);
 bool is_pow2(unsigned n);
 int validate(lfbm5d_ctx* c, int step, const lfbm5d_params* P, unsigned aw, unsigned ah, unsigned C, bool bm3d = false);
+/* images that are mirror-padded by nHW pixels must be at least that wide and high */
+int check_padding(lfbm5d_ctx* c, unsigned W, unsigned H, unsigned nHW);
 /* the part of GroupArgs that follows from the pass's parameters (thresholds, lambda rule, sigma table, options, scratch) */
 int group_args_of_pass(lfbm5d_ctx* c, lfbm5d::GroupArgs& ga, const lfbm5d_params* P);
 int fold_counters(lfbm5d_ctx* c, const lfbm5d_params* P, unsigned A, unsigned C, int step, int slot = 0);

@@ -169,6 +169,16 @@ int validate(lfbm5d_ctx* c, int step, const lfbm5d_params* P, unsigned aw, unsig
     return 0;
 }
 
+/* Every entry that mirror-pads an image by the search range (symetrize, utilities.cpp:215-263): the mirror reflects once, so an image
+ * narrower or lower than the padding would be read beyond its edge -- and the reference's own padding is undefined there (it copies
+ * border columns from border columns it has not written yet).  Refused before anything is launched. */
+int check_padding(lfbm5d_ctx* c, unsigned W, unsigned H, unsigned nHW) {
+    if (W < nHW || H < nHW)
+        return fail(c, "unsupported: image smaller than the search range nSim + nDisp (" + std::to_string(W) + " x " + std::to_string(H) +
+                       " pixels, range " + std::to_string(nHW) + "): the mirror padding reflects once");
+    return 0;
+}
+
 /* What a group launch takes from the pass's parameters rather than from its buffers: the transforms, the hard threshold's lambda
  * (core:206-207), the sigma table, the thresholds of the fast hard-thresholding chain, the context's kernel options and the HBM
  * scratch of the general forms.  ga holds the geometry already (Wb, Hb, C, A, k, N, step, bm3d).  One function for pass_impl and

@@ -313,6 +313,7 @@ int run_step(lfbm5d_ctx* c, int step, const lfbm5d_params* P, float* d_noisy, co
     }
     if (ang_major != LFBM5D_ROWMAJOR && ang_major != LFBM5D_COLMAJOR) return fail(c, "bad ang_major");
     if (validate(c, step, P, asw, asw, C)) return 1;
+    if (check_padding(c, W, H, P->nSim + P->nDisp)) return 1;
     hipStream_t s = c->stream;
     const size_t img = (size_t)C * W * H;
     if (C == 3 && P->color_space > LFBM5D_RGB) return fail(c, "bad color space");
@@ -421,6 +422,8 @@ static int run_denoise_whole(lfbm5d_ctx* c, const lfbm5d_params* P1, const lfbm5
     const int n_lanes = std::max(1, std::min(8, c->opt->lanes));
     const int max_windows = c->opt->max_windows;
     const int nranks = emu > 1 ? emu : c->world;
+    /* both steps pad: refused here, before the first step of either form has run or a host light field has travelled */
+    if (check_padding(c, W, H, P1->nSim + P1->nDisp) || check_padding(c, W, H, P2->nSim + P2->nDisp)) return 1;
     bool fused = C == 3 && c->tiles <= 1 && !c->opt->step_sharding && !c->opt->data_driven_schedule &&
                  c->opt->fused != 0 && P1->color_space == P2->color_space &&
                  2 * an1 + 1 <= std::min(awidth, aheight) && 2 * an2 + 1 <= std::min(awidth, aheight);
@@ -716,6 +719,7 @@ int run_denoise(lfbm5d_ctx* c, const lfbm5d_params* P1, const lfbm5d_params* P2,
                 float* d_out, unsigned ang_major, unsigned awidth, unsigned aheight, unsigned an1, unsigned an2, unsigned W, unsigned H,
                 unsigned C, const HostIO* io) {
     const int emu = c->opt->emulate_world, nranks = emu > 1 ? emu : c->world;
+    if (check_padding(c, W, H, P1->nSim + P1->nDisp) || check_padding(c, W, H, P2->nSim + P2->nDisp)) return 1;
     const unsigned halo0 = c->opt->band_halo > 0 ? (unsigned)c->opt->band_halo : std::max(P1->nSim + P1->nDisp + P1->k, P2->nSim + P2->nDisp + P2->k);
     const int S = c->opt->spatial_bands == 0 ? auto_bands(awidth, aheight, H, halo0, nranks) : c->opt->spatial_bands;   /* 0: the rule */
     if (S <= 1 || nranks <= 1) return run_denoise_whole(c, P1, P2, d_noisy, h_mask, d_basic, d_out, ang_major, awidth, aheight, an1, an2, W, H, C, io);

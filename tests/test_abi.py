@@ -33,8 +33,16 @@ def test_struct_layouts_match_header():
     assert C.sizeof(core.AggDebugStruct) == 8 * 8 + 6 * 8 + 18 * 4
     # lfbm5d_group_debug: 14 pointers, 7 sizes, 12 unsigned
     assert C.sizeof(core.GroupDebugStruct) == 14 * 8 + 7 * 8 + 12 * 4
+    # lfbm5d_window_debug: 16 pointers, 6 sizes, 22 unsigned
+    assert C.sizeof(core.WindowDebugStruct) == 16 * 8 + 6 * 8 + 22 * 4
+    assert core.WindowDebugStruct.lf_stride.offset == 16 * 8 and core.WindowDebugStruct.op.offset == 22 * 8
+    assert core.WindowDebugStruct.counter_words.offset == 22 * 8 + 20 * 4
     src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "lfbm5d.h")).read(), flags=re.S)
-    for name, struct in (("lfbm5d_agg_debug", core.AggDebugStruct), ("lfbm5d_group_debug", core.GroupDebugStruct)):
+    # the op numbers of the header's enum are the positions in core.WINDOW_OPS
+    ops = dict(re.findall(r"LFBM5D_WOP_([A-Z_]+) = (\d+)", src))
+    assert {k.lower(): int(v) for k, v in ops.items()} == {n: i for i, n in enumerate(core.WINDOW_OPS)}
+    for name, struct in (("lfbm5d_agg_debug", core.AggDebugStruct), ("lfbm5d_group_debug", core.GroupDebugStruct),
+                         ("lfbm5d_window_debug", core.WindowDebugStruct)):
         body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), src, flags=re.S).group(1)
         fields = []
         for decl in body.split(";"):
