@@ -1221,10 +1221,20 @@ hipError_t launch_bm_scan(hipStream_t s, const ScanArgs& a) {
     return hipGetLastError();
 }
 
+/* k_self_select keeps one 64-bit key per candidate in dynamic LDS: (2 nSim + 1)^2 * 8 bytes, 75 272 at nSim = 48 (validate's
+ * limit) -- above the 64 KiB a launch gets without the attribute from nSim = 45 on.  Per DEVICE, like prepare_scan2_kernels:
+ * raised for the current device by every context creation. */
+constexpr int kSelectLdsLimit = 97 * 97 * (int)sizeof(unsigned long long);
+
+hipError_t prepare_select_kernels() {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_self_select), hipFuncAttributeMaxDynamicSharedMemorySize, kSelectLdsLimit);
+}
+
 hipError_t launch_self_select(hipStream_t s, const float* scores, const unsigned* refs, unsigned n_refs,
                               unsigned W, unsigned nSim, unsigned N, float thr, unsigned* self_idx,
                               unsigned* self_cnt, unsigned grid_cols, unsigned nHW, unsigned p, unsigned last_r, unsigned last_c) {
     const unsigned Ns = 2 * nSim + 1;
+    if ((size_t)Ns * Ns * sizeof(unsigned long long) > (size_t)kSelectLdsLimit) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_self_select, dim3(n_refs), dim3(64), (size_t)Ns * Ns * sizeof(unsigned long long), s,
                        scores, refs, n_refs, (int)W, (int)nSim, (int)N, thr, self_idx, self_cnt,
                        (int)grid_cols, (int)nHW, (int)p, (int)last_r, (int)last_c);

@@ -357,6 +357,7 @@ hipError_t launch_stereo_argmin3(hipStream_t s, const float* tables, const unsig
 hipError_t launch_stereo_argmin2(hipStream_t s, const float* tables, const unsigned* st_of_slot, unsigned n_slots,
                                  unsigned W, unsigned H, unsigned k, unsigned nDisp, float thr,
                                  unsigned* best, unsigned char* shape);
+hipError_t prepare_select_kernels();   /* per device, like prepare_scan2_kernels: the LDS limit of k_self_select ((2 * 48 + 1)^2 keys of 8 bytes) */
 hipError_t launch_self_select(hipStream_t s, const float* scores, const unsigned* refs, unsigned n_refs,
                               unsigned W, unsigned nSim, unsigned N, float thr, unsigned* self_idx,
                               unsigned* self_cnt,

@@ -110,6 +110,61 @@ def self_search(plane, k, N, nSim, nDisp, tau, refs):
     return dict(idx=idx, cnt=cnt, n_pass=n_pass, tie_cut=tie_cut, tie_any=tie_any, thr_equal=(tests == thr).any(1))
 
 
+def self_search_stream(plane, k, N, nSim, nDisp, tau, refs):
+    """self_search with one displacement table alive at a time (memory O(plane); self_search keeps (nSim + 1)(2 nSim + 1) planes,
+    4753 at nSim = 48).  From table (di, dj) it gathers the forward value at `refs` -- candidate (di, dj) -- and, for di > 0, the
+    backward candidate (-di, -dj): tested with the table's value at `refs`, scored with its value at refs - (di, dj).
+    Returns (the dict of self_search, rows): rows [R][(2 nSim + 1)^2] int64 are the score rows as a filled table holds them,
+    candidate (dip, djp) at (djp + nSim)(2 nSim + 1) + (dip if dip >= 0 else dip + 2 nSim + 1) -- scan order -- with 2 * threshold
+    where the scored position lies outside the band (what the table kernels never write)."""
+    a = np.asarray(plane).astype(np.int64)
+    H, W = a.shape
+    refs = np.asarray(refs).astype(np.int64)
+    R = len(refs)
+    assert N > 1
+    nHW, Ns = nSim + nDisp, 2 * nSim + 1
+    thr = threshold(tau, k)
+    band = np.zeros((H, W), bool)
+    band[nHW:H - nHW, nHW:W - nHW] = True
+    ys, xs = slice(nHW, H - nHW), slice(nHW, W - nHW)
+    tests, scores, posn = (np.zeros((R, Ns * Ns), np.int64) for _ in range(3))
+    for di in range(0, nSim + 1):
+        for dj in range(-nSim, nSim + 1):
+            D = np.zeros((H, W), np.int64)
+            D[ys, xs] = (a[nHW + di:H - nHW + di, nHW + dj:W - nHW + dj] - a[ys, xs]) ** 2
+            t = np.full((H, W), 2 * thr, np.int64)
+            t[band] = _box(D, k)[band]
+            t = t.reshape(-1)
+            e = (dj + nSim) * Ns + di
+            tests[:, e] = scores[:, e] = t[refs]
+            posn[:, e] = refs + di * W + dj
+            if di > 0:
+                e, c = (-dj + nSim) * Ns + (Ns - di), refs - di * W - dj
+                tests[:, e], scores[:, e], posn[:, e] = t[refs], t[c], c
+    ok = tests < thr
+    n_pass = ok.sum(1)
+    keyed = np.where(ok, scores, BIG)
+    o = np.argsort(keyed, axis=1, kind="stable")[:, :N + 1]                               # (score, scan order)
+    s_sorted, p_sorted = np.take_along_axis(keyed, o, 1), np.take_along_axis(posn, o, 1)
+    idx = np.zeros((R, N), np.uint32)
+    cnt = np.zeros(R, np.uint32)
+    tie_cut, tie_any = np.zeros(R, bool), np.zeros(R, bool)
+    for r in range(R):
+        n = int(n_pass[r])
+        if n == 0:
+            idx[r, :2] = refs[r]; cnt[r] = 2
+            continue
+        nSx = N if n >= N else 1 << (n.bit_length() - 1)
+        idx[r, :nSx] = p_sorted[r, :nSx]
+        cnt[r] = nSx
+        if nSx == 1:
+            idx[r, 1] = idx[r, 0]; cnt[r] = 2
+        head = s_sorted[r, :min(nSx + 1, n)]
+        tie_cut[r] = nSx < n and head[nSx] == head[nSx - 1]
+        tie_any[r] = bool((head[1:] == head[:-1]).any())
+    return dict(idx=idx, cnt=cnt, n_pass=n_pass, tie_cut=tie_cut, tie_any=tie_any, thr_equal=(tests == thr).any(1)), scores
+
+
 def region(H, W, k, nDisp):
     """Rows / columns at which the disparity search is defined (and compared)."""
     return slice(nDisp, H - nDisp - k + 1), slice(nDisp, W - nDisp - k + 1)
