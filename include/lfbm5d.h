@@ -1009,7 +1009,7 @@ typedef struct lfbm5d_group_debug {
     const float* basic;         /* the same of the pilot: step 2 only (else unused, may be NULL) */
     const unsigned* refs;       /* [n_refs_total] reference patches, flat positions i * Wb + j */
     const unsigned* self_idx;   /* [n_refs_total][N] the stack of every reference patch in the processed SAI */
-    const unsigned* self_cnt;   /* [n_refs_total] its size: a power of two in 1..N */
+    const unsigned* self_cnt;   /* [n_refs_total] its size: a power of two in 1..N (bm3d: 2..N, the selection stores a single match twice) */
     const unsigned* best;       /* [A][Wb*Hb] disparity match of every position (entry pst unused) */
     const unsigned char* shape; /* [A][Wb*Hb] non-zero: the SAI belongs to the angular shape of the reference patch at this position */
     float* filt;                /* out: the launch's groups [g - ref_begin][N][A][C][k*k], or SAI-major [A][g - ref_begin][N][C][k*k] */

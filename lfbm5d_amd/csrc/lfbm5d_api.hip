@@ -798,6 +798,9 @@ int lfbm5d_debug_group(lfbm5d_ctx* c, const lfbm5d_group_debug* d) {
         for (unsigned g = 0; g < ng; g++) {
             if (!inside(refs[g])) return fail(c, "debug_group: a reference patch lies outside [0, Hb-k] x [0, Wb-k]");
             if (!is_pow2(cnt[g]) || cnt[g] > N) return fail(c, "debug_group: a stack size (self_cnt) is not a power of two in 1..N");
+            /* BM3D needs N >= 2 (validate), so its selection always runs, and that stores a single match twice (duplicate rule,
+             * lfbm5d_bm.hip): k_group_bm3d8 has no fibre of one -- its default branch would read 31 stack slots nobody wrote */
+            if (d->bm3d && cnt[g] < 2) return fail(c, "debug_group: a BM3D stack of one patch (self_cnt 1): block matching stores a single match twice");
             for (unsigned n = 0; n < cnt[g]; n++)
                 if (!inside(idx[(size_t)g * N + n])) return fail(c, "debug_group: a stack entry (self_idx) lies outside [0, Hb-k] x [0, Wb-k]");
         }

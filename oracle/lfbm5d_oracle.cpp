@@ -1308,6 +1308,81 @@ int run_step(int step, const orc_params* P, float* LF_noisy, const unsigned* mas
 /* ------------------------------------------------------------------------------------------ */
 /* Per-SAI BM3D (LFBM3Ddenoising): bm3d.cpp:86-690, bm3d_LF.cpp:75-125, nb_threads == 1          */
 /* ------------------------------------------------------------------------------------------ */
+/* One group of a BM3D step on the caller's stack idx[0 .. nSx): gather + 2-D forward (bm3d.cpp:393-401 / :594-606), Hadamard
+ * shrinkage along the stack (:914-966 / :980-1027), the group weight (sd_weighting :1345-1373 with useSD) and the 2-D inverse of
+ * every filtered patch (:428-432 / :639-643).  patches [c][n][k2], w [c].  bm3d_step and orc_bm3d_group both run this. */
+void bm3d_group(int step, const float* noisy, const float* basic, unsigned Wb, unsigned Hb, unsigned C, unsigned k, const Norms2D& n2,
+                unsigned tau_2D, const float* sig, float lambda3D, unsigned useSD, const unsigned* idx, unsigned nSx,
+                std::vector<float>& patches, float* w) {
+    const unsigned k2 = k * k;
+    const size_t plane = (size_t)Wb * Hb;
+    const int S = step == 2 ? 2 : 1;
+    /* group_3D[s][c][pq][n] (bm3d.cpp:393-401 / :594-606); patches at column Wb - k read the tables'
+     * zero initialisation (bm3d.cpp:737, :857) */
+    std::vector<float> X((size_t)S * C * k2 * nSx, 0.0f), tmp(k2);
+    for (int s2 = 0; s2 < S; s2++) {
+        const float* src = (step == 2 && s2 == 1) ? basic : noisy;   /* s2 = 0: img, 1: est */
+        for (unsigned c = 0; c < C; c++)
+            for (unsigned n = 0; n < nSx; n++) {
+                const unsigned pos = idx[n];
+                if (pos % Wb >= Wb - k) continue;
+                if (tau_2D == ORC_DCT) dct2d_fwd(src + c * plane + pos, Wb, tmp.data(), k, n2);
+                else bior_fwd(src + c * plane + pos, Wb, tmp.data(), k);
+                for (unsigned pq = 0; pq < k2; pq++) X[(((size_t)s2 * C + c) * k2 + pq) * nSx + n] = tmp[pq];
+            }
+    }
+    float weight[4] = {0, 0, 0, 0};
+    const float coef = 1.0f / (float)nSx;
+    float* img = X.data();
+    float* est = X.data() + (size_t)C * k2 * nSx;
+    float* F;
+    if (step == 1) {   /* bm3d.cpp:914-966 */
+        const float coef_norm = std::sqrt((float)nSx);
+        for (unsigned v = 0; v < k2 * C; v++) hadamard(img + v * nSx, nSx);
+        for (unsigned c = 0; c < C; c++) {
+            const float T = lambda3D * sig[c] * coef_norm;
+            float* g = img + (size_t)c * nSx * k2;
+            for (unsigned i = 0; i < k2 * nSx; i++) { if (std::fabs(g[i]) > T) weight[c]++; else g[i] = 0.0f; }
+        }
+        for (unsigned v = 0; v < k2 * C; v++) hadamard(img + v * nSx, nSx);
+        for (size_t i = 0; i < (size_t)C * k2 * nSx; i++) img[i] *= coef;
+        F = img;
+    } else {           /* bm3d.cpp:980-1027 */
+        for (unsigned v = 0; v < k2 * C; v++) { hadamard(img + v * nSx, nSx); hadamard(est + v * nSx, nSx); }
+        for (unsigned c = 0; c < C; c++) {
+            const size_t dc = (size_t)c * nSx * k2;
+            for (unsigned i = 0; i < k2 * nSx; i++) {
+                float value = est[dc + i] * est[dc + i] * coef;
+                value /= (value + sig[c] * sig[c]);
+                est[dc + i] = img[dc + i] * value * coef;
+                weight[c] += value;
+            }
+        }
+        for (unsigned v = 0; v < k2 * C; v++) hadamard(est + v * nSx, nSx);
+        F = est;
+    }
+    if (!useSD)
+        for (unsigned c = 0; c < C; c++)
+            w[c] = weight[c] > 0.0f ? 1.0f / (float)(sig[c] * sig[c] * weight[c]) : 1.0f;
+    else {             /* sd_weighting bm3d.cpp:1345-1373: reads the first nSx*k2 entries -- channel 0 -- for every channel */
+        const unsigned Nn = nSx * k2;
+        for (unsigned c = 0; c < C; c++) {
+            float mean = 0.0f, sd = 0.0f;
+            for (unsigned i = 0; i < Nn; i++) { mean += F[i]; sd += F[i] * F[i]; }
+            const float res = (sd - mean * mean / (float)Nn) / (float)(Nn - 1);
+            w[c] = res > 0.0f ? 1.0f / std::sqrt(res) : 0.0f;
+        }
+    }
+    /* inverse 2-D of every filtered patch (bm3d.cpp:428-432 / :639-643) */
+    patches.assign((size_t)C * nSx * k2, 0.0f);
+    for (unsigned c = 0; c < C; c++)
+        for (unsigned n = 0; n < nSx; n++) {
+            float* pp = &patches[((size_t)c * nSx + n) * k2];
+            for (unsigned pq = 0; pq < k2; pq++) pp[pq] = F[((size_t)c * k2 + pq) * nSx + n];
+            if (tau_2D == ORC_DCT) dct2d_inv(pp, k, n2); else bior_inv(pp, k);
+        }
+}
+
 /* One step on a mirror-padded image [C][Hb][Wb] (bm3d_1st_step bm3d.cpp:315-505, bm3d_2nd_step :507-690):
  * out = numerator / denominator over the whole padded image.  tau_2D in {DCT, BIOR}; the third
  * dimension is always the Hadamard transform (ht_filtering_hadamard :914-966,
@@ -1356,71 +1431,7 @@ int bm3d_step(int step, float sigma, float lambda3D, const float* noisy, const f
             const unsigned nSx = self_cnt[slot];
             G3& go = outs[jj];
             go.nSx = nSx;
-            const int S = step == 2 ? 2 : 1;
-            /* group_3D[s][c][pq][n] (bm3d.cpp:393-401 / :594-606); patches at column Wb - k read the tables'
-             * zero initialisation (bm3d.cpp:737, :857) */
-            std::vector<float> X((size_t)S * C * k2 * nSx, 0.0f), tmp(k2);
-            for (int s2 = 0; s2 < S; s2++) {
-                const float* src = (step == 2 && s2 == 1) ? basic : noisy;   /* s2 = 0: img, 1: est */
-                for (unsigned c = 0; c < C; c++)
-                    for (unsigned n = 0; n < nSx; n++) {
-                        const unsigned pos = self_idx[slot * Nst + n];
-                        if (pos % Wb >= Wb - k) continue;
-                        if (tau_2D == ORC_DCT) dct2d_fwd(src + c * plane + pos, Wb, tmp.data(), k, n2);
-                        else bior_fwd(src + c * plane + pos, Wb, tmp.data(), k);
-                        for (unsigned pq = 0; pq < k2; pq++) X[(((size_t)s2 * C + c) * k2 + pq) * nSx + n] = tmp[pq];
-                    }
-            }
-            float weight[4] = {0, 0, 0, 0};
-            const float coef = 1.0f / (float)nSx;
-            float* img = X.data();
-            float* est = X.data() + (size_t)C * k2 * nSx;
-            float* F;
-            if (step == 1) {   /* bm3d.cpp:914-966 */
-                const float coef_norm = std::sqrt((float)nSx);
-                for (unsigned v = 0; v < k2 * C; v++) hadamard(img + v * nSx, nSx);
-                for (unsigned c = 0; c < C; c++) {
-                    const float T = lambda3D * sig[c] * coef_norm;
-                    float* g = img + (size_t)c * nSx * k2;
-                    for (unsigned i = 0; i < k2 * nSx; i++) { if (std::fabs(g[i]) > T) weight[c]++; else g[i] = 0.0f; }
-                }
-                for (unsigned v = 0; v < k2 * C; v++) hadamard(img + v * nSx, nSx);
-                for (size_t i = 0; i < (size_t)C * k2 * nSx; i++) img[i] *= coef;
-                F = img;
-            } else {           /* bm3d.cpp:980-1027 */
-                for (unsigned v = 0; v < k2 * C; v++) { hadamard(img + v * nSx, nSx); hadamard(est + v * nSx, nSx); }
-                for (unsigned c = 0; c < C; c++) {
-                    const size_t dc = (size_t)c * nSx * k2;
-                    for (unsigned i = 0; i < k2 * nSx; i++) {
-                        float value = est[dc + i] * est[dc + i] * coef;
-                        value /= (value + sig[c] * sig[c]);
-                        est[dc + i] = img[dc + i] * value * coef;
-                        weight[c] += value;
-                    }
-                }
-                for (unsigned v = 0; v < k2 * C; v++) hadamard(est + v * nSx, nSx);
-                F = est;
-            }
-            if (!useSD)
-                for (unsigned c = 0; c < C; c++)
-                    go.w[c] = weight[c] > 0.0f ? 1.0f / (float)(sig[c] * sig[c] * weight[c]) : 1.0f;
-            else {             /* sd_weighting bm3d.cpp:1345-1373: reads the first nSx*k2 entries -- channel 0 -- for every channel */
-                const unsigned Nn = nSx * k2;
-                for (unsigned c = 0; c < C; c++) {
-                    float mean = 0.0f, sd = 0.0f;
-                    for (unsigned i = 0; i < Nn; i++) { mean += F[i]; sd += F[i] * F[i]; }
-                    const float res = (sd - mean * mean / (float)Nn) / (float)(Nn - 1);
-                    go.w[c] = res > 0.0f ? 1.0f / std::sqrt(res) : 0.0f;
-                }
-            }
-            /* inverse 2-D of every filtered patch (bm3d.cpp:428-432 / :639-643) */
-            go.patches.assign((size_t)C * nSx * k2, 0.0f);
-            for (unsigned c = 0; c < C; c++)
-                for (unsigned n = 0; n < nSx; n++) {
-                    float* pp = &go.patches[((size_t)c * nSx + n) * k2];
-                    for (unsigned pq = 0; pq < k2; pq++) pp[pq] = F[((size_t)c * k2 + pq) * nSx + n];
-                    if (tau_2D == ORC_DCT) dct2d_inv(pp, k, n2); else bior_inv(pp, k);
-                }
+            bm3d_group(step, noisy, basic, Wb, Hb, C, k, n2, tau_2D, sig, lambda3D, useSD, &self_idx[slot * Nst], nSx, go.patches, go.w);
         }
         /* aggregation in the reference's order (bm3d.cpp:434-463 / :645-674) */
         for (size_t jj = 0; jj < cols.size(); jj++) {
@@ -1645,6 +1656,35 @@ int orc_group(int step, const orc_params* P, unsigned aw, unsigned ah, unsigned 
             for (unsigned c = 0; c < C; c++)
                 std::memcpy(out + (((size_t)st * C + c) * cx.N) * cx.k2, &go.patches[(((size_t)st * C + c) * go.nSx) * cx.k2],
                             (size_t)go.nSx * cx.k2 * sizeof(float));
+    }
+    return 0;
+}
+
+/* bm3d_group -- the group loop of bm3d_step -- on tables the caller supplies, in the style of orc_group: one image [C][Hb][Wb], the
+ * stacks self_idx [R][N] / self_cnt [R] (refs[g] is self_idx[g][0] in a pass; it is not read).  P gives sigma, lambda, N, k, useSD,
+ * tau_2D and the colour space; the stack transform is Hadamard.  patches [g][c][N][k2], the stack padded to N with zeros. */
+int orc_bm3d_group(int step, const orc_params* P, unsigned Wb, unsigned Hb, unsigned C, const float* noisy, const float* basic,
+                   const unsigned* refs, const unsigned* self_idx, const unsigned* self_cnt, unsigned ref_begin, unsigned n_groups,
+                   float* patches, float* w, unsigned* nSx) {
+    (void)refs;
+    if (C > 3 || (step == 2 && !basic) || (P->tau_2D != ORC_DCT && P->tau_2D != ORC_BIOR) || P->N < 1) return 1;
+    float sig[4];
+    if (sigma_table(P->sigma, C, P->color_space, sig)) return 1;
+    const unsigned k = P->k, k2 = k * k, N = P->N;
+    Norms2D n2; n2.k = k; dct2d_norms(k, n2.cn, n2.cni);
+    const size_t per_group = (size_t)C * N * k2;
+    #pragma omp parallel for schedule(dynamic, 1) num_threads(g_threads > 0 ? g_threads : omp_get_max_threads())
+    for (int i = 0; i < (int)n_groups; i++) {
+        const unsigned g = ref_begin + (unsigned)i, n = self_cnt[g];
+        std::vector<float> pp;
+        float wg[4] = {0, 0, 0, 0};
+        bm3d_group(step, noisy, basic, Wb, Hb, C, k, n2, P->tau_2D, sig, P->lambda, P->useSD, self_idx + (size_t)g * N, n, pp, wg);
+        nSx[i] = n;
+        for (unsigned c = 0; c < C; c++) w[(size_t)i * C + c] = wg[c];
+        float* out = patches + (size_t)i * per_group;
+        std::fill(out, out + per_group, 0.0f);
+        for (unsigned c = 0; c < C; c++)
+            std::memcpy(out + (size_t)c * N * k2, &pp[(size_t)c * n * k2], (size_t)n * k2 * sizeof(float));
     }
     return 0;
 }

@@ -142,6 +142,16 @@ int orc_group(int step, const orc_params* P, unsigned aw, unsigned ah, unsigned 
               const unsigned char* shape, unsigned ref_begin, unsigned n_groups,
               float* patches, float* w, unsigned* nSx, unsigned* use_sadct);
 
+/* ---- the group loop of orc_bm3d_step alone (bm3d.cpp:393-432 / :594-643), on stacks the caller supplies ----
+ * One image [C][Hb][Wb]; self_idx[R][N], self_cnt[R] as the step's block matching builds them (refs is not read: a stack's first
+ * entry is its reference); P gives sigma, lambda, N, k, useSD, tau_2D (dct or bior) and the colour space, the stack transform is
+ * Hadamard, stack entries at columns >= Wb - k are zero patches.  For the groups [ref_begin, ref_begin + n_groups):
+ * patches[i][c][N][k*k] (stack entries beyond nSx zero), w[i][C] (with useSD every channel has channel 0's, as in the reference),
+ * nSx[i].  orc_bm3d_step runs the same function per group. */
+int orc_bm3d_group(int step, const orc_params* P, unsigned Wb, unsigned Hb, unsigned C, const float* noisy, const float* basic,
+                   const unsigned* refs, const unsigned* self_idx, const unsigned* self_cnt, unsigned ref_begin, unsigned n_groups,
+                   float* patches, float* w, unsigned* nSx);
+
 /* ---- whole steps (run_bm5d_1st_step / run_bm5d_2nd_step, nb_threads == 1 semantics) ----
  * LF buffers are [awidth*aheight][C*W*H] contiguous, mutated in place exactly like the reference
  * (colour forward at entry, inverse at exit).  max_windows > 0 stops after that many angular

@@ -81,6 +81,8 @@ def lib():
                            C.c_uint, C.c_int, C.c_int, C.POINTER(Stats)]
     L.orc_group.argtypes = [C.c_int, C.POINTER(Params), C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint, _f32p, C.c_void_p, _u32p,
                             C.c_uint, C.c_int, _u32p, _u32p, _u32p, _u32p, _u8p, C.c_uint, C.c_uint, _f32p, _f32p, _u32p, _u32p]
+    L.orc_bm3d_group.argtypes = [C.c_int, C.POINTER(Params), C.c_uint, C.c_uint, C.c_uint, _f32p, C.c_void_p, _u32p, _u32p, _u32p,
+                                 C.c_uint, C.c_uint, _f32p, _f32p, _u32p]
     L.orc_run_step1.argtypes = [C.POINTER(Params), _f32p, _u32p, _f32p, C.c_uint, C.c_uint, C.c_uint,
                                 C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_int, C.POINTER(Stats)]
     L.orc_run_step2.argtypes = [C.POINTER(Params), _f32p, _u32p, _f32p, _f32p, C.c_uint, C.c_uint,
@@ -271,3 +273,25 @@ def group(step, P, aw, ah, Wb, Hb, Cc, noisy, basic, mask, pst, fill_quirk, refs
     if rc:
         raise RuntimeError("orc_group failed")
     return patches, w, nSx, sa
+
+
+def bm3d_group(step, P, Wb, Hb, Cc, noisy, basic, refs, self_idx, self_cnt, ref_begin=0, n_groups=None):
+    """orc_bm3d_group: the group loop of bm3d_step on the caller's stacks (one image, Hadamard along the stack).  Returns patches
+    [g][c][N][k*k] (stack entries beyond nSx zero), w [g][C], nSx [g]."""
+    L = lib()
+    N, k2 = max(1, P.N), P.k * P.k
+    refs = np.ascontiguousarray(refs, np.uint32)
+    n_groups = len(refs) - ref_begin if n_groups is None else n_groups
+    patches = np.zeros((n_groups, Cc, N, k2), np.float32)
+    w = np.zeros((n_groups, Cc), np.float32)
+    nSx = np.zeros(n_groups, np.uint32)
+    b = None
+    if basic is not None:
+        basic = np.ascontiguousarray(basic, np.float32)
+        b = basic.ctypes.data_as(C.c_void_p)
+    rc = L.orc_bm3d_group(step, C.byref(P), Wb, Hb, Cc, np.ascontiguousarray(noisy, np.float32).reshape(-1), b, refs,
+                          np.ascontiguousarray(self_idx, np.uint32).reshape(-1), np.ascontiguousarray(self_cnt, np.uint32),
+                          ref_begin, n_groups, patches.reshape(-1), w.reshape(-1), nSx)
+    if rc:
+        raise RuntimeError("orc_bm3d_group failed")
+    return patches, w, nSx

@@ -14,7 +14,8 @@ transform's; the pilot of the Wiener step is a smoothed copy.
 
 `expected_kernels` restates the dispatch of launch_group (lfbm5d_group_*.hip) in Python: what each run is meant to reach.
 
-Out of scope: the per-SAI BM3D flavour (A = 1) and windows beyond 7 x 7 SAIs.
+Sections F and G (wide_cases, bm3d_cases) hold windows of 7 x 7 to 17 x 17 SAIs and the per-SAI BM3D flavour (A = 1).  Their
+hard-threshold cases run lambda 3.5; default-lambda decisions on wide windows stay with the whole-pass tests.
 """
 from types import SimpleNamespace
 
@@ -78,7 +79,7 @@ def all_shapes(A, pst, mask):
 
 
 def wide_shapes(rng, aw, pst, n_random):
-    """5 x 5 windows: seeded random shapes, plus every shape with a single SAI in some row or column besides pst's."""
+    """Windows of 5 x 5 SAIs and more: seeded random shapes, plus every shape with a single SAI in some row or column besides pst's."""
     A = aw * aw
     out = [int(sum(1 << int(st) for st in np.flatnonzero(rng.random(A) < rng.uniform(0.2, 0.95))) | (1 << pst)) for _ in range(n_random)]
     ps, pt = divmod(pst, aw)
@@ -92,9 +93,12 @@ def wide_shapes(rng, aw, pst, n_random):
 
 def build(name, seed, *, step, tau2, tau4, tau5, k, N, C=3, aw=3, mask=None, pst=None, fill_quirk=1, useSD=0, sigma=25.0, lam=2.7,
           shapes="all", nsx="each", n_groups=None, scale=1.0, pilot="smooth", const=False, edges=False, same=False, runs=((),),
-          ref_begin=0, launch=None, sai_major=False):
+          ref_begin=0, launch=None, sai_major=None, bm3d=False, section="", amp=None):
     rng = np.random.default_rng(seed)
+    if bm3d:   # the per-SAI flavour: one image, stacks of 2 .. N (block matching stores a single match twice), Hadamard along the stack
+        aw, shapes = 1, ([1] * n_groups if shapes == "all" else shapes)
     A = aw * aw
+    sai_major = A >= SAI_MAJOR_MIN_A if sai_major is None else sai_major      # what a pass does
     pst = A // 2 if pst is None else pst
     mask = np.ones(A, np.uint32) if mask is None else np.asarray(mask, np.uint32)
     Wb = Hb = window_side(k)
@@ -102,7 +106,7 @@ def build(name, seed, *, step, tau2, tau4, tau5, k, N, C=3, aw=3, mask=None, pst
     tau2, tau4, tau5 = t(tau2), t(tau4), t(tau5)
     if shapes == "all":
         shapes = all_shapes(A, pst, mask)
-    sizes = [1 << i for i in range(N.bit_length())]          # 1, 2, ..., N
+    sizes = [1 << i for i in range(1 if bm3d else 0, N.bit_length())]          # 1, 2, ..., N (BM3D: from 2)
     if nsx == "each":
         groups = [(sh, n) for sh in shapes for n in sizes]
     else:   # one group per shape; the stack sizes in equal shares, dealt by a seeded permutation (not by the shape's bits)
@@ -138,7 +142,7 @@ def build(name, seed, *, step, tau2, tau4, tau5, k, N, C=3, aw=3, mask=None, pst
     # With a 2-D transform the texture is strong, so that more than the DC of a patch survives the threshold and the filtered patches
     # have structure; without one every pixel is a coefficient set of its own, a strong texture under stacks from anywhere in the
     # window puts a fifth of the pairs inside the gap, and the noise alone tells the pixels apart.
-    noisy = texture(rng, A, C, Hb, Wb, sigma, scale, const, amp=6.0 if tau2 == ID else 40.0)
+    noisy = texture(rng, A, C, Hb, Wb, sigma, scale, const, amp=(6.0 if tau2 == ID else 40.0) if amp is None else amp)
     basic = None
     if step == 2:
         basic = smooth(noisy)
@@ -155,7 +159,8 @@ def build(name, seed, *, step, tau2, tau4, tau5, k, N, C=3, aw=3, mask=None, pst
                            fill_quirk=fill_quirk, useSD=useSD, sigma_in=float(sigma) * scale, sigma=sigma_table(float(sigma) * scale, C),
                            lam=lam, Wb=Wb, Hb=Hb, R=R, refs=refs, self_idx=idx, self_cnt=cnt, best=best, shape=shape, noisy=noisy,
                            basic=basic, runs=tuple(tuple(r) for r in runs), ref_begin=ref_begin,
-                           launch=R - ref_begin if launch is None else launch, sai_major=sai_major, nSim=6, nDisp=2, p=3)
+                           launch=R - ref_begin if launch is None else launch, sai_major=sai_major, bm3d=bool(bm3d), section=section,
+                           nSim=6, nDisp=2, p=3)
 
 
 def params_tuple(case):
@@ -165,11 +170,13 @@ def params_tuple(case):
 
 # ---- the dispatch of launch_group, restated ----
 GENERIC_LDS_LIMIT = 160 * 1024 - 8192
-SLAB_FLOATS_MAX = 28800
+SLAB_FLOATS, SLAB_FLOATS_MAX = 18432, 28800
+MAX_A = 49                  # kMaxA: beyond it k_group_shape<true> and k_group_big<., true>, the large shape record
+SAI_MAJOR_MIN_A = 121       # kSaiMajorMinA: a pass writes filt SAI-major from 11 x 11 SAIs on
 
 
 def _uses_slab(c, opt):
-    if "no_slab_kernel" in opt or c.useSD or c.aw not in range(3, 18, 2) or c.N > (16 if c.aw > 9 else 32):
+    if "no_slab_kernel" in opt or c.bm3d or c.useSD or c.aw not in range(3, 18, 2) or c.N > (16 if c.aw > 9 else 32):
         return False
     if c.tau2 == DCT and c.k not in (8, 12, 16):
         return False
@@ -183,9 +190,20 @@ def _uses_slab(c, opt):
     return S * c.N * c.A * c.k * c.k * 4 > (150 if c.tau2 == ID else 64) * 1024
 
 
+def slab_log2(c):
+    """slab_log2 of lfbm5d_group_slab.hip: log2 of the pixels a slab of k_group_slab holds."""
+    per_px = (2 if c.step == 2 else 1) * c.N * c.A
+    ls = 6
+    while ls > 2 and (per_px << ls) > SLAB_FLOATS:
+        ls -= 1
+    if (per_px << ls) > SLAB_FLOATS_MAX:
+        ls = 1
+    return ls
+
+
 def expected_kernels(c, opt=()):
     k2, bytes_ = c.k * c.k, c.A * c.C * c.Wb * c.Hb * 4
-    names = ["k_group_pos", "k_group_shape<true>" if c.A > 49 else "k_group_shape<false>"]
+    names = ["k_group_pos", "k_group_shape<true>" if c.A > MAX_A else "k_group_shape<false>"]
     all_sa = c.tau4 == SADCT and not c.mask.all() and "no_sa_kernels" not in opt
     haar = c.tau5 == HAAR
     if "group_generic" not in opt:
@@ -214,23 +232,26 @@ def expected_kernels(c, opt=()):
                     return names + ["k_group_dct8w3_u"] + (["k_group_dct8w3_list"] if c.tau4 == SADCT else [])
                 return names + ["k_group_dct8w3<false>"]
             return names + ["k_group_dct8w2<true>" if haar else "k_group_dct8w2<false>"]
-        if c.aw >= 5 and c.tau2 == ID and c.step == 1 and c.N <= 8 and k2 <= 256 and bytes_ < 0x7fffffff:
+        if c.aw >= 5 and c.tau2 == ID and c.step == 1 and not c.bm3d and c.N <= 8 and k2 <= 256 and bytes_ < 0x7fffffff:
             split = not (c.useSD or "wide_nosplit" in opt)
             return names + (["k_group_idw<AW, SLAB, true>", "k_group_idw_weight"] if split else ["k_group_idw<AW, SLAB, false>"])
+        if c.bm3d and c.A == 1 and c.k == 8 and c.tau5 == HADAMARD and c.tau2 in (DCT, BIOR):
+            return names + ["k_group_bm3d8<%d, %s>" % (c.step, "true" if c.tau2 == BIOR else "false")]
         if _uses_slab(c, opt):
             return names + ["k_group_slab<%d, WA, MAXN>" % c.step]
     rows_form = (c.tau2 == BIOR and c.k in (8, 16)) or (c.tau2 == DCT and c.k in (8, 12, 16))
     tmp = (256 // c.k) * c.k * (c.k + 1) if rows_form else max(256, k2)
     lds = ((2 if c.step == 2 else 1) * c.N * c.A * k2 + tmp) * 4
-    if lds > GENERIC_LDS_LIMIT or c.A > 49:
-        return names + ["k_group_big<%d, %s>" % (c.step, "true" if c.A > 49 else "false")]
+    if lds > GENERIC_LDS_LIMIT or c.A > MAX_A:
+        return names + ["k_group_big<%d, %s>" % (c.step, "true" if c.A > MAX_A else "false")]
     return names + ["k_group<%d>" % c.step]
 
 
-# every __global__ of lfbm5d_group_{ht,wiener,generic,wide,slab}.hip, by the text the dispatchers record; not reached on purpose:
-# k_group_bm3d8 (per-SAI BM3D), k_group_big<.., true> and k_group_shape<true> (windows beyond 7 x 7)
+# every __global__ of lfbm5d_group_{ht,wiener,generic,wide,slab}.hip, by the text the dispatchers record
 ALL_KERNELS = [
-    "k_group_pos", "k_group_shape<false>", "k_group<1>", "k_group<2>", "k_group_big<1, false>", "k_group_big<2, false>",
+    "k_group_pos", "k_group_shape<false>", "k_group_shape<true>", "k_group<1>", "k_group<2>",
+    "k_group_big<1, false>", "k_group_big<2, false>", "k_group_big<1, true>", "k_group_big<2, true>",
+    "k_group_bm3d8<1, true>", "k_group_bm3d8<1, false>", "k_group_bm3d8<2, true>", "k_group_bm3d8<2, false>",
     "k_group_id_haar_fast", "k_group_id_haar", "k_group_id_any", "k_group_id_haar_list", "k_group_id_any_list",
     "k_group_id_haar_sa", "k_group_id_any_sa",
     "k_group_bior16_haar", "k_group_bior16_any", "k_group_dct16_haar", "k_group_dct16_any",
@@ -327,4 +348,102 @@ def cases():
         C=1, runs=((), ("no_slab_kernel",)))
     add("ht-id-haar-k8-5x5-saimajor", 193, sigma=100.0, step=1, tau2="id", tau4="sadct", tau5="haar", k=8, N=8, aw=5, shapes=w5[:40], nsx="cycle",
         sai_major=True, C=1)
+    out += wide_cases() + bm3d_cases()
+    return out
+
+
+def thin(rng, aw, pst, count):
+    """`count` shapes of an aw x aw window from wide_shapes: half seeded random ones, the rest drawn from the lone-SAI shapes (a lone
+    SAI in another row or column, and the same next to pst's full row)."""
+    n_random = count // 2
+    sh = wide_shapes(rng, aw, pst, n_random)
+    pick = np.sort(rng.choice(np.arange(n_random, len(sh)), size=count - n_random, replace=False))
+    return sh[:n_random] + [sh[int(i)] for i in pick]
+
+
+def wide_cases():
+    """F. windows of 7 x 7 to 17 x 17 SAIs.  Hard-threshold cases take lambda 3.5, with a sigma of 75 .. 100 without a 2-D transform and of 30 .. 50 and a
+    texture of twice the amplitude with one (so that more than k^2 coefficients survive in a quarter of the pairs): at the default 2.7 a pair
+    of such a window holds so many coefficients that more than 5 % of the pairs are open whatever sigma is (7 x 7: 5 / 64, 9 x 9:
+    7 / 64, 17 x 17 with N = 1: 16 / 64); default-lambda decisions on wide windows stay with the whole-pass tests.  The Wiener cases
+    run the default parameters.  C = 1 unless a case says otherwise; from 11 x 11 on filt is SAI-major, as in a pass."""
+    out = []
+
+    def add(name, seed, aw, n, pst=None, **kw):
+        kw.setdefault("C", 1)
+        pst_ = aw * aw // 2 if pst is None else pst
+        shapes = thin(np.random.default_rng(1000 + seed), aw, pst_, max(n, 4))      # (one group: the first, a random shape)
+        out.append(build(name, seed, aw=aw, pst=pst, shapes=shapes, n_groups=n, nsx="cycle", tau4="sadct", section="F", **kw))
+
+    ht = dict(step=1, lam=3.5)
+    idw = dict(step=1, lam=3.5, tau2="id", tau5="haar")
+    # k_group_idw<AW, SLAB, .> of every window side
+    add("ht-id-haar-k8-n8-7x7", 301, 7, 56, sigma=75.0, k=8, N=8, **idw)
+    add("ht-id-haar-k16-9x9", 302, 9, 48, sigma=75.0, k=16, N=4, **idw)
+    add("ht-id-haar-k6-11x11", 303, 11, 32, sigma=75.0, k=6, N=4, runs=((), ("filt_group_major",)), **idw)     # 36 pixels: a slab tail
+    add("ht-id-haar-k8-c3-13x13", 304, 13, 24, sigma=75.0, k=8, N=2, C=3, **idw)
+    add("ht-id-haar-k10-15x15", 305, 15, 24, sigma=75.0, k=10, N=2, runs=((), ("wide_nosplit",)), **idw)        # 100 pixels: a slab tail
+    add("ht-id-haar-k8-15x15-sd", 306, 15, 24, sigma=75.0, k=8, N=4, useSD=1, **idw)
+    add("ht-id-haar-k8-17x17", 307, 17, 16, sigma=75.0, k=8, N=2, **idw)
+    # k_group_slab<STEP, WA, MAXN> of every window side, and every slab tier (ls) of slab_log2
+    add("ht-bior-haar-k8-n8-7x7", 310, 7, 56, sigma=35.0, amp=80.0, tau2="bior", tau5="haar", k=8, N=8, **ht)                          # ls 5
+    add("wien-id-haar-k8-7x7", 311, 7, 48, step=2, tau2="id", tau5="haar", k=8, N=8)                             # ls 4; 196 KB of stacks
+    add("ht-dct-hw-k8-9x9", 312, 9, 48, sigma=35.0, amp=80.0, tau2="dct", tau5="hw", k=8, N=8, runs=((), ("no_slab_kernel",)), **ht)   # ls 4
+    add("ht-dct-haar-k12-n2-9x9", 315, 9, 48, sigma=30.0, amp=80.0, tau2="dct", tau5="haar", k=12, N=2, **ht)                          # ls 6
+    add("wien-dct-haar-k8-n32-9x9", 314, 9, 32, step=2, tau2="dct", tau5="haar", k=8, N=32)                      # ls 2, MAXN = 32, 81 KB of LDS
+    add("wien-dct-haar-k8-11x11", 315, 11, 32, step=2, tau2="dct", tau5="haar", k=8, N=8, runs=((), ("filt_group_major",)))   # ls 3
+    add("wien-dct-haar-k8-n16-13x13", 316, 13, 24, step=2, tau2="dct", tau5="haar", k=8, N=16, runs=((), ("no_slab_kernel",)))   # ls 2 beyond 72 KB
+    add("ht-bior-dct5-k8-15x15", 317, 15, 24, sigma=50.0, amp=80.0, tau2="bior", tau5="dct", k=8, N=8, **ht)                           # ls 3
+    add("wien-dct-haar-k8-n16-17x17", 318, 17, 12, step=2, tau2="dct", tau5="haar", k=8, N=16)                   # ls 1
+    # the general kernels: k_group<.> at A = 49 (stacks below the slab rule's 64 KB), k_group_big<., true> beyond
+    add("ht-bior-haar-k4-7x7", 320, 7, 56, sigma=35.0, amp=80.0, tau2="bior", tau5="haar", k=4, N=8, **ht)
+    add("wien-dct-haar-k8-n2-7x7", 321, 7, 56, step=2, tau2="dct", tau5="haar", k=8, N=2)
+    add("ht-dct-haar-k8-9x9-sd", 322, 9, 48, sigma=35.0, amp=80.0, tau2="dct", tau5="haar", k=8, N=4, useSD=1, **ht)
+    add("wien-dct-haar-k8-9x9-sd", 323, 9, 48, step=2, tau2="dct", tau5="haar", k=8, N=4, useSD=1)
+    add("ht-dct-haar-k10-9x9", 324, 9, 48, sigma=35.0, amp=80.0, tau2="dct", tau5="haar", k=10, N=4, **ht)
+    # empty SAIs (every group is shape-adaptive), and a subset pass: pst off-centre, no zero column
+    m9, m13 = np.ones(81, np.uint32), np.ones(169, np.uint32)
+    m9[[0, 13, 44, 80]] = 0
+    m13[[5, 30, 31, 100, 168]] = 0
+    add("ht-id-haar-k8-9x9-empty", 330, 9, 48, sigma=75.0, k=8, N=4, mask=m9, **idw)
+    add("wien-dct-haar-k8-13x13-empty", 331, 13, 24, step=2, tau2="dct", tau5="haar", k=8, N=8, mask=m13)
+    add("ht-id-haar-k8-11x11-subset", 332, 11, 32, pst=3 * 11 + 8, sigma=75.0, k=8, N=4, fill_quirk=0, **idw)
+    # launch edges
+    add("ht-id-haar-k8-9x9-band", 340, 9, 48, sigma=75.0, k=8, N=4, ref_begin=5, launch=21, **idw)
+    add("wien-dct-haar-k8-9x9-band", 341, 9, 48, step=2, tau2="dct", tau5="haar", k=8, N=8, ref_begin=5, launch=21)
+    add("ht-id-haar-k8-9x9-1group", 350, 9, 1, sigma=75.0, k=8, N=4, **idw)
+    add("wien-dct-haar-k8-9x9-1group", 343, 9, 1, step=2, tau2="dct", tau5="haar", k=8, N=8)
+    add("ht-id-haar-k8-9x9-edges", 344, 9, 48, sigma=100.0, k=8, N=4, edges=True, **idw)
+    add("wien-dct-haar-k8-9x9-edges", 345, 9, 48, step=2, tau2="dct", tau5="haar", k=8, N=8, edges=True)
+    return out
+
+
+def bm3d_cases():
+    """G. the per-SAI BM3D flavour: one image (A = 1), 2-D transform and Hadamard along stacks of 2 .. N patches.  With useSD the
+    reference weights every channel by channel 0's deviation (the aggregation's wchan0); the group kernels store each channel's own,
+    so those cases have one channel."""
+    out = []
+
+    def add(name, seed, n, **kw):
+        kw.setdefault("C", 1)
+        kw.setdefault("k", 8)
+        out.append(build(name, seed, bm3d=True, n_groups=n, nsx="cycle", tau4="id", tau5="hw", section="G", **kw))
+
+    ht = dict(step=1, lam=3.5, sigma=25.0, amp=80.0)
+    add("bm3d-ht-bior-n16-c3", 401, 64, tau2="bior", N=16, C=3, runs=((), ("group_generic",)), **ht)
+    add("bm3d-ht-dct-n32", 402, 60, tau2="dct", N=32, **ht)
+    add("bm3d-wien-bior-n32", 403, 60, step=2, tau2="bior", N=32)
+    add("bm3d-wien-dct-n16-c3", 404, 64, step=2, tau2="dct", N=16, C=3, runs=((), ("group_generic",)))
+    add("bm3d-ht-dct-n16-sd", 405, 64, tau2="dct", N=16, useSD=1, **ht)
+    add("bm3d-wien-bior-n16-sd", 406, 64, step=2, tau2="bior", N=16, useSD=1)
+    add("bm3d-ht-bior-n16-edges", 407, 64, tau2="bior", N=16, edges=True, **ht)
+    add("bm3d-wien-dct-n16-same", 408, 64, step=2, tau2="dct", N=16, same=True)
+    for n in (1, 3, 4, 5):      # the kernel packs four groups into a workgroup
+        add("bm3d-ht-dct-n16-%dgroups" % n, 410 + n, n, tau2="dct", N=16, **ht)
+        add("bm3d-wien-bior-n16-%dgroups" % n, 420 + n, n, step=2, tau2="bior", N=16)
+    add("bm3d-ht-bior-n16-band", 430, 13, tau2="bior", N=16, ref_begin=3, launch=6, **ht)
+    add("bm3d-wien-dct-n16-band", 431, 13, step=2, tau2="dct", N=16, ref_begin=3, launch=6)
+    # 12 x 12 patches (BM3D's choice at high sigma): the general kernel under bm3d
+    add("bm3d-ht-dct-k12-n16", 440, 48, tau2="dct", k=12, N=16, **ht)
+    add("bm3d-wien-dct-k12-n16", 441, 48, step=2, tau2="dct", k=12, N=16)
     return out

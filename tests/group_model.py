@@ -12,6 +12,9 @@ of the kernels' butterflies): tests/test_group_model.py measures float32 round-o
 Scales are the reference's, not the textbook's: the shape-adaptive DCT and the DCT along the stack leave 1-D pieces longer than one
 at twice the orthonormal scale (core:3229-3276), the Hadamard transform is unnormalised, and the hard threshold of each is
 lambda sigma_c sqrt2 times the matching factor (core:2431).  tests/test_oracle_*.py tie those to the compiled reference.
+
+A case with `bm3d` set is the per-SAI BM3D flavour (bm3d.cpp:315-690): one image, no angular transform, Hadamard along stacks of
+2 .. N patches, the threshold lambda sigma_c without the sqrt2 (bm3d.cpp:941), the SD weight over nSx k^2 values (:1345-1373).
 """
 import functools
 
@@ -226,7 +229,7 @@ def positions(case):
     in_shape = np.zeros((R, A), bool)
     for st in range(A):
         in_shape[:, st] = True if st == case.pst else (bool(case.mask[st]) & (case.shape.reshape(A, plane)[st][case.refs] != 0))
-    ok = present & (in_shape[:, None, :] if case.tau4 == SADCT else True)
+    ok = present & (in_shape[:, None, :] if case.tau4 == SADCT and not case.bm3d else True)
     aggpos = np.where(ok, ((pos // Wb) << 16) | (pos % Wb), ABSENT).astype(np.uint32)
     return pos, present, zero, in_shape, np.ascontiguousarray(aggpos.transpose(2, 0, 1))   # aggpos [A][R][N]
 
@@ -253,21 +256,21 @@ class Chain:
         R, N, A = case.R, case.N, case.A
         aw = int(round(np.sqrt(A)))
         self.T2f, self.T2i = transform_2d(case.tau2, case.k, True), transform_2d(case.tau2, case.k, False)
-        bits = (in_shape.astype(np.int64) << np.arange(A)).sum(1) if A <= 62 else None
-        if A > 62:
-            raise NotImplementedError("windows beyond 7 x 7 are out of this model's scope")
+        # a shape's bits as a Python int: 17 x 17 windows have 289 of them
+        bits = np.array([sum(1 << int(i) for i in np.flatnonzero(row)) for row in in_shape], dtype=object)
         full = (1 << A) - 1
-        self.use_sadct = (bits != full) if case.tau4 == SADCT else np.zeros(R, bool)
+        tau4 = ID if case.bm3d else case.tau4      # the per-SAI BM3D flavour has one image: no angular transform whatever tau4 says
+        self.use_sadct = (bits != full).astype(bool) if tau4 == SADCT else np.zeros(R, bool)
         self.support = np.ones((R, A), bool)     # in-shape coefficients (mask_dct) of every group
         self.A4f = self.A4i = None
-        if case.tau4 != ID:
+        if tau4 != ID:
             D = dct_ortho(aw)
             Df = np.kron(D, D)
             self.A4f = np.broadcast_to(Df, (R, A, A)).copy()
             self.A4i = np.broadcast_to(Df.T, (R, A, A)).copy()
-            for b in np.unique(bits[self.use_sadct]):
+            for b in set(bits[self.use_sadct]):
                 F, G, md = sadct_matrices(int(b), aw)
-                sel = self.use_sadct & (bits == b)
+                sel = self.use_sadct & (bits == b).astype(bool)
                 self.A4f[sel], self.A4i[sel], self.support[sel] = F, G, md
             self.A4f, self.A4i = self.A4f.astype(dtype), self.A4i.astype(dtype)
         self.A5f, self.A5i = np.zeros((R, N, N), dtype), np.zeros((R, N, N), dtype)
@@ -302,8 +305,12 @@ class Chain:
 
 
 def thresholds(case):
-    """T[g][c]: lambda sigma_c sqrt2 in the kernels' float32 expression, times the scale factor of the stack transform."""
+    """T[g][c]: lambda sigma_c sqrt2 in the kernels' float32 expression, times the scale factor of the stack transform.  The per-SAI
+    BM3D flavour (bm3d.cpp:941) has lambda sigma_c without the sqrt2, and no lambda / sqrt2 rule: group_args_of_pass leaves its
+    lambda alone."""
     lam = np.float32(case.lam)
+    if case.bm3d:
+        return np.array([np.float32(lam * np.float32(s)) for s in case.sigma], np.float64)
     if case.step == 1 and case.tau2 == ID and case.tau4 == DCT:
         lam = np.float32(lam / np.float32(SQRT2))   # core:206-207
     return np.array([np.float32(np.float32(lam * np.float32(s)) * np.float32(1.41421356237309505)) for s in case.sigma], np.float64)
@@ -347,8 +354,8 @@ def run(case, dtype=np.float64):
         v = np.where(valid, v, 0)
         wsum = v.sum(axis=(1, 2, 4), dtype=dtype).astype(np.float64)
     F4 = ch.inv5(Xf)
-    if case.useSD:   # sd_weighting_5d (core:3140-3173) on the filtered angular coefficients, Nn = nSx A
-        Nn = (case.self_cnt.astype(np.float64) * A)[:, None]
+    if case.useSD:   # sd_weighting_5d (core:3140-3173) on the filtered angular coefficients, Nn = nSx A; BM3D (bm3d.cpp:1345-1373): nSx k^2
+        Nn = (case.self_cnt.astype(np.float64) * (k2 if case.bm3d else A))[:, None]
         m = F4.sum(axis=(1, 2, 4), dtype=dtype).astype(np.float64)
         q = (F4 * F4).sum(axis=(1, 2, 4), dtype=dtype).astype(np.float64)
         with np.errstate(divide="ignore", invalid="ignore"):

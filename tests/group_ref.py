@@ -18,6 +18,9 @@ OPEN_CAP = 0.05      # at most this share of a case's (group, channel) pairs may
 
 def oracle_group(case):
     P = O.make_params(*K.params_tuple(case))
+    if case.bm3d:      # the group loop of the oracle's bm3d_step; filt as [g][n][0][c][k2]
+        pat, w, nSx = O.bm3d_group(case.step, P, case.Wb, case.Hb, case.C, case.noisy, case.basic, case.refs, case.self_idx, case.self_cnt)
+        return np.ascontiguousarray(pat.transpose(0, 2, 1, 3)[:, :, None]), w, nSx, np.zeros_like(nSx)
     pat, w, nSx, sa = O.group(case.step, P, case.aw, case.aw, case.Wb, case.Hb, case.C, case.noisy, case.basic, case.mask, case.pst,
                               case.fill_quirk, case.refs, case.self_idx, case.self_cnt, case.best, case.shape)
     return np.ascontiguousarray(pat.transpose(0, 3, 1, 2, 4)), w, nSx, sa      # filt as [g][n][st][c][k2]

@@ -4,7 +4,7 @@ Every case of tests/group_cases.py goes through lfbm5d_debug_group -- launch_gro
 supplies -- under each of its option sets, and is compared with tests/group_model.py:
 
   - aggpos, the two counters (sum of nSx, shape-adaptive groups) and the whole-group entries (| 7 << 29) of the group list are the
-    model's; the kernels launched are the ones the dispatch restated in group_cases.expected_kernels names;
+    model's (windows beyond 7 x 7 SAIs list nothing: the list is read by kernels of 3 x 3 windows only); the kernels launched are the ones the dispatch restated in group_cases.expected_kernels names;
   - hard-threshold step: the survivor count recovered from wgt equals the model's for every (group, channel) without a coefficient
     inside the gap (group_model.gap_of), differs by at most the number of such coefficients otherwise, and wgt is the float32
     evaluation of 1 / (sigma_c^2 count) bit for bit;
@@ -14,8 +14,11 @@ supplies -- under each of its option sets, and is compared with tests/group_mode
   - Wiener and SD weights: relative error <= 4 max(E_w, sqrt(n) eps32), n = nSx A k^2 terms; weights beyond float32's range as large;
   - slots no patch belongs to (stack positions beyond nSx, empty SAIs, SAIs outside the shape) are not compared.
 
-Out of scope: the per-SAI BM3D flavour (A = 1) and windows beyond 7 x 7 SAIs (k_group_big<.., true>, k_group_shape<true>); the seam
-takes both.  Low-sigma decisions stay with tests/test_gpu_ht_decisions.py.
+The cases cover the 3 x 3 windows' dedicated kernels, windows of 5 x 5 to 17 x 17 SAIs (every window side of k_group_idw and
+k_group_slab, the large shape record, the general kernels' HBM form; from 11 x 11 on filt is SAI-major as in a pass) and the per-SAI
+BM3D flavour (A = 1, launched with bm3d set).  The hard-threshold cases of the wide windows run lambda 3.5: default-lambda
+decisions on wide windows stay with the whole-pass tests (tests/test_gpu_parity.py), low-sigma decisions with
+tests/test_gpu_ht_decisions.py.
 """
 import numpy as np
 import pytest
@@ -53,7 +56,7 @@ def launch(ctx, case, opt=()):
     R, N, A, C, k2 = case.R, case.N, case.A, case.C, case.k * case.k
     rb, nb = case.ref_begin, case.launch
     per = N * C * k2
-    stride = nb * per + 32 if case.sai_major else 0
+    stride = nb * per + 32 if case.sai_major and "filt_group_major" not in opt else 0    # (the option matters to passes only: here the stride is the layout)
     filt = torch.full((A * stride if stride else nb * A * per,), float("nan"), device="cuda")
     wgt = torch.full((R * C,), -7.0, device="cuda")
     aggpos = torch.full((A * R * N,), SENTINEL, dtype=torch.int32, device="cuda")
@@ -66,7 +69,7 @@ def launch(ctx, case, opt=()):
                                               dev(case.self_idx.reshape(-1)), dev(case.self_cnt), dev(case.best.reshape(-1)),
                                               torch.from_numpy(case.shape.reshape(-1)).cuda(), filt, wgt, aggpos, case.mask, case.pst,
                                               fill_quirk=case.fill_quirk, n_refs_total=R, ref_begin=rb, n_groups=nb,
-                                              filt_sai_stride=stride)
+                                              filt_sai_stride=stride, bm3d=int(case.bm3d))
         lst = ctx.last_group_list()
     finally:
         for o in opt:
@@ -100,7 +103,9 @@ def test_group_kernels_against_the_model(ctx, case):
         assert (aggpos[:, rest] == SENTINEL).all() and (w[rest] == -7.0).all(), (tag, "rows outside the launch were written")
         assert n_stack == int(m["nSx"][sl].sum()) and n_sa == int(m["use_sadct"][sl].sum()), (tag, "counters", n_stack, n_sa)
         whole = sorted(int(e & 0x1FFFFFFF) for e in lst if e >> 29 == 7)
-        assert whole == sorted(int(g) for g in np.flatnonzero(m["use_sadct"]) if rb <= g < rb + nb), (tag, "group list")
+        # (k_group_shape<true>, the large shape record, lists nothing: only kernels of 3 x 3 windows read the list)
+        listed = np.flatnonzero(m["use_sadct"]) if case.A <= K.MAX_A else []
+        assert whole == sorted(int(g) for g in listed if rb <= g < rb + nb), (tag, "group list")
         # values
         res = M.compare(case, m, f, w[sl], sl)
         print("%s %s: E_filt gpu %.3g (oracle %.3g, second %.3g), E_w gpu %.3g (oracle %.3g, second %.3g), open %d / %d"
@@ -118,8 +123,8 @@ def test_group_kernels_against_the_model(ctx, case):
 
 
 def test_every_group_kernel_was_reached(ctx):
-    """The union of the kernel texts over all cases holds every __global__ of the five group files but k_group_bm3d8,
-    k_group_big<.., true> and k_group_shape<true> (tests/test_group_model.py ties this list to the sources)."""
+    """The union of the kernel texts over all cases holds every __global__ of the five group files in every spelling a dispatcher
+    launches (tests/test_group_model.py ties this list to the sources)."""
     for case in CASES:
         if case.name not in _seen:      # run alone: the texts do not depend on the data
             for opt in case.runs:
@@ -134,45 +139,71 @@ def _passes():
     return PASSES
 
 
-@pytest.mark.parametrize("i", range(3), ids=["wien-k8-n8", "ht-k16-n4-empty-sai", "ht-k6"])
+# two wide windows behind the three 3 x 3 passes: (name, step, sigma, parameters, empty SAI, window side, crop)
+WIDE_PASSES = [
+    ("ht-id-n4-9x9", 1, 25.0, (4, 4, 2, 8, 4, "id", "sadct", "haar"), None, 9, 48),             # group-major filt, the large shape record
+    ("wien-dct-n2-11x11-empty-sai", 2, 25.0, (2, 4, 2, 8, 4, "dct", "sadct", "haar"), 7, 11, 40),   # SAI-major filt
+]
+
+
+@pytest.mark.parametrize("i", range(5), ids=["wien-k8-n8", "ht-k16-n4-empty-sai", "ht-k6"] + [p[0] for p in WIDE_PASSES])
 def test_group_and_aggregate_seams_give_the_pass(ctx, i):
     import agg_model as AM
     import helpers as Hh
     from lfbm5d_amd import core
     from test_gpu_parity import gpu_pass, window
-    name, step, sigma, pk, empty = _passes()[i]
-    win, Wb, Hb, Cc = window(sigma, pk, 64)
+    if i < 3:
+        name, step, sigma, pk, empty = _passes()[i]
+        aw = 3
+        win, Wb, Hb, Cc = window(sigma, pk, 64)
+    else:   # as tests/test_gpu_parity.py's wide-window passes: a textured light field with a real disparity
+        name, step, sigma, pk, empty, aw, crop = WIDE_PASSES[i - 3]
+        Cc = 3
+        _, noisy = Hh.noisy_lf(Hh.textured_lf(aw, aw, crop, crop)[:, :Cc], sigma)
+        win, Wb, Hb = Hh.padded_window(noisy, crop, crop, Cc, pk[1] + pk[2])
     N, nSim, nDisp, k, p = pk[:5]
-    A, pst, plane = 9, 4, Wb * Hb
+    A, plane = aw * aw, Wb * Hb
+    pst = A // 2
     mask = np.ones(A, np.uint32)
     if empty is not None:
         mask[empty] = 0
+        if aw > 3:
+            win[empty] = 0
+    proc = (mask == 0).astype(np.uint32) if aw > 3 else None      # (the schedule marks empty SAIs as processed)
+    wide = dict(cst=pst, pst=pst, aw=aw)
     basic = None
     if step == 2:
-        n1, d1 = gpu_pass(ctx, 1, sigma, (4,) + pk[1:5] + ("id", "sadct", "haar"), win, None, Wb, Hb, Cc)
+        n1, d1 = gpu_pass(ctx, 1, sigma, (4,) + pk[1:5] + ("id", "sadct", "haar"), win, None, Wb, Hb, Cc,
+                          **(dict(mask=mask, proc=proc, **wide) if aw > 3 else {}))
         basic = np.ascontiguousarray(Hh.estimate(n1, d1, win).astype(np.float32))
-    num, den = gpu_pass(ctx, step, sigma, pk, win, basic, Wb, Hb, Cc, mask=mask)
+    num, den = gpu_pass(ctx, step, sigma, pk, win, basic, Wb, Hb, Cc, mask=mask, proc=proc, **wide)
     refs, idx, cnt, best, shape = ctx.last_bm(N, A, plane)
     R = len(refs)
     g = AM.Geom(Wb=Wb, Hb=Hb, C=Cc, A=A, k=k, N=N, p=p, nSim=nSim, nDisp=nDisp, pst=pst, mask=mask)
     assert g.R == R
-    filt = torch.full((R * N * A * Cc * k * k,), float("nan"), device="cuda")
+    per = N * Cc * k * k
+    stride = R * per if A >= K.SAI_MAJOR_MIN_A else 0       # the layout of the pass
+    filt = torch.full((R * A * per,), float("nan"), device="cuda")
     wgt = torch.zeros(R * Cc, device="cuda")
     aggpos = torch.full((A * R * N,), SENTINEL, dtype=torch.int32, device="cuda")
     d_win = torch.from_numpy(win).cuda().reshape(-1)
-    ctx.debug_group(step, core.make_params(sigma, 2.7, *pk), 3, 3, Wb, Hb, Cc, d_win, None if basic is None else dev(basic.reshape(-1)),
-                    dev(refs), dev(idx.reshape(-1)), dev(cnt), dev(best.reshape(-1)), torch.from_numpy(shape.reshape(-1)).cuda(),
-                    filt, wgt, aggpos, mask, pst, fill_quirk=1, n_refs_total=R)
+    text, _, _ = ctx.debug_group(step, core.make_params(sigma, 2.7, *pk), aw, aw, Wb, Hb, Cc, d_win, None if basic is None else dev(basic.reshape(-1)),
+                                 dev(refs), dev(idx.reshape(-1)), dev(cnt), dev(best.reshape(-1)), torch.from_numpy(shape.reshape(-1)).cuda(),
+                                 filt, wgt, aggpos, mask, pst, fill_quirk=1, n_refs_total=R, filt_sai_stride=stride)
+    if aw > 3:
+        assert "k_group_shape<true>" in text, text
     d_num, d_den = torch.zeros(A * Cc * plane, device="cuda"), torch.zeros(A * Cc * plane, device="cuda")
-    ctx.debug_aggregate(d_num, d_den, filt, wgt, aggpos, mask, np.zeros(A, np.uint32), n_refs_total=R, ref_begin=0, n_groups=R,
-                        n_ref_rows=g.n_ref_rows, n_ref_cols=g.n_ref_cols, Wb=Wb, Hb=Hb, C_=Cc, A=A, k=k, N=N, pst=pst, p=p, nSim=nSim,
-                        nDisp=nDisp)
+    ctx.debug_aggregate(d_num, d_den, filt, wgt, aggpos, mask, np.zeros(A, np.uint32) if proc is None else proc, n_refs_total=R, ref_begin=0,
+                        n_groups=R, n_ref_rows=g.n_ref_rows, n_ref_cols=g.n_ref_cols, Wb=Wb, Hb=Hb, C_=Cc, A=A, k=k, N=N, pst=pst, p=p,
+                        nSim=nSim, nDisp=nDisp, filt_sai_stride=stride)
     assert AM.same_bits(d_den.cpu().numpy(), den.reshape(-1)).all(), name
     assert AM.same_bits(d_num.cpu().numpy(), num.reshape(-1)).all(), name
 
 
 # ---- the seam refuses what the kernels take for granted ----
-def _small():
+def _small(bm3d=False):
+    if bm3d:
+        return K.build("refusals-bm3d", 5, step=2, tau2="dct", tau4="id", tau5="hw", k=8, N=4, C=1, nsx="cycle", n_groups=16, bm3d=True)
     return K.build("refusals", 5, step=2, tau2="dct", tau4="sadct", tau5="haar", k=8, N=4, C=1, nsx="cycle", n_groups=16)
 
 
@@ -199,6 +230,7 @@ BAD = [
     ("null-wgt", dict(null="wgt"), "NULL"), ("null-aggpos", dict(null="aggpos"), "NULL"), ("null-mask", dict(null="mask"), "NULL"),
     ("C-2", dict(C=2), "chnls"), ("k-1", dict(k=1), "patch size"), ("k-33", dict(k=33), "patch size"),
     ("N-3", dict(N=3), "power of two"), ("N-64", dict(N=64), "power of two"),
+    ("bm3d-cnt-1", dict(bm3d=True, cnt=1), "BM3D stack of one patch"),
     ("cnt-0", dict(cnt=0), "stack size"), ("cnt-3", dict(cnt=3), "stack size"), ("cnt-above-N", dict(cnt=8), "stack size"),
     ("refs-outside", dict(outside="refs"), "reference patch lies outside"),
     ("refs-column-outside", dict(outside="refs-column"), "reference patch lies outside"),
@@ -231,7 +263,7 @@ def _call(ctx, case, t, change):
                            t["noisy"], t["basic"], t["refs"], t["self_idx"], t["self_cnt"], t["best"], t["shape"], t["filt"], t["wgt"],
                            t["aggpos"], t["mask"], change.get("pst", case.pst), fill_quirk=1, n_refs_total=R,
                            ref_begin=change.get("ref_begin", 0), n_groups=R, filt_floats=change.get("filt_floats"),
-                           filt_sai_stride=stride, null=(change["null_field"],) if "null_field" in change else ())
+                           filt_sai_stride=stride, bm3d=int(case.bm3d), null=(change["null_field"],) if "null_field" in change else ())
 
 
 def _tensors(case):
@@ -247,7 +279,8 @@ def _tensors(case):
 def test_seam_refuses_invalid_arguments(ctx, name, change, message):
     import lfbm5d_amd as L
     change = dict(change)
-    case = _small()
+    bm3d = bool(change.pop("bm3d", False))
+    case = _small(bm3d)
     if "cnt" in change:
         case.self_cnt[2] = change["cnt"]
     if "outside" in change:
@@ -273,8 +306,8 @@ def test_seam_refuses_invalid_arguments(ctx, name, change, message):
     # nothing was launched: filt and wgt are as they were, and the same call without the fault runs
     for n, x in keep.items():
         assert bool((x == (3.0 if n == "filt" else 5.0)).all()), n
-    good = _small()
+    good = _small(bm3d)
     t = _tensors(good)
     text, n_stack, n_sa = _call(ctx, good, t, {})
-    assert text.startswith("k_group_pos+k_group_shape<false>+k_group_dct8w3_u") and n_stack == int(good.self_cnt.sum())
+    assert text.startswith("k_group_pos+k_group_shape<false>+" + ("k_group_bm3d8<2, false>" if bm3d else "k_group_dct8w3_u")) and n_stack == int(good.self_cnt.sum())
     assert not bool((t["wgt"] == 5.0).any()) and not bool((t["filt"] == 3.0).all())
