@@ -1130,6 +1130,8 @@ int lfbm5d_device_count(void);
 #include "lfbm5d_views.h"
 /* ---- joint repair of defects and missing views by a mask-aware plane sweep (lfbm5d_repair_*) ---- */
 #include "lfbm5d_repair.h"
+/* ---- spatially correlated noise: autocorrelation, GPU measurement, per-coefficient variance table (lfbm5d_corr_*, lfbm5d_*_corr_*) ---- */
+#include "lfbm5d_corr.h"
 
 #ifdef __cplusplus
 }

@@ -19,8 +19,9 @@ from .core import (Context, Params, Bm3dParams, Stats, run_bm5d_1st_step, run_bm
                    PhotoParamsStruct, PhotoResultStruct, Equalise, photo_params, photo_edges, photo_ratio, photo_solve, equalise,
                    ClipEstimateStruct, ClipNoiseLevel, clip_fit, noise_level_clipped, denoise_clipped,
                    PgclipModelStruct, PgclipEstimateStruct, PgclipCurvesStruct, PgclipEstimate, PgclipCurves, pgclip_fit, pgclip_curves,
-                   pgclip_estimate, denoise_pgclip, denoise_views, window_sigma, views_from_gains)
-from .synth import add_view_noise
+                   pgclip_estimate, denoise_pgclip, denoise_views, window_sigma, views_from_gains,
+                   CorrEstimateStruct, CorrEstimate, CORR_WHITE, corr_measure, corr_from_kernel, corr_table, denoise_corr)
+from .synth import add_view_noise, add_correlated_noise
 
 __all__ = ["Context", "Params", "Bm3dParams", "Stats", "run_bm5d_1st_step", "run_bm5d_2nd_step", "run_bm3d_LF", "shard_rows",
            "YUV", "YCBCR", "OPP", "RGB", "ID", "DCT", "SADCT", "BIOR", "HADAMARD", "HAAR",
@@ -36,4 +37,6 @@ __all__ = ["Context", "Params", "Bm3dParams", "Stats", "run_bm5d_1st_step", "run
            "PhotoParamsStruct", "PhotoResultStruct", "Equalise", "photo_params", "photo_edges", "photo_ratio", "photo_solve", "equalise",
            "ClipEstimateStruct", "ClipNoiseLevel", "clip_fit", "noise_level_clipped", "denoise_clipped",
            "PgclipModelStruct", "PgclipEstimateStruct", "PgclipCurvesStruct", "PgclipEstimate", "PgclipCurves", "pgclip_fit", "pgclip_curves",
-           "pgclip_estimate", "denoise_pgclip", "denoise_views", "window_sigma", "views_from_gains", "add_view_noise"]
+           "pgclip_estimate", "denoise_pgclip", "denoise_views", "window_sigma", "views_from_gains", "add_view_noise",
+           "CorrEstimateStruct", "CorrEstimate", "CORR_WHITE", "corr_measure", "corr_from_kernel", "corr_table", "denoise_corr",
+           "add_correlated_noise"]

@@ -438,6 +438,24 @@ class PgclipCurves(NamedTuple):
     struct: PgclipCurvesStruct
 
 
+class CorrEstimateStruct(C.Structure):
+    """lfbm5d_corr_estimate (include/lfbm5d_corr.h)."""
+    _fields_ = [("acf", C.c_double * 49), ("sigma", C.c_double), ("cut", C.c_double), ("blocks", C.c_ulonglong),
+                ("selected", C.c_ulonglong), ("block", C.c_uint), ("reserved", C.c_uint)]
+
+
+class CorrEstimate(NamedTuple):
+    """Result of Context.corr_measure / corr_measure (include/lfbm5d_corr.h): the autocorrelation of the noise at the lags -3..3
+    (float64 [7][7], 1 at [3][3]), the marginal level of the selected blocks (biased low when fraction < 1), the number of blocks,
+    the number selected, the largest score selected and the block size used."""
+    acf: np.ndarray
+    sigma: float
+    blocks: int
+    selected: int
+    cut: float
+    block: int
+
+
 class NoiseLevel(NamedTuple):
     """Result of Context.noise_level / noise_level: sigma of the whole light field (what to pass as `sigma`), per stored channel
     (grey: [0] only), the size m of the noise subspace, the patches pooled, the eigenvalues of the pooled covariance (ascending)
@@ -698,6 +716,20 @@ def lib():
         L.lfbm5d_step2_views_device.argtypes = [vp, dp, dp, pp, fp, up, fp, fp] + [C.c_uint] * 7
         L.lfbm5d_bm3d_lf_views_device.argtypes = [vp, dp, dp, bp, bp, fp, up, fp, fp] + [C.c_uint] * 4
         L.lfbm5d_last_window_sigmas.argtypes = [vp, C.POINTER(C.c_float), C.c_uint]
+    if hasattr(L, "lfbm5d_denoise_corr_device"):   # (absent from older builds loaded through LFBM5D_HIP_LIB for A/B runs)
+        dp, pp = C.POINTER(C.c_double), C.POINTER(Params)
+        L.lfbm5d_corr_error.argtypes = []
+        L.lfbm5d_corr_error.restype = C.c_char_p
+        L.lfbm5d_corr_check.argtypes = [dp]
+        L.lfbm5d_corr_from_kernel.argtypes = [dp, C.c_uint, C.c_uint, dp]
+        L.lfbm5d_corr_table.argtypes = [dp, C.c_uint, C.c_uint, C.POINTER(C.c_float), C.POINTER(C.c_float), up]
+        L.lfbm5d_corr_measure_device.argtypes = [vp, fp, up] + [C.c_uint] * 5 + [C.c_double, C.POINTER(CorrEstimateStruct)]
+        L.lfbm5d_corr_measure_host_sai.argtypes = [vp, vp, up] + [C.c_uint] * 5 + [C.c_double, C.POINTER(CorrEstimateStruct)]
+        L.lfbm5d_denoise_corr_device.argtypes = [vp, dp, pp, pp, fp, up, fp, fp] + [C.c_uint] * 8
+        L.lfbm5d_denoise_corr_host_sai.argtypes = [vp, dp, pp, pp, fp, up, fp, fp] + [C.c_uint] * 8
+        L.lfbm5d_step1_corr_device.argtypes = [vp, dp, pp, fp, up, fp] + [C.c_uint] * 7
+        L.lfbm5d_step2_corr_device.argtypes = [vp, dp, pp, fp, up, fp, fp] + [C.c_uint] * 7
+        L.lfbm5d_debug_group_corr.argtypes = [vp, C.POINTER(GroupDebugStruct), dp]
     L.lfbm5d_malloc.argtypes = [C.POINTER(vp), C.c_size_t]
     L.lfbm5d_free.argtypes = [vp]
     L.lfbm5d_memcpy_h2d.argtypes = [vp, vp, C.c_size_t]
@@ -1115,6 +1147,47 @@ def views_from_gains(sigma, gain, mask=None):
     return out[:g.shape[0]]
 
 
+CORR_WHITE = np.zeros((7, 7), np.float64)
+CORR_WHITE[3, 3] = 1.0
+CORR_WHITE.setflags(write=False)
+
+
+def _acf49(acf):
+    a = np.ascontiguousarray(np.asarray(acf, dtype=np.float64).reshape(-1))
+    if a.size != 49:
+        raise LfBm5dError("an autocorrelation holds 7 x 7 values (lags -3..3)")
+    return a
+
+
+def corr_from_kernel(taps):
+    """The autocorrelation [7][7] of white noise filtered by `taps` (up to 7 x 7; a demosaicking or resampling kernel), 1 at lag 0
+    (lfbm5d_corr_from_kernel, include/lfbm5d_corr.h).  Host only, needs no GPU."""
+    g = np.ascontiguousarray(np.atleast_2d(np.asarray(taps, dtype=np.float64)))
+    if g.ndim != 2:
+        raise LfBm5dError("corr_from_kernel: the taps are a 2-D array of up to 7 x 7 values")
+    out = np.zeros(49, np.float64)
+    dp = C.POINTER(C.c_double)
+    if lib().lfbm5d_corr_from_kernel(g.ctypes.data_as(dp), g.shape[0], g.shape[1], out.ctypes.data_as(dp)) != 0:
+        raise LfBm5dError(lib().lfbm5d_corr_error().decode())
+    return out.reshape(7, 7)
+
+
+def corr_table(acf, tau_2D, k):
+    """(s, v, clamped): the variance factor v [k*k] of every coefficient of the 2-D transform tau_2D (ID, DCT, BIOR or their names) on
+    k x k patches under noise of autocorrelation `acf`, s = sqrt(v), both float32 as the kernels take them, and the number of
+    entries raised to the floor 1 / 64 (lfbm5d_corr_table, include/lfbm5d_corr.h).  Host only, needs no GPU."""
+    a = _acf49(acf)
+    k = int(k)
+    n = k * k if 2 <= k <= 32 else 1
+    s, v = np.zeros(n, np.float32), np.zeros(n, np.float32)
+    cl = C.c_uint(0)
+    tau = TAU[tau_2D] if isinstance(tau_2D, str) else int(tau_2D)
+    fp = C.POINTER(C.c_float)
+    if lib().lfbm5d_corr_table(a.ctypes.data_as(C.POINTER(C.c_double)), tau, k, s.ctypes.data_as(fp), v.ctypes.data_as(fp), C.byref(cl)) != 0:
+        raise LfBm5dError(lib().lfbm5d_corr_error().decode())
+    return s, v, int(cl.value)
+
+
 def sr_defaults(scale, /, **changes):
     """lfbm5d_sr_defaults (host only): the SrParams the library starts from for `scale`; keyword arguments replace fields
     (kernel may be "bicubic" / "gaussian")."""
@@ -1405,6 +1478,62 @@ class Context:
                                                    m.ctypes.data_as(C.POINTER(C.c_uint)), _dev_ptr(basic), _dev_ptr(denoised), ang_major,
                                                    awidth, aheight, an, int(W), int(H), int(Cc)))
         return used[:m.size]
+
+    # ---- spatially correlated noise (include/lfbm5d_corr.h) ----
+    def corr_measure(self, LF, LF_SAI_mask, width, height, chnls, block=16, fraction=None):
+        """The autocorrelation of the noise at the lags -3..3 from the block autocovariance of `LF` (lfbm5d_corr_measure_*).
+        fraction = 1 on a flat-field or dark-frame light field (or the difference of two captures): the calibration.  A small
+        fraction (None: the default, 0.1) on the noisy light field itself: the blind estimate from its flattest blocks; its sigma is
+        biased low.  LF: a CUDA float32 tensor [asize][C*H*W] (device form, read only), a float32 numpy array of that shape or a
+        list of per-SAI float32 arrays (host form, staged through HBM; bit-identical).  Returns a CorrEstimate."""
+        m = _u32(LF_SAI_mask)
+        res = CorrEstimateStruct()
+        tail = (m.ctypes.data_as(C.POINTER(C.c_uint)), m.size, int(width), int(height), int(chnls), int(block),
+                0.0 if fraction is None else float(fraction), C.byref(res))
+        if fraction is not None and float(fraction) == 0.0:
+            raise LfBm5dError("corr_measure: fraction must be in (0, 1] (None = the default)")
+        if isinstance(LF, (list, tuple, np.ndarray)):
+            self._ck(self._L.lfbm5d_corr_measure_host_sai(self._h, _sai_ptrs(self._host_sais(LF), m), *tail))
+        else:
+            self._ck(self._L.lfbm5d_corr_measure_device(self._h, _dev_ptr(LF), *tail))
+        return CorrEstimate(np.array(res.acf, np.float64).reshape(7, 7), float(res.sigma), int(res.blocks), int(res.selected),
+                            float(res.cut), int(res.block))
+
+    def denoise_corr(self, acf, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, Cc):
+        """denoise() under noise of autocorrelation `acf` [7][7] (lfbm5d_denoise_corr_*): every 2-D coefficient is thresholded and
+        Wiener-shrunk with its own variance factor (corr_table); P1.sigma / P2.sigma stay the marginal level.  General group kernels
+        only; with the white autocorrelation bit-identical to denoise() under option group_generic.  CUDA float32 tensors (device
+        form), or float32 numpy arrays / lists of per-SAI arrays (host form, in / out like denoise(); bit-identical)."""
+        m = _u32(mask)
+        mp = m.ctypes.data_as(C.POINTER(C.c_uint))
+        a = _acf49(acf)
+        head = (self._h, a.ctypes.data_as(C.POINTER(C.c_double)), C.byref(P1), C.byref(P2))
+        tail = (ang_major, awidth, aheight, an1, an2, int(W), int(H), int(Cc))
+        if isinstance(noisy, (list, tuple, np.ndarray)):
+            n, b, d = (self._host_sais(x) for x in (noisy, basic, denoised))
+            self._ck(self._L.lfbm5d_denoise_corr_host_sai(*head, _sai_ptrs(n, m), mp, _sai_ptrs(b, m), _sai_ptrs(d, m), *tail))
+        else:
+            self._ck(self._L.lfbm5d_denoise_corr_device(*head, _dev_ptr(noisy), mp, _dev_ptr(basic), _dev_ptr(denoised), *tail))
+
+    def step1_corr(self, acf, P, noisy, mask, basic, ang_major, awidth, aheight, an, W, H, Cc):
+        """step1() under noise of autocorrelation `acf` (lfbm5d_step1_corr_device; CUDA tensors): see denoise_corr()."""
+        m = _u32(mask)
+        a = _acf49(acf)
+        self._ck(self._L.lfbm5d_step1_corr_device(self._h, a.ctypes.data_as(C.POINTER(C.c_double)), C.byref(P), _dev_ptr(noisy),
+                                                  m.ctypes.data_as(C.POINTER(C.c_uint)), _dev_ptr(basic), ang_major, awidth, aheight, an,
+                                                  int(W), int(H), int(Cc)))
+
+    def step2_corr(self, acf, P, noisy, mask, basic, denoised, ang_major, awidth, aheight, an, W, H, Cc):
+        """step2() under noise of autocorrelation `acf` (lfbm5d_step2_corr_device; CUDA tensors): see denoise_corr()."""
+        m = _u32(mask)
+        a = _acf49(acf)
+        self._ck(self._L.lfbm5d_step2_corr_device(self._h, a.ctypes.data_as(C.POINTER(C.c_double)), C.byref(P), _dev_ptr(noisy),
+                                                  m.ctypes.data_as(C.POINTER(C.c_uint)), _dev_ptr(basic), _dev_ptr(denoised), ang_major,
+                                                  awidth, aheight, an, int(W), int(H), int(Cc)))
+
+    def debug_group_corr(self, acf, *args, **kw):
+        """lfbm5d_debug_group_corr: debug_group() with the variance table of `acf` -- the general kernels' table forms alone."""
+        return self.debug_group(*args, _acf=_acf49(acf), **kw)
 
     def bm3d_lf_views(self, sigma_sai, hard, wien, noisy, mask, basic, denoised, W, H, Cc):
         """bm3d_lf() with a view table (lfbm5d_bm3d_lf_views_device; CUDA tensors): SAI v is filtered with sigma_sai[v] in both steps
@@ -2310,7 +2439,7 @@ class Context:
         self._ck(self._L.lfbm5d_debug_aggregate(self._h, C.byref(a)))
 
     def debug_group(self, step, P, aw, ah, Wb, Hb, C_, noisy, basic, refs, self_idx, self_cnt, best, shape, filt, wgt, aggpos, mask, pst,
-                    *, fill_quirk=1, n_refs_total, ref_begin=0, n_groups=None, filt_sai_stride=0, filt_floats=None, bm3d=0, null=()):
+                    *, fill_quirk=1, n_refs_total, ref_begin=0, n_groups=None, filt_sai_stride=0, filt_floats=None, bm3d=0, null=(), _acf=None):
         """lfbm5d_debug_group: the group launch alone.  noisy, basic, filt, wgt: float32 CUDA tensors; refs, self_idx, self_cnt, best,
         aggpos: int32 CUDA tensors holding the uint32 words; shape: a uint8 CUDA tensor; mask: a sequence of A integers; P: Params.
         filt, wgt and aggpos are written.  A None tensor goes to the library as a NULL pointer (which it refuses, `basic` in step 1
@@ -2360,7 +2489,10 @@ class Context:
         a.bm3d = int(bm3d)
         for name in null:
             setattr(a, name, None)
-        self._ck(self._L.lfbm5d_debug_group(self._h, C.byref(a)))
+        if _acf is not None:   # (debug_group_corr)
+            self._ck(self._L.lfbm5d_debug_group_corr(self._h, C.byref(a), _acf.ctypes.data_as(C.POINTER(C.c_double))))
+        else:
+            self._ck(self._L.lfbm5d_debug_group(self._h, C.byref(a)))
         return text.value.decode(), int(counters[0]), int(counters[1])
 
     def debug_window(self, op, *, list=None, slot_mask=None, **f):
@@ -2503,6 +2635,16 @@ def equalise(noisy, mask, ang_major, awidth, aheight, width, height, chnls, retu
 def denoise_views(sigma_sai, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls, ctx=None):
     """Context.denoise_views on the process-wide context (or `ctx`): the two-step job with one noise level per SAI."""
     return (ctx or _ctx()).denoise_views(sigma_sai, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls)
+
+
+def corr_measure(LF, LF_SAI_mask, width, height, chnls, block=16, fraction=None, ctx=None):
+    """Context.corr_measure on the process-wide context (or `ctx`): the autocorrelation of the noise, measured on the GPU."""
+    return (ctx or _ctx()).corr_measure(LF, LF_SAI_mask, width, height, chnls, block, fraction)
+
+
+def denoise_corr(acf, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls, ctx=None):
+    """Context.denoise_corr on the process-wide context (or `ctx`): the two-step job under spatially correlated noise."""
+    return (ctx or _ctx()).denoise_corr(acf, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls)
 
 
 def denoise_pg(model, P1, P2, noisy, mask, basic, denoised, ang_major, awidth, aheight, an1, an2, W, H, chnls, ctx=None):

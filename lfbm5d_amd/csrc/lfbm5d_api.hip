@@ -88,6 +88,7 @@ void lfbm5d_destroy(lfbm5d_ctx* c) {
     c->photo.table.release(); c->photo.sweep_table.release(); c->photo.stats.release(); c->photo.pred.release(); c->photo.disp.release(); c->photo.x.release();
     c->repair.valid.release(); c->repair.mid.release(); c->repair.rem.release(); c->repair.tiles.release(); c->repair.table.release();
     c->repair.stats.release(); c->repair.codes.release(); c->repair.host.release();
+    c->corr_store.dev.release(); c->corrm.lags.release(); c->corrm.score.release(); c->corrm.part.release();
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     if (c->h_small) (void)hipHostFree(c->h_small);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -520,7 +521,7 @@ int run_bm3d_lf(lfbm5d_ctx* c, const lfbm5d_bm3d_params* Hd, const lfbm5d_bm3d_p
         std::string e;
         lfbm5d_ctx* x = new_ctx(c->device, e);
         if (!x) return fail(c, "lane context: " + e);
-        x->opt = c->opt;
+        x->opt = c->opt; x->corr = c->corr;
         c->lanes.push_back(x);
     }
     HIPCK(c, hipStreamSynchronize(c->stream));   /* the caller's stream has produced d_noisy */
@@ -775,7 +776,7 @@ int lfbm5d_debug_group(lfbm5d_ctx* c, const lfbm5d_group_debug* d) {
     if (launch_patches * (d->filt_sai_stride ? 1u : A) * patch >= (1ull << 32)) return fail(c, "debug_group: patch offsets beyond 32 bits");
     if (d->image_floats < (u64)A * C * plane) return fail(c, "debug_group: noisy / basic are smaller than [A][C][Hb][Wb]");
     if (d->table_words < (u64)A * plane) return fail(c, "debug_group: best / shape are smaller than [A][Wb*Hb]");
-    if (d->filt_sai_stride && (A == 9 || A == 1) && !(c->opt->kernels & kOptGroupGeneric))
+    if (d->filt_sai_stride && (A == 9 || A == 1) && !(c->opt->kernels & kOptGroupGeneric) && !c->corr->n)
         return fail(c, "debug_group: SAI-major filt is written by the general kernels only (wider windows, option group_generic)");
     if (d->filt_sai_stride ? (d->filt_sai_stride < launch_patches * patch || d->filt_floats < d->filt_sai_stride * A)
                            : d->filt_floats < launch_patches * A * patch)
@@ -854,7 +855,7 @@ int lfbm5d_debug_group(lfbm5d_ctx* c, const lfbm5d_group_debug* d) {
     ga.filt_sai_stride = d->filt_sai_stride;
     ga.filt = d->filt - (size_t)d->ref_begin * (d->filt_sai_stride ? per_group / A : per_group);
     std::string trace;
-    hipError_t e = launch_group(s, ga, &trace);
+    hipError_t e = launch_group(s, ga, &trace, corr_table_of_pass(c, ga));
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e == hipSuccess) e = hipMemcpy(after, d_counters, sizeof(after), hipMemcpyDeviceToHost);
     const hipError_t e_back = hipMemcpy(d_counters, before, sizeof(before), hipMemcpyHostToDevice);   /* also when the launch failed */

@@ -119,6 +119,18 @@
  *                     models and refinement steps assume one sigma) it is an error, and so is any other value.  With a ground truth
  *                     LFBM5D_VIEW_SIGMA_ADD=<edge> (0 < edge <= 1) synthesises noise of sigma / g_v on view v in place of uniform
  *                     noise, g the vignette of LFBM5D_EQUALISE_ADD: what a devignetted capture carries.  Unset, the output is unchanged;
+ *   LFBM5D_NOISE_CORR=auto | <file> | kernel:<file>   spatially correlated noise (denoise_corr_LF, run_bm5d.h; include/lfbm5d_corr.h): every
+ *                     2-D coefficient is thresholded and Wiener-shrunk with its own variance factor under the noise's autocorrelation,
+ *                     both steps as one job on the general group kernels (slower than the dedicated ones).  `auto` measures the
+ *                     autocorrelation on the flattest blocks of the noisy light field (corr_measure_LF); <file> holds it as 49 numbers
+ *                     (lags -3..3 row-major, 1 at lag 0); kernel:<file> holds the taps of the filter the noise went through, one row
+ *                     per line, up to 7 x 7.  The command's sigma stays the marginal level.  Prints `Noise correlation: lag-1 <h> <v>,
+ *                     variance factors <min>..<max> (step 1), <min>..<max> (step 2), <n> clamped; from <estimate|file|kernel>`.
+ *                     Together with LFBM5D_SIGMA=auto|poisson*, LFBM5D_CLIP, LFBM5D_VIEW_SIGMA, LFBM5D_REPAIR, LFBM5D_DEFECTS,
+ *                     LFBM5D_MISSING, LFBM5D_DETECT or LFBM5D_EQUALISE it is an error, and LFBM3Ddenoising refuses it (the per-SAI BM3D
+ *                     flavour is not covered).  With a ground truth LFBM5D_NOISE_CORR_ADD=<file> (taps as for kernel:) filters the
+ *                     synthesised noise by those taps, normalised to unit energy and periodic at the image border, so that its
+ *                     marginal level stays sigma.  Unset, the output is unchanged;
  *   LFBM5D_REPORT_SSIM=1  the average SSIM next to every average PSNR on stdout and an SSIM block behind every PSNR block of the
  *                     results file, computed on the GPU on the images as the files hold them (cli_quality.h); any other value is an
  *                     error; unset, the output is unchanged.
@@ -135,6 +147,7 @@
 #include <sys/time.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <cctype>
 #include <cmath>
 #include <cstdio>
@@ -805,6 +818,116 @@ bool view_sigma_mode(int& mode, double& add, int smode, bool gt) {
     return true;
 }
 
+/* taps of LFBM5D_NOISE_CORR=kernel:<file> / LFBM5D_NOISE_CORR_ADD=<file>: one row per line, 1..7 rows of 1..7 numbers, all rows as long */
+bool read_taps(const char* var, const char* path, vector<double>& g, unsigned& gh, unsigned& gw) {
+    ifstream f(path);
+    if (!f) { cout << var << ": cannot read \"" << path << "\"" << endl; return false; }
+    g.clear(); gh = gw = 0;
+    string line;
+    while (getline(f, line)) {
+        istringstream ls(line);
+        vector<double> row;
+        string tok;
+        while (ls >> tok) {
+            char* end = nullptr;
+            const double v = strtod(tok.c_str(), &end);
+            if (end == tok.c_str() || *end || !std::isfinite(v)) { cout << var << ": \"" << tok << "\" in \"" << path << "\" is not a finite number" << endl; return false; }
+            row.push_back(v);
+        }
+        if (row.empty()) continue;
+        if (gh && row.size() != gw) { cout << var << ": the rows of \"" << path << "\" differ in length" << endl; return false; }
+        gw = (unsigned)row.size(); gh++;
+        g.insert(g.end(), row.begin(), row.end());
+    }
+    if (gh < 1 || gh > 7 || gw < 1 || gw > 7) { cout << var << ": \"" << path << "\" must hold 1..7 rows of 1..7 taps" << endl; return false; }
+    return true;
+}
+
+/* LFBM5D_NOISE_CORR / LFBM5D_NOISE_CORR_ADD: mode 0 when unset, 1 = auto, 2 = <file>, 3 = kernel:<file>; acf filled for 2 and 3; add_taps
+ * empty when unset; false (message printed) on a malformed value, a combination the header comment excludes, or LFBM5D_NOISE_CORR_ADD
+ * without a ground truth */
+bool noise_corr_mode(int& mode, vector<double>& acf, vector<double>& add_taps, unsigned& add_h, unsigned& add_w, int smode, bool gt, bool bm3d) {
+    mode = 0; add_h = add_w = 0;
+    if (const char* e = env("LFBM5D_NOISE_CORR")) {
+        if (bm3d) { cout << "LFBM5D_NOISE_CORR is not supported by LFBM3Ddenoising (the per-SAI BM3D flavour has no variance table)" << endl; return false; }
+        if (smode != 0) { cout << "LFBM5D_NOISE_CORR cannot be combined with LFBM5D_SIGMA (the command's sigma is the marginal level of the correlated noise)" << endl; return false; }
+        for (const char* other : {"LFBM5D_CLIP", "LFBM5D_VIEW_SIGMA", "LFBM5D_REPAIR", "LFBM5D_DEFECTS", "LFBM5D_MISSING", "LFBM5D_DETECT", "LFBM5D_EQUALISE"})
+            if (env(other)) { cout << "LFBM5D_NOISE_CORR cannot be combined with " << other << " (their stages assume white noise)" << endl; return false; }
+        if (!*e) { cout << "LFBM5D_NOISE_CORR must be \"auto\", a file of 49 numbers or kernel:<file of taps>, or unset; got \"\"" << endl; return false; }
+        if (!strcmp(e, "auto")) mode = 1;
+        else if (!strncmp(e, "kernel:", 7)) {
+            vector<double> g; unsigned gh, gw;
+            if (!read_taps("LFBM5D_NOISE_CORR", e + 7, g, gh, gw)) return false;
+            acf.assign(49, 0.0);
+            if (lfbm5d_corr_from_kernel(g.data(), gh, gw, acf.data())) { cout << "LFBM5D_NOISE_CORR: " << lfbm5d_corr_error() << endl; return false; }
+            mode = 3;
+        } else {
+            ifstream f(e);
+            if (!f) { cout << "LFBM5D_NOISE_CORR must be \"auto\", a file of 49 numbers or kernel:<file of taps>, or unset; cannot read \"" << e << "\"" << endl; return false; }
+            acf.clear();
+            string tok;
+            while (f >> tok) {
+                char* end = nullptr;
+                const double v = strtod(tok.c_str(), &end);
+                if (end == tok.c_str() || *end) { cout << "LFBM5D_NOISE_CORR: \"" << tok << "\" in \"" << e << "\" is not a number" << endl; return false; }
+                acf.push_back(v);
+            }
+            if (acf.size() != 49) { cout << "LFBM5D_NOISE_CORR: \"" << e << "\" must hold 49 numbers (the lags -3..3 row-major), it holds " << acf.size() << endl; return false; }
+            if (lfbm5d_corr_check(acf.data())) { cout << "LFBM5D_NOISE_CORR: " << lfbm5d_corr_error() << endl; return false; }
+            mode = 2;
+        }
+    }
+    if (const char* e = env("LFBM5D_NOISE_CORR_ADD")) {
+        if (bm3d) { cout << "LFBM5D_NOISE_CORR_ADD is not supported by LFBM3Ddenoising" << endl; return false; }
+        if (!gt) { cout << "LFBM5D_NOISE_CORR_ADD needs a source light field to synthesise the noisy one from" << endl; return false; }
+        if (smode >= 2) { cout << "LFBM5D_NOISE_CORR_ADD cannot be combined with LFBM5D_SIGMA=poisson (the synthesised noise is Gaussian)" << endl; return false; }
+        if (!read_taps("LFBM5D_NOISE_CORR_ADD", e, add_taps, add_h, add_w)) return false;
+        double en = 0.0;
+        for (double v : add_taps) en += v * v;
+        if (!(en > 0.0)) { cout << "LFBM5D_NOISE_CORR_ADD: the taps are all zero" << endl; return false; }
+        for (double& v : add_taps) v /= sqrt(en);
+    }
+    return true;
+}
+
+/* LFBM5D_NOISE_CORR_ADD: the synthesised noise (noisy - clean) of every plane filtered by the unit-energy taps, periodic at the border */
+void correlate_noise_LF(const vector<vector<float> >& LF, const vector<unsigned>& mask, vector<vector<float> >& LF_noisy, unsigned W, unsigned H,
+                        unsigned C, const vector<double>& g, unsigned gh, unsigned gw) {
+    parallel_sais((unsigned)LF.size(), [&](unsigned st) {
+        if (!mask[st]) return true;
+        vector<double> n((size_t)W * H);
+        for (unsigned c = 0; c < C; c++) {
+            const size_t o = (size_t)c * W * H;
+            for (size_t q = 0; q < n.size(); q++) n[q] = (double)LF_noisy[st][o + q] - (double)LF[st][o + q];
+            for (unsigned y = 0; y < H; y++)
+                for (unsigned x = 0; x < W; x++) {
+                    double z = 0.0;
+                    for (unsigned i = 0; i < gh; i++)
+                        for (unsigned j = 0; j < gw; j++)
+                            z += g[i * gw + j] * n[(size_t)((y + i + H - gh / 2) % H) * W + (x + j + W - gw / 2) % W];
+                    LF_noisy[st][o + (size_t)y * W + x] = LF[st][o + (size_t)y * W + x] + (float)z;
+                }
+        }
+        return true;
+    });
+}
+
+/* LFBM5D_NOISE_CORR: the line that reports the autocorrelation the filter ran with and the variance tables of both steps */
+bool print_noise_corr(const vector<double>& acf, int mode, const int* t2, const unsigned* k) {
+    float lo[2] = {1.0f, 1.0f}, hi[2] = {1.0f, 1.0f};
+    unsigned clamped = 0;
+    for (int i = 0; i < 2; i++) {
+        vector<float> v((size_t)k[i] * k[i]);
+        unsigned cl = 0;
+        if (lfbm5d_corr_table(acf.data(), (unsigned)t2[i], k[i], nullptr, v.data(), &cl)) { cout << "LFBM5D_NOISE_CORR: " << lfbm5d_corr_error() << endl; return false; }
+        lo[i] = *std::min_element(v.begin(), v.end()); hi[i] = *std::max_element(v.begin(), v.end());
+        clamped += cl;
+    }
+    cout << "Noise correlation: lag-1 " << acf[3 * 7 + 4] << " " << acf[4 * 7 + 3] << ", variance factors " << lo[0] << ".." << hi[0] << " (step 1), "
+         << lo[1] << ".." << hi[1] << " (step 2), " << clamped << " clamped; from " << (mode == 1 ? "estimate" : mode == 2 ? "file" : "kernel") << endl;
+    return true;
+}
+
 /* the smooth vignette of LFBM5D_EQUALISE_ADD and LFBM5D_VIEW_SIGMA_ADD: view (s, t) gets 1 - (1 - edge) rho^2, rho its angular distance from
  * the centre, 1 at the corners */
 double vignette_gain(unsigned s, unsigned t, unsigned aw, unsigned ah, double edge) {
@@ -1023,6 +1146,7 @@ bool estimate_sigma_LF(const vector<vector<float> >& LF_noisy, const vector<unsi
 } // namespace
 
 #ifdef LFBM3D_CLI
+constexpr bool NC_BM3D = true;
 int main(int argc, char** argv) {
     cout << "*********************************************************************************************************************" << endl;
     cout << "********************************************              START               ***************************************" << endl;
@@ -1079,6 +1203,8 @@ int main(int argc, char** argv) {
     vector<double> eq_gains;
     int vs_mode = 0; double vs_add = 0.0;
     if (!view_sigma_mode(vs_mode, vs_add, smode, gt)) return EXIT_FAILURE;
+    int nc_mode = 0; vector<double> nc_acf, nc_add; unsigned nc_add_h = 0, nc_add_w = 0;
+    if (!noise_corr_mode(nc_mode, nc_acf, nc_add, nc_add_h, nc_add_w, smode, gt, NC_BM3D)) return EXIT_FAILURE;
     unsigned dsteps = 1;
     if (!disparity_steps_mode(dsteps, detect || !missing.empty() || eq_mode)) return EXIT_FAILURE;
     float occl = 0.0f;
@@ -1229,6 +1355,7 @@ int main(int argc, char** argv) {
     return EXIT_SUCCESS;
 }
 #else
+constexpr bool NC_BM3D = false;
 int main(int argc, char** argv) {
     cout << "*********************************************************************************************************************" << endl;
     cout << "********************************************              START               ***************************************" << endl;
@@ -1284,6 +1411,8 @@ int main(int argc, char** argv) {
     vector<double> eq_gains;
     int vs_mode = 0; double vs_add = 0.0;
     if (!view_sigma_mode(vs_mode, vs_add, smode, gt)) return EXIT_FAILURE;
+    int nc_mode = 0; vector<double> nc_acf, nc_add; unsigned nc_add_h = 0, nc_add_w = 0;
+    if (!noise_corr_mode(nc_mode, nc_acf, nc_add, nc_add_h, nc_add_w, smode, gt, NC_BM3D)) return EXIT_FAILURE;
     unsigned dsteps = 1;
     if (!disparity_steps_mode(dsteps, detect || !missing.empty() || eq_mode)) return EXIT_FAILURE;
     float occl = 0.0f;
@@ -1308,6 +1437,7 @@ int main(int argc, char** argv) {
         t = now_s();
         const vector<double> vs_sigmas = vs_add > 0.0 ? vignette_sigmas(sigma, ang_major, aw, ah, vs_add) : vector<double>();
         add_noise_LF(LF, mask, LF_noisy, sigma, smode == 3 || smode == 5 ? pg : nullptr, vs_add > 0.0 ? &vs_sigmas : nullptr);
+        if (!nc_add.empty()) correlate_noise_LF(LF, mask, LF_noisy, W, H, C, nc_add, nc_add_h, nc_add_w);
         cout << "done in " << now_s() - t << "s." << endl;
         if (eq_add > 0.0) add_vignette_LF(LF_noisy, mask, ang_major, aw, ah, eq_add);
         if (clip_add) clip_round_LF(LF_noisy, mask, clip_lo, clip_hi);
@@ -1384,7 +1514,7 @@ int main(int argc, char** argv) {
      * inverse(estimate) between the calls: the two differ (0.015 dB on the test light field) because the reference's colour matrices are not
      * inverses of each other */
     const char* one_job_s = env("LFBM5D_ONE_JOB");
-    const bool one_job = smode >= 2 || clip_on || vs_mode || (one_job_s && *one_job_s && *one_job_s != '0');   /* the Poisson-Gaussian, the clipped and the per-view path are one job */
+    const bool one_job = smode >= 2 || clip_on || vs_mode || nc_mode || (one_job_s && *one_job_s && *one_job_s != '0');   /* the Poisson-Gaussian, the clipped and the per-view path are one job */
     cout << endl << " ---> Running LFBM5D filter <--- " << endl << endl << (one_job ? "Steps 1 and 2 running as one job..." : "Step 1 running...") << endl;
     const double tb = now_s();
     double t1 = now_s();
@@ -1415,6 +1545,16 @@ int main(int argc, char** argv) {
                              t5[1], cs, nb_threads) != EXIT_SUCCESS) return EXIT_FAILURE;
         job = now_s() - t1;
         print_view_sigmas(table, mask, window_sigmas, vs_mode == 1);
+    } else if (nc_mode) {
+        if (nc_mode == 1) {   /* the blind shape from the noisy light field; the command's sigma stays the marginal level */
+            double s_est = 0.0;
+            if (corr_measure_LF(LF_noisy, mask, W, H, C, 0, 0.0, nc_acf, s_est) != EXIT_SUCCESS) return EXIT_FAILURE;
+        }
+        if (denoise_corr_LF(nc_acf, sigma, lambda, LF_noisy, mask, LF_basic, LF_den, ang_major, aw, ah, anH, anW, W, H, C, N[0], nSim[0], nDisp[0],
+                            k[0], p[0], sd[0] != 0, t2[0], t4[0], t5[0], N[1], nSim[1], nDisp[1], k[1], p[1], sd[1] != 0, t2[1], t4[1], t5[1], cs,
+                            nb_threads) != EXIT_SUCCESS) return EXIT_FAILURE;
+        job = now_s() - t1;
+        if (!print_noise_corr(nc_acf, nc_mode, t2, k)) return EXIT_FAILURE;
     } else if (one_job) {
         if (run_bm5d(sigma, lambda, LF_noisy, mask, LF_basic, LF_den, ang_major, aw, ah, anH, anW, W, H, C, N[0], nSim[0], nDisp[0], k[0], p[0],
                      sd[0] != 0, t2[0], t4[0], t5[0], N[1], nSim[1], nDisp[1], k[1], p[1], sd[1] != 0, t2[1], t4[1], t5[1], cs, nb_threads) != EXIT_SUCCESS)

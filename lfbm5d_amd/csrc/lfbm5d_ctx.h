@@ -186,6 +186,12 @@ struct lfbm5d_ctx {
      * unsound positions per tile, the source lists with the float tables and the missing list, the counters, the code planes when the
      * caller wants none, the host form's flag, code and disparity planes */
     struct RepairBufs { DevBuf valid, mid, rem, tiles, table, stats, codes, host; } repair;
+    /* correlated noise (include/lfbm5d_corr.h, lfbm5d_corr.hip).  The variance tables of the job that is running, one per step
+     * ([2][k*k] floats each: s, then v; `n` of them, found by the pass's tau_2D and k), set and cleared by the lfbm5d_*_corr_* entry
+     * points like views.table; lane contexts point at their parent's.  The measurement's per-block lag sums, scores and chunk sums. */
+    struct CorrTables { unsigned n = 0, tau2[2] = {0, 0}, k[2] = {0, 0}; size_t off[2] = {0, 0}; DevBuf dev; };
+    CorrTables corr_store; CorrTables* corr = &corr_store;
+    struct CorrBufs { DevBuf lags, score, part; } corrm;
     /* window lanes (run_graph; the per-SAI BM3D steps): extra contexts on the same device, each with its own stream, window
      * buffers and per-pass work buffers; owned by this context */
     std::vector<lfbm5d_ctx*> lanes;
@@ -230,6 +236,8 @@ int validate(lfbm5d_ctx* c, int step, const lfbm5d_params* P, unsigned aw, unsig
 int check_padding(lfbm5d_ctx* c, unsigned W, unsigned H, unsigned nHW);
 /* the part of GroupArgs that follows from the pass's parameters (thresholds, lambda rule, sigma table, options, scratch) */
 int group_args_of_pass(lfbm5d_ctx* c, lfbm5d::GroupArgs& ga, const lfbm5d_params* P);
+/* the variance table (include/lfbm5d_corr.h) launch_group takes with these arguments; NULL when the running job has none */
+const float* corr_table_of_pass(lfbm5d_ctx* c, const lfbm5d::GroupArgs& ga);
 int fold_counters(lfbm5d_ctx* c, const lfbm5d_params* P, unsigned A, unsigned C, int step, int slot = 0);
 /* A lane's (or an emulated rank's) counters and event times into the job's context: every field a pass adds to.  Not added:
  * windows, messages, lane_windows -- the job counts those on its own context as it enqueues, a lane's are zero; ms_comm -- the

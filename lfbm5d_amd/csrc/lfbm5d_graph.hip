@@ -283,7 +283,7 @@ struct GraphRun {
             std::string e;
             lfbm5d_ctx* x = new_ctx(c->device, e);
             if (!x) return fail(c, "lane context: " + e);
-            x->opt = c->opt;
+            x->opt = c->opt; x->corr = c->corr;
             c->lanes.push_back(x);
         }
         ipc = c->ipc && nranks > 1 && !emulate;

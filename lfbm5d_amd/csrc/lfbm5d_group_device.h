@@ -35,6 +35,12 @@ inline void group_note(std::string* trace, const char* name) {
 }
 #define LFBM5D_LAUNCH(trace, kern, ...) do { group_note(trace, #kern); hipLaunchKernelGGL(kern, __VA_ARGS__); } while (0)
 hipError_t prepare_group_slab();
+/* the general kernels (lfbm5d_group_generic.hip) and their variance-table forms (lfbm5d_corr.hip, include/lfbm5d_corr.h) */
+constexpr int kGenericLdsLimit = 160 * 1024 - 8192;   /* dynamic LDS of k_group: its static part (positions of up to 32 x 49 patches) is 6.3 KB */
+constexpr unsigned kBigBlocks = 1024;   /* persistent workgroups of k_group_big (four per CU) */
+size_t group_tmp_floats(const GroupArgs& a);
+hipError_t launch_group_corr(hipStream_t s, const GroupArgs& a, const float* tab, std::string* trace);
+hipError_t prepare_group_corr();
 bool group_uses_slab(const GroupArgs& a);
 size_t group_slab_scratch_bytes(const GroupArgs& a);
 hipError_t prepare_group_ht();
@@ -818,9 +824,11 @@ template <int NS, class T> __device__ __forceinline__ void dct5_inv(T* v, TbPtr 
 /* 5th-dimension transform + shrinkage + inverse of one (st, pq) fibre held in registers.
  * o: noisy fibre, e: pilot fibre (Wiener); the filtered fibre is returned in o (HT) / e (Wiener).
  * HT: core:2408-2505 / :2281-2391; Wiener: core:2826-2925 / :2706-2810. */
-template <int NS, int STEP>
+/* CORR (include/lfbm5d_corr.h): T and sig2 carry the fibre's variance factor already; vw is that factor, the weight of a survivor
+ * (hard threshold) or of a Wiener value in the group weight, in place of 1. */
+template <int NS, int STEP, bool CORR = false>
 __device__ __forceinline__ void shrink_fibre(float* o, float* e, unsigned tau5, float T, float sig2,
-                                             bool in_shape, float& wacc, TbPtr tb) {
+                                             bool in_shape, float& wacc, TbPtr tb, float vw = 1.0f) {
     const bool haar = tau5 == 9, dct = tau5 == 5;
     if (dct) { dct5_fwd<NS>(o, tb); if (STEP == 2) dct5_fwd<NS>(e, tb); }
     else if (NS > 1) {
@@ -833,7 +841,7 @@ __device__ __forceinline__ void shrink_fibre(float* o, float* e, unsigned tau5, 
             const float Th = haar ? T : (dct ? T * 2.0f : T * sqrtf((float)NS));
 #pragma unroll
             for (int n = 0; n < NS; n++) {
-                if (fabsf(o[n]) > Th) wacc += 1.0f; else o[n] = 0.0f;
+                if (fabsf(o[n]) > Th) wacc += CORR ? vw : 1.0f; else o[n] = 0.0f;
             }
         } else {
             const float hc = 1.0f / (float)NS;
@@ -843,7 +851,7 @@ __device__ __forceinline__ void shrink_fibre(float* o, float* e, unsigned tau5, 
                 float value = plain ? e[n] * e[n] : e[n] * e[n] * hc;
                 value = __fdiv_rn(value, value + sig2);
                 e[n] = plain ? o[n] * value : o[n] * value * hc;
-                wacc += value;
+                wacc += CORR ? value * vw : value;
             }
         }
     }
@@ -863,10 +871,10 @@ __device__ __forceinline__ void shrink_fibre(float* o, float* e, unsigned tau5, 
 }
 
 /* the same on a fibre stored in the LDS stack */
-template <int NS, int STEP>
+template <int NS, int STEP, bool CORR = false>
 __device__ __forceinline__ void filter5(float* S0, float* S1, int base, int stride, unsigned tau5,
                                         float T, float sig2, bool in_shape, float& wacc, float& s1, float& s2,
-                                        TbPtr tb) {
+                                        TbPtr tb, float vw = 1.0f) {
     float o[NS], e[NS];
 #pragma unroll
     for (int n = 0; n < NS; n++) o[n] = S0[base + n * stride];
@@ -874,7 +882,7 @@ __device__ __forceinline__ void filter5(float* S0, float* S1, int base, int stri
 #pragma unroll
         for (int n = 0; n < NS; n++) e[n] = S1[base + n * stride];
     }
-    shrink_fibre<NS, STEP>(o, e, tau5, T, sig2, in_shape, wacc, tb);
+    shrink_fibre<NS, STEP, CORR>(o, e, tau5, T, sig2, in_shape, wacc, tb, vw);
     float* r = STEP == 1 ? o : e;
     float* dst = STEP == 1 ? S0 : S1;
 #pragma unroll

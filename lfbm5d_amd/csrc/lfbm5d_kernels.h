@@ -384,7 +384,8 @@ hipError_t launch_stereo_argmin(hipStream_t s, const float* tables, const unsign
                                 unsigned* best, unsigned char* shape);
 hipError_t prepare_group_kernels();   /* once per device: LDS limits of the group kernels */
 /* trace (lfbm5d_debug_group; NULL in a pass): receives the names of the kernels launched, joined by + */
-hipError_t launch_group(hipStream_t s, const GroupArgs& a, std::string* trace = nullptr);
+/* corr_tab (include/lfbm5d_corr.h; NULL: none): the pass's variance table [2][k*k] on the device; a.opt must then carry group_generic */
+hipError_t launch_group(hipStream_t s, const GroupArgs& a, std::string* trace = nullptr, const float* corr_tab = nullptr);
 size_t group_lds_bytes(const GroupArgs& a);
 /* HBM scratch (bytes) launch_group needs for this configuration: 0 unless the generic path's stacks exceed the LDS */
 size_t group_scratch_bytes(const GroupArgs& a);

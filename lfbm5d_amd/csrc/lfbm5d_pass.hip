@@ -208,11 +208,24 @@ int group_args_of_pass(lfbm5d_ctx* c, GroupArgs& ga, const lfbm5d_params* P) {
         }
     }
     ga.opt = c->opt->kernels;
+    if (c->corr->n) {   /* a job with variance tables (include/lfbm5d_corr.h): the general kernels, as under option group_generic */
+        if (ga.bm3d) return fail(c, "correlated noise: the per-SAI BM3D flavour is not covered (include/lfbm5d_corr.h)");
+        if (!corr_table_of_pass(c, ga)) return fail(c, "correlated noise: the job holds no variance table for this pass's tau_2D and patch size");
+        ga.opt |= kOptGroupGeneric;
+    }
     if (const size_t sb = group_scratch_bytes(ga)) {   /* generic path with stacks beyond the 160 KiB LDS: HBM scratch slices */
         HIPCK(c, c->gscratch.reserve(sb));
         ga.scratch = c->gscratch.as<float>(); ga.scratch_floats = sb / sizeof(float);
     }
     return 0;
+}
+
+/* The variance table [2][k*k] (device) of the running job for this pass's 2-D transform and patch size; NULL: the job has none. */
+const float* corr_table_of_pass(lfbm5d_ctx* c, const GroupArgs& ga) {
+    const lfbm5d_ctx::CorrTables& T = *c->corr;
+    for (unsigned i = 0; i < T.n; i++)
+        if (T.tau2[i] == ga.tau2 && T.k[i] == ga.k) return T.dev.as<float>() + T.off[i];
+    return nullptr;
 }
 
 /* ------------------------------------------------------------------------------------------ */
@@ -519,6 +532,7 @@ int pass_impl(lfbm5d_ctx* c, int step, const lfbm5d_params* P, unsigned aw, unsi
     ga.mask_bits = mask_bits; ga.proc_bits = proc_bits;
     ga.step = step; ga.fill_quirk = centre ? 1u : 0u; ga.bm3d = bm3d ? 1u : 0u;
     if (group_args_of_pass(c, ga, P)) return 1;
+    const float* const corr_tab = corr_table_of_pass(c, ga);
     AggArgs aa;
     std::memset(&aa, 0, sizeof(aa));
     aa.num = d_num; aa.den = d_den; aa.wgt = ga.wgt; aa.aggpos = ga.aggpos; aa.n_refs_total = R; aa.refs = ga.refs;
@@ -539,7 +553,7 @@ int pass_impl(lfbm5d_ctx* c, int step, const lfbm5d_params* P, unsigned aw, unsi
         ga.filt_sai_stride = aa.filt_sai_stride = sai_major ? (unsigned long long)n_groups * (per_group / A) : 0ull;
         ga.filt = c->filt.as<float>() - (size_t)ref_begin * per_group_bias;   /* (the group kernels index filt by absolute group number) */
         aa.filt = c->filt.as<float>(); aa.filt_bytes = (unsigned long long)n_groups * per_group * sizeof(float);
-        if (n_groups) HIPCK(c, launch_group(s, ga));
+        if (n_groups) HIPCK(c, launch_group(s, ga, nullptr, corr_tab));
         HIPCK(c, hipEventRecord(pe.e[2], s));
         if (n_groups) HIPCK(c, launch_aggregate(s, aa));
         HIPCK(c, hipEventRecord(pe.e[3], s));
@@ -551,7 +565,7 @@ int pass_impl(lfbm5d_ctx* c, int step, const lfbm5d_params* P, unsigned aw, unsi
             ga.filt_sai_stride = aa.filt_sai_stride = sai_major ? (unsigned long long)nb * (per_group / A) : 0ull;
             ga.ref_begin = b0; ga.n_groups = nb; ga.filt = c->filt.as<float>() - (size_t)b0 * per_group_bias;
             aa.ref_begin = b0; aa.n_groups = nb; aa.filt = c->filt.as<float>(); aa.filt_bytes = (unsigned long long)nb * per_group * sizeof(float);
-            HIPCK(c, launch_group(s, ga));
+            HIPCK(c, launch_group(s, ga, nullptr, corr_tab));
             if (first) HIPCK(c, hipEventRecord(pe.e[2], s));
             first = false;
             HIPCK(c, launch_aggregate(s, aa));

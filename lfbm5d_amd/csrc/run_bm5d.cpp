@@ -1145,6 +1145,63 @@ int denoise_views_LF(std::vector<double>& sigma_sai, std::vector<float>& window_
     return EXIT_SUCCESS;
 }
 
+/* run_bm5d under spatially correlated noise (include/lfbm5d_corr.h): the caller's vectors, one pointer per SAI */
+int denoise_corr_LF(const std::vector<double>& acf, const float sigma, const float lambdaHard5D, std::vector<std::vector<float> >& LF_noisy,
+                    std::vector<unsigned>& LF_SAI_mask, std::vector<std::vector<float> >& LF_basic, std::vector<std::vector<float> >& LF_denoised,
+                    const unsigned ang_major, const unsigned awidth, const unsigned aheight, const unsigned anHard, const unsigned anWien,
+                    const unsigned width, const unsigned height, const unsigned chnls, const unsigned NHard, const unsigned nSimHard,
+                    const unsigned nDispHard, const unsigned kHard, const unsigned pHard, const bool useSDHard, const unsigned tau_2D_hard,
+                    unsigned tau_4D_hard, const unsigned tau_5D_hard, const unsigned NWien, const unsigned nSimWien, const unsigned nDispWien,
+                    const unsigned kWien, const unsigned pWien, const bool useSDWien, const unsigned tau_2D_wien, unsigned tau_4D_wien,
+                    const unsigned tau_5D_wien, const unsigned color_space, const unsigned nb_threads) {
+    const unsigned asize = awidth * aheight;
+    if (LF_noisy.size() != asize || LF_SAI_mask.size() != asize || acf.size() != 49) {
+        std::cout << "denoise_corr_LF: light field and mask must hold awidth*aheight SAIs, the autocorrelation 49 values" << std::endl;
+        return EXIT_FAILURE;
+    }
+    lfbm5d_ctx* ctx = context();
+    if (!ctx) return EXIT_FAILURE;
+    lfbm5d_set_tiles(ctx, tiles_for(nb_threads));
+    if (LF_basic.size() != asize) LF_basic.resize(asize);
+    if (LF_denoised.size() != asize) LF_denoised.resize(asize);
+    const size_t img = (size_t)width * height * chnls;
+    const std::vector<float*> noisy = sai_ptrs(LF_noisy, LF_SAI_mask, img, false), basic = sai_ptrs(LF_basic, LF_SAI_mask, img, true),
+                              den = sai_ptrs(LF_denoised, LF_SAI_mask, img, true);
+    if (!inputs_ok(noisy, LF_SAI_mask, "denoise_corr_LF")) return EXIT_FAILURE;
+    const lfbm5d_params P1 = make(sigma, lambdaHard5D, NHard, nSimHard, nDispHard, kHard, pHard, useSDHard, tau_2D_hard, tau_4D_hard, tau_5D_hard, color_space);
+    const lfbm5d_params P2 = make(sigma, 0.0f, NWien, nSimWien, nDispWien, kWien, pWien, useSDWien, tau_2D_wien, tau_4D_wien, tau_5D_wien, color_space);
+    if (lfbm5d_denoise_corr_host_sai(ctx, acf.data(), &P1, &P2, noisy.data(), LF_SAI_mask.data(), basic.data(), den.data(), ang_major, awidth,
+                                     aheight, anHard, anWien, width, height, chnls) != 0) {
+        std::cout << "LFBM5D GPU backend: " << lfbm5d_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+    }
+    return EXIT_SUCCESS;
+}
+
+int corr_measure_LF(const std::vector<std::vector<float> >& LF, const std::vector<unsigned>& LF_SAI_mask, const unsigned width,
+                    const unsigned height, const unsigned chnls, const unsigned block, const double fraction, std::vector<double>& acf,
+                    double& sigma) {
+    if (LF.size() != LF_SAI_mask.size()) {
+        std::cout << "corr_measure_LF: light field and mask must hold the same number of SAIs" << std::endl;
+        return EXIT_FAILURE;
+    }
+    lfbm5d_ctx* ctx = context();
+    if (!ctx) return EXIT_FAILURE;
+    const size_t img = (size_t)width * height * chnls;
+    std::vector<const float*> p(LF.size(), nullptr);
+    for (size_t st = 0; st < LF.size(); st++) if (LF_SAI_mask[st] && LF[st].size() == img) p[st] = LF[st].data();
+    for (size_t st = 0; st < LF.size(); st++)
+        if (LF_SAI_mask[st] && !p[st]) { std::cout << "corr_measure_LF: a non-empty SAI does not hold width*height*chnls values" << std::endl; return EXIT_FAILURE; }
+    lfbm5d_corr_estimate r;
+    if (lfbm5d_corr_measure_host_sai(ctx, p.data(), LF_SAI_mask.data(), (unsigned)LF.size(), width, height, chnls, block, fraction, &r) != 0) {
+        std::cout << "LFBM5D GPU backend: " << lfbm5d_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+    }
+    acf.assign(r.acf, r.acf + 49);
+    sigma = r.sigma;
+    return EXIT_SUCCESS;
+}
+
 int views_from_gains(const double sigma, const std::vector<double>& gains, const unsigned chnls, const std::vector<unsigned>& LF_SAI_mask,
                      std::vector<double>& sigma_sai) {
     const size_t asize = LF_SAI_mask.size();

@@ -610,6 +610,49 @@ int denoise_views_LF(
 ,   const unsigned nb_threads
 );
 
+//! Spatially correlated noise -- not in the reference: run_bm5d under noise of autocorrelation acf (49 doubles: the lags -3..3 row-major,
+//! 1 at lag 0; include/lfbm5d_corr.h; lfbm5d_denoise_corr_host_sai): every 2-D coefficient is thresholded and Wiener-shrunk with its own
+//! variance factor, sigma stays the marginal level.  General group kernels only.  Everything else as run_bm5d.  Returns EXIT_SUCCESS, or
+//! EXIT_FAILURE with the message on stdout.
+int denoise_corr_LF(
+    const std::vector<double> &acf
+,   const float sigma
+,   const float lambdaHard5D
+,   std::vector<std::vector<float> > &LF_noisy
+,   std::vector<unsigned> &LF_SAI_mask
+,   std::vector<std::vector<float> > &LF_basic
+,   std::vector<std::vector<float> > &LF_denoised
+,   const unsigned ang_major
+,   const unsigned awidth
+,   const unsigned aheight
+,   const unsigned anHard
+,   const unsigned anWien
+,   const unsigned width
+,   const unsigned height
+,   const unsigned chnls
+,   const unsigned NHard, const unsigned nSimHard, const unsigned nDispHard, const unsigned kHard, const unsigned pHard
+,   const bool useSDHard, const unsigned tau_2D_hard, unsigned tau_4D_hard, const unsigned tau_5D_hard
+,   const unsigned NWien, const unsigned nSimWien, const unsigned nDispWien, const unsigned kWien, const unsigned pWien
+,   const bool useSDWien, const unsigned tau_2D_wien, unsigned tau_4D_wien, const unsigned tau_5D_wien
+,   const unsigned color_space
+,   const unsigned nb_threads
+);
+
+//! The autocorrelation of the noise of LF at the lags -3..3 (acf: 49 doubles) from the block autocovariance of its flattest blocks
+//! (lfbm5d_corr_measure_host_sai, include/lfbm5d_corr.h): block = 8, 16, 32 or 0 (16); fraction in (0, 1] or 0 (the default, 0.1); 1 on a
+//! flat-field light field is the calibration.  sigma receives the marginal level of the selected blocks (biased low when fraction < 1).
+int corr_measure_LF(
+    const std::vector<std::vector<float> > &LF
+,   const std::vector<unsigned> &LF_SAI_mask
+,   const unsigned width
+,   const unsigned height
+,   const unsigned chnls
+,   const unsigned block
+,   const double fraction
+,   std::vector<double> &acf
+,   double &sigma
+);
+
 //! The view table equalisation leaves behind: sigma_v = sigma sqrt(mean_c g_{v,c}^-2) over the stored channels (lfbm5d_views_from_gains);
 //! `gains` holds 3 doubles per SAI, as equalise_LF returns them.  Host only.  Returns EXIT_SUCCESS, or EXIT_FAILURE with the message on
 //! stdout.

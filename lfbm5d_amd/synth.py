@@ -130,6 +130,42 @@ def add_view_noise(clean, sigma_sai, seed=1):
     return res
 
 
+def gaussian_taps(width, size=7):
+    """size x size taps of a Gaussian of standard deviation `width` pixels, normalised to unit energy (sum of squares 1)."""
+    x = np.arange(size, dtype=np.float64) - (size - 1) / 2
+    g = np.exp(-0.5 * (x / float(width)) ** 2)
+    g = np.outer(g, g)
+    return g / np.sqrt((g * g).sum())
+
+
+def add_correlated_noise(clean, sigma, kernel, seed=1):
+    """Spatially correlated Gaussian noise of marginal standard deviation `sigma` on `clean` ([...][H][W]: the last two axes are a
+    plane): white noise of add_noise_mt19937's generator -- one MT19937 stream, two draws per sample, plane after plane in memory
+    order -- filtered by `kernel` (up to 7 x 7 taps, any scale: it is normalised to unit energy, so the marginal level stays sigma).
+    Each plane draws (H + gh - 1) x (W + gw - 1) samples and keeps the part the taps cover fully: the noise is stationary up to
+    the border.  Its autocorrelation is corr_from_kernel(kernel).  Returns float32."""
+    clean = np.ascontiguousarray(clean, dtype=np.float32)
+    g = np.atleast_2d(np.asarray(kernel, dtype=np.float64))
+    if clean.ndim < 2 or g.ndim != 2 or not (g * g).sum() > 0:
+        raise ValueError("add_correlated_noise: clean is [...][H][W], kernel a 2-D array of taps that are not all zero")
+    g = g / np.sqrt((g * g).sum())
+    gh, gw = g.shape
+    H, W = clean.shape[-2:]
+    planes = clean.reshape(-1, H, W)
+    res = np.empty_like(planes)
+    rs = np.random.RandomState(int(seed) & 0xFFFFFFFF)
+    for i in range(planes.shape[0]):
+        n = (H + gh - 1) * (W + gw - 1)
+        u = rs.random_sample(2 * n)
+        w = (np.sqrt(-2.0 * np.log(u[0::2])) * np.cos(2.0 * np.pi * u[1::2])).reshape(H + gh - 1, W + gw - 1)
+        z = np.zeros((H, W), np.float64)
+        for y in range(gh):
+            for x in range(gw):
+                z += g[y, x] * w[y:y + H, x:x + W]
+        res[i] = planes[i] + (float(sigma) * z).astype(np.float32)
+    return res.reshape(clean.shape)
+
+
 def add_poisson_gaussian(clean, a, b, seed=1):
     """Poisson-Gaussian noise var(z | y) = a y + b on `clean` (any shape, nominally 0..255) from numpy's default_rng(seed):
     a * poisson(clean / a) + normal(0, sqrt(b)); a = 0 gives the Gaussian part alone.  Negative values of `clean` count as 0 for the
