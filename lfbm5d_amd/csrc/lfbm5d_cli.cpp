@@ -1143,10 +1143,96 @@ bool estimate_sigma_LF(const vector<vector<float> >& LF_noisy, const vector<unsi
             "rgb|yuv|ycbcr|opp nbThreads resultsFile" << endl;
 }
 
+/* every LFBM5D_* mode of the header comment, as both commands read it */
+struct Modes {
+    double pg[2] = {0.0, 0.0}; int smode = 0;                                           /* LFBM5D_SIGMA (sigma_mode) */
+    int qmode = 0;                                                                      /* LFBM5D_REPORT_SSIM */
+    double imp_k = -1.0, imp_add = 0.0;
+    bool joint = false; int rep_iter = -1;
+    const char* def_dir = nullptr; int def_iter = -1;
+    vector<unsigned> missing; int miss_iter = -1;
+    bool detect = false; double det_k = -1.0; const char* det_save = nullptr;
+    int eq_mode = 0; double eq_add = 0.0;
+    int vs_mode = 0; double vs_add = 0.0;
+    int nc_mode = 0; vector<double> nc_acf, nc_add; unsigned nc_add_h = 0, nc_add_w = 0;
+    unsigned dsteps = 1;
+    float occl = 0.0f;
+    bool clip_on = false, clip_add = false; double clip_lo = 0.0, clip_hi = 255.0;
+    double pc_lo = 0.0, pc_hi = 255.0;                                                  /* LFBM5D_SIGMA=poisson-clipped: its range */
+};
+
+/* in the order the commands have always read them: the first bad value's message is the one printed.  bm3d: LFBM3Ddenoising, which
+ * refuses LFBM5D_NOISE_CORR.  false: the message is out */
+bool read_modes(Modes& m, unsigned ang_major, unsigned aw, unsigned ah, unsigned s0, unsigned t0, bool gt, bool bm3d) {
+    return (m.smode = sigma_mode(m.pg)) >= 0 && (m.qmode = cli_quality::ssim_mode()) >= 0 && impulse_mode(m.imp_k, m.imp_add) &&
+           repair_mode(m.joint, m.rep_iter, m.smode) && defects_mode(m.def_dir, m.def_iter) &&
+           missing_mode(m.missing, m.miss_iter, ang_major, aw, ah, s0, t0) && detect_mode(m.detect, m.det_k, m.det_save) &&
+           equalise_mode(m.eq_mode, m.eq_add, m.smode, gt) && view_sigma_mode(m.vs_mode, m.vs_add, m.smode, gt) &&
+           noise_corr_mode(m.nc_mode, m.nc_acf, m.nc_add, m.nc_add_h, m.nc_add_w, m.smode, gt, bm3d) &&
+           disparity_steps_mode(m.dsteps, m.detect || !m.missing.empty() || m.eq_mode) && occlusion_mode(m.occl, m.detect || !m.missing.empty()) &&
+           clip_mode(m.clip_on, m.clip_lo, m.clip_hi, m.clip_add, m.smode) && clip_range_mode(m.pc_lo, m.pc_hi);
+}
+
+/* The noisy light field: with a ground truth (gt) the source is loaded, the noise the modes ask for is added and the result is saved;
+ * without one it is loaded from its directory.  Then LFBM5D_EQUALISE and LFBM5D_DETECT, which come ahead of every repair.  (LFBM3Ddenoising
+ * never has taps to filter the noise with: it refuses the variable.)  false: the message is out */
+bool noisy_LF(Modes& m, bool gt, const char* src, const char* d_noisy, const char* name, const char* sep, unsigned ang_major, unsigned aw, unsigned ah,
+              unsigned s0, unsigned t0, float sigma, vector<vector<float> >& LF, vector<vector<float> >& LF_noisy, vector<unsigned>& mask, unsigned& W,
+              unsigned& H, unsigned& C, vector<double>& eq_gains, vector<vector<unsigned char> >& detected) {
+    if (gt) {
+        double t = now_s();
+        if (load_LF(src, name, sep, LF, mask, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return false;
+        cout << "Loading LF elapsed time = " << now_s() - t << "s." << endl;
+        LF_noisy.assign(aw * ah, vector<float>((size_t)W * H * C, 0.0f));
+        const bool poisson = m.smode == 3 || m.smode == 5;
+        if (poisson) cout << endl << "Add noise [Poisson-Gaussian, a = " << m.pg[0] << ", b = " << m.pg[1] << "] ... " << flush;
+        else if (m.vs_add > 0.0) cout << endl << "Add noise [sigma = " << sigma << " / vignette, corner views x " << m.vs_add << "] ... " << flush;
+        else cout << endl << "Add noise [sigma = " << sigma << "] ... " << flush;
+        t = now_s();
+        const vector<double> vs_sigmas = m.vs_add > 0.0 ? vignette_sigmas(sigma, ang_major, aw, ah, m.vs_add) : vector<double>();
+        add_noise_LF(LF, mask, LF_noisy, sigma, poisson ? m.pg : nullptr, m.vs_add > 0.0 ? &vs_sigmas : nullptr);
+        if (!m.nc_add.empty()) correlate_noise_LF(LF, mask, LF_noisy, W, H, C, m.nc_add, m.nc_add_h, m.nc_add_w);
+        cout << "done in " << now_s() - t << "s." << endl;
+        if (m.eq_add > 0.0) add_vignette_LF(LF_noisy, mask, ang_major, aw, ah, m.eq_add);
+        if (m.clip_add) clip_round_LF(LF_noisy, mask, m.clip_lo, m.clip_hi);
+        if (m.smode == 5) clip_round_LF(LF_noisy, mask, m.pc_lo, m.pc_hi);   /* the given clipped model: the data are what it describes */
+        if (m.imp_add > 0.0) add_impulses_LF(LF_noisy, mask, m.imp_add);
+        for (size_t st = 0; st < m.missing.size(); st++) if (m.missing[st]) LF_noisy[st].assign(LF_noisy[st].size(), 0.0f);   /* dropped */
+        cout << endl << "Save noisy light field..." << endl;
+        if (save_LF(d_noisy, name, sep, LF_noisy, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return false;
+    } else if (load_LF(d_noisy, name, sep, LF_noisy, mask, ang_major, aw, ah, s0, t0, W, H, C, m.missing.empty() ? nullptr : &m.missing) != EXIT_SUCCESS)
+        return false;
+    if (m.eq_mode && !equalise_noisy_LF(LF_noisy, mask, ang_major, aw, ah, W, H, C, m.dsteps, eq_gains)) return false;
+    return !m.detect || detect_LF(LF_noisy, mask, m.det_k, m.det_save, name, sep, ang_major, aw, ah, s0, t0, W, H, C, m.missing, detected, m.dsteps);
+}
+
+/* what both commands run behind their repairs: LFBM5D_IMPULSE, then the sigma of LFBM5D_SIGMA=auto (est_mask: without the reconstructed SAIs) */
+bool settle_noisy_LF(const Modes& m, vector<vector<float> >& LF_noisy, const vector<unsigned>& mask, const vector<unsigned>& est_mask, unsigned W,
+                     unsigned H, unsigned C, float& sigma) {
+    if (m.imp_k >= 0.0 && !repair_impulses_LF(LF_noisy, mask, W, H, C, m.imp_k)) return false;
+    if (m.smode != 1) return true;
+    return m.clip_on ? estimate_sigma_clipped_LF(LF_noisy, est_mask, W, H, C, m.clip_lo, m.clip_hi, sigma) : estimate_sigma_LF(LF_noisy, est_mask, W, H, C, sigma);
+}
+
+/* PSNR and RMSE (with LFBM5D_REPORT_SSIM: SSIM too) of a light field against the source: the averages into avg, say() prints what the command
+ * says about them, the blocks go to the end of the results file.  false: the GPU backend failed (message on stdout) */
+struct Quality {
+    const vector<vector<float> >& source; const vector<unsigned>& mask; const char* results; unsigned ang_major, aw, ah, W, H, C; int ssim;
+    template <class Say> bool report(const char* label, const vector<vector<float> >& LF_x, cli_quality::Avg& avg, Say say) const {
+        vector<float> ps, rm; float sp = 0, ar = 0, sr = 0;
+        cli_quality::Block qb;
+        psnr_LF(source, LF_x, mask, ps, avg.psnr, sp, rm, ar, sr);
+        if (ssim && !cli_quality::compute(source, LF_x, mask, W, H, C, avg, qb)) return false;
+        say();
+        write_psnr(results, label, mask, ang_major, aw, ah, ps, avg.psnr, sp, rm, ar, sr);
+        if (ssim) cli_quality::write(results, label, mask, ang_major, aw, ah, qb);
+        return true;
+    }
+};
+
 } // namespace
 
 #ifdef LFBM3D_CLI
-constexpr bool NC_BM3D = true;
 int main(int argc, char** argv) {
     cout << "*********************************************************************************************************************" << endl;
     cout << "********************************************              START               ***************************************" << endl;
@@ -1183,163 +1269,98 @@ int main(int argc, char** argv) {
     const unsigned nb_threads = atoi(argv[a++]);
     const char* results = argv[a++];
     if (!ang_major || cs < 0) { cout << "Problem while reading parameters from command line !" << endl; return EXIT_FAILURE; }
-    double pg[2] = {0.0, 0.0};
-    const int smode = sigma_mode(pg);
-    if (smode < 0) return EXIT_FAILURE;
-    const int qmode = cli_quality::ssim_mode();
-    if (qmode < 0) return EXIT_FAILURE;
-    double imp_k = -1.0, imp_add = 0.0;
-    if (!impulse_mode(imp_k, imp_add)) return EXIT_FAILURE;
-    bool joint = false; int rep_iter = -1;
-    if (!repair_mode(joint, rep_iter, smode)) return EXIT_FAILURE;
-    const char* def_dir = nullptr; int def_iter = -1;
-    if (!defects_mode(def_dir, def_iter)) return EXIT_FAILURE;
-    vector<unsigned> missing; int miss_iter = -1;
-    if (!missing_mode(missing, miss_iter, ang_major, aw, ah, s0, t0)) return EXIT_FAILURE;
-    bool detect = false; double det_k = -1.0; const char* det_save = nullptr;
-    if (!detect_mode(detect, det_k, det_save)) return EXIT_FAILURE;
-    int eq_mode = 0; double eq_add = 0.0;
-    if (!equalise_mode(eq_mode, eq_add, smode, gt)) return EXIT_FAILURE;
+    Modes m;
+    if (!read_modes(m, ang_major, aw, ah, s0, t0, gt, true)) return EXIT_FAILURE;
+    unsigned pc_levels = 0; double pc_fmax = 0.0;   /* LFBM5D_SIGMA=poisson-clipped: its fit */
     vector<double> eq_gains;
-    int vs_mode = 0; double vs_add = 0.0;
-    if (!view_sigma_mode(vs_mode, vs_add, smode, gt)) return EXIT_FAILURE;
-    int nc_mode = 0; vector<double> nc_acf, nc_add; unsigned nc_add_h = 0, nc_add_w = 0;
-    if (!noise_corr_mode(nc_mode, nc_acf, nc_add, nc_add_h, nc_add_w, smode, gt, NC_BM3D)) return EXIT_FAILURE;
-    unsigned dsteps = 1;
-    if (!disparity_steps_mode(dsteps, detect || !missing.empty() || eq_mode)) return EXIT_FAILURE;
-    float occl = 0.0f;
-    if (!occlusion_mode(occl, detect || !missing.empty())) return EXIT_FAILURE;
-    bool clip_on = false, clip_add = false; double clip_lo = 0.0, clip_hi = 255.0;
-    if (!clip_mode(clip_on, clip_lo, clip_hi, clip_add, smode)) return EXIT_FAILURE;
-    double pc_lo = 0.0, pc_hi = 255.0; unsigned pc_levels = 0; double pc_fmax = 0.0;   /* LFBM5D_SIGMA=poisson-clipped: its range, its fit */
-    if (!clip_range_mode(pc_lo, pc_hi)) return EXIT_FAILURE;
 
     vector<vector<float> > LF, LF_noisy, LF_basic, LF_den, LF_diff;
     vector<unsigned> mask;
     unsigned W = 0, H = 0, C = 0;
     const unsigned awh = aw * ah;
-    if (gt) {
-        double t = now_s();
-        if (load_LF(src, name, sep, LF, mask, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
-        cout << "Loading LF elapsed time = " << now_s() - t << "s." << endl;
-        LF_noisy.assign(awh, vector<float>((size_t)W * H * C, 0.0f));
-        if (smode == 3 || smode == 5) cout << endl << "Add noise [Poisson-Gaussian, a = " << pg[0] << ", b = " << pg[1] << "] ... " << flush;
-        else if (vs_add > 0.0) cout << endl << "Add noise [sigma = " << sigma << " / vignette, corner views x " << vs_add << "] ... " << flush;
-        else cout << endl << "Add noise [sigma = " << sigma << "] ... " << flush;
-        t = now_s();
-        const vector<double> vs_sigmas = vs_add > 0.0 ? vignette_sigmas(sigma, ang_major, aw, ah, vs_add) : vector<double>();
-        add_noise_LF(LF, mask, LF_noisy, sigma, smode == 3 || smode == 5 ? pg : nullptr, vs_add > 0.0 ? &vs_sigmas : nullptr);
-        cout << "done in " << now_s() - t << "s." << endl;
-        if (eq_add > 0.0) add_vignette_LF(LF_noisy, mask, ang_major, aw, ah, eq_add);
-        if (clip_add) clip_round_LF(LF_noisy, mask, clip_lo, clip_hi);
-        if (smode == 5) clip_round_LF(LF_noisy, mask, pc_lo, pc_hi);   /* the given clipped model: the data are what it describes */
-        if (imp_add > 0.0) add_impulses_LF(LF_noisy, mask, imp_add);
-        for (size_t st = 0; st < missing.size(); st++) if (missing[st]) LF_noisy[st].assign(LF_noisy[st].size(), 0.0f);   /* dropped */
-        cout << endl << "Save noisy light field..." << endl;
-        if (save_LF(d_noisy, name, sep, LF_noisy, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
-    } else {
-        if (load_LF(d_noisy, name, sep, LF_noisy, mask, ang_major, aw, ah, s0, t0, W, H, C, missing.empty() ? nullptr : &missing) != EXIT_SUCCESS)
-            return EXIT_FAILURE;
-    }
-    if (eq_mode && !equalise_noisy_LF(LF_noisy, mask, ang_major, aw, ah, W, H, C, dsteps, eq_gains)) return EXIT_FAILURE;
     vector<vector<unsigned char> > detected;
-    if (detect && !detect_LF(LF_noisy, mask, det_k, det_save, name, sep, ang_major, aw, ah, s0, t0, W, H, C, missing, detected, dsteps)) return EXIT_FAILURE;
+    if (!noisy_LF(m, gt, src, d_noisy, name, sep, ang_major, aw, ah, s0, t0, sigma, LF, LF_noisy, mask, W, H, C, eq_gains, detected)) return EXIT_FAILURE;
     vector<unsigned> est_mask = mask;   /* the sigma estimate does not look at reconstructed SAIs */
-    if (joint && (def_dir || !detected.empty() || !missing.empty())) {   /* one joint fill in place of the two below */
+    if (m.joint && (m.def_dir || !detected.empty() || !m.missing.empty())) {   /* one joint fill in place of the two below */
         vector<vector<unsigned char> > defects;
         const unsigned hard[9] = {8, 8, 3, 8, 3, 0, LFBM5D_DCT, LFBM5D_SADCT, LFBM5D_HAAR};
-        if (!def_dir) defects.swap(detected);
-        else if (!load_defects(def_dir, name, sep, defects, mask, ang_major, aw, ah, s0, t0, W, H, C)) return EXIT_FAILURE;
-        if (!repair_joint_LF(LF_noisy, defects, mask, missing, ang_major, aw, ah, 1, W, H, C, 0, 0, 0.0f, lambda, hard, (unsigned)cs, true)) return EXIT_FAILURE;
+        if (!m.def_dir) defects.swap(detected);
+        else if (!load_defects(m.def_dir, name, sep, defects, mask, ang_major, aw, ah, s0, t0, W, H, C)) return EXIT_FAILURE;
+        if (!repair_joint_LF(LF_noisy, defects, mask, m.missing, ang_major, aw, ah, 1, W, H, C, 0, 0, 0.0f, lambda, hard, (unsigned)cs, true)) return EXIT_FAILURE;
         cout << "Joint repair: the fill alone (the refinement steps run in LFBM5Ddenoising)" << endl;
-        for (size_t st = 0; st < missing.size(); st++) if (missing[st]) est_mask[st] = 0;
-        missing.clear(); def_dir = nullptr; detected.clear();
+        for (size_t st = 0; st < m.missing.size(); st++) if (m.missing[st]) est_mask[st] = 0;
+        m.missing.clear(); m.def_dir = nullptr; detected.clear();
     }
-    if (!missing.empty()) {   /* the synthesis alone, for the same reason as the fill alone below */
+    if (!m.missing.empty()) {   /* the synthesis alone, for the same reason as the fill alone below */
         const unsigned hard[9] = {8, 8, 3, 8, 3, 0, LFBM5D_DCT, LFBM5D_SADCT, LFBM5D_HAAR};
-        if (!synthesise_missing_LF(LF_noisy, mask, missing, ang_major, aw, ah, 1, W, H, C, 0, 0, 0.0f, lambda, hard, (unsigned)cs, true, dsteps, occl)) return EXIT_FAILURE;
+        if (!synthesise_missing_LF(LF_noisy, mask, m.missing, ang_major, aw, ah, 1, W, H, C, 0, 0, 0.0f, lambda, hard, (unsigned)cs, true, m.dsteps, m.occl)) return EXIT_FAILURE;
         cout << "View synthesis: the synthesis alone (the refinement steps run in LFBM5Ddenoising)" << endl;
-        for (size_t st = 0; st < missing.size(); st++) if (missing[st]) est_mask[st] = 0;
+        for (size_t st = 0; st < m.missing.size(); st++) if (m.missing[st]) est_mask[st] = 0;
     }
-    if (def_dir || !detected.empty()) {   /* the fill alone: the refinement loop needs the 5-D step's parameters, which this command does not have */
+    if (m.def_dir || !detected.empty()) {   /* the fill alone: the refinement loop needs the 5-D step's parameters, which this command does not have */
         vector<vector<unsigned char> > defects;
         const unsigned hard[9] = {8, 8, 3, 8, 3, 0, LFBM5D_DCT, LFBM5D_SADCT, LFBM5D_HAAR};
-        if (!def_dir) defects.swap(detected);
-        else if (!load_defects(def_dir, name, sep, defects, mask, ang_major, aw, ah, s0, t0, W, H, C)) return EXIT_FAILURE;
+        if (!m.def_dir) defects.swap(detected);
+        else if (!load_defects(m.def_dir, name, sep, defects, mask, ang_major, aw, ah, s0, t0, W, H, C)) return EXIT_FAILURE;
         if (!inpaint_defects_LF(LF_noisy, defects, mask, ang_major, aw, ah, 1, W, H, C, 0, 0, 0.0f, lambda, hard, (unsigned)cs, true)) return EXIT_FAILURE;
         cout << "Defect inpainting: the fill alone (the refinement steps run in LFBM5Ddenoising)" << endl;
     }
-    if (imp_k >= 0.0 && !repair_impulses_LF(LF_noisy, mask, W, H, C, imp_k)) return EXIT_FAILURE;
-    if (smode == 1 && !(clip_on ? estimate_sigma_clipped_LF(LF_noisy, est_mask, W, H, C, clip_lo, clip_hi, sigma)
-                                : estimate_sigma_LF(LF_noisy, est_mask, W, H, C, sigma))) return EXIT_FAILURE;
+    if (!settle_noisy_LF(m, LF_noisy, mask, est_mask, W, H, C, sigma)) return EXIT_FAILURE;
     LF_basic.assign(awh, vector<float>((size_t)W * H * C, 0.0f));
     LF_den = LF_basic; LF_diff = LF_basic;
-    vector<float> ps, rm; float sp = 0, ar = 0, sr = 0;
     cli_quality::Avg ap_n, ap_b, ap_d;
-    cli_quality::Block qb;
-    if (gt) {
-        psnr_LF(LF, LF_noisy, mask, ps, ap_n.psnr, sp, rm, ar, sr);
-        if (qmode && !cli_quality::compute(LF, LF_noisy, mask, W, H, C, ap_n, qb)) return EXIT_FAILURE;
-        cout << endl << "Average PSNR:" << endl << "- Noisy light field: " << ap_n << endl;
-        write_psnr(results, "noisy", mask, ang_major, aw, ah, ps, ap_n.psnr, sp, rm, ar, sr);
-        if (qmode) cli_quality::write(results, "noisy", mask, ang_major, aw, ah, qb);
-    }
+    const Quality quality = {LF, mask, results, ang_major, aw, ah, W, H, C, m.qmode};
+    if (gt && !quality.report("noisy", LF_noisy, ap_n, [&]() { cout << endl << "Average PSNR:" << endl << "- Noisy light field: " << ap_n << endl; }))
+        return EXIT_FAILURE;
     cout << endl << " ---> Running LFBM3D filter <--- " << endl << endl;
     const double tb = now_s();
     char sub[] = "SAI";
-    if (smode >= 4) {   /* clipped Poisson-Gaussian noise: the same between the clipped model's stabiliser and its exact unbiased inverse */
-        if (smode == 4 && pgclip_estimate_LF(LF_noisy, mask, W, H, C, pc_lo, pc_hi, pg[0], pg[1], pc_levels, pc_fmax) != EXIT_SUCCESS) return EXIT_FAILURE;
+    if (m.smode >= 4) {   /* clipped Poisson-Gaussian noise: the same between the clipped model's stabiliser and its exact unbiased inverse */
+        if (m.smode == 4 && pgclip_estimate_LF(LF_noisy, mask, W, H, C, m.pc_lo, m.pc_hi, m.pg[0], m.pg[1], pc_levels, pc_fmax) != EXIT_SUCCESS) return EXIT_FAILURE;
         vector<vector<float> > LF_t = LF_noisy;
-        if (pgclip_forward_LF(pg[0], pg[1], pc_lo, pc_hi, LF_t, mask, W, H, C, sigma) != EXIT_SUCCESS) return EXIT_FAILURE;
-        print_pgclip_model(smode == 4, pg, pc_lo, pc_hi, pc_levels, pc_fmax, sigma);
+        if (pgclip_forward_LF(m.pg[0], m.pg[1], m.pc_lo, m.pc_hi, LF_t, mask, W, H, C, sigma) != EXIT_SUCCESS) return EXIT_FAILURE;
+        print_pgclip_model(m.smode == 4, m.pg, m.pc_lo, m.pc_hi, pc_levels, pc_fmax, sigma);
         if (run_bm3d_LF(sigma, LF_t, mask, LF_basic, LF_den, W, H, C, n[0], n[1], k[0], k[1], N[0], N[1], p[0], p[1], sd[0] != 0, sd[1] != 0,
                         t2[0], t2[1], lambda, cs, nb_threads, sub) != EXIT_SUCCESS) return EXIT_FAILURE;
-        if (pgclip_inverse_LF(pg[0], pg[1], pc_lo, pc_hi, LF_basic, mask, W, H, C) != EXIT_SUCCESS ||
-            pgclip_inverse_LF(pg[0], pg[1], pc_lo, pc_hi, LF_den, mask, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
+        if (pgclip_inverse_LF(m.pg[0], m.pg[1], m.pc_lo, m.pc_hi, LF_basic, mask, W, H, C) != EXIT_SUCCESS ||
+            pgclip_inverse_LF(m.pg[0], m.pg[1], m.pc_lo, m.pc_hi, LF_den, mask, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
     } else
-    if (smode >= 2) {   /* Poisson-Gaussian noise: stabilise a copy, filter it with the sigma that leaves, invert the results */
-        if (smode == 2 && !estimate_pg_LF(LF_noisy, mask, W, H, C, pg)) return EXIT_FAILURE;
+    if (m.smode >= 2) {   /* Poisson-Gaussian noise: stabilise a copy, filter it with the sigma that leaves, invert the results */
+        if (m.smode == 2 && !estimate_pg_LF(LF_noisy, mask, W, H, C, m.pg)) return EXIT_FAILURE;
         vector<vector<float> > LF_t = LF_noisy;
-        if (pg_forward_LF(pg[0], pg[1], LF_t, mask, W, H, C, sigma) != EXIT_SUCCESS) return EXIT_FAILURE;
-        print_pg_model(smode == 2, pg, sigma);
+        if (pg_forward_LF(m.pg[0], m.pg[1], LF_t, mask, W, H, C, sigma) != EXIT_SUCCESS) return EXIT_FAILURE;
+        print_pg_model(m.smode == 2, m.pg, sigma);
         if (run_bm3d_LF(sigma, LF_t, mask, LF_basic, LF_den, W, H, C, n[0], n[1], k[0], k[1], N[0], N[1], p[0], p[1], sd[0] != 0, sd[1] != 0,
                         t2[0], t2[1], lambda, cs, nb_threads, sub) != EXIT_SUCCESS) return EXIT_FAILURE;
-        if (pg_inverse_LF(pg[0], pg[1], LF_basic, mask, W, H, C) != EXIT_SUCCESS || pg_inverse_LF(pg[0], pg[1], LF_den, mask, W, H, C) != EXIT_SUCCESS)
+        if (pg_inverse_LF(m.pg[0], m.pg[1], LF_basic, mask, W, H, C) != EXIT_SUCCESS || pg_inverse_LF(m.pg[0], m.pg[1], LF_den, mask, W, H, C) != EXIT_SUCCESS)
             return EXIT_FAILURE;
     } else
-    if (vs_mode) {   /* one noise level per SAI: every SAI is its own "window" */
+    if (m.vs_mode) {   /* one noise level per SAI: every SAI is its own "window" */
         vector<double> table;
-        if (vs_mode == 2 && views_from_gains((double)sigma, eq_gains, C, mask, table) != EXIT_SUCCESS) return EXIT_FAILURE;
+        if (m.vs_mode == 2 && views_from_gains((double)sigma, eq_gains, C, mask, table) != EXIT_SUCCESS) return EXIT_FAILURE;
         if (bm3d_views_LF(table, LF_noisy, mask, LF_basic, LF_den, W, H, C, n[0], n[1], k[0], k[1], N[0], N[1], p[0], p[1], sd[0] != 0, sd[1] != 0,
                           t2[0], t2[1], lambda, cs) != EXIT_SUCCESS) return EXIT_FAILURE;
         vector<float> each;
         for (size_t st = 0; st < table.size(); st++) if (mask[st]) each.push_back((float)table[st]);
-        print_view_sigmas(table, mask, each, vs_mode == 1);
+        print_view_sigmas(table, mask, each, m.vs_mode == 1);
     } else
     if (run_bm3d_LF(sigma, LF_noisy, mask, LF_basic, LF_den, W, H, C, n[0], n[1], k[0], k[1], N[0], N[1], p[0], p[1], sd[0] != 0, sd[1] != 0,
                     t2[0], t2[1], lambda, cs, nb_threads, sub) != EXIT_SUCCESS) return EXIT_FAILURE;
-    if (clip_on) {   /* the filter saw the clipped data; its results go through the inverse of the clipped mean */
-        if (declip_LF(sigma, clip_lo, clip_hi, LF_basic, mask, W, H, C) != EXIT_SUCCESS || declip_LF(sigma, clip_lo, clip_hi, LF_den, mask, W, H, C) != EXIT_SUCCESS)
+    if (m.clip_on) {   /* the filter saw the clipped data; its results go through the inverse of the clipped mean */
+        if (declip_LF(sigma, m.clip_lo, m.clip_hi, LF_basic, mask, W, H, C) != EXIT_SUCCESS || declip_LF(sigma, m.clip_lo, m.clip_hi, LF_den, mask, W, H, C) != EXIT_SUCCESS)
             return EXIT_FAILURE;
-        print_declipping(clip_lo, clip_hi, sigma);
+        print_declipping(m.clip_lo, m.clip_hi, sigma);
     }
-    if (eq_mode == 1 && !(restore_LF(LF_basic, mask, eq_gains, aw, ah, W, H, C) && restore_LF(LF_den, mask, eq_gains, aw, ah, W, H, C))) return EXIT_FAILURE;
+    if (m.eq_mode == 1 && !(restore_LF(LF_basic, mask, eq_gains, aw, ah, W, H, C) && restore_LF(LF_den, mask, eq_gains, aw, ah, W, H, C))) return EXIT_FAILURE;
     const double secs = now_s() - tb;
-    if (gt) {
-        psnr_LF(LF, LF_basic, mask, ps, ap_b.psnr, sp, rm, ar, sr);
-        if (qmode && !cli_quality::compute(LF, LF_basic, mask, W, H, C, ap_b, qb)) return EXIT_FAILURE;
-        write_psnr(results, "basic", mask, ang_major, aw, ah, ps, ap_b.psnr, sp, rm, ar, sr);
-        if (qmode) cli_quality::write(results, "basic", mask, ang_major, aw, ah, qb);
-    }
+    if (gt && !quality.report("basic", LF_basic, ap_b, []() {})) return EXIT_FAILURE;
     cout << endl << "Save basic light field..." << endl;
     if (save_LF(d_basic, name, sep, LF_basic, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
     if (gt) {
-        psnr_LF(LF, LF_den, mask, ps, ap_d.psnr, sp, rm, ar, sr);
-        if (qmode && !cli_quality::compute(LF, LF_den, mask, W, H, C, ap_d, qb)) return EXIT_FAILURE;
-        cout << endl << "Average PSNR:" << endl << "- Noisy light field: " << ap_n << endl << "- Basic light field: " << ap_b << endl
-             << "- Denoised light field: " << ap_d << endl << endl;
-        write_psnr(results, "denoised", mask, ang_major, aw, ah, ps, ap_d.psnr, sp, rm, ar, sr);
-        if (qmode) cli_quality::write(results, "denoised", mask, ang_major, aw, ah, qb);
+        if (!quality.report("denoised", LF_den, ap_d, [&]() {
+                cout << endl << "Average PSNR:" << endl << "- Noisy light field: " << ap_n << endl << "- Basic light field: " << ap_b << endl
+                     << "- Denoised light field: " << ap_d << endl << endl; }))
+            return EXIT_FAILURE;
         diff_LF(LF, LF_den, mask, LF_diff, sigma);
     }
     cout << endl << "Save denoised light field..." << endl;
@@ -1355,7 +1376,6 @@ int main(int argc, char** argv) {
     return EXIT_SUCCESS;
 }
 #else
-constexpr bool NC_BM3D = false;
 int main(int argc, char** argv) {
     cout << "*********************************************************************************************************************" << endl;
     cout << "********************************************              START               ***************************************" << endl;
@@ -1391,170 +1411,111 @@ int main(int argc, char** argv) {
     const unsigned nb_threads = atoi(argv[a++]);
     const char* results = argv[a++];
     if (!ang_major || cs < 0) { cout << "Problem while reading parameters from command line !" << endl; usage(argv[0]); return EXIT_FAILURE; }
-    double pg[2] = {0.0, 0.0};
-    const int smode = sigma_mode(pg);
-    if (smode < 0) return EXIT_FAILURE;
-    const int qmode = cli_quality::ssim_mode();
-    if (qmode < 0) return EXIT_FAILURE;
-    double imp_k = -1.0, imp_add = 0.0;
-    if (!impulse_mode(imp_k, imp_add)) return EXIT_FAILURE;
-    bool joint = false; int rep_iter = -1;
-    if (!repair_mode(joint, rep_iter, smode)) return EXIT_FAILURE;
-    const char* def_dir = nullptr; int def_iter = -1;
-    if (!defects_mode(def_dir, def_iter)) return EXIT_FAILURE;
-    vector<unsigned> missing; int miss_iter = -1;
-    if (!missing_mode(missing, miss_iter, ang_major, aw, ah, s0, t0)) return EXIT_FAILURE;
-    bool detect = false; double det_k = -1.0; const char* det_save = nullptr;
-    if (!detect_mode(detect, det_k, det_save)) return EXIT_FAILURE;
-    int eq_mode = 0; double eq_add = 0.0;
-    if (!equalise_mode(eq_mode, eq_add, smode, gt)) return EXIT_FAILURE;
+    Modes m;
+    if (!read_modes(m, ang_major, aw, ah, s0, t0, gt, false)) return EXIT_FAILURE;
+    unsigned pc_levels = 0; double pc_fmax = 0.0;   /* LFBM5D_SIGMA=poisson-clipped: its fit */
     vector<double> eq_gains;
-    int vs_mode = 0; double vs_add = 0.0;
-    if (!view_sigma_mode(vs_mode, vs_add, smode, gt)) return EXIT_FAILURE;
-    int nc_mode = 0; vector<double> nc_acf, nc_add; unsigned nc_add_h = 0, nc_add_w = 0;
-    if (!noise_corr_mode(nc_mode, nc_acf, nc_add, nc_add_h, nc_add_w, smode, gt, NC_BM3D)) return EXIT_FAILURE;
-    unsigned dsteps = 1;
-    if (!disparity_steps_mode(dsteps, detect || !missing.empty() || eq_mode)) return EXIT_FAILURE;
-    float occl = 0.0f;
-    if (!occlusion_mode(occl, detect || !missing.empty())) return EXIT_FAILURE;
-    bool clip_on = false, clip_add = false; double clip_lo = 0.0, clip_hi = 255.0;
-    if (!clip_mode(clip_on, clip_lo, clip_hi, clip_add, smode)) return EXIT_FAILURE;
-    double pc_lo = 0.0, pc_hi = 255.0; unsigned pc_levels = 0; double pc_fmax = 0.0;   /* LFBM5D_SIGMA=poisson-clipped: its range, its fit */
-    if (!clip_range_mode(pc_lo, pc_hi)) return EXIT_FAILURE;
 
     vector<vector<float> > LF, LF_noisy, LF_basic, LF_den, LF_diff;
     vector<unsigned> mask;
     unsigned W = 0, H = 0, C = 0;
     const unsigned awh = aw * ah;
-    if (gt) {
-        double t = now_s();
-        if (load_LF(src, name, sep, LF, mask, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
-        cout << "Loading LF elapsed time = " << now_s() - t << "s." << endl;
-        LF_noisy.assign(awh, vector<float>((size_t)W * H * C, 0.0f));
-        if (smode == 3 || smode == 5) cout << endl << "Add noise [Poisson-Gaussian, a = " << pg[0] << ", b = " << pg[1] << "] ... " << flush;
-        else if (vs_add > 0.0) cout << endl << "Add noise [sigma = " << sigma << " / vignette, corner views x " << vs_add << "] ... " << flush;
-        else cout << endl << "Add noise [sigma = " << sigma << "] ... " << flush;
-        t = now_s();
-        const vector<double> vs_sigmas = vs_add > 0.0 ? vignette_sigmas(sigma, ang_major, aw, ah, vs_add) : vector<double>();
-        add_noise_LF(LF, mask, LF_noisy, sigma, smode == 3 || smode == 5 ? pg : nullptr, vs_add > 0.0 ? &vs_sigmas : nullptr);
-        if (!nc_add.empty()) correlate_noise_LF(LF, mask, LF_noisy, W, H, C, nc_add, nc_add_h, nc_add_w);
-        cout << "done in " << now_s() - t << "s." << endl;
-        if (eq_add > 0.0) add_vignette_LF(LF_noisy, mask, ang_major, aw, ah, eq_add);
-        if (clip_add) clip_round_LF(LF_noisy, mask, clip_lo, clip_hi);
-        if (smode == 5) clip_round_LF(LF_noisy, mask, pc_lo, pc_hi);   /* the given clipped model: the data are what it describes */
-        if (imp_add > 0.0) add_impulses_LF(LF_noisy, mask, imp_add);
-        for (size_t st = 0; st < missing.size(); st++) if (missing[st]) LF_noisy[st].assign(LF_noisy[st].size(), 0.0f);   /* dropped */
-        cout << endl << "Save noisy light field..." << endl;
-        if (save_LF(d_noisy, name, sep, LF_noisy, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
-    } else {
-        if (load_LF(d_noisy, name, sep, LF_noisy, mask, ang_major, aw, ah, s0, t0, W, H, C, missing.empty() ? nullptr : &missing) != EXIT_SUCCESS)
-            return EXIT_FAILURE;
-    }
-    if (eq_mode && !equalise_noisy_LF(LF_noisy, mask, ang_major, aw, ah, W, H, C, dsteps, eq_gains)) return EXIT_FAILURE;
     vector<vector<unsigned char> > defects;
+    if (!noisy_LF(m, gt, src, d_noisy, name, sep, ang_major, aw, ah, s0, t0, sigma, LF, LF_noisy, mask, W, H, C, eq_gains, defects)) return EXIT_FAILURE;
     const unsigned def_hard[9] = {N[0], nSim[0], nDisp[0], k[0], p[0], sd[0], (unsigned)t2[0], (unsigned)t4[0], (unsigned)t5[0]};
     unsigned def_steps = 0;
     vector<unsigned> est_mask = mask;   /* the sigma estimate does not look at reconstructed SAIs */
     unsigned view_steps = 0;
-    if (detect && !detect_LF(LF_noisy, mask, det_k, det_save, name, sep, ang_major, aw, ah, s0, t0, W, H, C, missing, defects, dsteps)) return EXIT_FAILURE;
     unsigned rep_steps = 0;
-    const bool joint_job = joint && (def_dir || !defects.empty() || !missing.empty());
+    const bool joint_job = m.joint && (m.def_dir || !defects.empty() || !m.missing.empty());
     if (joint_job) {   /* one joint fill now, one loop behind the sigma estimate, in place of the two stages below */
         lfbm5d_repair_params rp;
         lfbm5d_repair_defaults(&rp);
-        rep_steps = rep_iter >= 0 ? (unsigned)rep_iter : rp.iterations;
-        if (def_dir && !load_defects(def_dir, name, sep, defects, mask, ang_major, aw, ah, s0, t0, W, H, C)) return EXIT_FAILURE;
-        if (!repair_joint_LF(LF_noisy, defects, mask, missing, ang_major, aw, ah, anH, W, H, C, 0, rep_steps, 0.0f, lambda, def_hard, (unsigned)cs, true))
+        rep_steps = m.rep_iter >= 0 ? (unsigned)m.rep_iter : rp.iterations;
+        if (m.def_dir && !load_defects(m.def_dir, name, sep, defects, mask, ang_major, aw, ah, s0, t0, W, H, C)) return EXIT_FAILURE;
+        if (!repair_joint_LF(LF_noisy, defects, mask, m.missing, ang_major, aw, ah, anH, W, H, C, 0, rep_steps, 0.0f, lambda, def_hard, (unsigned)cs, true))
             return EXIT_FAILURE;
-        for (size_t st = 0; st < missing.size(); st++) if (missing[st]) est_mask[st] = 0;
+        for (size_t st = 0; st < m.missing.size(); st++) if (m.missing[st]) est_mask[st] = 0;
     }
-    const bool have_defects = !joint_job && (def_dir || !defects.empty());
-    if (!joint_job && !missing.empty()) {
+    const bool have_defects = !joint_job && (m.def_dir || !defects.empty());
+    if (!joint_job && !m.missing.empty()) {
         lfbm5d_view_params vp;
         lfbm5d_view_defaults(&vp);
-        view_steps = smode >= 2 ? 0u : miss_iter >= 0 ? (unsigned)miss_iter : vp.iterations;
-        if (!synthesise_missing_LF(LF_noisy, mask, missing, ang_major, aw, ah, anH, W, H, C, 0, view_steps, 0.0f, lambda, def_hard, (unsigned)cs, true, dsteps, occl))
+        view_steps = m.smode >= 2 ? 0u : m.miss_iter >= 0 ? (unsigned)m.miss_iter : vp.iterations;
+        if (!synthesise_missing_LF(LF_noisy, mask, m.missing, ang_major, aw, ah, anH, W, H, C, 0, view_steps, 0.0f, lambda, def_hard, (unsigned)cs, true, m.dsteps, m.occl))
             return EXIT_FAILURE;
-        if (smode >= 2) cout << "View synthesis: the synthesis alone (LFBM5D_SIGMA=poisson: the refinement steps assume one sigma)" << endl;
-        for (size_t st = 0; st < missing.size(); st++) if (missing[st]) est_mask[st] = 0;
+        if (m.smode >= 2) cout << "View synthesis: the synthesis alone (LFBM5D_SIGMA=poisson: the refinement steps assume one sigma)" << endl;
+        for (size_t st = 0; st < m.missing.size(); st++) if (m.missing[st]) est_mask[st] = 0;
     }
     if (have_defects) {
         lfbm5d_inpaint_params ip;
         lfbm5d_inpaint_defaults(&ip);
-        def_steps = smode >= 2 ? 0u : def_iter >= 0 ? (unsigned)def_iter : ip.iterations;
-        if (def_dir && !load_defects(def_dir, name, sep, defects, mask, ang_major, aw, ah, s0, t0, W, H, C)) return EXIT_FAILURE;
+        def_steps = m.smode >= 2 ? 0u : m.def_iter >= 0 ? (unsigned)m.def_iter : ip.iterations;
+        if (m.def_dir && !load_defects(m.def_dir, name, sep, defects, mask, ang_major, aw, ah, s0, t0, W, H, C)) return EXIT_FAILURE;
         if (!inpaint_defects_LF(LF_noisy, defects, mask, ang_major, aw, ah, anH, W, H, C, 0, def_steps, 0.0f, lambda, def_hard, (unsigned)cs, true))
             return EXIT_FAILURE;
-        if (smode >= 2) cout << "Defect inpainting: the fill alone (LFBM5D_SIGMA=poisson: the refinement steps assume one sigma)" << endl;
+        if (m.smode >= 2) cout << "Defect inpainting: the fill alone (LFBM5D_SIGMA=poisson: the refinement steps assume one sigma)" << endl;
     }
-    if (imp_k >= 0.0 && !repair_impulses_LF(LF_noisy, mask, W, H, C, imp_k)) return EXIT_FAILURE;
-    if (smode == 1 && !(clip_on ? estimate_sigma_clipped_LF(LF_noisy, est_mask, W, H, C, clip_lo, clip_hi, sigma)
-                                : estimate_sigma_LF(LF_noisy, est_mask, W, H, C, sigma))) return EXIT_FAILURE;
-    if (rep_steps && !repair_joint_LF(LF_noisy, defects, mask, missing, ang_major, aw, ah, anH, W, H, C, rep_steps, rep_steps, sigma, lambda, def_hard,
+    if (!settle_noisy_LF(m, LF_noisy, mask, est_mask, W, H, C, sigma)) return EXIT_FAILURE;
+    if (rep_steps && !repair_joint_LF(LF_noisy, defects, mask, m.missing, ang_major, aw, ah, anH, W, H, C, rep_steps, rep_steps, sigma, lambda, def_hard,
                                       (unsigned)cs, false)) return EXIT_FAILURE;
-    if (view_steps && !synthesise_missing_LF(LF_noisy, mask, missing, ang_major, aw, ah, anH, W, H, C, view_steps, view_steps, sigma, lambda, def_hard,
-                                             (unsigned)cs, false, dsteps, occl)) return EXIT_FAILURE;
+    if (view_steps && !synthesise_missing_LF(LF_noisy, mask, m.missing, ang_major, aw, ah, anH, W, H, C, view_steps, view_steps, sigma, lambda, def_hard,
+                                             (unsigned)cs, false, m.dsteps, m.occl)) return EXIT_FAILURE;
     if (def_steps && !inpaint_defects_LF(LF_noisy, defects, mask, ang_major, aw, ah, anH, W, H, C, def_steps, def_steps, sigma, lambda, def_hard,
                                          (unsigned)cs, false)) return EXIT_FAILURE;
     LF_basic.assign(awh, vector<float>((size_t)W * H * C, 0.0f));
     LF_den = LF_basic; LF_diff = LF_basic;
-    vector<float> ps, rm; float sp = 0, ar = 0, sr = 0;
     cli_quality::Avg ap_n, ap_b, ap_d;
-    cli_quality::Block qb;
-    if (gt) {
-        psnr_LF(LF, LF_noisy, mask, ps, ap_n.psnr, sp, rm, ar, sr);
-        if (qmode && !cli_quality::compute(LF, LF_noisy, mask, W, H, C, ap_n, qb)) return EXIT_FAILURE;
-        cout << endl << "Average PSNR:" << endl << "- Noisy light field: " << ap_n << endl;
-        write_psnr(results, "noisy", mask, ang_major, aw, ah, ps, ap_n.psnr, sp, rm, ar, sr);
-        if (qmode) cli_quality::write(results, "noisy", mask, ang_major, aw, ah, qb);
-    }
+    const Quality quality = {LF, mask, results, ang_major, aw, ah, W, H, C, m.qmode};
+    if (gt && !quality.report("noisy", LF_noisy, ap_n, [&]() { cout << endl << "Average PSNR:" << endl << "- Noisy light field: " << ap_n << endl; }))
+        return EXIT_FAILURE;
     /* LFBM5D_ONE_JOB=1 (not in the reference): both steps as one job (run_bm5d, run_bm5d.h) -- the same denoised files and PSNR, one time for
      * both.  The BASIC light field saved and reported in this mode is the one the job returns at its end, inverse(forward(inverse(estimate)))
      * -- what LF_basic holds after run_bm5d_2nd_step's lossy colour round trip (bm5d.cpp:829, :1416) -- where the two-call form saves
      * inverse(estimate) between the calls: the two differ (0.015 dB on the test light field) because the reference's colour matrices are not
      * inverses of each other */
     const char* one_job_s = env("LFBM5D_ONE_JOB");
-    const bool one_job = smode >= 2 || clip_on || vs_mode || nc_mode || (one_job_s && *one_job_s && *one_job_s != '0');   /* the Poisson-Gaussian, the clipped and the per-view path are one job */
+    const bool one_job = m.smode >= 2 || m.clip_on || m.vs_mode || m.nc_mode || (one_job_s && *one_job_s && *one_job_s != '0');   /* the Poisson-Gaussian, the clipped and the per-view path are one job */
     cout << endl << " ---> Running LFBM5D filter <--- " << endl << endl << (one_job ? "Steps 1 and 2 running as one job..." : "Step 1 running...") << endl;
     const double tb = now_s();
     double t1 = now_s();
     double job = 0.0;
-    if (smode >= 4) {
-        if (denoise_pgclip_LF(pg[0], pg[1], pc_lo, pc_hi, smode == 4, sigma, pc_levels, pc_fmax, lambda, LF_noisy, mask, LF_basic, LF_den, ang_major, aw,
+    if (m.smode >= 4) {
+        if (denoise_pgclip_LF(m.pg[0], m.pg[1], m.pc_lo, m.pc_hi, m.smode == 4, sigma, pc_levels, pc_fmax, lambda, LF_noisy, mask, LF_basic, LF_den, ang_major, aw,
                               ah, anH, anW, W, H, C, N[0], nSim[0], nDisp[0], k[0], p[0], sd[0] != 0, t2[0], t4[0], t5[0], N[1], nSim[1], nDisp[1], k[1],
                               p[1], sd[1] != 0, t2[1], t4[1], t5[1], cs, nb_threads) != EXIT_SUCCESS) return EXIT_FAILURE;
         job = now_s() - t1;
-        print_pgclip_model(smode == 4, pg, pc_lo, pc_hi, pc_levels, pc_fmax, sigma);
-    } else if (smode >= 2) {
-        if (denoise_pg_LF(pg[0], pg[1], smode == 2, sigma, lambda, LF_noisy, mask, LF_basic, LF_den, ang_major, aw, ah, anH, anW, W, H, C, N[0],
+        print_pgclip_model(m.smode == 4, m.pg, m.pc_lo, m.pc_hi, pc_levels, pc_fmax, sigma);
+    } else if (m.smode >= 2) {
+        if (denoise_pg_LF(m.pg[0], m.pg[1], m.smode == 2, sigma, lambda, LF_noisy, mask, LF_basic, LF_den, ang_major, aw, ah, anH, anW, W, H, C, N[0],
                           nSim[0], nDisp[0], k[0], p[0], sd[0] != 0, t2[0], t4[0], t5[0], N[1], nSim[1], nDisp[1], k[1], p[1], sd[1] != 0, t2[1],
                           t4[1], t5[1], cs, nb_threads) != EXIT_SUCCESS) return EXIT_FAILURE;
         job = now_s() - t1;
-        print_pg_model(smode == 2, pg, sigma);
-    } else if (clip_on) {
-        if (denoise_clipped_LF(sigma, clip_lo, clip_hi, lambda, LF_noisy, mask, LF_basic, LF_den, ang_major, aw, ah, anH, anW, W, H, C, N[0], nSim[0], nDisp[0],
+        print_pg_model(m.smode == 2, m.pg, sigma);
+    } else if (m.clip_on) {
+        if (denoise_clipped_LF(sigma, m.clip_lo, m.clip_hi, lambda, LF_noisy, mask, LF_basic, LF_den, ang_major, aw, ah, anH, anW, W, H, C, N[0], nSim[0], nDisp[0],
                                k[0], p[0], sd[0] != 0, t2[0], t4[0], t5[0], N[1], nSim[1], nDisp[1], k[1], p[1], sd[1] != 0, t2[1], t4[1], t5[1], cs,
                                nb_threads) != EXIT_SUCCESS) return EXIT_FAILURE;
         job = now_s() - t1;
-        print_declipping(clip_lo, clip_hi, sigma);
-    } else if (vs_mode) {
+        print_declipping(m.clip_lo, m.clip_hi, sigma);
+    } else if (m.vs_mode) {
         vector<double> table; vector<float> window_sigmas;
-        if (vs_mode == 2 && views_from_gains((double)sigma, eq_gains, C, mask, table) != EXIT_SUCCESS) return EXIT_FAILURE;
+        if (m.vs_mode == 2 && views_from_gains((double)sigma, eq_gains, C, mask, table) != EXIT_SUCCESS) return EXIT_FAILURE;
         if (denoise_views_LF(table, window_sigmas, lambda, LF_noisy, mask, LF_basic, LF_den, ang_major, aw, ah, anH, anW, W, H, C, N[0], nSim[0],
                              nDisp[0], k[0], p[0], sd[0] != 0, t2[0], t4[0], t5[0], N[1], nSim[1], nDisp[1], k[1], p[1], sd[1] != 0, t2[1], t4[1],
                              t5[1], cs, nb_threads) != EXIT_SUCCESS) return EXIT_FAILURE;
         job = now_s() - t1;
-        print_view_sigmas(table, mask, window_sigmas, vs_mode == 1);
-    } else if (nc_mode) {
-        if (nc_mode == 1) {   /* the blind shape from the noisy light field; the command's sigma stays the marginal level */
+        print_view_sigmas(table, mask, window_sigmas, m.vs_mode == 1);
+    } else if (m.nc_mode) {
+        if (m.nc_mode == 1) {   /* the blind shape from the noisy light field; the command's sigma stays the marginal level */
             double s_est = 0.0;
-            if (corr_measure_LF(LF_noisy, mask, W, H, C, 0, 0.0, nc_acf, s_est) != EXIT_SUCCESS) return EXIT_FAILURE;
+            if (corr_measure_LF(LF_noisy, mask, W, H, C, 0, 0.0, m.nc_acf, s_est) != EXIT_SUCCESS) return EXIT_FAILURE;
         }
-        if (denoise_corr_LF(nc_acf, sigma, lambda, LF_noisy, mask, LF_basic, LF_den, ang_major, aw, ah, anH, anW, W, H, C, N[0], nSim[0], nDisp[0],
+        if (denoise_corr_LF(m.nc_acf, sigma, lambda, LF_noisy, mask, LF_basic, LF_den, ang_major, aw, ah, anH, anW, W, H, C, N[0], nSim[0], nDisp[0],
                             k[0], p[0], sd[0] != 0, t2[0], t4[0], t5[0], N[1], nSim[1], nDisp[1], k[1], p[1], sd[1] != 0, t2[1], t4[1], t5[1], cs,
                             nb_threads) != EXIT_SUCCESS) return EXIT_FAILURE;
         job = now_s() - t1;
-        if (!print_noise_corr(nc_acf, nc_mode, t2, k)) return EXIT_FAILURE;
+        if (!print_noise_corr(m.nc_acf, m.nc_mode, t2, k)) return EXIT_FAILURE;
     } else if (one_job) {
         if (run_bm5d(sigma, lambda, LF_noisy, mask, LF_basic, LF_den, ang_major, aw, ah, anH, anW, W, H, C, N[0], nSim[0], nDisp[0], k[0], p[0],
                      sd[0] != 0, t2[0], t4[0], t5[0], N[1], nSim[1], nDisp[1], k[1], p[1], sd[1] != 0, t2[1], t4[1], t5[1], cs, nb_threads) != EXIT_SUCCESS)
@@ -1567,36 +1528,32 @@ int main(int argc, char** argv) {
     if (one_job) cout << endl << "Steps 1 and 2 done in " << job << " secs." << endl << endl;
     else cout << endl << "Step 1 done in " << step1 << " secs." << endl << endl;
     vector<vector<float> > LF_basic_eq;   /* LFBM5D_EQUALISE=auto: step 2 reads the equalised basic estimate, the file gets the restored one */
-    if (eq_mode == 1) {
+    if (m.eq_mode == 1) {
         LF_basic_eq = LF_basic;
         if (!restore_LF(LF_basic, mask, eq_gains, aw, ah, W, H, C)) return EXIT_FAILURE;
         if (one_job && !restore_LF(LF_den, mask, eq_gains, aw, ah, W, H, C)) return EXIT_FAILURE;
     }
     if (gt) {
-        psnr_LF(LF, LF_basic, mask, ps, ap_b.psnr, sp, rm, ar, sr);
-        if (qmode && !cli_quality::compute(LF, LF_basic, mask, W, H, C, ap_b, qb)) return EXIT_FAILURE;
-        cout << endl << "Average PSNR:" << endl << "- Noisy light field: " << ap_n << endl << "- Basic light field: " << ap_b << endl;
-        write_psnr(results, "basic", mask, ang_major, aw, ah, ps, ap_b.psnr, sp, rm, ar, sr);
-        if (qmode) cli_quality::write(results, "basic", mask, ang_major, aw, ah, qb);
+        if (!quality.report("basic", LF_basic, ap_b, [&]() {
+                cout << endl << "Average PSNR:" << endl << "- Noisy light field: " << ap_n << endl << "- Basic light field: " << ap_b << endl; }))
+            return EXIT_FAILURE;
         diff_LF(LF, LF_basic, mask, LF_diff, sigma);
     }
     cout << endl << "Save basic light field..." << endl;
     if (save_LF(d_basic, name, sep, LF_basic, ang_major, aw, ah, s0, t0, W, H, C) != EXIT_SUCCESS) return EXIT_FAILURE;
     if (!one_job) cout << endl << endl << "Step 2 running..." << endl;
     t1 = now_s();
-    if (eq_mode == 1 && !one_job) LF_basic.swap(LF_basic_eq);
+    if (m.eq_mode == 1 && !one_job) LF_basic.swap(LF_basic_eq);
     if (!one_job && run_bm5d_2nd_step(sigma, LF_noisy, mask, LF_basic, LF_den, ang_major, aw, ah, anW, W, H, C, N[1], nSim[1], nDisp[1], k[1], p[1],
                           sd[1] != 0, t2[1], t4[1], t5[1], cs, nb_threads) != EXIT_SUCCESS) return EXIT_FAILURE;
     const double step2 = one_job ? 0.0 : now_s() - t1;
     if (!one_job) cout << endl << "Step 2 done in " << step2 << " secs." << endl << endl;
-    if (eq_mode == 1 && !one_job && !restore_LF(LF_den, mask, eq_gains, aw, ah, W, H, C)) return EXIT_FAILURE;
+    if (m.eq_mode == 1 && !one_job && !restore_LF(LF_den, mask, eq_gains, aw, ah, W, H, C)) return EXIT_FAILURE;
     if (gt) {
-        psnr_LF(LF, LF_den, mask, ps, ap_d.psnr, sp, rm, ar, sr);
-        if (qmode && !cli_quality::compute(LF, LF_den, mask, W, H, C, ap_d, qb)) return EXIT_FAILURE;
-        cout << endl << "Average PSNR:" << endl << "- Noisy light field: " << ap_n << endl << "- Basic light field: " << ap_b << endl
-             << "- Denoised light field: " << ap_d << endl << endl;
-        write_psnr(results, "denoised", mask, ang_major, aw, ah, ps, ap_d.psnr, sp, rm, ar, sr);
-        if (qmode) cli_quality::write(results, "denoised", mask, ang_major, aw, ah, qb);
+        if (!quality.report("denoised", LF_den, ap_d, [&]() {
+                cout << endl << "Average PSNR:" << endl << "- Noisy light field: " << ap_n << endl << "- Basic light field: " << ap_b << endl
+                     << "- Denoised light field: " << ap_d << endl << endl; }))
+            return EXIT_FAILURE;
         diff_LF(LF, LF_den, mask, LF_diff, sigma);
     }
     cout << endl << "Save denoised light field..." << endl;

@@ -242,17 +242,6 @@ int estimate(lfbm5d_ctx* c, const std::string& who, const float* d_lf, const uns
     return 0;
 }
 
-/* the non-empty SAIs at their places in [asize][C*H*W] of the context's staging buffer */
-int stage(lfbm5d_ctx* c, const std::string& who, const float* const* h_lf, const unsigned* h_mask, unsigned asize, size_t img, DevBuf& buf) {
-    if (!h_lf || !h_mask) return fail(c, who + "NULL pointer for a required buffer");
-    const auto nonempty = [&](unsigned st) { return h_mask[st] != 0; };
-    (void)hipSetDevice(c->device);
-    HIPCK(c, buf.reserve(std::max<size_t>(1, (size_t)asize * img) * sizeof(float)));
-    if (upload_planes(c, who, h_lf, buf.as<float>(), asize, img, nonempty)) return 1;
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return 0;
-}
-
 /* launches only: the caller synchronises.  nne = 0: build the SAI list from the mask first. */
 template <bool INVERSE>
 int transform(lfbm5d_ctx* c, const std::string& who, const PgCoef& k, const float* d_in, float* d_out, unsigned nne, unsigned W, unsigned H, unsigned C) {
@@ -372,20 +361,10 @@ int lfbm5d_denoise_pg_host_sai(lfbm5d_ctx* c, const lfbm5d_pg_model* model, lfbm
                                unsigned ang_major, unsigned awidth, unsigned aheight, unsigned an1, unsigned an2, unsigned W, unsigned H, unsigned C) {
     if (!c) return 1;
     const std::string who = "lfbm5d_denoise_pg_host_sai: ";
-    if (!h_basic || !h_denoised) return fail(c, who + "NULL pointer for a required buffer");
     if (check_chnls(c, who, C)) return 1;
-    const unsigned asize = awidth * aheight;
-    const size_t img = (size_t)C * W * H;
-    const auto nonempty = [&](unsigned st) { return h_mask[st] != 0; };
-    if (h_mask && (check_planes(c, who, h_basic, asize, nonempty) || check_planes(c, who, h_denoised, asize, nonempty))) return 1;
-    if (stage(c, who, h_noisy, h_mask, asize, img, c->h2d_noisy)) return 1;
-    HIPCK(c, c->h2d_basic.reserve(std::max<size_t>(1, (size_t)asize * img) * sizeof(float)));
-    HIPCK(c, c->h2d_out.reserve(std::max<size_t>(1, (size_t)asize * img) * sizeof(float)));
-    float* const db = c->h2d_basic.as<float>(); float* const dd = c->h2d_out.as<float>();
-    if (denoise_pg(c, who, model, used, P1, P2, c->h2d_noisy.as<float>(), h_mask, db, dd, ang_major, awidth, aheight, an1, an2, W, H, C)) return 1;
-    if (download_planes(c, h_basic, db, asize, img, nonempty) || download_planes(c, h_denoised, dd, asize, img, nonempty)) return 1;
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return host_sai_job(c, who, h_noisy, h_mask, h_basic, h_denoised, awidth * aheight, (size_t)C * W * H, [&](float* dn, float* db, float* dd) {
+        return denoise_pg(c, who, model, used, P1, P2, dn, h_mask, db, dd, ang_major, awidth, aheight, an1, an2, W, H, C);
+    });
 }
 
 } /* extern "C" */

@@ -236,17 +236,6 @@ int denoise_pgclip(lfbm5d_ctx* c, const std::string& who, const lfbm5d_pgclip_mo
     return 0;
 }
 
-/* the non-empty SAIs at their places in [asize][img] of a staging buffer of the context, waited for */
-int stage(lfbm5d_ctx* c, const std::string& who, const float* const* h_lf, const unsigned* h_mask, unsigned asize, size_t img, DevBuf& buf) {
-    if (!h_lf || !h_mask) return fail(c, who + "NULL pointer for a required buffer");
-    const auto nonempty = [&](unsigned st) { return h_mask[st] != 0; };
-    (void)hipSetDevice(c->device);
-    HIPCK(c, buf.reserve(std::max<size_t>(1, (size_t)asize * img) * sizeof(float)));
-    if (upload_planes(c, who, h_lf, buf.as<float>(), asize, img, nonempty)) return 1;
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return 0;
-}
-
 } /* namespace */
 
 extern "C" {
@@ -308,21 +297,10 @@ int lfbm5d_denoise_pgclip_host_sai(lfbm5d_ctx* c, const lfbm5d_pgclip_model* mod
                                    unsigned aheight, unsigned an1, unsigned an2, unsigned W, unsigned H, unsigned C) {
     if (!c) return 1;
     const std::string who = "lfbm5d_denoise_pgclip_host_sai: ";
-    if (!h_basic || !h_denoised || !h_mask) return fail(c, who + "NULL pointer for a required buffer");
     if (check_chnls(c, who, C)) return 1;
-    const unsigned asize = awidth * aheight;
-    const size_t img = (size_t)C * W * H;
-    const auto nonempty = [&](unsigned st) { return h_mask[st] != 0; };
-    if (check_planes(c, who, h_basic, asize, nonempty) || check_planes(c, who, h_denoised, asize, nonempty)) return 1;
-    if (stage(c, who, h_noisy, h_mask, asize, img, c->h2d_noisy)) return 1;
-    HIPCK(c, c->h2d_basic.reserve(std::max<size_t>(1, (size_t)asize * img) * sizeof(float)));
-    HIPCK(c, c->h2d_out.reserve(std::max<size_t>(1, (size_t)asize * img) * sizeof(float)));
-    float* const db = c->h2d_basic.as<float>(); float* const dd = c->h2d_out.as<float>();
-    if (denoise_pgclip(c, who, model, lo, hi, used, s_used, est, P1, P2, c->h2d_noisy.as<float>(), h_mask, db, dd, ang_major, awidth, aheight, an1, an2, W,
-                       H, C)) return 1;
-    if (download_planes(c, h_basic, db, asize, img, nonempty) || download_planes(c, h_denoised, dd, asize, img, nonempty)) return 1;
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return host_sai_job(c, who, h_noisy, h_mask, h_basic, h_denoised, awidth * aheight, (size_t)C * W * H, [&](float* dn, float* db, float* dd) {
+        return denoise_pgclip(c, who, model, lo, hi, used, s_used, est, P1, P2, dn, h_mask, db, dd, ang_major, awidth, aheight, an1, an2, W, H, C);
+    });
 }
 
 } /* extern "C" */

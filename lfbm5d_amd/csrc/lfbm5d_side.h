@@ -109,11 +109,40 @@ int upload_planes(lfbm5d_ctx* c, const std::string& who, const T* const* h, T* d
     return 0;
 }
 
+/* the non-empty SAIs at their places in [asize][img] of a staging buffer of the context, waited for */
+inline int stage(lfbm5d_ctx* c, const std::string& who, const float* const* h_lf, const unsigned* h_mask, unsigned asize, size_t img, DevBuf& buf) {
+    if (!h_lf || !h_mask) return fail(c, who + "NULL pointer for a required buffer");
+    const auto nonempty = [&](unsigned st) { return h_mask[st] != 0; };
+    (void)hipSetDevice(c->device);
+    HIPCK(c, buf.reserve(std::max<size_t>(1, (size_t)asize * img) * sizeof(float)));
+    if (upload_planes(c, who, h_lf, buf.as<float>(), asize, img, nonempty)) return 1;
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 /* enqueues the copies (output planes are checked with check_planes before the stage runs); the caller synchronises */
 template <class T, class Take>
 int download_planes(lfbm5d_ctx* c, T* const* h, const T* d, unsigned asize, size_t n, Take take) {
     for (unsigned st = 0; st < asize; st++)
         if (take(st)) HIPCK(c, hipMemcpyAsync(h[st], d + (size_t)st * n, n * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+    return 0;
+}
+
+/* The host form of a two-step job on stabilised data: the output planes are checked, the noisy light field is staged, job(d_noisy,
+ * d_basic, d_denoised) runs the device form on the context's staging buffers, both estimates are downloaded and waited for. */
+template <class Job>
+int host_sai_job(lfbm5d_ctx* c, const std::string& who, const float* const* h_noisy, const unsigned* h_mask, float* const* h_basic,
+                 float* const* h_denoised, unsigned asize, size_t img, Job job) {
+    if (!h_basic || !h_denoised || !h_mask) return fail(c, who + "NULL pointer for a required buffer");
+    const auto nonempty = [&](unsigned st) { return h_mask[st] != 0; };
+    if (check_planes(c, who, h_basic, asize, nonempty) || check_planes(c, who, h_denoised, asize, nonempty)) return 1;
+    if (stage(c, who, h_noisy, h_mask, asize, img, c->h2d_noisy)) return 1;
+    HIPCK(c, c->h2d_basic.reserve(std::max<size_t>(1, (size_t)asize * img) * sizeof(float)));
+    HIPCK(c, c->h2d_out.reserve(std::max<size_t>(1, (size_t)asize * img) * sizeof(float)));
+    float* const db = c->h2d_basic.as<float>(); float* const dd = c->h2d_out.as<float>();
+    if (job(c->h2d_noisy.as<float>(), db, dd)) return 1;
+    if (download_planes(c, h_basic, db, asize, img, nonempty) || download_planes(c, h_denoised, dd, asize, img, nonempty)) return 1;
+    HIPCK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 
